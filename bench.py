@@ -20,6 +20,11 @@ timing barrier / max and one end-of-run gather of per-rank summaries.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run measures the headline alone: build the batch, warm up (+ the untimed conditioning steps), time `--steps` steps, print
+the line.  `--full` adds everything else: the per-kernel table and roofline, the CPU baseline and the oracle cross-checks, the
+as-written and host hand-over figures, configs 3 and 5 on the same clock (`aux_configs`), the single-filter latency streams and
+the detail file.  `--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy.
+
 Roofline: `roofline.achieved` of the dominant kernel = EXECUTED FP64 operations per launch (rocprofv3 SQ counters committed
 under profiles/, read from profiles/counters.json — bench.py cannot collect PMC itself) / the kernel's HIP-event time
 measured live inside the timed region; <= peak by construction.  The ALGORITHMIC rate (SURVEY §8(d)'s dense formulation of
@@ -456,6 +461,30 @@ def oracle_parity_sample(ctx, one_step, steps, frames, gnss, n_prior, ld, N, F, 
                 max_rel_dx_err=max(dxe) if dxe else None)
 
 
+DUMP_LIMIT = 64 << 20                    # --dump-outputs: bytes in all
+DUMP_COV_FILTERS = 64                    # posterior covariances dumped: at most this many filters, a fixed seeded sample of the batch
+DUMP_SEED = 0x1A6F10
+
+
+def dump_outputs(out_dir, ctx, B, arrays):
+    """--dump-outputs: the results of the last timed step as float64 .npy files (integers are exact in float64).  The posterior
+    covariances (B x n x n: 254 MB at the default workload) are a fixed sample of the batch, `cov_filters` names which."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = ctx.n(0)
+    room = DUMP_LIMIT - sum(a.nbytes for a in out.values()) - (1 << 20)
+    S = max(1, min(B, DUMP_COV_FILTERS, room // (8 * n * n + 8)))
+    sample = np.sort(np.random.default_rng(DUMP_SEED).choice(B, S, replace=False))
+    covs = [ctx.cov_get(int(b)) for b in sample]
+    assert all(P.shape == (n, n) for P in covs), "filters of one batch share their state size"
+    out["cov_filters"] = sample.astype(np.float64)
+    out["cov"] = np.ascontiguousarray(np.stack(covs), dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, "dump of %d bytes > %d" % (total, DUMP_LIMIT)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -484,8 +513,15 @@ def parse_args():
                     "observation, rho = 2C - 3 rows per feature); auxiliary workload, never the default line")
     ap.add_argument("--no-aux", action="store_true", help="skip the auxiliary config-3 / config-5 passes of the default run")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-filter latency figures (C++ shim stream) of the default run")
-    ap.add_argument("--detail", default=DETAIL_JSON, help="where the full result (per-kernel tables, notes) is written")
+    ap.add_argument("--detail", default=DETAIL_JSON, help="where the full result (per-kernel tables, notes) is written (--full)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-kernel table and roofline, CPU baseline, oracle "
+                    "cross-checks, as-written and host hand-over figures, aux configs 3 / 5, latency streams, the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0: dx, accept masks, row counts, a fixed "
+                         "sample of posterior covariances, GNSS / landmark results where the workload has them) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.literal:
         args.state = "literal"
     return args
@@ -558,9 +594,9 @@ def run_workload(args, grp, aux=False):
             ctx.sync(); blocks.append((time.perf_counter() - t_b) / 20 * 1e3)
         cond = dict(steps=20 * len(blocks), seconds=time.perf_counter() - t_c0, first_block_ms_per_step=blocks[0], last_block_ms_per_step=blocks[-1])
     # Per-kernel table: a separate UNTIMED pass of 3 steps with a HIP-event pair around every launch (an event pair
-    # per launch costs ~6 % of the step, so the timed region below only brackets the dominant kernel).
+    # per launch costs ~6 % of the step, so the timed region below only brackets the dominant kernel).  --full only.
     prof, dom_name = {}, None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         ctx.profile_select(None); ctx.profile_reset(); ctx.profile_enable(True)
         for _ in range(3):
             one_step()
@@ -620,10 +656,17 @@ def run_workload(args, grp, aux=False):
     if real_lm:
         dxl, lm_rows, lacc, lgam, lst = ctx.landmark_fetch()
         ok = ok and bool(np.isfinite(dxl).all() and (lst == 0).all() and (lm_rows > 0).all())
+    if args.dump_outputs and rank == 0 and not aux:
+        arrays = dict(dx=dx[:, :N], accepted=acc[:, :F], rows=rows)
+        if gnss is not None:
+            arrays.update(gnss_dx=dxg[:, :N], gnss_rows=gn_used, gnss_keep=keep, gnss_gamma=gam, gnss_status=st)
+        if real_lm:
+            arrays.update(lm_dx=dxl[:, :N], lm_rows=lm_rows, lm_accepted=lacc, lm_gamma=lgam, lm_status=lst)
+        dump_outputs(args.dump_outputs, ctx, B, arrays)
     # N > 1: every rank cross-checks its FIRST filter against the oracle (covariance, accept mask) - a rank whose device or
-    # library misbehaves shows up in the line, not only rank 0's
+    # library misbehaves shows up in the line, not only rank 0's (--full)
     rank_par = [0.0, 1.0]
-    if world > 1 and not real_lm:
+    if args.full and world > 1 and not real_lm:
         rp = oracle_parity_sample(ctx, one_step, steps, frames, gnss, infos[0]["n_prior"], ld, N, F, 1)
         rank_par = [rp["max_rel_cov_err"], float(rp["accept_mask_equal"])]
     # one end-of-run gather of per-rank summaries
@@ -636,11 +679,13 @@ def run_workload(args, grp, aux=False):
         per_kernel, total_flops = algorithmic_flops(F_used, F, C, N, synth.IMU_PER_FRAME)
         bytes_k = algorithmic_bytes(N, synth.IMU_PER_FRAME, F, C)
         wkey = "c%d_B%d_F%d_C%d_N%d" % (args.config, B, F, C, N) + ("_lmreal" if real_lm else "") + ("" if stereo else "_mono")
-        counters, csrc, rec_build = load_counters(args.counters, wkey)
-        live_build = capi.build_id()
-        kernels, roofline = price_kernels(prof, dom_name, counters, csrc, rec_build, live_build, C, B, per_kernel, bytes_k, stereo=stereo)
+        counters, csrc, kernels, roofline = None, None, {}, None
+        if args.full:
+            counters, csrc, rec_build = load_counters(args.counters, wkey)
+            live_build = capi.build_id()
+            kernels, roofline = price_kernels(prof, dom_name, counters, csrc, rec_build, live_build, C, B, per_kernel, bytes_k, stereo=stereo)
         cpu, parity = None, None
-        if world > 1 and not real_lm:
+        if args.full and world > 1 and not real_lm:
             parity = dict(sample=world, filters="filter 0 of every rank", max_rel_cov_err=float(summ[:, 3].max()),
                           per_rank_rel_cov_err=[float(x) for x in summ[:, 3]], accept_mask_equal=bool(summ[:, 4].all()))
         oracle_1t = None
@@ -650,7 +695,7 @@ def run_workload(args, grp, aux=False):
             parity = oracle_parity_sample(ctx, one_step, steps, frames, gnss, infos[0]["n_prior"], ld, N, F, 2 if big else 8)
             # (python-side structure packing included: an upper bound of the oracle's single-thread update time, for the latency line)
             oracle_1t = (time.perf_counter() - t_or) / parity["sample"] * 1e3
-        if world == 1 and not args.no_cpu and not real_lm and not aux:      # the C oracle's frame has no landmark update: parity of that path is tests/test_landmark_batch.py
+        if args.full and world == 1 and not args.no_cpu and not real_lm and not aux:      # the C oracle's frame has no landmark update: parity of that path is tests/test_landmark_batch.py
             cpu, (P1, n1, dx1, acc1, S) = cpu_baseline(ctx, steps, frames, infos[0]["n_prior"], ld, quick=args.quick_cpu)
             ctx.frame_run(restore_prior=True)
             dxg, accg, rowsg = ctx.frame_fetch(0, S)
@@ -1017,7 +1062,7 @@ def _rnd(x, sig=6):
     return x
 
 
-def compact_line(full):
+def compact_line(full, detail=True):
     """The ONE JSON line the driver parses, from the full result dict: the contract's keys, `roofline` and `cpu_baseline` reduced
     to their figures, a compact `aux_configs`; per-kernel tables, notes, the host hand-over and the as-written figures stay in
     bench_detail.json.  VERDICT r03 #1: the round-3 line (22 KB) no longer fitted the driver's stdout tail."""
@@ -1085,7 +1130,8 @@ def compact_line(full):
                            same_result=tk.get("same_result_as_staged_frame"), stagers8_aggregate=s8.get("tracks"), error=tk.get("error"))
         h["bytes_per_update"] = hh.get("input_bytes_per_update")
         out["host_handover"] = h
-    out["detail"] = "bench_detail.json (per-kernel table, notes, host hand-over, as-written cap-20 figures)"
+    if detail:
+        out["detail"] = "bench_detail.json (per-kernel table, notes, host hand-over, as-written cap-20 figures)"
     line = json.dumps(_rnd(out))
     assert len(line) < LINE_LIMIT, "bench line %d chars >= %d: move keys to bench_detail.json" % (len(line), LINE_LIMIT)
     return line
@@ -1098,8 +1144,8 @@ def main():
     out = run_workload(args, grp, aux=False)
     # BASELINE configs 3 and 5 on the same clock: after the headline measurement the default single-GPU run
     # makes a short pass over each and reports it under `aux_configs` (same steps / warm-up, no CPU timing, an in-run oracle
-    # parity sample each).  The headline keys above are config 2's alone.
-    if grp.world == 1 and args.config == 2 and not args.no_aux and args.method == "factored" and args.landmarks == "padded":
+    # parity sample each).  The headline keys above are config 2's alone.  --full only.
+    if args.full and grp.world == 1 and args.config == 2 and not args.no_aux and args.method == "factored" and args.landmarks == "padded":
         aux = {}
         for cfg in (3, 5):
             a = argparse.Namespace(**vars(args))
@@ -1115,12 +1161,13 @@ def main():
                 lat["config5"]["oracle_1thread_update_ms"] = aux["config5"].get("oracle_update_ms_upper_bound")
             out["latency_b1_ms"] = lat
     if grp.rank == 0:
-        try:
-            with open(args.detail, "w") as f:
-                json.dump(out, f, indent=1)
-        except OSError as e:                       # read-only checkout: the line still goes out
-            print("bench.py: could not write %s: %s" % (args.detail, e), file=sys.stderr)
-        print(compact_line(out))
+        if args.full:
+            try:
+                with open(args.detail, "w") as f:
+                    json.dump(out, f, indent=1)
+            except OSError as e:                   # read-only checkout: the line still goes out
+                print("bench.py: could not write %s: %s" % (args.detail, e), file=sys.stderr)
+        print(compact_line(out, detail=args.full))
     grp.close()
 
 

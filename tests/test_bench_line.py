@@ -6,6 +6,8 @@ import json
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -130,3 +132,36 @@ def test_library_build_id_matches_the_sources():
     src = build.source_build_id()
     assert live == src
     assert live["kernels"]["k_feat_gate4"] == "kernels_factored.hip" and len(live["tu"]) == len(build.HIP_SOURCES)
+
+
+def _plain_run(out_dir):
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+           "--dump-outputs", str(out_dir)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) prints the headline only, times exactly --steps steps, and --dump-outputs writes what the last
+    timed step computed; the same arguments give the same inputs, so two runs dump the same arrays."""
+    import numpy as np
+    d = _plain_run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["metric"] == "ekf_updates_per_sec" and d["unit"] == "updates/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["results_finite"] is True
+    assert abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-4
+    assert "roofline" not in d and "aux_configs" not in d and "latency_b1_ms" not in d and d["cpu_baseline"] is None
+    z = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(z) == {"dx", "accepted", "rows", "cov", "cov_filters"}
+    assert z["dx"].shape == (8, 249) and z["accepted"].shape == (8, 150) and z["cov"].shape == (8, 243, 243)
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in z.values())
+    assert (z["rows"] == 66).all() and z["accepted"].sum() > 0 and sum(a.nbytes for a in z.values()) <= 64 << 20
+    _plain_run(tmp_path / "b")
+    for k, a in z.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / (k + ".npy"))), k

@@ -2,7 +2,7 @@
 (`python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 ...`), both contexts on device 0 (INGVIO_DEVICE=0) and
 gloo carrying the barrier / max / gather (RCCL refuses two ranks on one device; INGVIO_DIST_BACKEND=gloo).  Checks the contract
 of the line, not a scaling figure: one JSON line from rank 0 only, n_gpus = 2, one per-rank time each, value = all ranks'
-updates / the slowest rank's time, and the in-run oracle cross-check of BOTH ranks' first filter."""
+updates / the slowest rank's time, and the in-run oracle cross-check of BOTH ranks' first filter (a `--full` figure)."""
 import json
 import os
 import subprocess
@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run_bench(extra, port):
     env = dict(os.environ, INGVIO_DIST_BACKEND="gloo", INGVIO_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-cpu", "--no-aux", "--steps", "3", "--warmup", "1"] + extra
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--no-cpu", "--no-aux", "--steps", "3", "--warmup", "1"] + extra
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

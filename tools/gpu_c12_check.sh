@@ -1,5 +1,5 @@
 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "twelve or window_size" 2>&1 | tail -3
-python bench.py --clones 12 --no-aux --no-latency --no-cpu 2>/dev/null | python -c "
+python bench.py --full --clones 12 --no-aux --no-latency --no-cpu 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('c12',d['value'],d['ms_per_step'])"
 python -c "
 import json;d=json.load(open('bench_detail.json'));print({k:(round(v.get('avg_ms'),4),v.get('kernel')) for k,v in d['kernels'].items()})"

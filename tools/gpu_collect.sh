@@ -1,10 +1,11 @@
 #!/bin/bash
 # Profile collection of a round in ONE GPU call: for every workload rocprofv3 kernel stats + the PMC passes (tools/gpu_counters.sh ->
-# gpurun_out/counters.json with the library's build id, kernel_stats_<tag>.csv, counters_<tag>.csv), then the bench line of the same
-# workload priced with those counters (gpurun_out/bench_<tag>.json + bench_<tag>_detail.json).
+# $RESULTS/counters.json with the library's build id, kernel_stats_<tag>.csv, counters_<tag>.csv), then the bench line of the same
+# workload priced with those counters ($RESULTS/bench_<tag>.json + bench_<tag>_detail.json).
 #   tools/gpu_collect.sh [c2 c3 c5 c2n87 c2n93 c5lit c2lm ...]      (default: c2 c3 c5)
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+RESULTS=${RESULTS:-results}; export RESULTS          # where the tools write (git-ignored)
+mkdir -p $RESULTS
 W="${*:-c2 c3 c5}"
 args() { case $1 in
   c2) echo "--config 2";; c3) echo "--config 3";; c5) echo "--config 5";;
@@ -22,11 +23,12 @@ for w in $W; do
   EXTRA="--no-aux --no-latency"
   [ $w = c2 ] && EXTRA=""
   [ $w = c2 ] || EXTRA="$EXTRA --no-cpu"
-  python bench.py $(args $w) $EXTRA --counters gpurun_out/counters.json --detail gpurun_out/bench_${w}_detail.json 2> gpurun_out/bench_$w.err | tail -1 > gpurun_out/bench_$w.json
+  python bench.py --full $(args $w) $EXTRA --counters $RESULTS/counters.json --detail $RESULTS/bench_${w}_detail.json 2> $RESULTS/bench_$w.err | tail -1 > $RESULTS/bench_$w.json
   python - $w <<'PY'
+import os
 import json, sys
 w = sys.argv[1]
-d = json.load(open("gpurun_out/bench_%s.json" % w)); r = d.get("roofline") or {}
+d = json.load(open(os.environ["RESULTS"] + "/bench_%s.json" % w)); r = d.get("roofline") or {}
 print(w, "value", round(d["value"]), "ms/step", round(d["ms_per_step"], 4), "roofline", r.get("kernel"), "frac", r.get("frac"), "useful", r.get("useful_frac"),
       "stale", r.get("counters_stale"), "whole", d.get("whole_step_frac_fp64_peak"), "parity", (d.get("parity_vs_oracle") or {}).get("max_rel_cov_err"))
 PY

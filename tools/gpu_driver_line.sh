@@ -1,9 +1,9 @@
 #!/bin/bash
-# the driver's command, N times, with the figures of the line that matter: bash tools/gpu_driver_line.sh [n] [extra bench args]
+# the driver's command with --full (for the roofline and aux_configs figures), N times: bash tools/gpu_driver_line.sh [n] [extra bench args]
 cd "$(dirname "$0")/.."
 N=${1:-2}; shift
 for i in $(seq $N); do
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 "$@" 2>/dev/null | tail -1 > /tmp/line.json
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 "$@" 2>/dev/null | tail -1 > /tmp/line.json
   python3 - <<'PY'
 import json
 d = json.load(open("/tmp/line.json"))

@@ -1,8 +1,9 @@
 #!/bin/bash
 # rocprofv3 timeline (kernels + copies) of the pipelined track-store hand-over loop: bash tools/gpu_handover_trace.sh
 cd "$(dirname "$0")/.."
+RESULTS=${RESULTS:-results}; export RESULTS          # where the tools write (git-ignored)
 export TMPDIR=/tmp
-OUT=gpurun_out/handover_trace
+OUT=$RESULTS/handover_trace
 rm -rf $OUT; mkdir -p $OUT
 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT -o ht -- python - <<'PY' > $OUT/stdout.txt 2>&1
 import os, sys, time
@@ -25,12 +26,13 @@ ctx.close()
 PY
 tail -2 $OUT/stdout.txt
 python - <<'PY'
+import os
 import csv, glob
 rows = []
-for f in glob.glob("gpurun_out/handover_trace/**/*kernel_trace.csv", recursive=True):
+for f in glob.glob(os.environ["RESULTS"] + "/handover_trace/**/*kernel_trace.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"][:30], "q" + r["Queue_Id"]))
-for f in glob.glob("gpurun_out/handover_trace/**/*memory_copy_trace.csv", recursive=True):
+for f in glob.glob(os.environ["RESULTS"] + "/handover_trace/**/*memory_copy_trace.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), "COPY " + r.get("Direction", "")[:24], ""))
 rows.sort()

@@ -1,7 +1,7 @@
 """ingvio_qr_compress on the three shapes VERDICT r02 asks for — the literal config-2 SPQR shape 6150 x 66, the literal config-5
 stack 35100 x 180 (both rank n - 6, real stacked MSCKF Jacobians), BASELINE's nominal 6000 x 800 (cond 1e3) — with both methods.
 Device time = the HIP-event time of the captured launch graph (profile slot of the QR stage), host time = the whole call incl.
-PCIe.  Writes gpurun_out/qr_shapes.json."""
+PCIe.  Writes $RESULTS/qr_shapes.json (default results/)."""
 import json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -39,6 +39,6 @@ for name, A, b in shapes:
         out.append(rec)
         print("%-18s %6d x %3d %-11s device %8.3f ms  call %8.2f ms  %6.2f TFLOP/s (%.3f of FP64 peak)  |R^T R - H^T H| %.1e" %
               (name, m, n, method, dev_ms, host_ms, rec["tflops"], rec["frac_fp64_peak"], e))
-os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-json.dump(out, open(os.path.join(ROOT, "gpurun_out", "qr_shapes.json"), "w"), indent=1)
+os.makedirs(os.path.join(ROOT, os.environ.get("RESULTS", "results")), exist_ok=True)
+json.dump(out, open(os.path.join(ROOT, os.environ.get("RESULTS", "results"), "qr_shapes.json"), "w"), indent=1)
 ctx.close()

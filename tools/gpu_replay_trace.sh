@@ -2,6 +2,7 @@
 # rocprofv3 kernel + memory-copy trace of the single-filter latency stream through the C++ shim (what the device does per camera callback).
 # usage (GPU box): bash tools/gpu_replay_trace.sh [config2|config5]
 cd "$(dirname "$0")/.."
+RESULTS=${RESULTS:-results}; export RESULTS          # where the tools write (git-ignored)
 export TMPDIR=/tmp
 W=${1:-config2}
 case $W in
@@ -15,7 +16,7 @@ esac
 EXTRA=()
 case $W in sw11) EXTRA=(--set "frame_select_interval: 5");; esac
 case $W in config2|config5) EXTRA=(--set "hip_max_valid_ids: 0" --set "hip_compress_rule: 1");; esac
-OUT=gpurun_out/replay_trace_$W
+OUT=$RESULTS/replay_trace_$W
 rm -rf $OUT; mkdir -p $OUT
 rocprofv3 --kernel-trace --memory-copy-trace --stats -d $OUT -o rt --output-format csv -- ingvio_amd/lib/ingvio_replay --synth "$SPEC" --time "${EXTRA[@]}" > $OUT/stdout.txt 2> $OUT/stderr.txt
 tail -1 $OUT/stdout.txt

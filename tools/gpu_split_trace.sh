@@ -1,6 +1,7 @@
 #!/bin/bash
 # kernel timeline of the split frame step (rocprofv3 --kernel-trace): tools/gpu_split_trace.sh <parts> <outdir>
-P=${1:-2}; OUT=${2:-gpurun_out/r06a/trace_p$P}
+RESULTS=${RESULTS:-results}; export RESULTS          # where the tools write (git-ignored)
+P=${1:-2}; OUT=${2:-$RESULTS/r06a/trace_p$P}
 export TMPDIR=/tmp
 mkdir -p $OUT
 INGVIO_FRAME_PARTS=$P rocprofv3 --kernel-trace --output-format csv -d $OUT -- python - <<'PY'

@@ -1,8 +1,9 @@
 #!/bin/bash
-# copies the summaries of a collection (tools/gpu_collect.sh, tools/gpu_full_tests.sh, tools/gpu_final_b1.sh) from gpurun_out/ (scratch)
+# copies the summaries of a collection (tools/gpu_collect.sh, tools/gpu_full_tests.sh, tools/gpu_final_b1.sh) from $RESULTS/ (scratch)
 # into profiles/ (tracked) under the round's prefix: bash tools/publish_profiles.sh r06
 cd "$(dirname "$0")/.."
-R=${1:-r06}; G=gpurun_out; P=profiles
+RESULTS=${RESULTS:-results}; export RESULTS          # where the tools write (git-ignored)
+R=${1:-r06}; G=$RESULTS; P=profiles
 cp $G/counters.json $P/counters.json
 for w in c2 c3 c5 c2n87 c2n93 c5lit c2lm c2mono c2c12; do
   [ -f $G/bench_$w.json ] && cp $G/bench_$w.json $P/${R}_bench_$w.json
