@@ -411,7 +411,7 @@ int ingvio_msckf_update_tri(ingvio_ctx* ctx, int b0, int nb, const ingvio_msckf_
  * synchronisation between the stages.  stage() uploads inputs (outside any timed region),
  * run() only enqueues kernels, fetch() synchronises and downloads. */
 typedef struct {
-    int k;                    /* IMU steps                                                          */
+    int k;                    /* IMU steps, 1 <= k <= 64, the same for every filter of a call (see below) */
     const double* Phi;        /* [k][225]                                                           */
     const double* G;          /* [k][180]                                                           */
     const double* dt;         /* [k]                                                                */
@@ -420,6 +420,10 @@ typedef struct {
     int marg_idx;             /* idx of the clone to marginalise afterwards, -1: none               */
 } ingvio_frame_step;
 
+/* k, sigma, sigma_cb and sigma_rw are held once per context: ingvio_frame_run propagates every filter of the batch with the last
+ * stage's values.  A stage of the whole batch (b0 = 0, nb = batch) may change them; a stage of part of the batch must repeat the
+ * values of the frame already staged for the other filters, or it is refused with INGVIO_E_ARG and changes nothing.  The same
+ * holds for ingvio_frame_stage_tracks. */
 int ingvio_frame_stage(ingvio_ctx* ctx, int b0, int nb, const ingvio_frame_step* steps,
                        const ingvio_msckf_frame* frames, const ingvio_msckf_opts* opts,
                        const double sigma[4], int enable_gnss, double sigma_cb, double sigma_rw);
@@ -457,7 +461,7 @@ typedef struct {
     const unsigned long long* feat_sel;           /* [n_feat] or NULL: every stored observation of the track takes part          */
 } ingvio_track_frame;
 typedef struct {
-    int k;                        /* IMU steps (the same for every filter of a call)                                              */
+    int k;                        /* IMU steps, 1 <= k <= 64 (the same for every filter of a call; partial stages: as ingvio_frame_stage) */
     const double* imu;            /* [k][7] gyro (3), accel (3), dt of each step, as ImuPropagator::propagateUntil forms them     */
     double R[9], p[3], v[3], bg[3], ba[3], gravity[3];      /* State::_extended_pose (row-major R), biases, gravity at the frame's start */
     int gnss_idx[5];

@@ -2389,6 +2389,19 @@ int ingvio_qr_compress(ingvio_ctx* c, const double* H, int ldh, int m, int n, co
     }
 }
 
+// ingvio_frame_run propagates the whole batch with ONE k, sigma, sigma_cb, sigma_rw (the last stage's): d_Phi / d_G / d_dt of filter b
+// sit at b * k * 225 ... for that k.  A stage of part of the batch must therefore keep the settings of the frame already staged for
+// the other filters; only a stage of the whole batch may change them.
+static bool partial_stage_mismatch(ingvio_ctx* c, int nb, int k, const double sigma[4], double scb, double srw)
+{
+    if (!c->staged || nb == c->d.batch) return false;
+    if (k != c->st_k || memcmp(sigma, c->st_sigma, 32) || memcmp(&scb, &c->st_scb, 8) || memcmp(&srw, &c->st_srw, 8)) {
+        c->err = "a stage of part of the batch with k / sigma / sigma_cb / sigma_rw other than the staged frame's";
+        return true;
+    }
+    return false;
+}
+
 static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step* steps, const ingvio_msckf_frame* frames,
                             const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, bool async)
 {
@@ -2398,6 +2411,7 @@ static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_st
     if (async && (b0 != 0 || nb != c->d.batch)) return INGVIO_E_ARG;      // a whole input set is replaced
     const int k = steps[0].k;
     if (k < 1 || k > KMAX) return INGVIO_E_ARG;
+    if (partial_stage_mismatch(c, nb, k, sigma, scb, srw)) return INGVIO_E_ARG;
     if (!opts->chi2_table || opts->chi2_len < 2 || opts->chi2_len > CHI2_CAP) return INGVIO_E_ARG;
     for (int i = 0; i < nb; ++i)
         if (steps[i].k != k || !steps[i].Phi || !steps[i].G || !steps[i].dt) return INGVIO_E_ARG;
@@ -2528,6 +2542,7 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
     if (async && (b0 != 0 || nb != c->d.batch)) return INGVIO_E_ARG;
     const int k = steps[0].k, T = c->trk.t_max, cm = c->d.c_max, fm = c->d.f_max;
     if (k < 1 || k > KMAX) return INGVIO_E_ARG;
+    if (partial_stage_mismatch(c, nb, k, sigma, scb, srw)) return INGVIO_E_ARG;
     if (!opts->chi2_table || opts->chi2_len < 2 || opts->chi2_len > CHI2_CAP) return INGVIO_E_ARG;
     // ---- layout (counts only), then validation + packing per filter on a few host threads; nothing of the context is touched before
     //      every filter's delta has been found consistent (the pinned slab is scratch) ----
@@ -2651,6 +2666,7 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
     TrackStore store{ c->trk.uv, c->trk.mask, c->trk.pf, T, cm };
     FrameOut fo{ c->d_clone_idx, c->d_clone_R, c->d_clone_p, c->d_nclones, c->d_nfeat, c->d_pf, c->d_anchor, c->d_mask, c->d_uv, c->d_dof, cm, fm };
     launch_imu_steps(ts, b0, nb, k, c->d_Phi, c->d_G, c->d_dt, c->d_R, S);
+    if (hipGetLastError() != hipSuccess) return fail(INGVIO_E_HIP);       // before the store kernels change the track store
     launch_tracks_apply(ts, store, b0, nb, S);
     launch_tracks_gather(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S);
     if (hipGetLastError() != hipSuccess) return fail(INGVIO_E_HIP);

@@ -128,18 +128,22 @@ __device__ __forceinline__ void put(double* M, int r0, int c0, const M3& B)     
 
 }  // namespace
 
+#define IMU_STEPS_CH 16    // samples whose Phi | G pass through LDS together
+
 // One wave per filter, lane s = IMU sample s of the frame (ImuPropagator::propagateUntil's loop over stateAndCovTransition, the analytic
 // branch), from the nominal state the host holds at the frame's start.  The nominal recursion (R, p, v) is sequential in the samples
 // but cheap (three Gamma functions and two matrix-vector products per step), the transition matrices are not (Psi_1, Psi_2: a dozen
 // 3 x 3 products and eight sin / cos each): every lane runs the cheap recursion up to ITS sample and forms only its own Phi and G; the
-// matrices go through LDS so that the stores are coalesced.  (The first version ran one THREAD per filter over all k samples: 165-200 us
-// per 512 filters on the copy stream, under the update's apply kernel.)
+// matrices go through LDS so that the stores are coalesced, IMU_STEPS_CH samples at a time: a static 51.8 KB buffer for every k <= KMAX
+// (k samples at once would be 405 * 8 * k bytes of dynamic LDS, above the 160 KiB of a CU from k = 51 on - such a launch never starts).
+// (The first version ran one THREAD per filter over all k samples: 165-200 us per 512 filters on the copy stream, under the update's
+// apply kernel.)
 // imu [k][7] = gyro (3), accel (3), dt; st0 [24] = R (9, row-major), p, v, bg, ba, gravity.  Writes Phi [k][225], G [k][180], dt [k]
 // of the filter's input slot and the IMU rotation at clone time R_out [9] (StateManager::augmentSlidingWindowPose reads it).
 __global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, int b0, int nb, int kcap /* = k of every filter */, double* __restrict__ PhiAll, double* __restrict__ GAll,
                                                   double* __restrict__ dtAll, double* __restrict__ Rall)
 {
-    extern __shared__ double sm[];                                     // [k][405]: Phi | G of sample s
+    __shared__ double sm[IMU_STEPS_CH * 405];                          // [IMU_STEPS_CH][405]: Phi | G of samples c0 .. c0 + 15
     const int bl = blockIdx.x, lane = threadIdx.x;
     const int* h = ts.hdr + (size_t)bl * TRK_HDR;
     const int k = h[TRK_K];
@@ -175,33 +179,37 @@ __global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, int b0, int nb,
         const V3 vn = vk + dt * g + dt * (RG1 * a);
         const V3 pn = pk + dt * vk + (0.5 * dt * dt) * g + (dt * dt) * (RG2 * a);
         const M3 P1 = Rk * psi1_func(w, a, dt, sc), P2 = Rk * psi2_func(w, a, dt, sc);
-        if (lane < k) {
-            double* Phi = sm + (size_t)sm_s * 405;
-            double* G = Phi + 225;
-            for (int i = 0; i < 405; ++i) Phi[i] = 0.0;
-            for (int i = 0; i < 15; ++i) Phi[i * 15 + i] = 1.0;                        // :105
-            put(G, 0, 0, Rk);                                                           // :112-117
-            put(G, 3, 0, skew(pk) * Rk);
-            put(G, 6, 0, skew(vk) * Rk);
-            put(G, 6, 3, Rk);
-            put(G, 9, 6, I3);
-            put(G, 12, 9, I3);
-            put(Phi, 3, 0, (0.5 * dt * dt) * skew(g));                                 // :150
-            put(Phi, 3, 6, dt * I3);
-            put(Phi, 6, 0, dt * skew(g));
-            put(Phi, 0, 9, -(dt * RG1));
-            put(Phi, 6, 12, -(dt * RG1));
-            put(Phi, 3, 12, -((dt * dt) * RG2));
-            put(Phi, 6, 9, -(dt * (skew(vn) * RG1)) + P1);                             // :159
-            put(Phi, 3, 9, -(dt * (skew(pn) * RG1)) + P2);                             // :161
+        double* Phi0 = PhiAll + (size_t)(b0 + bl) * kcap * 225;
+        double* G0 = GAll + (size_t)(b0 + bl) * kcap * 180;
+        for (int c0 = 0; c0 < k; c0 += IMU_STEPS_CH) {
+            const int cnt = min(IMU_STEPS_CH, k - c0);
+            if (lane < k && lane >= c0 && lane < c0 + cnt) {
+                double* Phi = sm + (size_t)(sm_s - c0) * 405;
+                double* G = Phi + 225;
+                for (int i = 0; i < 405; ++i) Phi[i] = 0.0;
+                for (int i = 0; i < 15; ++i) Phi[i * 15 + i] = 1.0;                        // :105
+                put(G, 0, 0, Rk);                                                           // :112-117
+                put(G, 3, 0, skew(pk) * Rk);
+                put(G, 6, 0, skew(vk) * Rk);
+                put(G, 6, 3, Rk);
+                put(G, 9, 6, I3);
+                put(G, 12, 9, I3);
+                put(Phi, 3, 0, (0.5 * dt * dt) * skew(g));                                 // :150
+                put(Phi, 3, 6, dt * I3);
+                put(Phi, 6, 0, dt * skew(g));
+                put(Phi, 0, 9, -(dt * RG1));
+                put(Phi, 6, 12, -(dt * RG1));
+                put(Phi, 3, 12, -((dt * dt) * RG2));
+                put(Phi, 6, 9, -(dt * (skew(vn) * RG1)) + P1);                             // :159
+                put(Phi, 3, 9, -(dt * (skew(pn) * RG1)) + P2);                             // :161
+            }
+            __syncthreads();
+            for (int e = lane; e < cnt * 405; e += 64) {
+                const int q = e / 405, r = e - q * 405, s = c0 + q;
+                if (r < 225) Phi0[(size_t)s * 225 + r] = sm[e]; else G0[(size_t)s * 180 + r - 225] = sm[e];
+            }
+            __syncthreads();                                            // the next chunk reuses the buffer
         }
-    }
-    __syncthreads();
-    double* Phi0 = PhiAll + (size_t)(b0 + bl) * kcap * 225;
-    double* G0 = GAll + (size_t)(b0 + bl) * kcap * 180;
-    for (int e = lane; e < k * 405; e += 64) {
-        const int s = e / 405, r = e - s * 405;
-        if (r < 225) Phi0[(size_t)s * 225 + r] = sm[e]; else G0[(size_t)s * 180 + r - 225] = sm[e];
     }
     if (lane < k) dtAll[(size_t)(b0 + bl) * kcap + lane] = imu[7 * lane + 6];
     if (lane == 0) {                                                  // every lane's recursion ended behind the last sample
@@ -316,7 +324,7 @@ __global__ __launch_bounds__(256) void k_tracks_gather(TrackStage ts, TrackStore
 
 void launch_imu_steps(const TrackStage& ts, int b0, int nb, int kcap, double* Phi, double* G, double* dt, double* R, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_imu_steps, dim3(nb), dim3(64), sizeof(double) * 405 * (size_t)kcap, st, ts, b0, nb, kcap, Phi, G, dt, R);
+    hipLaunchKernelGGL(k_imu_steps, dim3(nb), dim3(64), 0, st, ts, b0, nb, kcap, Phi, G, dt, R);
 }
 void launch_tracks_apply(const TrackStage& ts, const TrackStore& store, int b0, int nb, hipStream_t st)
 {

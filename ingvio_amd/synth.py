@@ -339,18 +339,19 @@ def frame_from_filter(flt, pf, uv, obs_mask=None, anchor=None, dof=None, stereo=
 
 
 def build_case(cov_factory, transition, seed=0, F=150, C=11, n_gnss=6, n_landmarks=52, stereo=True,
-               outlier_every=20, table=None, lm_sigma=1.0):
+               outlier_every=20, table=None, lm_sigma=1.0, k=IMU_PER_FRAME):
     """Config-2 style case.  Runs C-1 propagate+clone cycles to create a realistic prior, then
     prepares the measured frame: k IMU steps, clone #C, F features seen by all C clones, marginalise
     the oldest clone afterwards.  Returns (flt, step, frame, info) with the covariance engine inside
-    ``flt.cov`` holding the PRIOR (N = 21 + n_gnss + 3*n_landmarks + 6*(C-1))."""
+    ``flt.cov`` holding the PRIOR (N = 21 + n_gnss + 3*n_landmarks + 6*(C-1)).  ``k`` is the measured
+    frame's step count only: the prior's cycles keep IMU_PER_FRAME steps."""
     rng = np.random.default_rng(0x1A6F10 + seed)
     flt = Filter(cov_factory, transition, t0=0.1 * seed, n_gnss=n_gnss, n_landmarks=n_landmarks, lm_sigma=lm_sigma)
     for _ in range(C - 1):
         flt.propagate_cov(flt.imu_steps(rng))
         flt.clone()
     # the measured frame: nominal propagation now, covariance work left to the caller
-    steps = flt.imu_steps(rng)
+    steps = flt.imu_steps(rng, k=k)
     t_new = flt.t
     clone_times = [c["t"] for c in flt.clones] + [t_new]
     oldest = flt.clones[0]["name"]
