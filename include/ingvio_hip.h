@@ -411,7 +411,7 @@ int ingvio_msckf_update_tri(ingvio_ctx* ctx, int b0, int nb, const ingvio_msckf_
  * synchronisation between the stages.  stage() uploads inputs (outside any timed region),
  * run() only enqueues kernels, fetch() synchronises and downloads. */
 typedef struct {
-    int k;                    /* IMU steps, 1 <= k <= 64, the same for every filter of a call (see below) */
+    int k;                    /* IMU steps, 1 <= k <= 64, per filter (see below)                    */
     const double* Phi;        /* [k][225]                                                           */
     const double* G;          /* [k][180]                                                           */
     const double* dt;         /* [k]                                                                */
@@ -420,10 +420,11 @@ typedef struct {
     int marg_idx;             /* idx of the clone to marginalise afterwards, -1: none               */
 } ingvio_frame_step;
 
-/* k, sigma, sigma_cb and sigma_rw are held once per context: ingvio_frame_run propagates every filter of the batch with the last
- * stage's values.  A stage of the whole batch (b0 = 0, nb = batch) may change them; a stage of part of the batch must repeat the
- * values of the frame already staged for the other filters, or it is refused with INGVIO_E_ARG and changes nothing.  The same
- * holds for ingvio_frame_stage_tracks. */
+/* k, sigma, sigma_cb and sigma_rw are held per filter: ingvio_frame_run propagates filter b with the k of its own step and the noise
+ * of the stage that staged it.  steps[i].k may differ between the filters of one call (each in 1..64; one out of range: INGVIO_E_ARG,
+ * nothing changed).  sigma, sigma_cb and sigma_rw become the settings of the filters [b0, b0+nb) the call stages; the other filters
+ * keep those of the frame last staged for them.  The first stage after ingvio_ctx_create or after a failed stage gives every filter
+ * its settings.  ingvio_frame_set_imu_noise sets them per filter.  The same holds for ingvio_frame_stage_tracks. */
 int ingvio_frame_stage(ingvio_ctx* ctx, int b0, int nb, const ingvio_frame_step* steps,
                        const ingvio_msckf_frame* frames, const ingvio_msckf_opts* opts,
                        const double sigma[4], int enable_gnss, double sigma_cb, double sigma_rw);
@@ -434,6 +435,11 @@ int ingvio_frame_stage(ingvio_ctx* ctx, int b0, int nb, const ingvio_frame_step*
 int ingvio_frame_stage_async(ingvio_ctx* ctx, int b0, int nb, const ingvio_frame_step* steps,
                              const ingvio_msckf_frame* frames, const ingvio_msckf_opts* opts,
                              const double sigma[4], int enable_gnss, double sigma_cb, double sigma_rw);
+/* noise [nb][6] = {noise_g, noise_a, noise_bg, noise_ba, sigma_cb, sigma_rw} of filters [b0, b0+nb) for the frame currently
+ * staged (sync or async); INGVIO_E_ARG if nothing is staged, the range or pointer is bad, a value is not finite, or a split
+ * step (ingvio_frame_run_phase 1 -> 2) is pending.  A frame already running is not affected.  After ingvio_frame_stage_async the
+ * values travel on the copy stream into the pending input set: run(i); stage_async(i+1); set_imu_noise(i+1); fetch(i). */
+int ingvio_frame_set_imu_noise(ingvio_ctx* ctx, int b0, int nb, const double* noise);
 /* ---- device-resident track store: the frame hand-over as a DELTA (round 6) -------------------------------------------------
  * The reference's MapServer gains ONE observation per live feature per camera frame (MapServerManager::collectStereoMeas,
  * MapServerManager.cpp:146-217) and forgets the observations of the clones that leave the window (KeyframeUpdate::
@@ -461,7 +467,7 @@ typedef struct {
     const unsigned long long* feat_sel;           /* [n_feat] or NULL: every stored observation of the track takes part          */
 } ingvio_track_frame;
 typedef struct {
-    int k;                        /* IMU steps, 1 <= k <= 64 (the same for every filter of a call; partial stages: as ingvio_frame_stage) */
+    int k;                        /* IMU steps, 1 <= k <= 64, per filter (as ingvio_frame_stage)                                  */
     const double* imu;            /* [k][7] gyro (3), accel (3), dt of each step, as ImuPropagator::propagateUntil forms them     */
     double R[9], p[3], v[3], bg[3], ba[3], gravity[3];      /* State::_extended_pose (row-major R), biases, gravity at the frame's start */
     int gnss_idx[5];

@@ -25,7 +25,7 @@ EXPORTS = [
     "ingvio_cov_set", "ingvio_cov_get", "ingvio_get_n", "ingvio_cov_get_marginal", "ingvio_cov_snapshot",
     "ingvio_cov_restore", "ingvio_propagate", "ingvio_propagate_fused", "ingvio_augment_clone", "ingvio_marginalize",
     "ingvio_append_independent", "ingvio_ekf_update", "ingvio_chi2_gamma", "ingvio_msckf_update", "ingvio_msckf_update_tri", "ingvio_qr_compress",
-    "ingvio_frame_stage", "ingvio_frame_stage_async", "ingvio_frame_fetch_begin", "ingvio_frame_fetch_end", "ingvio_tracks_create", "ingvio_frame_stage_tracks", "ingvio_frame_run", "ingvio_set_frame_parts", "ingvio_frame_fetch", "ingvio_profile_enable", "ingvio_profile_select",
+    "ingvio_frame_stage", "ingvio_frame_stage_async", "ingvio_frame_set_imu_noise", "ingvio_frame_fetch_begin", "ingvio_frame_fetch_end", "ingvio_tracks_create", "ingvio_frame_stage_tracks", "ingvio_frame_run", "ingvio_set_frame_parts", "ingvio_frame_fetch", "ingvio_profile_enable", "ingvio_profile_select",
     "ingvio_profile_reset",
     "ingvio_profile_get", "ingvio_set_msckf_method", "ingvio_set_qr_method", "ingvio_landmark_stage", "ingvio_landmark_run",
     "ingvio_landmark_fetch", "ingvio_frame_run_phase", "ingvio_info_set", "ingvio_debug_read", "ingvio_triangulate",
@@ -694,6 +694,12 @@ class Context:
         def call(_keep=(keeps, chi2, sa, fa, o, sg)):
             self._chk(fn(self.h, b0, nb, sa, fa, C.byref(o), _d(sg), int(enable_gnss), C.c_double(sigma_cb), C.c_double(sigma_rw)))
         return call
+
+    def frame_set_imu_noise(self, b0, noise):
+        """ingvio_frame_set_imu_noise: noise [nb][6] = (noise_g, noise_a, noise_bg, noise_ba, sigma_cb, sigma_rw) of filters
+        [b0, b0 + nb) for the frame currently staged (after frame_stage_prepare(use_async=True): the pending one)"""
+        nz = f64(np.asarray(noise, dtype=np.float64).reshape(-1, 6))
+        self._chk(self.L.ingvio_frame_set_imu_noise(self.h, int(b0), nz.shape[0], _d(nz)))
 
     def frame_run(self, restore_prior=False):
         self._chk(self.L.ingvio_frame_run(self.h, 1 if restore_prior else 0))

@@ -20,6 +20,7 @@
 #include <unistd.h>
 #include <string>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -70,7 +71,8 @@ struct ingvio_ctx {
     bool phase_restore = false;      // the pending split step was started with restore_prior
     unsigned long long mut_seq = 0, strip_seq = 0;
     // propagation / structure staging
-    double *d_Phi, *d_G, *d_dt, *d_R, *d_blk;
+    double *d_Phi, *d_G, *d_dt, *d_R, *d_blk;      // d_Phi / d_G / d_dt of the frame path: filter b's steps at b * KMAX (fixed slots)
+    double* d_prm = nullptr;                        // [B][8] per-filter IMU parameters of the staged frame: sigma[4], sigma_cb, sigma_rw, k, 0
     int *d_gnss, *d_idx;
     int* d_zero_idx = nullptr;      // [B] zeros: "marginalise nothing at 0" = an out-of-place write-back without compaction (frame with landmarks)
     // frame staging
@@ -142,8 +144,8 @@ struct ingvio_ctx {
     char* d_multi = nullptr;            // ingvio_chi2_gamma_multi: packed blocks (grown on demand)
     size_t multi_cap = 0;
     // staged frame state
-    int st_k, st_stereo, st_enable_gnss, st_fmax_used;
-    double st_sigma[4], st_scb, st_srw;
+    int st_stereo, st_enable_gnss, st_fmax_used;
+    std::vector<double> st_prm;    // [B][8] host copy of d_prm (the input set the d_* pointers name)
     MsckfOpts st_op;
     std::vector<int> st_gnss;      // [B][5] clock-state indices of the staged steps (a stage with the same ones keeps the strip restore valid)
     std::vector<int> st_marg;      // per filter marg idx
@@ -155,7 +157,7 @@ struct ingvio_ctx {
     // PCIe while frame i computes; the sets swap roles at every asynchronous stage
     struct InputSet {
         double *Phi = nullptr, *G = nullptr, *dt = nullptr, *R = nullptr, *clone_R = nullptr, *clone_p = nullptr, *pf = nullptr, *uv = nullptr,
-               *chi2 = nullptr, *noise = nullptr;
+               *chi2 = nullptr, *noise = nullptr, *prm = nullptr;
         int *gnss = nullptr, *idx = nullptr, *clone_idx = nullptr, *nclones = nullptr, *nfeat = nullptr, *anchor = nullptr, *dof = nullptr;
         unsigned long long* mask = nullptr;
     } alt;
@@ -371,6 +373,21 @@ struct Uploader {
         }
         if (hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream ? stream : c->st) != hipSuccess) rc = INGVIO_E_HIP;
     }
+    // rows of `width` elements at src + r * spitch into dst + r * dpitch: ONE copy (or upload kernel) for a batch of strided rows
+    template <class T>
+    void copy_rows(T* dst, size_t dpitch, const T* src, size_t spitch, size_t width, size_t rows)
+    {
+        if (rows == 1 || (width == spitch && width == dpitch)) { copy(dst, src, rows == 1 ? width : width * rows); return; }
+        const size_t bytes = sizeof(T) * width * rows;
+        if (!width || !rows) return;
+        if (!stream && bytes <= UPLOAD_KERNEL_MAX && ((sizeof(T) * (width | spitch | dpitch)) & 3) == 0 && (((uintptr_t)dst | (uintptr_t)src) & 3) == 0) {
+            launch_upload_rows(dst, sizeof(T) * dpitch, src, sizeof(T) * spitch, sizeof(T) * width, rows, c->st);
+            if (hipGetLastError() != hipSuccess) rc = INGVIO_E_HIP;
+            return;
+        }
+        if (hipMemcpy2DAsync(dst, sizeof(T) * dpitch, src, sizeof(T) * spitch, sizeof(T) * width, rows, hipMemcpyHostToDevice, stream ? stream : c->st) != hipSuccess)
+            rc = INGVIO_E_HIP;
+    }
     int end()
     {
         if (rc) { c->err = "upload from the pinned staging slab failed (hipMemcpyAsync / k_upload_words launch)"; return rc; }
@@ -548,7 +565,7 @@ int prepare_async_set(ingvio_ctx* c)
                 a.clone_R = q.clone_R; a.clone_p = q.clone_p; a.pf = q.pf; a.uv = q.uv; a.mask = q.mask;
             }
         }
-        rc |= dalloc(c, &a.chi2, CHI2_CAP); rc |= dalloc(c, &a.noise, B);
+        rc |= dalloc(c, &a.chi2, CHI2_CAP); rc |= dalloc(c, &a.noise, B); rc |= dalloc(c, &a.prm, (size_t)B * 8);
         if (rc) return INGVIO_E_HIP;
         HIPCHK(c, hipStreamSynchronize(c->st));                        // the zero fills of dalloc
         HIPCHK(c, hipStreamCreateWithFlags(&c->st_copy, hipStreamNonBlocking));
@@ -566,7 +583,7 @@ void swap_input_sets(ingvio_ctx* c)
     std::swap(c->d_gnss, a.gnss); std::swap(c->d_idx, a.idx); std::swap(c->d_clone_idx, a.clone_idx);
     std::swap(c->d_nclones, a.nclones); std::swap(c->d_nfeat, a.nfeat); std::swap(c->d_anchor, a.anchor); std::swap(c->d_dof, a.dof);
     std::swap(c->d_clone_R, a.clone_R); std::swap(c->d_clone_p, a.clone_p); std::swap(c->d_pf, a.pf); std::swap(c->d_uv, a.uv);
-    std::swap(c->d_chi2, a.chi2); std::swap(c->d_mask, a.mask); std::swap(c->d_noise, a.noise);
+    std::swap(c->d_chi2, a.chi2); std::swap(c->d_mask, a.mask); std::swap(c->d_noise, a.noise); std::swap(c->d_prm, a.prm);
     c->upc.chi2_ok = false; c->upc.noise_ok = false;
     c->set_id ^= 1;
 }
@@ -919,6 +936,7 @@ int ingvio_ctx_create(const ingvio_ctx_desc* desc, ingvio_ctx** out)
 #endif
     memset(c->prof_ms, 0, sizeof c->prof_ms); memset(c->prof_calls, 0, sizeof c->prof_calls);
     c->h_n.assign(B, 0); c->h_cur.assign(B, 0); c->h_n_snap.assign(B, 0); c->st_marg.assign(B, -1); c->st_cidx_hi.assign(B, -1); c->st_gnss.assign((size_t)B * 5, -2);
+    c->st_prm.assign((size_t)B * 8, 0.0);
     c->h_nclones.assign(B, desc->c_max);
     // Consecutive filters' covariances must not sit a power of two apart: with ldp = 256 the stride would be 512 KB, and the SAME
     // element of every filter (the window block P_cc every gate wave of a filter reads, 64 filters per XCD) would fall into the same
@@ -940,6 +958,7 @@ int ingvio_ctx_create(const ingvio_ctx_desc* desc, ingvio_ctx** out)
     rc |= dalloc(c, &c->d_Phi, (size_t)B * KMAX * 225); rc |= dalloc(c, &c->d_G, (size_t)B * KMAX * 180);
     rc |= dalloc(c, &c->d_dt, (size_t)B * KMAX); rc |= dalloc(c, &c->d_R, (size_t)B * 9);
     rc |= dalloc(c, &c->d_blk, (size_t)B * 36); rc |= dalloc(c, &c->d_gnss, (size_t)B * 5); rc |= dalloc(c, &c->d_idx, B);
+    rc |= dalloc(c, &c->d_prm, (size_t)B * 8);
     rc |= dalloc(c, &c->d_zero_idx, B);
     if (!rc && hipMemset(c->d_zero_idx, 0, sizeof(int) * (size_t)B) != hipSuccess) rc = 1;
     {
@@ -998,7 +1017,7 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
                      c->gn.feph, c->gn.fobs, c->gn.frcv, c->gn.front,
                      c->dw.Hd, c->dw.X, c->dw.Y, c->dw.Tb, c->dw.noise, c->dw.noiseB, c->dw.m, c->dw.cidx, c->lm.pose, c->lm.pf, c->lm.uv, c->lm.gamma, c->lm.idx, c->lm.n_lm,
                      c->lm.lm_idx, c->lm.anchor_idx, c->lm.tracked, c->lm.accept, c->lm.dx, c->d_xchg, c->dw.U, c->dw.rowmap, c->d_zero_idx,
-                     c->d_Asum, c->d_used_sum, c->d_Tflat, c->d_imu, c->d_tri_mask };
+                     c->d_Asum, c->d_used_sum, c->d_Tflat, c->d_imu, c->d_tri_mask, c->d_prm };
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& sl : c->pin) { if (sl.p) hipHostFree(sl.p); if (sl.ev) hipEventDestroy(sl.ev); }
     if (c->h_result) hipHostFree(c->h_result);
@@ -1007,7 +1026,7 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
     for (int* p : { c->gn.mf, c->gn.ncf }) if (p) hipFree(p);
     {
         auto& a = c->alt;
-        void* ap[] = { a.Phi, a.G, a.dt, a.R, a.gnss, a.idx, a.chi2, a.noise };      // its frame arrays: d_frame_slab (freed above)
+        void* ap[] = { a.Phi, a.G, a.dt, a.R, a.gnss, a.idx, a.chi2, a.noise, a.prm };      // its frame arrays: d_frame_slab (freed above)
         for (void* p : ap) if (p) hipFree(p);
         if (c->st_copy) hipStreamDestroy(c->st_copy);
         if (c->ev_copy) hipEventDestroy(c->ev_copy);
@@ -1147,8 +1166,8 @@ int ingvio_propagate_fused(ingvio_ctx* c, int b0, int nb, int k, const double* P
         up.copy(c->d_imu, img, tot);
         if (up.end()) return INGVIO_E_HIP;
         ProfScope p(c, PF_PROPAGATE);
-        launch_propagate(view(c), b0, nb, c->d.n_max, (const double*)c->d_imu, (const double*)(c->d_imu + oG), (const double*)(c->d_imu + odt), k,
-                         with_gnss ? (const int*)(c->d_imu + ogn) : nullptr, sigma, enable_gnss, scb, srw, c->st);
+        launch_propagate(view(c), b0, nb, c->d.n_max, (const double*)c->d_imu, (const double*)(c->d_imu + oG), (const double*)(c->d_imu + odt), k, k,
+                         nullptr, with_gnss ? (const int*)(c->d_imu + ogn) : nullptr, sigma, enable_gnss, scb, srw, c->st);
         return last_launch(c);
     }
     const UpItem items[4] = { { c->d_Phi, Phi, 8 * (size_t)nb * k * 225 }, { c->d_G, G, 8 * (size_t)nb * k * 180 }, { c->d_dt, dt, 8 * (size_t)nb * k },
@@ -1156,7 +1175,7 @@ int ingvio_propagate_fused(ingvio_ctx* c, int b0, int nb, int k, const double* P
     if (stage_small(c, items, 4)) return INGVIO_E_HIP;
     {
         ProfScope p(c, PF_PROPAGATE);
-        launch_propagate(view(c), b0, nb, c->d.n_max, c->d_Phi, c->d_G, c->d_dt, k, with_gnss ? c->d_gnss : nullptr,
+        launch_propagate(view(c), b0, nb, c->d.n_max, c->d_Phi, c->d_G, c->d_dt, k, k, nullptr, with_gnss ? c->d_gnss : nullptr,
                          sigma, enable_gnss, scb, srw, c->st);
     }
     return last_launch(c);                      // no stream synchronisation: the inputs were staged through the pinned ring (stage_small)
@@ -2389,17 +2408,35 @@ int ingvio_qr_compress(ingvio_ctx* c, const double* H, int ldh, int m, int n, co
     }
 }
 
-// ingvio_frame_run propagates the whole batch with ONE k, sigma, sigma_cb, sigma_rw (the last stage's): d_Phi / d_G / d_dt of filter b
-// sit at b * k * 225 ... for that k.  A stage of part of the batch must therefore keep the settings of the frame already staged for
-// the other filters; only a stage of the whole batch may change them.
-static bool partial_stage_mismatch(ingvio_ctx* c, int nb, int k, const double sigma[4], double scb, double srw)
+// Per-filter IMU parameters of the staged frame.  Filter b propagates k_b steps from its own slot of d_Phi / d_G / d_dt (b * KMAX steps
+// in: partial stages never touch another filter's steps) with its own sigma / sigma_cb / sigma_rw, held in d_prm [b][8] and mirrored on
+// the host (st_prm).  A stage sets them for the filters it stages; the first stage after creation or after a failed stage sets them for
+// every filter (k and noise of its first step for the filters it does not stage).  Packs the blocks to upload into `blk` and returns
+// their first filter; *count = their number.
+static int stage_imu_params(ingvio_ctx* c, int b0, int nb, const int* ks, const double sigma[4], double scb, double srw, double* blk, int* count)
 {
-    if (!c->staged || nb == c->d.batch) return false;
-    if (k != c->st_k || memcmp(sigma, c->st_sigma, 32) || memcmp(&scb, &c->st_scb, 8) || memcmp(&srw, &c->st_srw, 8)) {
-        c->err = "a stage of part of the batch with k / sigma / sigma_cb / sigma_rw other than the staged frame's";
-        return true;
+    const bool all = !c->staged;
+    const int lo = all ? 0 : b0, hi = all ? c->d.batch : b0 + nb;
+    for (int b = lo; b < hi; ++b) {
+        double* h = &c->st_prm[(size_t)b * 8];
+        h[0] = sigma[0]; h[1] = sigma[1]; h[2] = sigma[2]; h[3] = sigma[3]; h[4] = scb; h[5] = srw;
+        h[6] = (double)(b >= b0 && b < b0 + nb ? ks[b - b0] : ks[0]); h[7] = 0.0;
+        memcpy(blk + (size_t)(b - lo) * 8, h, 64);
     }
-    return false;
+    *count = hi - lo;
+    return lo;
+}
+
+// launch_propagate's IMU arguments for filters [b0, b0 + nb): k and the noise as scalar kernel arguments when every filter of the launch
+// shares them (the headline case: k is then no memory round trip in front of the kernel), else prm = the filters' blocks (k_propagate<.., true>)
+struct ImuLaunch { int k; double sigma[4], scb, srw; const double* prm; };
+static ImuLaunch imu_launch(const ingvio_ctx* c, int b0, int nb)
+{
+    const double* h = &c->st_prm[(size_t)b0 * 8];
+    ImuLaunch L{ (int)h[6], { h[0], h[1], h[2], h[3] }, h[4], h[5], nullptr };
+    for (int i = 1; i < nb; ++i)
+        if (memcmp(h, h + (size_t)i * 8, 7 * sizeof(double))) { L.prm = c->d_prm + (size_t)b0 * 8; break; }
+    return L;
 }
 
 static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step* steps, const ingvio_msckf_frame* frames,
@@ -2409,12 +2446,12 @@ static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_st
     // ---- validation: nothing of the context is modified until every input has been accepted ---------------------------
     if (check_range(c, b0, nb) || !steps || !frames || !opts || !sigma) return INGVIO_E_ARG;
     if (async && (b0 != 0 || nb != c->d.batch)) return INGVIO_E_ARG;      // a whole input set is replaced
-    const int k = steps[0].k;
-    if (k < 1 || k > KMAX) return INGVIO_E_ARG;
-    if (partial_stage_mismatch(c, nb, k, sigma, scb, srw)) return INGVIO_E_ARG;
     if (!opts->chi2_table || opts->chi2_len < 2 || opts->chi2_len > CHI2_CAP) return INGVIO_E_ARG;
-    for (int i = 0; i < nb; ++i)
-        if (steps[i].k != k || !steps[i].Phi || !steps[i].G || !steps[i].dt) return INGVIO_E_ARG;
+    int k = 0;                                                              // the call's largest step count: the slab's stride
+    for (int i = 0; i < nb; ++i) {
+        if (steps[i].k < 1 || steps[i].k > KMAX || !steps[i].Phi || !steps[i].G || !steps[i].dt) return INGVIO_E_ARG;
+        if (steps[i].k > k) k = steps[i].k;
+    }
     int fmx = 0;
     // clone indices are checked against the buffer only (grow < 0): the live size at run time depends on whether the run
     // restores the snapshot; ingvio_frame_run checks them against the live state before its first launch
@@ -2428,7 +2465,7 @@ static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_st
         if (rc) return rc;
     }
     rc = upl.begin(pad64(8 * n * k * 225) + pad64(8 * n * k * 180) + pad64(8 * n * k) + pad64(8 * n * 9) + pad64(4 * n * 5) + pad64(4 * n) +
-                   pad64(8 * CHI2_CAP) + pad64(8 * n) + frames_bytes(c, nb) + 1024);
+                   pad64(8 * CHI2_CAP) + pad64(8 * n) + pad64(64 * (size_t)c->d.batch) + frames_bytes(c, nb) + 1024);
     if (rc) return rc;
     // ---- from here on only HIP runtime errors can occur; they invalidate the staged frame -----------------------------
     // new clock-state indices: the next restore is a full one (the strips the last step wrote are named by the OLD indices); a stage
@@ -2462,24 +2499,33 @@ static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_st
         for (int q = 0; q < frames[i].n_clones; ++q) if (frames[i].clone_idx[q] > hi) hi = frames[i].clone_idx[q];
         c->st_cidx_hi[b0 + i] = hi;
     }
-    // everything goes through ONE pinned slab: packed by a few host threads, copied asynchronously, no stream sync
+    // everything goes through ONE pinned slab: packed by a few host threads, copied asynchronously, no stream sync.  Filter i's steps
+    // sit k (the call's largest count) apart in the slab and KMAX apart on the device: one strided copy each for Phi, G and dt
     double* Phi = upl.take<double>(n * k * 225); double* G = upl.take<double>(n * k * 180); double* dt = upl.take<double>(n * k);
     double* R = upl.take<double>(n * 9); int* gi = upl.take<int>(n * 5); int* mi = upl.take<int>(n);
-    double* chi2 = upl.take<double>(CHI2_CAP); double* nz = upl.take<double>(n);
+    double* chi2 = upl.take<double>(CHI2_CAP); double* nz = upl.take<double>(n); double* prm = upl.take<double>(8 * (size_t)c->d.batch);
     const double var = opts->noise * opts->noise;
     parallel_for(nb, [=](int i) {
-        memcpy(Phi + (size_t)i * k * 225, steps[i].Phi, 8 * (size_t)k * 225);
-        memcpy(G + (size_t)i * k * 180, steps[i].G, 8 * (size_t)k * 180);
-        memcpy(dt + (size_t)i * k, steps[i].dt, 8 * (size_t)k);
+        const size_t ki = steps[i].k;
+        memcpy(Phi + (size_t)i * k * 225, steps[i].Phi, 8 * ki * 225);
+        memcpy(G + (size_t)i * k * 180, steps[i].G, 8 * ki * 180);
+        memcpy(dt + (size_t)i * k, steps[i].dt, 8 * ki);
         memcpy(R + (size_t)i * 9, steps[i].R_i2w, 72);
         for (int g = 0; g < 5; ++g) gi[(size_t)i * 5 + g] = steps[i].gnss_idx[g];
         mi[i] = steps[i].marg_idx;
         nz[i] = var;
     });
     memcpy(chi2, opts->chi2_table, 8 * (size_t)opts->chi2_len);
-    upl.copy(c->d_Phi + (size_t)b0 * k * 225, Phi, n * k * 225);
-    upl.copy(c->d_G + (size_t)b0 * k * 180, G, n * k * 180);
-    upl.copy(c->d_dt + (size_t)b0 * k, dt, n * k);
+    upl.copy_rows(c->d_Phi + (size_t)b0 * KMAX * 225, (size_t)KMAX * 225, Phi, (size_t)k * 225, (size_t)k * 225, n);
+    upl.copy_rows(c->d_G + (size_t)b0 * KMAX * 180, (size_t)KMAX * 180, G, (size_t)k * 180, (size_t)k * 180, n);
+    upl.copy_rows(c->d_dt + (size_t)b0 * KMAX, (size_t)KMAX, dt, (size_t)k, (size_t)k, n);
+    {
+        std::vector<int> ks((size_t)nb);
+        for (int i = 0; i < nb; ++i) ks[i] = steps[i].k;
+        int np = 0;
+        const int p0 = stage_imu_params(c, b0, nb, ks.data(), sigma, scb, srw, prm, &np);
+        upl.copy(c->d_prm + (size_t)p0 * 8, prm, (size_t)np * 8);
+    }
     upl.copy(c->d_R + (size_t)b0 * 9, R, n * 9);
     upl.copy(c->d_gnss + (size_t)b0 * 5, gi, n * 5);
     upl.copy(c->d_idx + b0, mi, n);
@@ -2498,8 +2544,7 @@ static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_st
         if (hipEventRecord(c->ev_copy, c->st_copy) != hipSuccess) return fail(INGVIO_E_HIP);
         c->copy_pending = true;
     }
-    c->st_k = k; c->st_stereo = opts->stereo; c->st_enable_gnss = enable_gnss; c->st_scb = scb; c->st_srw = srw;
-    memcpy(c->st_sigma, sigma, 32);
+    c->st_stereo = opts->stereo; c->st_enable_gnss = enable_gnss;
     if (!c->staged || fmx > c->st_fmax_used) c->st_fmax_used = fmx;
     c->staged = true;
     return INGVIO_OK;
@@ -2540,9 +2585,7 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
     if (check_range(c, b0, nb) || !steps || !frames || !opts || !sigma) return INGVIO_E_ARG;
     if (!c->trk.t_max) { c->err = "ingvio_frame_stage_tracks without ingvio_tracks_create"; return INGVIO_E_ARG; }
     if (async && (b0 != 0 || nb != c->d.batch)) return INGVIO_E_ARG;
-    const int k = steps[0].k, T = c->trk.t_max, cm = c->d.c_max, fm = c->d.f_max;
-    if (k < 1 || k > KMAX) return INGVIO_E_ARG;
-    if (partial_stage_mismatch(c, nb, k, sigma, scb, srw)) return INGVIO_E_ARG;
+    const int T = c->trk.t_max, cm = c->d.c_max, fm = c->d.f_max;
     if (!opts->chi2_table || opts->chi2_len < 2 || opts->chi2_len > CHI2_CAP) return INGVIO_E_ARG;
     // ---- layout (counts only), then validation + packing per filter on a few host threads; nothing of the context is touched before
     //      every filter's delta has been found consistent (the pinned slab is scratch) ----
@@ -2552,7 +2595,7 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
     for (int i = 0; i < nb; ++i) {
         const ingvio_track_frame& f = frames[i];
         const ingvio_frame_step_raw& s = steps[i];
-        if (s.k != k || !s.imu) return INGVIO_E_ARG;
+        if (s.k < 1 || s.k > KMAX || !s.imu) return INGVIO_E_ARG;
         if (f.n_drop < 0 || f.n_drop > cm || f.n_free < 0 || f.n_free > T || f.n_obs < 0 || f.n_obs > T || f.n_pf < 0 || f.n_pf > T) return INGVIO_E_CAPACITY;
         if (f.n_clones < 0 || f.n_clones > cm || f.n_feat < 0 || f.n_feat > fm) return INGVIO_E_CAPACITY;
         if ((f.n_drop && !f.drop_slots) || (f.n_free && !f.free_tracks) || (f.n_obs && (!f.obs_track || !f.obs_uv)) || (f.n_pf && (!f.pf_track || !f.pf)) ||
@@ -2561,7 +2604,7 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
         if (f.n_feat > fmx) fmx = f.n_feat;
         int* h = &hdr[(size_t)i * TRK_HDR];
         h[TRK_N_DROP] = f.n_drop; h[TRK_APPEND] = f.append_slot; h[TRK_N_OBS] = f.n_obs; h[TRK_N_FREE] = f.n_free; h[TRK_N_PF] = f.n_pf;
-        h[TRK_N_CLONES] = f.n_clones; h[TRK_N_FEAT] = f.n_feat; h[TRK_K] = k; h[TRK_HAS_SEL] = f.feat_sel ? 1 : 0; h[TRK_MARG] = s.marg_idx;
+        h[TRK_N_CLONES] = f.n_clones; h[TRK_N_FEAT] = f.n_feat; h[TRK_K] = s.k; h[TRK_HAS_SEL] = f.feat_sel ? 1 : 0; h[TRK_MARG] = s.marg_idx;
         h[TRK_OFF_I] = (int)ni; h[TRK_OFF_D] = (int)nd; h[TRK_OFF_M] = (int)nm;
         int oi = 0, od = 0;
         h[TRK_I_DROP] = oi; oi += f.n_drop;
@@ -2575,7 +2618,7 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
         h[TRK_D_PF] = od; od += 3 * f.n_pf;
         h[TRK_D_CR] = od; od += 9 * f.n_clones;
         h[TRK_D_CP] = od; od += 3 * f.n_clones;
-        h[TRK_D_IMU] = od; od += 7 * k;
+        h[TRK_D_IMU] = od; od += 7 * s.k;
         h[TRK_D_STATE] = od; od += 24;
         ni += (size_t)oi; nd += ((size_t)od + 3) & ~(size_t)3;
         if (f.feat_sel) nm += (size_t)f.n_feat;
@@ -2585,7 +2628,7 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
     Uploader upl{ c };
     int rc = 0;
     if (async) { rc = prepare_async_set(c); if (rc) return rc; }
-    rc = upl.begin(total + pad64(8 * CHI2_CAP) + pad64(8 * (size_t)nb) + 1024);
+    rc = upl.begin(total + pad64(8 * CHI2_CAP) + pad64(8 * (size_t)nb) + pad64(64 * (size_t)c->d.batch) + 1024);
     if (rc) return rc;
     char* slab = upl.take<char>(total);
     int* hp = reinterpret_cast<int*>(slab);
@@ -2625,7 +2668,7 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
         }
         for (int g = 0; g < 5; ++g) ip[h[TRK_I_GNSS] + g] = s.gnss_idx[g];
         if (f.feat_sel) memcpy(mpool + h[TRK_OFF_M], f.feat_sel, 8 * (size_t)f.n_feat);
-        memcpy(dp + h[TRK_D_IMU], s.imu, 56 * (size_t)k);
+        memcpy(dp + h[TRK_D_IMU], s.imu, 56 * (size_t)s.k);
         double* st0 = dp + h[TRK_D_STATE];
         memcpy(st0, s.R, 72); memcpy(st0 + 9, s.p, 24); memcpy(st0 + 12, s.v, 24); memcpy(st0 + 15, s.bg, 24); memcpy(st0 + 18, s.ba, 24); memcpy(st0 + 21, s.gravity, 24);
     });
@@ -2653,19 +2696,26 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
         swap_input_sets(c);
         upl.stream = c->st_copy; S = c->st_copy; dstage = c->trk.stage[1];
     } else if (wait_inputs(c)) return fail(INGVIO_E_HIP);
-    double* chi2 = upl.take<double>(CHI2_CAP); double* nz = upl.take<double>(nb);
+    double* chi2 = upl.take<double>(CHI2_CAP); double* nz = upl.take<double>(nb); double* prm = upl.take<double>(8 * (size_t)c->d.batch);
     const double var = opts->noise * opts->noise;
     memcpy(chi2, opts->chi2_table, 8 * (size_t)opts->chi2_len);
     for (int i = 0; i < nb; ++i) nz[i] = var;
     upl.copy(dstage, slab, total);
     upl.copy(c->d_chi2, chi2, (size_t)opts->chi2_len);
     upl.copy(c->d_noise + b0, nz, (size_t)nb);
+    {
+        std::vector<int> ks((size_t)nb);
+        for (int i = 0; i < nb; ++i) ks[i] = steps[i].k;
+        int np = 0;
+        const int p0 = stage_imu_params(c, b0, nb, ks.data(), sigma, scb, srw, prm, &np);
+        upl.copy(c->d_prm + (size_t)p0 * 8, prm, (size_t)np * 8);
+    }
     c->upc.chi2_ok = false; c->upc.noise_ok = false;
     TrackStage ts{ reinterpret_cast<const int*>(dstage), reinterpret_cast<const int*>(dstage + off_i),
                    reinterpret_cast<const double*>(dstage + off_d), reinterpret_cast<const unsigned long long*>(dstage + off_m) };
     TrackStore store{ c->trk.uv, c->trk.mask, c->trk.pf, T, cm };
     FrameOut fo{ c->d_clone_idx, c->d_clone_R, c->d_clone_p, c->d_nclones, c->d_nfeat, c->d_pf, c->d_anchor, c->d_mask, c->d_uv, c->d_dof, cm, fm };
-    launch_imu_steps(ts, b0, nb, k, c->d_Phi, c->d_G, c->d_dt, c->d_R, S);
+    launch_imu_steps(ts, b0, nb, KMAX, c->d_Phi, c->d_G, c->d_dt, c->d_R, S);
     if (hipGetLastError() != hipSuccess) return fail(INGVIO_E_HIP);       // before the store kernels change the track store
     launch_tracks_apply(ts, store, b0, nb, S);
     launch_tracks_gather(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S);
@@ -2688,8 +2738,7 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
     memcpy(op.t_lr, opts->t_cl2cr, 24);
     op.var = var; op.max_accept = opts->max_accept; op.selected_variant = opts->selected_variant;
     op.chi2 = c->d_chi2; op.chi2_len = opts->chi2_len;
-    c->st_k = k; c->st_stereo = opts->stereo; c->st_enable_gnss = enable_gnss; c->st_scb = scb; c->st_srw = srw;
-    memcpy(c->st_sigma, sigma, 32);
+    c->st_stereo = opts->stereo; c->st_enable_gnss = enable_gnss;
     if (!c->staged || fmx > c->st_fmax_used) c->st_fmax_used = fmx;
     c->staged = true;
     return INGVIO_OK;
@@ -2707,6 +2756,33 @@ int ingvio_frame_stage_async(ingvio_ctx* c, int b0, int nb, const ingvio_frame_s
 {
     ENTER(c);
     return frame_stage_impl(c, b0, nb, steps, frames, opts, sigma, enable_gnss, scb, srw, true);
+}
+
+int ingvio_frame_set_imu_noise(ingvio_ctx* c, int b0, int nb, const double* noise)
+{
+    ENTER(c);
+    if (!c || phase_busy(c)) return INGVIO_E_ARG;
+    if (!c->staged) { c->err = "ingvio_frame_set_imu_noise without a staged frame"; return INGVIO_E_ARG; }
+    if (check_range(c, b0, nb) || !noise) return INGVIO_E_ARG;
+    for (size_t i = 0; i < (size_t)nb * 6; ++i)
+        if (!std::isfinite(noise[i])) { c->err = "ingvio_frame_set_imu_noise: a value is not finite"; return INGVIO_E_ARG; }
+    // after ingvio_frame_stage_async the values belong to the input set still on its way: on the copy stream, behind that stage's
+    // copies (the frame running on the compute stream reads the other set); otherwise on the compute stream, behind the frames
+    // already enqueued there
+    Uploader upl{ c };
+    if (c->copy_pending) upl.stream = c->st_copy;
+    if (int rc = upl.begin(pad64(64 * (size_t)nb) + 64)) return rc;
+    double* blk = upl.take<double>(8 * (size_t)nb);
+    for (int i = 0; i < nb; ++i) {
+        double* h = &c->st_prm[(size_t)(b0 + i) * 8];
+        memcpy(blk + (size_t)i * 8, noise + (size_t)i * 6, 48);
+        blk[(size_t)i * 8 + 6] = h[6]; blk[(size_t)i * 8 + 7] = 0.0;
+    }
+    upl.copy(c->d_prm + (size_t)b0 * 8, blk, 8 * (size_t)nb);
+    if (int rc = upl.end()) return rc;
+    if (c->copy_pending) HIPCHK(c, hipEventRecord(c->ev_copy, c->st_copy));
+    memcpy(&c->st_prm[(size_t)b0 * 8], blk, 64 * (size_t)nb);
+    return INGVIO_OK;
 }
 
 // The fused frame step of windows up to 16 clones with the batch dealt to P slices.  Slice p = filters [p B / P, (p + 1) B / P) rounded
@@ -2727,7 +2803,6 @@ static int frame_run_split(ingvio_ctx* c, int restore_prior, int P, bool gnss_fu
     const bool strips = restore_prior && c->strip_ok && c->mut_seq == c->strip_seq;
     if (restore_prior) { c->h_n = c->h_n_snap; std::fill(c->h_cur.begin(), c->h_cur.end(), 0); }
     for (int b = 0; b < B; ++b) c->h_n[b] += 6;
-    const int k = c->st_k;
     int rc = 0;
     auto range = [&](int p, int& b0, int& nb) {
         b0 = (int)((long long)B * p / P) & ~7;
@@ -2750,8 +2825,9 @@ static int frame_run_split(ingvio_ctx* c, int restore_prior, int P, bool gnss_fu
         }
         {
             ProfScope pr(c, PF_PROPAGATE);
-            launch_propagate(view(c), b0, nb, c->d.n_max, c->d_Phi + (size_t)b0 * k * 225, c->d_G + (size_t)b0 * k * 180, c->d_dt + (size_t)b0 * k, k,
-                             c->st_enable_gnss ? c->d_gnss + (size_t)b0 * 5 : nullptr, c->st_sigma, c->st_enable_gnss, c->st_scb, c->st_srw, q.st,
+            const ImuLaunch im = imu_launch(c, b0, nb);
+            launch_propagate(view(c), b0, nb, c->d.n_max, c->d_Phi + (size_t)b0 * KMAX * 225, c->d_G + (size_t)b0 * KMAX * 180, c->d_dt + (size_t)b0 * KMAX,
+                             im.k, KMAX, im.prm, c->st_enable_gnss ? c->d_gnss + (size_t)b0 * 5 : nullptr, im.sigma, c->st_enable_gnss, im.scb, im.srw, q.st,
                              c->d_R + (size_t)b0 * 9, c->d_status, from_snap ? c->Psnap : nullptr, c->d_n_snap);
         }
         c->tok_wait = c->tok_last; c->tok_rec = q.ev_gate;
@@ -2867,8 +2943,9 @@ static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
     {
         // one launch: status reset + K1 (k composed IMU steps) + K2 (clone) when a workgroup owns a whole filter
         ProfScope p(c, PF_PROPAGATE);
-        launch_propagate(view(c), 0, B, c->d.n_max, c->d_Phi, c->d_G, c->d_dt, c->st_k, c->st_enable_gnss ? c->d_gnss : nullptr,
-                         c->st_sigma, c->st_enable_gnss, c->st_scb, c->st_srw, c->st, c->d_R, c->d_status,
+        const ImuLaunch im = imu_launch(c, 0, B);
+        launch_propagate(view(c), 0, B, c->d.n_max, c->d_Phi, c->d_G, c->d_dt, im.k, KMAX, im.prm, c->st_enable_gnss ? c->d_gnss : nullptr,
+                         im.sigma, c->st_enable_gnss, im.scb, im.srw, c->st, c->d_R, c->d_status,
                          from_snap ? c->Psnap : nullptr, c->d_n_snap);
     }
     for (int b = 0; b < B; ++b) c->h_n[b] += 6;

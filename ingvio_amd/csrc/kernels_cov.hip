@@ -56,14 +56,20 @@ __device__ __forceinline__ void augment_filter(CovView cv, int b, const double* 
     if (tid == 0) cv.n[b] = n + 6;
 }
 
-template <bool SPLIT>      // SPLIT: the composition's steps on two waves (few filters: the launch site picks it for up to 64)
+// PERF: the launch mixes filters with different step counts or IMU / clock noise - filter bl's k and noise come from its parameter
+// block prm[bl] = { sigma[4], sigma_cb, sigma_rw, k, - } instead of the kernel arguments.  A template flag, not a run-time one (see SPLIT
+// below): k heads the kernel's critical chain (the first chunk's addresses), and the batch whose filters share it keeps it a scalar
+// argument - one dependent round trip less in front of every workgroup.  Filter bl's steps start at Phi + bl * kst * 225 (G, dt alike).
+template <bool SPLIT, bool PERF>      // SPLIT: the composition's steps on two waves (few filters: the launch site picks it for up to 64)
 __global__ __launch_bounds__(PROP_THREADS) void k_propagate(
     CovView cv, int b0, const double* __restrict__ Phi, const double* __restrict__ G,
-    const double* __restrict__ dts, int k, const int* __restrict__ gnss_idx,
-    double sg0, double sg1, double sg2, double sg3, int enable_gnss, double scb, double srw,
+    const double* __restrict__ dts, int k_arg, int kst, const double* __restrict__ prm, const int* __restrict__ gnss_idx,
+    double sg0_arg, double sg1_arg, double sg2_arg, double sg3_arg, int enable_gnss, double scb_arg, double srw_arg,
     const double* __restrict__ augR, int* __restrict__ status_clear, const double* __restrict__ snap, const int* __restrict__ n_snap)
 {
     const int bl = blockIdx.y, b = b0 + bl, tid = threadIdx.x;
+    const double* const prmB = PERF ? prm + (size_t)bl * 8 : nullptr;
+    const int k = PERF ? (int)prmB[6] : k_arg;
     if (status_clear && blockIdx.x == 0 && tid == 0) status_clear[b] = 0;
     // snap != nullptr (single-tile launches with the fused clone only): the step starts from the SNAPSHOT of the prior
     // (ingvio_frame_run(restore_prior) right after a fused frame step: half 0 still equals the snapshot outside the propagation's rows
@@ -94,9 +100,9 @@ __global__ __launch_bounds__(PROP_THREADS) void k_propagate(
         for (int j = 0; j < 6; ++j) qpre[j] = Ps[tid + (size_t)(15 + j) * ld];
     }
     dbg_stamp(16);
-    const double* PhiB = Phi + (size_t)bl * k * 225;
-    const double* GB = G + (size_t)bl * k * 180;
-    const double* dtB = dts + (size_t)bl * k;
+    const double* PhiB = Phi + (size_t)bl * kst * 225;
+    const double* GB = G + (size_t)bl * kst * 180;
+    const double* dtB = dts + (size_t)bl * kst;
     for (int s = tid; s < k; s += PROP_THREADS) sDt[s] = dtB[s];
     // Loads that depend on nothing go out first and in this order: the clock-state indices (tiny, the strip's columns depend on
     // them), the LAST chunk of (Phi, G) (the composition starts with it), then the strip rows P[r, A] of this wave as MFMA
@@ -104,6 +110,9 @@ __global__ __launch_bounds__(PROP_THREADS) void k_propagate(
     int giq[5];
 #pragma unroll
     for (int g = 0; g < 5; ++g) giq[g] = (enable_gnss && gnss_idx) ? gnss_idx[bl * 5 + g] : -1;
+    // the noise rides with the clock-state indices: first used after the last chunk's loads have returned (chunk_store)
+    const double sg0 = PERF ? prmB[0] : sg0_arg, sg1 = PERF ? prmB[1] : sg1_arg, sg2 = PERF ? prmB[2] : sg2_arg, sg3 = PERF ? prmB[3] : sg3_arg;
+    const double scb = PERF ? prmB[4] : scb_arg, srw = PERF ? prmB[5] : srw_arg;
     constexpr int PER = (PROP_KCH * 405 + PROP_THREADS - 1) / PROP_THREADS;
     const int nchunk = (k + PROP_KCH - 1) / PROP_KCH;
     double vch[PER];
@@ -568,6 +577,17 @@ __global__ __launch_bounds__(256) void k_upload_words(unsigned* __restrict__ dst
     }
 }
 
+// k_upload_words for `rows` rows of nwords words each, at src + r * spitch and dst + r * dpitch (words): a batch of IMU steps from
+// the pinned slab into the fixed per-filter slots of the input buffers.  grid = (blocks, rows).
+__global__ __launch_bounds__(256) void k_upload_rows(unsigned* __restrict__ dst, size_t dpitch, const unsigned* __restrict__ src, size_t spitch,
+                                                     size_t nwords)
+{
+    const size_t r = blockIdx.y;
+    const unsigned* s = src + r * spitch;
+    unsigned* d = dst + r * dpitch;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += (size_t)gridDim.x * blockDim.x) d[i] = s[i];
+}
+
 // snapshot / restore of every filter's live covariance (benchmark hygiene: each timed step starts
 // from the same prior).  grid = (col tiles, B).
 __global__ __launch_bounds__(256) void k_snapshot(CovView cv, double* __restrict__ snap, int* __restrict__ n_snap)
@@ -628,18 +648,19 @@ __global__ void k_post_restore(CovView cv, int b0, int nb, const int* __restrict
 
 // ---------------------------------------------------------------------------------------------
 #include "launch_ekf.h"
-void launch_propagate(CovView cv, int b0, int nb, int n_cap, const double* Phi, const double* G, const double* dt, int k,
-                      const int* gnss_idx, const double sigma[4], int enable_gnss, double scb, double srw, hipStream_t st,
+void launch_propagate(CovView cv, int b0, int nb, int n_cap, const double* Phi, const double* G, const double* dt, int k, int kst,
+                      const double* prm, const int* gnss_idx, const double sigma[4], int enable_gnss, double scb, double srw, hipStream_t st,
                       const double* augR, int* status_clear, const double* snap, const int* n_snap)
 {
     const int tiles = (n_cap + PROP_THREADS - 1) / PROP_THREADS;
     const bool fuse = augR && tiles == 1;
-if (nb <= 64) {     hipLaunchKernelGGL(k_propagate<true>, dim3(tiles, nb), dim3(PROP_THREADS), 0, st, cv, b0, Phi, G, dt, k, gnss_idx,
-                       sigma[0], sigma[1], sigma[2], sigma[3], enable_gnss, scb, srw, fuse ? augR : nullptr, status_clear,
-                       fuse ? snap : nullptr, n_snap); }
-    else {     hipLaunchKernelGGL(k_propagate<false>, dim3(tiles, nb), dim3(PROP_THREADS), 0, st, cv, b0, Phi, G, dt, k, gnss_idx,
-                       sigma[0], sigma[1], sigma[2], sigma[3], enable_gnss, scb, srw, fuse ? augR : nullptr, status_clear,
-                       fuse ? snap : nullptr, n_snap); }
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(tiles, nb), dim3(PROP_THREADS), 0, st, cv, b0, Phi, G, dt, k, kst, prm, gnss_idx,
+                           sigma[0], sigma[1], sigma[2], sigma[3], enable_gnss, scb, srw, fuse ? augR : nullptr, status_clear,
+                           fuse ? snap : nullptr, n_snap);
+    };
+    if (nb <= 64) { if (prm) go(k_propagate<true, true>); else go(k_propagate<true, false>); }
+    else { if (prm) go(k_propagate<false, true>); else go(k_propagate<false, false>); }
     if (augR && !fuse) hipLaunchKernelGGL(k_augment, dim3(nb), dim3(256), 0, st, cv, b0, augR);
 }
 bool propagate_can_restore(int n_cap) { return (n_cap + PROP_THREADS - 1) / PROP_THREADS == 1; }
@@ -675,6 +696,14 @@ void launch_upload_words(void* dst, const void* src_pinned, size_t bytes, hipStr
     if (blocks > 256) blocks = 256;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(k_upload_words, dim3(blocks), dim3(256), 0, st, (unsigned*)dst, (const unsigned*)src_pinned, nwords, vec4);
+}
+void launch_upload_rows(void* dst, size_t dpitch, const void* src_pinned, size_t spitch, size_t width, size_t rows, hipStream_t st)
+{
+    const size_t nwords = width >> 2;
+    int bx = (int)((nwords + 255) / 256);
+    if (bx > 64) bx = 64;
+    hipLaunchKernelGGL(k_upload_rows, dim3(bx, (unsigned)rows), dim3(256), 0, st, (unsigned*)dst, dpitch >> 2, (const unsigned*)src_pinned,
+                       spitch >> 2, nwords);
 }
 void launch_copy_ints(int* dst, const int* src, int count, hipStream_t st)
 {

@@ -139,8 +139,9 @@ __device__ __forceinline__ void put(double* M, int r0, int c0, const M3& B)     
 // (The first version ran one THREAD per filter over all k samples: 165-200 us per 512 filters on the copy stream, under the update's
 // apply kernel.)
 // imu [k][7] = gyro (3), accel (3), dt; st0 [24] = R (9, row-major), p, v, bg, ba, gravity.  Writes Phi [k][225], G [k][180], dt [k]
-// of the filter's input slot and the IMU rotation at clone time R_out [9] (StateManager::augmentSlidingWindowPose reads it).
-__global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, int b0, int nb, int kcap /* = k of every filter */, double* __restrict__ PhiAll, double* __restrict__ GAll,
+// of the filter's input slot (kst steps per filter, k its own count from the header) and the IMU rotation at clone time R_out [9]
+// (StateManager::augmentSlidingWindowPose reads it).
+__global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, int b0, int nb, int kst, double* __restrict__ PhiAll, double* __restrict__ GAll,
                                                   double* __restrict__ dtAll, double* __restrict__ Rall)
 {
     __shared__ double sm[IMU_STEPS_CH * 405];                          // [IMU_STEPS_CH][405]: Phi | G of samples c0 .. c0 + 15
@@ -179,8 +180,8 @@ __global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, int b0, int nb,
         const V3 vn = vk + dt * g + dt * (RG1 * a);
         const V3 pn = pk + dt * vk + (0.5 * dt * dt) * g + (dt * dt) * (RG2 * a);
         const M3 P1 = Rk * psi1_func(w, a, dt, sc), P2 = Rk * psi2_func(w, a, dt, sc);
-        double* Phi0 = PhiAll + (size_t)(b0 + bl) * kcap * 225;
-        double* G0 = GAll + (size_t)(b0 + bl) * kcap * 180;
+        double* Phi0 = PhiAll + (size_t)(b0 + bl) * kst * 225;
+        double* G0 = GAll + (size_t)(b0 + bl) * kst * 180;
         for (int c0 = 0; c0 < k; c0 += IMU_STEPS_CH) {
             const int cnt = min(IMU_STEPS_CH, k - c0);
             if (lane < k && lane >= c0 && lane < c0 + cnt) {
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, int b0, int nb,
             __syncthreads();                                            // the next chunk reuses the buffer
         }
     }
-    if (lane < k) dtAll[(size_t)(b0 + bl) * kcap + lane] = imu[7 * lane + 6];
+    if (lane < k) dtAll[(size_t)(b0 + bl) * kst + lane] = imu[7 * lane + 6];
     if (lane == 0) {                                                  // every lane's recursion ended behind the last sample
         double* Ro = Rall + (size_t)(b0 + bl) * 9;
         for (int i = 0; i < 9; ++i) Ro[i] = R.m[i];
@@ -322,9 +323,9 @@ __global__ __launch_bounds__(256) void k_tracks_gather(TrackStage ts, TrackStore
     }
 }
 
-void launch_imu_steps(const TrackStage& ts, int b0, int nb, int kcap, double* Phi, double* G, double* dt, double* R, hipStream_t st)
+void launch_imu_steps(const TrackStage& ts, int b0, int nb, int kst, double* Phi, double* G, double* dt, double* R, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_imu_steps, dim3(nb), dim3(64), 0, st, ts, b0, nb, kcap, Phi, G, dt, R);
+    hipLaunchKernelGGL(k_imu_steps, dim3(nb), dim3(64), 0, st, ts, b0, nb, kst, Phi, G, dt, R);
 }
 void launch_tracks_apply(const TrackStage& ts, const TrackStore& store, int b0, int nb, hipStream_t st)
 {

@@ -48,8 +48,10 @@ void launch_gamma(CovView cv, int b, const double* H, const double* res, const i
                   const double* noise, int r_kind, int mld, double* gamma_out, hipStream_t st);
 
 // kernels_cov.hip
-void launch_propagate(CovView cv, int b0, int nb, int n_cap, const double* Phi, const double* G, const double* dt, int k,
-                      const int* gnss_idx, const double sigma[4], int enable_gnss, double scb, double srw, hipStream_t st,
+// filter bl of the launch: steps at Phi + bl * kst * 225 (G, dt alike); prm == nullptr: every filter propagates k steps with sigma /
+// scb / srw, else with its own block prm[bl * 8 ..] = { sigma[4], scb, srw, k, - } (the k / sigma / scb / srw arguments are unused)
+void launch_propagate(CovView cv, int b0, int nb, int n_cap, const double* Phi, const double* G, const double* dt, int k, int kst,
+                      const double* prm, const int* gnss_idx, const double sigma[4], int enable_gnss, double scb, double srw, hipStream_t st,
                       const double* augR = nullptr, int* status_clear = nullptr,      // optional fused K2 / status reset
                       const double* snap = nullptr, const int* n_snap = nullptr);      // optional: start from the snapshot (when propagate_can_restore and augR)
 bool propagate_can_restore(int n_cap);
@@ -60,6 +62,7 @@ void launch_post_marg(CovView cv, int b0, int nb, const int* idx, int size, hipS
 void launch_append(CovView cv, int b0, int nb, int size, const double* blk, hipStream_t st);
 void launch_copy_ints(int* dst, const int* src, int count, hipStream_t st);
 void launch_upload_words(void* dst, const void* src_pinned, size_t bytes, hipStream_t st);      // bytes % 4 == 0; src: hipHostMalloc memory
+void launch_upload_rows(void* dst, size_t dpitch, const void* src_pinned, size_t spitch, size_t width, size_t rows, hipStream_t st);      // bytes, all % 4 == 0
 void launch_snapshot(CovView cv, int n_cap, double* snap, int* n_snap, hipStream_t st);
 void launch_restore_strips(CovView cv, int b0, int nb, int n_cap, const double* snap, const int* n_snap, const int* gnss_idx, hipStream_t st);      // filters [b0, b0 + nb)
 void launch_restore(CovView cv, int b0, int nb, int n_cap, const double* snap, const int* n_snap, hipStream_t st);

@@ -31,6 +31,6 @@ struct FrameOut {                       // FrameView with writable pointers (the
     double* uv; int* dof; int cmax, fmax;
 };
 
-void launch_imu_steps(const TrackStage& ts, int b0, int nb, int k, double* Phi, double* G, double* dt, double* R, hipStream_t st);
+void launch_imu_steps(const TrackStage& ts, int b0, int nb, int kst, double* Phi, double* G, double* dt, double* R, hipStream_t st);
 void launch_tracks_apply(const TrackStage& ts, const TrackStore& store, int b0, int nb, hipStream_t st);
 void launch_tracks_gather(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st);
