@@ -13,7 +13,8 @@
  *     as an FP64 column-major n_b x n_b matrix inside an ldp x ldp buffer (ldp = n_max rounded up
  *     to 16), i.e. exactly Eigen::MatrixXd's layout (State.h:133) so `Eigen::Map` + `cov_set/get`
  *     is a plain strided copy.  The host keeps the typed nominal values and the Type::idx()/size()
- *     table (VecState.h:32-54); only integers and small parameter blocks cross the boundary.
+ *     table (VecState.h:32-54); only integers and small parameter blocks cross the boundary - unless
+ *     the context holds them itself (ingvio_nominal_create, opt-in).
  *   - All pointer arguments are HOST pointers unless the name ends in `_dev`.  Inputs are read
  *     during the call only; outputs are written before the call returns (calls that return
  *     results synchronise the context's stream; pure state mutations are asynchronous).
@@ -477,6 +478,59 @@ int ingvio_tracks_create(ingvio_ctx* ctx, int t_max);             /* allocates (
 int ingvio_frame_stage_tracks(ingvio_ctx* ctx, int b0, int nb, const ingvio_frame_step_raw* steps, const ingvio_track_frame* frames,
                               const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double sigma_cb, double sigma_rw,
                               int async /* != 0: whole batch, on the copy stream into the second input set, as ingvio_frame_stage_async */);
+/* ---- device-resident nominal state (opt-in) ------------------------------------------------------------------
+ * The typed values behind the Type::idx() table - StateManager's _err_var list with its nominal values (State.h:95-127) - held per
+ * filter on the device, so that a closed-loop filter hands over only raw IMU samples and the track delta per frame: the device applies
+ * boxPlus with the frame's dx, drops the marginalised clone, shifts the indices behind it, integrates the IMU nominal state and forms
+ * the new clone's pose.  A context that never calls ingvio_nominal_create behaves exactly as without it.
+ * Variable kinds (values: R row-major, p, v; a Vec3 in p, a Scalar in p[0], a landmark's world position valuePosXyz in p): */
+#define INGVIO_NOM_NONE (-1)      /* free slot (a marginalised clone leaves one; the next clone takes the lowest free slot)       */
+#define INGVIO_NOM_SE23 0         /* PoseState SE23, 9 columns: the extended pose (PoseState.cpp:174-186)                         */
+#define INGVIO_NOM_SE3 1          /* PoseState SE3, 6 columns: clones, extrinsics (PoseState.cpp:79-88)                            */
+#define INGVIO_NOM_VEC3 2         /* VecState Vec3, 3 columns: biases (VecState.cpp:25-29)                                         */
+#define INGVIO_NOM_SCALAR 3       /* Scalar, 1 column: clock biases, FS, YOF (VecState.cpp:40-44)                                  */
+#define INGVIO_NOM_LANDMARK 4     /* AnchoredLandmark, 3 columns; anchor = slot of its anchor clone (AnchoredLandmark.cpp:227-243) */
+#define INGVIO_NOM_VAL 15         /* doubles per variable value                                                                    */
+typedef struct {
+    int n_var;                    /* slots in use (<= v_max); get: written                                                         */
+    int* kind; int* idx; int* anchor;     /* [n_var] kind, Type::idx(), anchor slot (landmarks) or -1                              */
+    double* val;                  /* [n_var][INGVIO_NOM_VAL] R (9), p (3), v (3)                                                   */
+    int n_clones; int* clone_var; /* slots of the window's clones (State::_sw_camleft_poses), ascending time; get: [c_max]        */
+    int v_ext, v_pose, v_bg, v_ba;        /* slots of _camleft_imu_extrinsics (SE3), _extended_pose (SE23), _bg, _ba (Vec3)        */
+    double gravity[3];
+} ingvio_nominal;
+/* allocates (or clears: every slot free) a table of up to v_max variables per filter */
+int ingvio_nominal_create(ingvio_ctx* ctx, int v_max);
+int ingvio_nominal_set(ingvio_ctx* ctx, int b0, int nb, const ingvio_nominal* nom);
+/* synchronises (the host's keyframe / marginalisation policy reads the clone poses here); the caller's arrays hold v_max / c_max entries */
+int ingvio_nominal_get(ingvio_ctx* ctx, int b0, int nb, ingvio_nominal* out);
+/* StateManager::boxPlus (StateManager.cpp:244-251) on the device with dx [nb][ldp] in the live index space (the dx of ingvio_gnss_fetch,
+ * ingvio_landmark_fetch, ingvio_ekf_update_batch).  Every variable reads dx only: the order of the variables does not matter. */
+int ingvio_nominal_box_plus(ingvio_ctx* ctx, int b0, int nb, const double* dx);
+/* ingvio_frame_stage_tracks with the nominal values taken from the device table: per filter only k, the IMU samples, gnss_idx and marg_idx
+ * (the idx of a window clone, -1: none).  frames[].n_clones / clone_idx / clone_R / clone_p are ignored: the window is the table's
+ * plus the new clone (appended at idx = the live N, at the end of the window, with pose T_i2w * T_cl2i of the propagated state,
+ * StateManager.cpp:263-272).  The following ingvio_frame_run ends, on the device and in this order, with boxPlus of the frame's dx
+ * (the index space of the update: new clone included, before the marginalisation), the drop of the marginalised clone and the shift of
+ * every later idx by 6 (StateManager.cpp:155-192).  async: as ingvio_frame_stage_tracks; the copy stream waits for the table of the
+ * frame enqueued last, so run(i); stage(i+1, async); fetch_begin(i); run(i+1); fetch_end(i) is a closed loop.
+ * Refused before anything changes: no table (INGVIO_E_ARG), a range other than the whole batch (b0 != 0 or nb != batch: the post-frame
+ * step covers every filter, INGVIO_E_ARG), a frame staged from the table that has not run yet (INGVIO_E_ARG), an
+ * in-frame GNSS or landmark stage or frame_parts > 1 (INGVIO_E_UNSUPPORTED), marg_idx not a window clone (INGVIO_E_NOT_IN_STATE), a
+ * landmark anchored to the clone that leaves (INGVIO_E_ARG), no free slot or a full window (INGVIO_E_CAPACITY).  While such a frame is
+ * staged and has not run, ingvio_frame_stage(_async), ingvio_frame_stage_tracks, ingvio_nominal_set / _box_plus, ingvio_cov_snapshot
+ * and ingvio_frame_run(restore_prior != 0) return INGVIO_E_ARG and ingvio_frame_run_phase INGVIO_E_UNSUPPORTED.  ingvio_cov_snapshot /
+ * ingvio_cov_restore copy the table with the covariance (restore abandons such a staged frame); a restore whose snapshot was taken
+ * before ingvio_nominal_create holds no table and is refused (INGVIO_E_ARG). */
+typedef struct {
+    int k;                        /* IMU steps, 1 <= k <= 64                                                                       */
+    const double* imu;            /* [k][7] gyro (3), accel (3), dt                                                                 */
+    int gnss_idx[5];
+    int marg_idx;
+} ingvio_frame_step_nominal;
+int ingvio_frame_stage_tracks_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,
+                                      const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double sigma_cb, double sigma_rw,
+                                      int async);
 int ingvio_frame_run(ingvio_ctx* ctx, int restore_prior);
 /* Throughput batches (round 6, an experiment kept selectable): ingvio_frame_run deals the batch to `parts` slices of filters, each
  * on its own HIP stream; the slices' throughput-bound segments (gate + Gram, apply) are chained by events so that only ONE runs at a

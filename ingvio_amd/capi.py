@@ -32,7 +32,12 @@ EXPORTS = [
     "ingvio_gnss_front_stage", "ingvio_gnss_front_fetch", "ingvio_gnss_update_batch", "ingvio_gnss_stage", "ingvio_gnss_run", "ingvio_gnss_fetch", "ingvio_mld", "ingvio_debug_msckf_info", "ingvio_debug_info_solution",
     "ingvio_info_reduce", "ingvio_info_commit", "ingvio_gnss_sat_eval",
     "ingvio_chi2_gamma_multi", "ingvio_ekf_update_batch", "ingvio_add_variable_delayed_invertible", "ingvio_add_variable_delayed", "ingvio_replace_var_linear",
+    "ingvio_nominal_create", "ingvio_nominal_set", "ingvio_nominal_get", "ingvio_nominal_box_plus", "ingvio_frame_stage_tracks_nominal",
 ]
+
+# device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
+NOM_NONE, NOM_SE23, NOM_SE3, NOM_VEC3, NOM_SCALAR, NOM_LANDMARK = -1, 0, 1, 2, 3, 4
+NOM_VAL = 15
 
 
 class GateBlock(C.Structure):
@@ -104,6 +109,27 @@ class TrackFrame(C.Structure):
 class FrameStepRaw(C.Structure):
     _fields_ = [("k", C.c_int), ("imu", c_dp), ("R", C.c_double * 9), ("p", C.c_double * 3), ("v", C.c_double * 3), ("bg", C.c_double * 3),
                 ("ba", C.c_double * 3), ("gravity", C.c_double * 3), ("gnss_idx", C.c_int * 5), ("marg_idx", C.c_int)]
+
+
+class Nominal(C.Structure):
+    _fields_ = [("n_var", C.c_int), ("kind", c_ip), ("idx", c_ip), ("anchor", c_ip), ("val", c_dp), ("n_clones", C.c_int), ("clone_var", c_ip),
+                ("v_ext", C.c_int), ("v_pose", C.c_int), ("v_bg", C.c_int), ("v_ba", C.c_int), ("gravity", C.c_double * 3)]
+
+
+class FrameStepNominal(C.Structure):
+    _fields_ = [("k", C.c_int), ("imu", c_dp), ("gnss_idx", C.c_int * 5), ("marg_idx", C.c_int)]
+
+
+def make_nominal(t):
+    """t: dict(kind [n], idx [n], anchor [n], val [n][15], clone_var [c], v_ext, v_pose, v_bg, v_ba, gravity [3])"""
+    keep = dict(kind=i32(t["kind"]), idx=i32(t["idx"]), anchor=i32(t["anchor"]), val=f64(np.asarray(t["val"], dtype=np.float64).reshape(-1, NOM_VAL)),
+                clone_var=i32(t["clone_var"]))
+    q = Nominal()
+    q.n_var = len(keep["kind"]); q.kind = _i(keep["kind"]); q.idx = _i(keep["idx"]); q.anchor = _i(keep["anchor"]); q.val = _d(keep["val"])
+    q.n_clones = len(keep["clone_var"]); q.clone_var = _i(keep["clone_var"])
+    q.v_ext, q.v_pose, q.v_bg, q.v_ba = int(t["v_ext"]), int(t["v_pose"]), int(t["v_bg"]), int(t["v_ba"])
+    q.gravity = (C.c_double * 3)(*np.asarray(t["gravity"], dtype=np.float64).reshape(3))
+    return q, keep
 
 
 _lib = None
@@ -229,6 +255,7 @@ class Context:
             raise IngvioError(rc, msg)
         self.batch, self.n_max, self.c_max, self.f_max, self.device = batch, n_max, c_max, f_max, device
         self.ldp = self.L.ingvio_ldp(self.h)
+        self.v_max = 0
 
     def close(self):
         if self.h:
@@ -674,6 +701,72 @@ class Context:
             _keep = (keeps, chi2, sg)
             self._chk(self.L.ingvio_frame_stage_tracks(self.h, b0, nb, sa, fa, C.byref(o), _d(sg), int(enable_gnss), C.c_double(sigma_cb),
                                                        C.c_double(sigma_rw), 1 if use_async else 0))
+        return call
+
+    # ---- device-resident nominal state -------------------------------------------------------------------------
+    def nominal_create(self, v_max):
+        """allocates / clears the per-filter nominal table of up to v_max variables (ingvio_nominal_create)"""
+        self._chk(self.L.ingvio_nominal_create(self.h, int(v_max)))
+        self.v_max = int(v_max)
+
+    def nominal_set(self, b0, tables):
+        """tables: one dict per filter of [b0, b0 + len(tables)) as make_nominal takes it"""
+        nb = len(tables)
+        arr = (Nominal * nb)()
+        keeps = []
+        for i, t in enumerate(tables):
+            q, k = make_nominal(t); arr[i] = q; keeps.append(k)
+        self._chk(self.L.ingvio_nominal_set(self.h, int(b0), nb, arr))
+
+    def nominal_get(self, b0=0, nb=None):
+        """synchronises; a list of dicts (kind, idx, anchor, val [n_var][15], clone_var, v_ext, v_pose, v_bg, v_ba, gravity)"""
+        nb = self.batch if nb is None else nb
+        vm = self.v_max
+        bufs = [dict(kind=np.zeros(vm, dtype=np.int32), idx=np.zeros(vm, dtype=np.int32), anchor=np.zeros(vm, dtype=np.int32),
+                     val=np.zeros((vm, NOM_VAL)), clone_var=np.zeros(max(self.c_max, 1), dtype=np.int32)) for _ in range(nb)]
+        arr = (Nominal * nb)()
+        for i, bf in enumerate(bufs):
+            arr[i].kind = _i(bf["kind"]); arr[i].idx = _i(bf["idx"]); arr[i].anchor = _i(bf["anchor"]); arr[i].val = _d(bf["val"])
+            arr[i].clone_var = _i(bf["clone_var"])
+        self._chk(self.L.ingvio_nominal_get(self.h, int(b0), nb, arr))
+        out = []
+        for i, bf in enumerate(bufs):
+            q = arr[i]
+            n, c = q.n_var, q.n_clones
+            out.append(dict(kind=bf["kind"][:n].copy(), idx=bf["idx"][:n].copy(), anchor=bf["anchor"][:n].copy(), val=bf["val"][:n].copy(),
+                            clone_var=bf["clone_var"][:c].copy(), v_ext=q.v_ext, v_pose=q.v_pose, v_bg=q.v_bg, v_ba=q.v_ba,
+                            gravity=np.array(q.gravity[:])))
+        return out
+
+    def nominal_box_plus(self, b0, dx):
+        """StateManager::boxPlus on the device: dx [nb][ldp] in the live index space (ingvio_nominal_box_plus)"""
+        d = f64(np.asarray(dx, dtype=np.float64).reshape(-1, self.ldp))
+        self._chk(self.L.ingvio_nominal_box_plus(self.h, int(b0), d.shape[0], _d(d)))
+
+    def frame_stage_tracks_nominal_prepare(self, b0, steps, track_frames, opts_frame, sigma, enable_gnss=0, sigma_cb=0.0, sigma_rw=0.0, max_accept=0,
+                                           compress_rule=1, selected_variant=0, use_async=False):
+        """as frame_stage_tracks_prepare, the nominal values from the device table (ingvio_frame_stage_tracks_nominal): steps are dicts
+        imu [k][7], gnss_idx (optional), marg_idx; track_frames need no clone arrays"""
+        nb = len(steps)
+        sa = (FrameStepNominal * nb)(); fa = (TrackFrame * nb)()
+        keeps = []
+        for i in range(nb):
+            imu = f64(steps[i]["imu"])
+            s = FrameStepNominal()
+            s.k = imu.shape[0]; s.imu = _d(imu)
+            s.gnss_idx = (C.c_int * 5)(*[int(x) for x in steps[i].get("gnss_idx", (-1,) * 5)])
+            s.marg_idx = int(steps[i].get("marg_idx", -1))
+            d = dict(track_frames[i])
+            d.setdefault("clone_idx", []); d.setdefault("clone_R", np.zeros((0, 9))); d.setdefault("clone_p", np.zeros((0, 3)))
+            f, k2 = make_track_frame(d)
+            sa[i] = s; fa[i] = f; keeps.append((imu, k2))
+        o, chi2 = make_opts(opts_frame, max_accept, compress_rule, selected_variant)
+        sg = f64(sigma)
+
+        def call():
+            _keep = (keeps, chi2, sg)
+            return self._chk(self.L.ingvio_frame_stage_tracks_nominal(self.h, b0, nb, sa, fa, C.byref(o), _d(sg), int(enable_gnss),
+                                                                      C.c_double(sigma_cb), C.c_double(sigma_rw), 1 if use_async else 0))
         return call
 
     def frame_stage_prepare(self, b0, steps, frames, sigma, enable_gnss=0, sigma_cb=0.0, sigma_rw=0.0, max_accept=0,

@@ -1,0 +1,221 @@
+"""Closed-loop batches of the device-resident nominal state (ingvio_nominal_*) - harness code shared by
+tests/test_gpu_nominal_state.py and tools/closed_loop_bench.py: inputs of a loop of frames (raw IMU samples, track deltas, the
+marginalised clone), the host reference that keeps the nominal values with the C oracle's functions and the Var semantics of
+oracle/stream_filter.py, and the two ways to drive a context (host loop, device loop)."""
+import numpy as np
+
+
+SE23, SE3, VEC3, SCALAR, LM, NONE = 0, 1, 2, 3, 4, -1
+SIZE = {SE23: 9, SE3: 6, VEC3: 3, SCALAR: 1, LM: 3}
+
+
+class HostTable:
+    """The table as the host keeps it: slots of {kind, idx, anchor slot, R, p, v}; free slots None (the next clone takes the lowest)."""
+
+    def __init__(self, slots, clones, v_ext, v_pose, v_bg, v_ba, gravity):
+        self.slots, self.clones = slots, clones
+        self.v_ext, self.v_pose, self.v_bg, self.v_ba, self.gravity = v_ext, v_pose, v_bg, v_ba, np.asarray(gravity, dtype=float)
+
+    def as_dict(self):
+        n = len(self.slots)
+        val = np.zeros((n, 15))
+        for i, s in enumerate(self.slots):
+            if s is not None:
+                val[i, 0:9] = s["R"].reshape(9); val[i, 9:12] = s["p"]; val[i, 12:15] = s["v"]
+        return dict(kind=[NONE if s is None else s["kind"] for s in self.slots], idx=[-1 if s is None else s["idx"] for s in self.slots],
+                    anchor=[-1 if s is None else s["anchor"] for s in self.slots], val=val, clone_var=list(self.clones), v_ext=self.v_ext,
+                    v_pose=self.v_pose, v_bg=self.v_bg, v_ba=self.v_ba, gravity=self.gravity)
+
+    def box_plus(self, dx):                                              # StateManager.cpp:245-251 with the Var.update of each kind
+        from oracle import oracle as orc
+        for s in self.slots:
+            if s is None:
+                continue
+            i = s["idx"]
+            if s["kind"] == SE23:
+                s["R"], s["p"], s["v"] = orc.se23_update(s["R"], s["p"], s["v"], dx[i:i + 9])
+            elif s["kind"] == SE3:
+                s["R"], s["p"] = orc.se3_update(s["R"], s["p"], dx[i:i + 6])
+            elif s["kind"] == SCALAR:
+                s["p"] = s["p"] + np.array([dx[i], 0.0, 0.0])
+            elif s["kind"] == VEC3:
+                s["p"] = s["p"] + dx[i:i + 3]
+            else:
+                a = self.slots[s["anchor"]]["idx"]
+                dth = dx[a:a + 3]
+                s["p"] = orc.gamma(dth, 0) @ s["p"] + orc.gamma(dth, 1) @ dx[i:i + 3]
+
+    def marginalize(self, idx):                                          # StateManager.cpp:155-192
+        drop = next(c for c in self.clones if self.slots[c]["idx"] == idx)
+        self.clones = [c for c in self.clones if c != drop]
+        self.slots[drop] = None
+        for s in self.slots:
+            if s is not None and s["idx"] > idx:
+                s["idx"] -= 6
+
+    def append_clone(self, idx):
+        e, x = self.slots[self.v_pose], self.slots[self.v_ext]
+        slot = next((i for i, s in enumerate(self.slots) if s is None), len(self.slots))
+        new = dict(kind=SE3, idx=idx, anchor=-1, R=e["R"] @ x["R"], p=e["R"] @ x["p"] + e["p"], v=np.zeros(3))
+        if slot == len(self.slots):
+            self.slots.append(new)
+        else:
+            self.slots[slot] = new
+        self.clones.append(slot)
+        return slot
+
+
+
+
+KS = (1, 9, 10, 33)
+
+
+def make_loop(B, n_frames, F=24, seed=5, ks=KS, windows=None):
+    """B filters of ragged windows; per frame and filter the raw IMU samples, the track delta and the marginalised clone (always the
+    window's second clone: the first one anchors the landmarks).  Only integers of the state enter the inputs, so they are prepared
+    in advance; the host reference keeps the values."""
+    from oracle import oracle as orc
+    from ingvio_amd import synth
+    cases = []
+    for b in range(B):
+        C = 5 + b % 7 if windows is None else windows[b % len(windows)]
+        flt, step, frame, info = synth.build_case(lambda P: orc.Cov(P, ld=160), orc.imu_transition, seed=seed + b, F=8, C=C, n_gnss=6, n_landmarks=2)
+        P = flt.cov.P() if callable(flt.cov.P) else flt.cov.P
+        raw = step["raw"]
+        slots = []
+
+        def add(kind, idx, R=None, p=None, v=None, anchor=-1):
+            slots.append(dict(kind=kind, idx=idx, anchor=anchor, R=np.eye(3) if R is None else np.array(R, dtype=float),
+                              p=np.zeros(3) if p is None else np.array(p, dtype=float), v=np.zeros(3) if v is None else np.array(v, dtype=float)))
+            return len(slots) - 1
+        v_pose = add(SE23, 0, raw["R"], raw["p"], raw["v"])
+        v_bg, v_ba = add(VEC3, 9, p=raw["bg"]), add(VEC3, 12, p=raw["ba"])
+        v_ext = add(SE3, 15, synth.R_CL2I, synth.T_CL2I)
+        clone_names = [c["name"] for c in flt.clones]
+        lm_vars = []
+        for nm, idx, size in flt.vars[4:]:
+            if nm.startswith("gnss") or nm == "yof":
+                add(SCALAR, idx, p=[0.1 * idx, 0.0, 0.0])
+            elif nm.startswith("lm"):
+                lm_vars.append((nm, idx))
+        clones = []
+        for c in flt.clones:
+            clones.append(add(SE3, flt.idx_of(c["name"]), c["R"], c["p"]))
+        rng = np.random.default_rng(300 + b)
+        for nm, idx in lm_vars:
+            add(LM, idx, p=synth.true_pose(flt.t)[1] + rng.normal(size=3) * 3.0, anchor=clones[0])
+        table = HostTable(slots, clones, v_ext, v_pose, v_bg, v_ba, raw["gravity"])
+        k = ks[b % len(ks)]
+        t0 = flt.t - len(step["dt"]) * synth.IMU_DT                     # the measured frame of build_case is not used
+        times, t = [], t0
+        for f in range(n_frames):
+            t += k * synth.IMU_DT
+            times.append(t)
+        pf_true, uv, _ = synth.make_features(rng, times, F, outlier_every=0)
+        imus, t = [], t0
+        for f in range(n_frames):
+            imu = np.zeros((k, 7))
+            for q in range(k):
+                gy, ac = synth.true_imu(t + synth.IMU_DT)
+                imu[q, 0:3] = gy + rng.normal(0, synth.PARAMS["noise_g"], 3)
+                imu[q, 3:6] = ac + rng.normal(0, synth.PARAMS["noise_a"], 3)
+                imu[q, 6] = synth.IMU_DT
+                t += synth.IMU_DT
+            imus.append(imu)
+        # integer bookkeeping of the window: clone idx list, slot observation flags, the marginalised idx per frame
+        cidx = [s["idx"] for s in (slots[c] for c in clones)]
+        n = P.shape[0]
+        has_obs = [False] * len(cidx)
+        frames = []
+        for f in range(n_frames):
+            drop = [1] if f > 0 else []
+            if f > 0:
+                del has_obs[1]
+            app = len(has_obs)
+            has_obs.append(True)
+            cidx = cidx + [n]
+            marg = cidx[1]
+            nobs = sum(has_obs)
+            d = dict(drop=drop, append=app, obs_track=list(range(F)), obs_uv=uv[:, f, :],
+                     feat_track=list(range(F)) if nobs >= 3 else [], feat_anchor=[app] * F if nobs >= 3 else [],
+                     feat_dof=[nobs - 1] * F if nobs >= 3 else [])
+            if f == 0:
+                d.update(pf_track=list(range(F)), pf=pf_true)
+            frames.append(dict(delta=d, imu=imus[f], marg=marg, new_idx=n))
+            cidx = [c - 6 if c > marg else c for c in cidx if c != marg]
+        cases.append(dict(P=P, table=table, frames=frames, step=step, frame=frame, C=C))
+    return cases
+
+
+
+def loop_ctx(cases, F, c_max=12):
+    from ingvio_amd import capi
+    n_max = max(c["P"].shape[0] for c in cases) + 6
+    ctx = capi.Context(batch=len(cases), n_max=((n_max + 15) // 16) * 16, c_max=c_max, f_max=F, m_max=64)
+    for b, c in enumerate(cases):
+        ctx.cov_set(b, c["P"])
+    ctx.tracks_create(F)
+    return ctx
+
+
+def stage_args(cases):
+    c0 = cases[0]
+    st = c0["step"]
+    return c0["frame"], st["sigma"], st["enable_gnss"], st["sigma_cb"], st["sigma_rw"]
+
+
+def nominal_stage(ctx, cases, f, use_async=False):
+    opts_frame, sigma, eg, scb, srw = stage_args(cases)
+    steps = [dict(imu=c["frames"][f]["imu"], gnss_idx=c["step"]["gnss_idx"], marg_idx=c["frames"][f]["marg"]) for c in cases]
+    return ctx.frame_stage_tracks_nominal_prepare(0, steps, [c["frames"][f]["delta"] for c in cases], opts_frame, sigma, eg, scb, srw,
+                                                  use_async=use_async)
+
+
+def host_step(ctx, cases, tabs, f):
+    """the reference loop: ingvio_frame_stage_tracks with host nominal values (oracle.imu_transition), then boxPlus / drop / shift"""
+    from oracle import oracle as orc
+    opts_frame, sigma, eg, scb, srw = stage_args(cases)
+    steps, tfs = [], []
+    for c, t in zip(cases, tabs):
+        fr = c["frames"][f]
+        e, bg, ba = t.slots[t.v_pose], t.slots[t.v_bg], t.slots[t.v_ba]
+        raw = dict(imu=fr["imu"], R=e["R"], p=e["p"], v=e["v"], bg=bg["p"], ba=ba["p"], gravity=t.gravity)
+        R, p, v = e["R"], e["p"], e["v"]
+        for q in range(fr["imu"].shape[0]):
+            R, p, v, _, _ = orc.imu_transition(R, p, v, bg["p"], ba["p"], fr["imu"][q, :3], fr["imu"][q, 3:6], t.gravity, fr["imu"][q, 6])
+        e["R"], e["p"], e["v"] = R, p, v
+        t.append_clone(fr["new_idx"])
+        steps.append(dict(raw=raw, gnss_idx=c["step"]["gnss_idx"], marg_idx=fr["marg"]))
+        cl = [t.slots[s] for s in t.clones]
+        tfs.append(dict(fr["delta"], clone_idx=[s["idx"] for s in cl], clone_R=np.stack([s["R"] for s in cl]), clone_p=np.stack([s["p"] for s in cl])))
+    ctx.frame_stage_tracks_prepare(0, steps, tfs, opts_frame, sigma, eg, scb, srw)()
+    ctx.frame_run()
+    dx, acc, rows = ctx.frame_fetch()
+    for b, (c, t) in enumerate(zip(cases, tabs)):
+        t.box_plus(dx[b])
+        t.marginalize(c["frames"][f]["marg"])
+    return dx, acc, rows
+
+
+
+def device_loop(ctx, cases, frames, pipelined):
+    out = []
+    if not pipelined:
+        for f in frames:
+            nominal_stage(ctx, cases, f)()
+            ctx.frame_run()
+            out.append(ctx.frame_fetch())
+        return out
+    nominal_stage(ctx, cases, frames[0], use_async=True)()
+    ctx.frame_run()
+    for i, f in enumerate(frames):
+        if i + 1 < len(frames):
+            nominal_stage(ctx, cases, frames[i + 1], use_async=True)()
+            ctx.frame_fetch_begin()
+            ctx.frame_run()
+            out.append(ctx.frame_fetch_end())
+        else:
+            out.append(ctx.frame_fetch())
+    return out
+
+

@@ -13,6 +13,7 @@
 #include "launch_chol.h"
 #include "launch_gnss.h"
 #include "launch_lmbatch.h"
+#include "launch_nominal.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -193,6 +194,19 @@ struct ingvio_ctx {
     hipEvent_t tok_wait = nullptr, tok_rec = nullptr;      // run_msckf_factored: wait before / record after its throughput segment (phase 1: gate + Gram, phase 2: apply)
     // device-resident track store (ingvio_tracks_create / ingvio_frame_stage_tracks, kernels_tracks.hip)
     struct Tracks { double *uv = nullptr, *pf = nullptr; unsigned long long* mask = nullptr; int t_max = 0; char* stage[2] = { nullptr, nullptr }; size_t stage_cap = 0; } trk;
+    // device-resident nominal state (ingvio_nominal_*, kernels_nominal.hip).  Every change of the integer records (slots,
+    // idx, window list) is decided by the host, so it keeps a mirror of them and validates a stage without a device round trip.
+    struct Nominal {
+        int vmax = 0, ir = 0, dr = 0;
+        int* ih = nullptr; double* dv = nullptr;              // the table (launch_nominal.h)
+        int* ih_snap = nullptr; double* dv_snap = nullptr;    // ingvio_cov_snapshot's copy
+        double* dx = nullptr;                                 // [B][ldp] dx of ingvio_nominal_box_plus
+        std::vector<int> h_ih, h_ih_snap;                     // host mirror of the integer records
+        bool has_snap = false;
+        bool pending = false;                                 // a frame staged from the table has not run yet
+        bool frame = false;                                   // the staged frame came from the table (it runs once)
+        hipEvent_t ev = nullptr; bool ev_valid = false;       // behind the post-frame kernel of the frame enqueued last
+    } nom;
     // profiling
     bool prof;
     std::vector<ProfRec> recs;
@@ -299,6 +313,38 @@ int join_parts(ingvio_ctx* c)
     return 0;
 }
 #define ENTER(c) do { if ((c) && (c)->split_pending && join_parts(c)) return INGVIO_E_HIP; } while (0)
+
+// device-resident nominal state: the event an asynchronous stage from the table waits for, recorded behind every use of the table on
+// the compute stream
+int nom_mark(ingvio_ctx* c)
+{
+    if (!c->nom.ev) HIPCHK(c, hipEventCreateWithFlags(&c->nom.ev, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->nom.ev, c->st));
+    c->nom.ev_valid = true;
+    return 0;
+}
+NomTable nom_table(ingvio_ctx* c) { return NomTable{ c->nom.ih, c->nom.dv, c->nom.vmax, c->nom.ir, c->nom.dr }; }
+
+// the marginalisation on the host mirror of filter b's integer record, exactly as k_nominal_update<true> does it on the device
+void nom_mirror_marg(ingvio_ctx* c, int b, int m)
+{
+    if (m < 0) return;
+    int* I = &c->nom.h_ih[(size_t)b * c->nom.ir];
+    int* var = I + NOM_IH;
+    const int nc = I[NOM_N_CLONES];
+    int w = 0, drop = -1;
+    for (int q = 0; q < nc; ++q) {
+        const int sl = I[NOM_CLONES + q];
+        if (drop < 0 && var[4 * sl + 1] == m) { drop = sl; continue; }
+        I[NOM_CLONES + w++] = sl;
+    }
+    I[NOM_N_CLONES] = w;
+    for (int v = 0; v < I[NOM_N_VAR]; ++v) {
+        if (var[4 * v] == NOM_KIND_NONE) continue;
+        if (v == drop) { var[4 * v] = NOM_KIND_NONE; var[4 * v + 1] = -1; var[4 * v + 2] = -1; }
+        else if (var[4 * v + 1] > m) var[4 * v + 1] -= 6;
+    }
+}
 
 int parts_prepare(ingvio_ctx* c, int P)
 {
@@ -1033,6 +1079,8 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
         for (auto e : c->ev_free) if (e) hipEventDestroy(e);
     }
     for (void* p : { (void*)c->trk.uv, (void*)c->trk.pf, (void*)c->trk.mask, (void*)c->trk.stage[0], (void*)c->trk.stage[1] }) if (p) hipFree(p);
+    for (void* p : { (void*)c->nom.ih, (void*)c->nom.dv, (void*)c->nom.ih_snap, (void*)c->nom.dv_snap, (void*)c->nom.dx }) if (p) hipFree(p);
+    if (c->nom.ev) hipEventDestroy(c->nom.ev);
     for (auto& r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (int p = 0; p < c->parts_alloc; ++p) { hipStreamDestroy(c->part[p].st); hipEventDestroy(c->part[p].ev_gate); hipEventDestroy(c->part[p].ev_apply); hipEventDestroy(c->part[p].ev_done); }
     if (c->ev_split_fork) hipEventDestroy(c->ev_split_fork);
@@ -1126,9 +1174,18 @@ int ingvio_cov_snapshot(ingvio_ctx* c)
     ENTER(c);
     if (phase_busy(c)) return INGVIO_E_ARG;
     if (!c) return INGVIO_E_ARG;
+    if (c->nom.pending) { c->err = "ingvio_cov_snapshot: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
     launch_snapshot(view(c), c->d.n_max, c->Psnap, c->d_n_snap, c->st);
     c->h_n_snap = c->h_n;
     c->has_snap = true;
+    if (c->nom.vmax) {                             // the nominal table travels with the covariance (device to device, same stream)
+        auto& m = c->nom;
+        HIPCHK(c, hipMemcpyAsync(m.ih_snap, m.ih, sizeof(int) * (size_t)c->d.batch * m.ir, hipMemcpyDeviceToDevice, c->st));
+        HIPCHK(c, hipMemcpyAsync(m.dv_snap, m.dv, sizeof(double) * (size_t)c->d.batch * m.dr, hipMemcpyDeviceToDevice, c->st));
+        m.h_ih_snap = m.h_ih;
+        m.has_snap = true;
+        if (nom_mark(c)) return INGVIO_E_HIP;
+    }
     return last_launch(c);
 }
 
@@ -1136,10 +1193,24 @@ int ingvio_cov_restore(ingvio_ctx* c)
 {
     ENTER(c);
     if (!c || !c->has_snap) return INGVIO_E_ARG;
+    if (c->nom.vmax && !c->nom.has_snap) {
+        c->err = "ingvio_cov_restore: the snapshot was taken before ingvio_nominal_create and holds no nominal table";
+        return INGVIO_E_ARG;
+    }
     c->phase_pending = false;                      // the way out of an abandoned split step: every filter returns to the snapshot
     launch_restore(view(c), 0, c->d.batch, c->d.n_max, c->Psnap, c->d_n_snap, c->st);
     c->h_n = c->h_n_snap;
     std::fill(c->h_cur.begin(), c->h_cur.end(), 0);
+    if (c->nom.vmax && c->nom.has_snap) {
+        auto& m = c->nom;
+        if (m.pending) { c->staged = false; m.pending = false; }      // the staged frame's clone is not in the restored table
+        m.frame = false;
+        if (wait_inputs(c)) return INGVIO_E_HIP;                     // an asynchronous stage from the table must land before it is overwritten
+        HIPCHK(c, hipMemcpyAsync(m.ih, m.ih_snap, sizeof(int) * (size_t)c->d.batch * m.ir, hipMemcpyDeviceToDevice, c->st));
+        HIPCHK(c, hipMemcpyAsync(m.dv, m.dv_snap, sizeof(double) * (size_t)c->d.batch * m.dr, hipMemcpyDeviceToDevice, c->st));
+        m.h_ih = m.h_ih_snap;
+        if (nom_mark(c)) return INGVIO_E_HIP;
+    }
     return last_launch(c);
 }
 
@@ -2443,6 +2514,7 @@ static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_st
                             const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, bool async)
 {
     if (phase_busy(c)) return INGVIO_E_ARG;
+    if (c && c->nom.pending) { c->err = "a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
     // ---- validation: nothing of the context is modified until every input has been accepted ---------------------------
     if (check_range(c, b0, nb) || !steps || !frames || !opts || !sigma) return INGVIO_E_ARG;
     if (async && (b0 != 0 || nb != c->d.batch)) return INGVIO_E_ARG;      // a whole input set is replaced
@@ -2547,6 +2619,7 @@ static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_st
     c->st_stereo = opts->stereo; c->st_enable_gnss = enable_gnss;
     if (!c->staged || fmx > c->st_fmax_used) c->st_fmax_used = fmx;
     c->staged = true;
+    c->nom.frame = false;                          // a flattened frame: no post-frame step
     return INGVIO_OK;
 }
 
@@ -2577,11 +2650,14 @@ int ingvio_tracks_create(ingvio_ctx* c, int t_max)
     return INGVIO_OK;
 }
 
-int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_raw* steps, const ingvio_track_frame* frames,
-                              const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, int async)
+// plan [nb][4] (device nominal stage, else nullptr): the new clone's variable slot, its idx, the window's clone count with it and the
+// table's slots in use after it; frames[i].n_clones is that count, the frames' clone arrays are not read
+static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_raw* steps, const ingvio_track_frame* frames,
+                                   const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, int async,
+                                   const int* plan)
 {
-    ENTER(c);
     if (phase_busy(c)) return INGVIO_E_ARG;
+    if (c && c->nom.pending) { c->err = "a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
     if (check_range(c, b0, nb) || !steps || !frames || !opts || !sigma) return INGVIO_E_ARG;
     if (!c->trk.t_max) { c->err = "ingvio_frame_stage_tracks without ingvio_tracks_create"; return INGVIO_E_ARG; }
     if (async && (b0 != 0 || nb != c->d.batch)) return INGVIO_E_ARG;
@@ -2599,27 +2675,29 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
         if (f.n_drop < 0 || f.n_drop > cm || f.n_free < 0 || f.n_free > T || f.n_obs < 0 || f.n_obs > T || f.n_pf < 0 || f.n_pf > T) return INGVIO_E_CAPACITY;
         if (f.n_clones < 0 || f.n_clones > cm || f.n_feat < 0 || f.n_feat > fm) return INGVIO_E_CAPACITY;
         if ((f.n_drop && !f.drop_slots) || (f.n_free && !f.free_tracks) || (f.n_obs && (!f.obs_track || !f.obs_uv)) || (f.n_pf && (!f.pf_track || !f.pf)) ||
-            (f.n_clones && (!f.clone_idx || !f.clone_R || !f.clone_p)) || (f.n_feat && (!f.feat_track || !f.feat_anchor || !f.feat_dof))) return INGVIO_E_ARG;
+            (f.n_clones && !plan && (!f.clone_idx || !f.clone_R || !f.clone_p)) || (f.n_feat && (!f.feat_track || !f.feat_anchor || !f.feat_dof))) return INGVIO_E_ARG;
         if (f.append_slot >= cm || (f.n_obs > 0 && f.append_slot < 0)) return INGVIO_E_ARG;
         if (f.n_feat > fmx) fmx = f.n_feat;
         int* h = &hdr[(size_t)i * TRK_HDR];
         h[TRK_N_DROP] = f.n_drop; h[TRK_APPEND] = f.append_slot; h[TRK_N_OBS] = f.n_obs; h[TRK_N_FREE] = f.n_free; h[TRK_N_PF] = f.n_pf;
         h[TRK_N_CLONES] = f.n_clones; h[TRK_N_FEAT] = f.n_feat; h[TRK_K] = s.k; h[TRK_HAS_SEL] = f.feat_sel ? 1 : 0; h[TRK_MARG] = s.marg_idx;
         h[TRK_OFF_I] = (int)ni; h[TRK_OFF_D] = (int)nd; h[TRK_OFF_M] = (int)nm;
+        if (plan) { h[TRK_NOM_SLOT] = plan[4 * i]; h[TRK_NOM_IDX] = plan[4 * i + 1]; h[TRK_NOM_NVAR] = plan[4 * i + 3]; }
         int oi = 0, od = 0;
         h[TRK_I_DROP] = oi; oi += f.n_drop;
         h[TRK_I_FREE] = oi; oi += f.n_free;
         h[TRK_I_OBS] = oi; oi += f.n_obs;
         h[TRK_I_PF] = oi; oi += f.n_pf;
-        h[TRK_I_CIDX] = oi; oi += f.n_clones;
+        const int nct = plan ? 0 : f.n_clones;          // from the device table: neither the clone table nor the start state travel
+        h[TRK_I_CIDX] = oi; oi += nct;
         h[TRK_I_FEAT] = oi; oi += f.n_feat;
         h[TRK_I_GNSS] = oi; oi += 5;
         od = (od + 3) & ~3; h[TRK_D_OBS] = od; od += 4 * f.n_obs;                 // 32-byte aligned: read as double4
         h[TRK_D_PF] = od; od += 3 * f.n_pf;
-        h[TRK_D_CR] = od; od += 9 * f.n_clones;
-        h[TRK_D_CP] = od; od += 3 * f.n_clones;
+        h[TRK_D_CR] = od; od += 9 * nct;
+        h[TRK_D_CP] = od; od += 3 * nct;
         h[TRK_D_IMU] = od; od += 7 * s.k;
-        h[TRK_D_STATE] = od; od += 24;
+        h[TRK_D_STATE] = od; od += plan ? 0 : 24;
         ni += (size_t)oi; nd += ((size_t)od + 3) & ~(size_t)3;
         if (f.feat_sel) nm += (size_t)f.n_feat;
     }
@@ -2651,7 +2729,7 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
         for (int q = 0; q < f.n_free; ++q) if (f.free_tracks[q] < 0 || f.free_tracks[q] >= T) err = 1;
         for (int q = 0; q < f.n_obs; ++q) if (f.obs_track[q] < 0 || f.obs_track[q] >= T) err = 1;
         for (int q = 0; q < f.n_pf; ++q) if (f.pf_track[q] < 0 || f.pf_track[q] >= T) err = 1;
-        for (int q = 0; q < f.n_clones; ++q) if (f.clone_idx[q] < 0 || f.clone_idx[q] + 6 > n_max) err = 1;
+        if (!plan) for (int q = 0; q < f.n_clones; ++q) if (f.clone_idx[q] < 0 || f.clone_idx[q] + 6 > n_max) err = 1;
         int* fw = ip + h[TRK_I_FEAT];
         for (int j = 0; j < f.n_feat; ++j) {
             if (f.feat_track[j] < 0 || f.feat_track[j] >= T || f.feat_anchor[j] < 0 || f.feat_anchor[j] >= f.n_clones || f.feat_dof[j] < 0 || f.feat_dof[j] > 255) err = 1;
@@ -2662,15 +2740,17 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
         if (f.n_free) memcpy(ip + h[TRK_I_FREE], f.free_tracks, 4 * (size_t)f.n_free);
         if (f.n_obs) { memcpy(ip + h[TRK_I_OBS], f.obs_track, 4 * (size_t)f.n_obs); memcpy(dp + h[TRK_D_OBS], f.obs_uv, 32 * (size_t)f.n_obs); }
         if (f.n_pf) { memcpy(ip + h[TRK_I_PF], f.pf_track, 4 * (size_t)f.n_pf); memcpy(dp + h[TRK_D_PF], f.pf, 24 * (size_t)f.n_pf); }
-        if (f.n_clones) {
+        if (f.n_clones && !plan) {
             memcpy(ip + h[TRK_I_CIDX], f.clone_idx, 4 * (size_t)f.n_clones);
             memcpy(dp + h[TRK_D_CR], f.clone_R, 72 * (size_t)f.n_clones); memcpy(dp + h[TRK_D_CP], f.clone_p, 24 * (size_t)f.n_clones);
         }
         for (int g = 0; g < 5; ++g) ip[h[TRK_I_GNSS] + g] = s.gnss_idx[g];
         if (f.feat_sel) memcpy(mpool + h[TRK_OFF_M], f.feat_sel, 8 * (size_t)f.n_feat);
         memcpy(dp + h[TRK_D_IMU], s.imu, 56 * (size_t)s.k);
-        double* st0 = dp + h[TRK_D_STATE];
-        memcpy(st0, s.R, 72); memcpy(st0 + 9, s.p, 24); memcpy(st0 + 12, s.v, 24); memcpy(st0 + 15, s.bg, 24); memcpy(st0 + 18, s.ba, 24); memcpy(st0 + 21, s.gravity, 24);
+        if (!plan) {
+            double* st0 = dp + h[TRK_D_STATE];
+            memcpy(st0, s.R, 72); memcpy(st0 + 9, s.p, 24); memcpy(st0 + 12, s.v, 24); memcpy(st0 + 15, s.bg, 24); memcpy(st0 + 18, s.ba, 24); memcpy(st0 + 21, s.gravity, 24);
+        }
     });
     for (int i = 0; i < nb; ++i) if (bad[i]) { c->err = "ingvio_frame_stage_tracks: a slot, track, clone index, anchor or dof is out of range"; return INGVIO_E_ARG; }
     // ---- from here on only HIP runtime errors can occur ----
@@ -2715,10 +2795,13 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
                    reinterpret_cast<const double*>(dstage + off_d), reinterpret_cast<const unsigned long long*>(dstage + off_m) };
     TrackStore store{ c->trk.uv, c->trk.mask, c->trk.pf, T, cm };
     FrameOut fo{ c->d_clone_idx, c->d_clone_R, c->d_clone_p, c->d_nclones, c->d_nfeat, c->d_pf, c->d_anchor, c->d_mask, c->d_uv, c->d_dof, cm, fm };
-    launch_imu_steps(ts, b0, nb, KMAX, c->d_Phi, c->d_G, c->d_dt, c->d_R, S);
+    const NomTable nt = nom_table(c);
+    // from the device table on the copy stream: the uploads above overlap the running frame, the kernels wait for its post-frame step
+    if (plan && async && c->nom.ev_valid && hipStreamWaitEvent(S, c->nom.ev, 0) != hipSuccess) return fail(INGVIO_E_HIP);
+    launch_imu_steps(ts, b0, nb, KMAX, c->d_Phi, c->d_G, c->d_dt, c->d_R, S, plan ? &nt : nullptr);
     if (hipGetLastError() != hipSuccess) return fail(INGVIO_E_HIP);       // before the store kernels change the track store
     launch_tracks_apply(ts, store, b0, nb, S);
-    launch_tracks_gather(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S);
+    launch_tracks_gather(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S, plan ? &nt : nullptr);
     if (hipGetLastError() != hipSuccess) return fail(INGVIO_E_HIP);
     rc = upl.end();
     if (rc) return fail(rc);
@@ -2729,10 +2812,22 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
     for (int i = 0; i < nb; ++i) {
         c->st_marg[b0 + i] = steps[i].marg_idx;
         int hi = -1;
-        for (int q = 0; q < frames[i].n_clones; ++q) if (frames[i].clone_idx[q] > hi) hi = frames[i].clone_idx[q];
+        if (plan) hi = plan[4 * i + 1];
+        else for (int q = 0; q < frames[i].n_clones; ++q) if (frames[i].clone_idx[q] > hi) hi = frames[i].clone_idx[q];
         c->st_cidx_hi[b0 + i] = hi;
         c->h_nclones[b0 + i] = frames[i].n_clones;
     }
+    if (plan) {                                   // the mirror follows what k_imu_steps<true> writes
+        for (int i = 0; i < nb; ++i) {
+            int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
+            const int slot = plan[4 * i], ncl = plan[4 * i + 2];
+            int* vc = I + NOM_IH + 4 * slot;
+            vc[0] = NOM_KIND_SE3; vc[1] = plan[4 * i + 1]; vc[2] = -1; vc[3] = 0;
+            I[NOM_CLONES + ncl - 1] = slot; I[NOM_N_CLONES] = ncl; I[NOM_N_VAR] = plan[4 * i + 3];
+        }
+        c->nom.pending = true;
+    }
+    c->nom.frame = plan != nullptr;
     MsckfOpts& op = c->st_op;
     memcpy(op.R_lr, opts->R_cl2cr, 72);
     memcpy(op.t_lr, opts->t_cl2cr, 24);
@@ -2742,6 +2837,201 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
     if (!c->staged || fmx > c->st_fmax_used) c->st_fmax_used = fmx;
     c->staged = true;
     return INGVIO_OK;
+}
+
+int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_raw* steps, const ingvio_track_frame* frames,
+                              const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, int async)
+{
+    ENTER(c);
+    return frame_stage_tracks_impl(c, b0, nb, steps, frames, opts, sigma, enable_gnss, scb, srw, async, nullptr);
+}
+
+// ---- device-resident nominal state -----------------------------------------------------------------------------
+static int nom_size(int kind) { return kind == NOM_KIND_SE23 ? 9 : kind == NOM_KIND_SE3 ? 6 : kind == NOM_KIND_SCALAR ? 1 : 3; }
+
+int ingvio_nominal_create(ingvio_ctx* c, int v_max)
+{
+    ENTER(c);
+    if (!c || phase_busy(c) || v_max < 1 || v_max > 4096) return INGVIO_E_ARG;
+    if (c->d.c_max > NOM_IH - NOM_CLONES) return INGVIO_E_UNSUPPORTED;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (c->st_copy) HIPCHK(c, hipStreamSynchronize(c->st_copy));
+    auto& m = c->nom;
+    const size_t B = c->d.batch;
+    if (m.vmax != v_max) {
+        for (void* p : { (void*)m.ih, (void*)m.dv, (void*)m.ih_snap, (void*)m.dv_snap, (void*)m.dx }) if (p) hipFree(p);
+        m.ih = nullptr; m.dv = nullptr; m.ih_snap = nullptr; m.dv_snap = nullptr; m.dx = nullptr; m.vmax = 0;
+        const int ir = NOM_IH + 4 * v_max, dr = NOM_DH + NOM_VD * v_max;
+        if (dalloc(c, &m.ih, B * ir) || dalloc(c, &m.dv, B * dr) || dalloc(c, &m.ih_snap, B * ir) || dalloc(c, &m.dv_snap, B * dr) ||
+            dalloc(c, &m.dx, B * c->ldp)) return INGVIO_E_HIP;
+        m.vmax = v_max; m.ir = ir; m.dr = dr;
+    }
+    m.h_ih.assign(B * m.ir, 0);
+    for (size_t b = 0; b < B; ++b) {
+        int* I = &m.h_ih[b * m.ir];
+        I[NOM_V_EXT] = I[NOM_V_POSE] = I[NOM_V_BG] = I[NOM_V_BA] = -1;
+        for (int v = 0; v < v_max; ++v) { I[NOM_IH + 4 * v] = NOM_KIND_NONE; I[NOM_IH + 4 * v + 1] = -1; I[NOM_IH + 4 * v + 2] = -1; }
+    }
+    HIPCHK(c, hipMemcpyAsync(m.ih, m.h_ih.data(), sizeof(int) * m.h_ih.size(), hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemsetAsync(m.dv, 0, sizeof(double) * B * m.dr, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    m.has_snap = false;
+    if (m.pending) { c->staged = false; m.pending = false; }
+    m.frame = false;
+    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
+}
+
+int ingvio_nominal_set(ingvio_ctx* c, int b0, int nb, const ingvio_nominal* nom)
+{
+    ENTER(c);
+    if (phase_busy(c) || check_range(c, b0, nb) || !nom) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    if (!m.vmax) { c->err = "ingvio_nominal_set without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = "ingvio_nominal_set: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    // ---- validation of every filter before anything is written ----
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_nominal& q = nom[i];
+        if (q.n_var < 0 || q.n_var > m.vmax || q.n_clones < 0 || q.n_clones > c->d.c_max) return INGVIO_E_CAPACITY;
+        if (q.n_var && (!q.kind || !q.idx || !q.anchor || !q.val)) return INGVIO_E_ARG;
+        if (q.n_clones && !q.clone_var) return INGVIO_E_ARG;
+        auto kind_of = [&](int v) { return v >= 0 && v < q.n_var ? q.kind[v] : -2; };
+        for (int v = 0; v < q.n_var; ++v) {
+            const int k = q.kind[v];
+            if (k < NOM_KIND_NONE || k > NOM_KIND_LM) return INGVIO_E_ARG;
+            if (k == NOM_KIND_NONE) continue;
+            if (q.idx[v] < 0 || q.idx[v] + nom_size(k) > c->d.n_max) return INGVIO_E_ARG;
+            if (k == NOM_KIND_LM && kind_of(q.anchor[v]) != NOM_KIND_SE3) return INGVIO_E_ARG;
+        }
+        for (int a = 0; a < q.n_clones; ++a) {
+            if (kind_of(q.clone_var[a]) != NOM_KIND_SE3) return INGVIO_E_ARG;
+            for (int b = 0; b < a; ++b) if (q.clone_var[b] == q.clone_var[a]) return INGVIO_E_ARG;
+        }
+        if ((q.v_ext >= 0 && kind_of(q.v_ext) != NOM_KIND_SE3) || (q.v_pose >= 0 && kind_of(q.v_pose) != NOM_KIND_SE23) ||
+            (q.v_bg >= 0 && kind_of(q.v_bg) != NOM_KIND_VEC3) || (q.v_ba >= 0 && kind_of(q.v_ba) != NOM_KIND_VEC3)) return INGVIO_E_ARG;
+    }
+    std::vector<int> ih((size_t)nb * m.ir, 0);
+    std::vector<double> dv((size_t)nb * m.dr, 0.0);
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_nominal& q = nom[i];
+        int* I = &ih[(size_t)i * m.ir];
+        double* D = &dv[(size_t)i * m.dr];
+        I[NOM_N_VAR] = q.n_var; I[NOM_N_CLONES] = q.n_clones;
+        I[NOM_V_EXT] = q.v_ext; I[NOM_V_POSE] = q.v_pose; I[NOM_V_BG] = q.v_bg; I[NOM_V_BA] = q.v_ba;
+        for (int a = 0; a < q.n_clones; ++a) I[NOM_CLONES + a] = q.clone_var[a];
+        for (int v = 0; v < m.vmax; ++v) {
+            const bool used = v < q.n_var && q.kind[v] != NOM_KIND_NONE;
+            I[NOM_IH + 4 * v] = used ? q.kind[v] : NOM_KIND_NONE;
+            I[NOM_IH + 4 * v + 1] = used ? q.idx[v] : -1;
+            I[NOM_IH + 4 * v + 2] = used && q.kind[v] == NOM_KIND_LM ? q.anchor[v] : -1;
+            if (used) memcpy(D + NOM_DH + (size_t)v * NOM_VD, q.val + (size_t)v * INGVIO_NOM_VAL, 8 * INGVIO_NOM_VAL);
+        }
+        memcpy(D, q.gravity, 24);
+    }
+    HIPCHK(c, hipMemcpyAsync(m.ih + (size_t)b0 * m.ir, ih.data(), sizeof(int) * ih.size(), hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(m.dv + (size_t)b0 * m.dr, dv.data(), sizeof(double) * dv.size(), hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    memcpy(&m.h_ih[(size_t)b0 * m.ir], ih.data(), sizeof(int) * ih.size());
+    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
+}
+
+int ingvio_nominal_get(ingvio_ctx* c, int b0, int nb, ingvio_nominal* out)
+{
+    ENTER(c);
+    if (check_range(c, b0, nb) || !out) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    if (!m.vmax) { c->err = "ingvio_nominal_get without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    for (int i = 0; i < nb; ++i) if (!out[i].kind || !out[i].idx || !out[i].anchor || !out[i].val || !out[i].clone_var) return INGVIO_E_ARG;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (c->st_copy) HIPCHK(c, hipStreamSynchronize(c->st_copy));      // an asynchronous stage from the table writes it there
+    std::vector<int> ih((size_t)nb * m.ir);
+    std::vector<double> dv((size_t)nb * m.dr);
+    HIPCHK(c, hipMemcpyAsync(ih.data(), m.ih + (size_t)b0 * m.ir, sizeof(int) * ih.size(), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(dv.data(), m.dv + (size_t)b0 * m.dr, sizeof(double) * dv.size(), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    for (int i = 0; i < nb; ++i) {
+        ingvio_nominal& q = out[i];
+        const int* I = &ih[(size_t)i * m.ir];
+        const double* D = &dv[(size_t)i * m.dr];
+        q.n_var = I[NOM_N_VAR]; q.n_clones = I[NOM_N_CLONES];
+        q.v_ext = I[NOM_V_EXT]; q.v_pose = I[NOM_V_POSE]; q.v_bg = I[NOM_V_BG]; q.v_ba = I[NOM_V_BA];
+        for (int a = 0; a < q.n_clones; ++a) q.clone_var[a] = I[NOM_CLONES + a];
+        for (int v = 0; v < q.n_var; ++v) {
+            q.kind[v] = I[NOM_IH + 4 * v]; q.idx[v] = I[NOM_IH + 4 * v + 1]; q.anchor[v] = I[NOM_IH + 4 * v + 2];
+            memcpy(q.val + (size_t)v * INGVIO_NOM_VAL, D + NOM_DH + (size_t)v * NOM_VD, 8 * INGVIO_NOM_VAL);
+        }
+        memcpy(q.gravity, D, 24);
+    }
+    return INGVIO_OK;
+}
+
+int ingvio_nominal_box_plus(ingvio_ctx* c, int b0, int nb, const double* dx)
+{
+    ENTER(c);
+    if (phase_busy(c) || check_range(c, b0, nb) || !dx) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    if (!m.vmax) { c->err = "ingvio_nominal_box_plus without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = "ingvio_nominal_box_plus: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    const size_t bytes = 8 * (size_t)nb * c->ldp;
+    Uploader upl{ c };
+    if (int rc = upl.begin(bytes + 64)) return rc;
+    double* h = upl.take<double>((size_t)nb * c->ldp);
+    memcpy(h, dx, bytes);
+    upl.copy(m.dx + (size_t)b0 * c->ldp, h, (size_t)nb * c->ldp);
+    if (int rc = upl.end()) return rc;
+    launch_nominal_update(nom_table(c), m.dx, c->ldp, nullptr, b0, nb, c->st);
+    if (int rc = last_launch(c)) return rc;
+    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
+}
+
+int ingvio_frame_stage_tracks_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,
+                                      const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, int async)
+{
+    ENTER(c);
+    if (phase_busy(c) || check_range(c, b0, nb) || !steps || !frames) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    if (!m.vmax) { c->err = "ingvio_frame_stage_tracks_nominal without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    // the post-frame step retracts, drops and shifts EVERY filter of the batch, and a second stage before the run is refused: the frame
+    // staged from the table is the whole batch's
+    if (b0 != 0 || nb != c->d.batch) { c->err = "ingvio_frame_stage_tracks_nominal stages the whole batch (b0 = 0, nb = batch)"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = "a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if ((c->gn.staged && c->gn.in_frame) || (c->lm.staged && c->lm.in_frame)) {
+        c->err = "the device nominal state does not take an in-frame GNSS or landmark stage";
+        return INGVIO_E_UNSUPPORTED;
+    }
+    if (c->parts_req > 1) { c->err = "the device nominal state runs with frame_parts = 1 only"; return INGVIO_E_UNSUPPORTED; }
+    // ---- the new clone's slot and idx and the marginalisation, on the host mirror (nothing changes before every filter passed) ----
+    std::vector<int> plan((size_t)nb * 4);
+    std::vector<ingvio_frame_step_raw> raw((size_t)nb);
+    std::vector<ingvio_track_frame> fr(frames, frames + nb);
+    for (int i = 0; i < nb; ++i) {
+        const int b = b0 + i;
+        const int* I = &m.h_ih[(size_t)b * m.ir];
+        const int* var = I + NOM_IH;
+        if (I[NOM_V_EXT] < 0 || I[NOM_V_POSE] < 0 || I[NOM_V_BG] < 0 || I[NOM_V_BA] < 0) {
+            c->err = "ingvio_frame_stage_tracks_nominal: the table names no extrinsics, pose or bias variable"; return INGVIO_E_ARG;
+        }
+        const int ncl = I[NOM_N_CLONES] + 1;
+        int slot = -1;
+        for (int v = 0; v < m.vmax && slot < 0; ++v) if (var[4 * v] == NOM_KIND_NONE) slot = v;
+        if (ncl > c->d.c_max || slot < 0 || c->h_n[b] + 6 > c->d.n_max) return INGVIO_E_CAPACITY;
+        const int idx = c->h_n[b], mg = steps[i].marg_idx;
+        if (mg >= 0) {
+            int ms = mg == idx ? slot : -1;
+            for (int q = 0; q < ncl - 1 && ms < 0; ++q) if (var[4 * I[NOM_CLONES + q] + 1] == mg) ms = I[NOM_CLONES + q];
+            if (ms < 0) { c->err = "ingvio_frame_stage_tracks_nominal: marg_idx names no clone of the window"; return INGVIO_E_NOT_IN_STATE; }
+            for (int v = 0; v < I[NOM_N_VAR]; ++v)
+                if (var[4 * v] == NOM_KIND_LM && var[4 * v + 2] == ms) {
+                    c->err = "ingvio_frame_stage_tracks_nominal: a landmark is anchored to the clone that leaves the window"; return INGVIO_E_ARG;
+                }
+        }
+        plan[4 * i] = slot; plan[4 * i + 1] = idx; plan[4 * i + 2] = ncl; plan[4 * i + 3] = std::max(I[NOM_N_VAR], slot + 1);
+        ingvio_frame_step_raw& r = raw[i];
+        memset(&r, 0, sizeof r);
+        r.k = steps[i].k; r.imu = steps[i].imu; r.marg_idx = mg;
+        memcpy(r.gnss_idx, steps[i].gnss_idx, sizeof r.gnss_idx);
+        fr[i].n_clones = ncl; fr[i].clone_idx = nullptr; fr[i].clone_R = nullptr; fr[i].clone_p = nullptr;
+    }
+    return frame_stage_tracks_impl(c, b0, nb, raw.data(), fr.data(), opts, sigma, enable_gnss, scb, srw, async, plan.data());
 }
 
 int ingvio_frame_stage(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step* steps, const ingvio_msckf_frame* frames,
@@ -2863,6 +3153,14 @@ static int frame_run_split(ingvio_ctx* c, int restore_prior, int P, bool gnss_fu
 static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
 {
     if (!c || !c->staged) return INGVIO_E_ARG;
+    if (c->nom.frame) {                                                     // a frame staged from the device nominal state
+        if (!c->nom.pending) { c->err = "the frame staged from the device nominal state has already run"; return INGVIO_E_ARG; }
+        if (phase) { c->err = "the split step does not take a frame staged from the device nominal state"; return INGVIO_E_UNSUPPORTED; }
+        if (restore_prior) { c->err = "restore_prior with a frame staged from the device nominal state (restore with ingvio_cov_restore before the stage)"; return INGVIO_E_ARG; }
+        if ((c->gn.staged && c->gn.in_frame) || (c->lm.staged && c->lm.in_frame) || c->parts_req > 1) {
+            c->err = "the device nominal state takes no in-frame GNSS / landmark stage and frame_parts = 1 only"; return INGVIO_E_UNSUPPORTED;
+        }
+    }
     if (phase && c->method != 1) return INGVIO_E_UNSUPPORTED;             // the split needs the information form's [A | b]
     // protocol of the split step: 1 -> (ingvio_debug_msckf_info / ingvio_info_set) -> 2, exactly once each; the accepted-feature
     // cap is a global order over the features and is not defined across shards
@@ -2996,6 +3294,13 @@ static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
     if (with_lm && !restore_prior) c->lm.staged = false;
     bool all_marg = true;
     for (int b = 0; b < B; ++b) { if (c->st_marg[b] >= 0) { c->h_n[b] -= 6; c->h_cur[b] ^= 1; } else all_marg = false; }
+    if (c->nom.pending) {                          // device nominal state: boxPlus with the frame's dx, drop + shift, behind the marginalisation
+        launch_nominal_update(nom_table(c), c->d_dx, c->ldp, c->d_idx, 0, B, c->st);
+        if (int rc2 = last_launch(c)) return rc2;
+        for (int b = 0; b < B; ++b) nom_mirror_marg(c, b, c->st_marg[b]);
+        c->nom.pending = false;
+        if (nom_mark(c)) return INGVIO_E_HIP;
+    }
     c->strip_ok = fuse && all_marg && restore_prior;
     c->strip_seq = c->mut_seq;
     if (gnss_here && !gnss_fuse) {                 // not foldable (large window, landmarks in the frame, many rows): its own pass, now

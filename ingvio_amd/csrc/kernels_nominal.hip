@@ -1,0 +1,116 @@
+// kernels_nominal.hip — the device-resident nominal state (ingvio_nominal_*): the retractions of StateManager::boxPlus and
+// the marginalisation's drop / index shift on the per-filter variable table of launch_nominal.h.
+//
+// One wave per filter, one lane per variable: every variable reads dx (and, for a landmark, its anchor's idx, which boxPlus does not
+// change) and writes only its own value, so the lanes are independent and all loads are in flight together.  The formulas follow the
+// C oracle (oracle/ingvio_oracle.c: orc_gamma, orc_se3_update, orc_se23_update) operation for operation, the small-angle branch
+// (|theta| < 1e-6: Gamma_0 = Gamma_1 = I) included.
+// gfx950 only.
+#include <hip/hip_runtime.h>
+
+#include "launch_nominal.h"
+
+namespace {
+
+// AuxGammaFunc.cpp:46-113 for m = 0, 1 (row-major out)
+__device__ __forceinline__ void gamma01(const double* v, double G0[9], double G1[9])
+{
+    const double theta = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    for (int i = 0; i < 9; ++i) { G0[i] = 0.0; G1[i] = 0.0; }
+    if (fabs(theta) < 1e-06) {
+        G0[0] = G0[4] = G0[8] = 1.0;
+        G1[0] = G1[4] = G1[8] = 1.0;
+        return;
+    }
+    const double n0 = v[0] / theta, n1 = v[1] / theta, n2 = v[2] / theta;
+    const double nx[9] = { 0.0, -n2, n1, n2, 0.0, -n0, -n1, n0, 0.0 };
+    double nx2[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) nx2[3 * i + j] = nx[3 * i] * nx[j] + nx[3 * i + 1] * nx[3 + j] + nx[3 * i + 2] * nx[6 + j];
+    double s, c;
+    sincos(theta, &s, &c);
+    const double a1 = s, a2 = 1.0 - c;                                   // Gamma_0
+    const double b1 = (1.0 - c) / theta, b2 = (theta - s) / theta;       // Gamma_1
+    for (int i = 0; i < 9; ++i) { G0[i] = a1 * nx[i] + a2 * nx2[i]; G1[i] = b1 * nx[i] + b2 * nx2[i]; }
+    G0[0] += 1.0; G0[4] += 1.0; G0[8] += 1.0;
+    G1[0] += 1.0; G1[4] += 1.0; G1[8] += 1.0;
+}
+
+__device__ __forceinline__ void mulv(const double A[9], const double* x, double y[3])
+{
+    for (int i = 0; i < 3; ++i) y[i] = A[3 * i] * x[0] + A[3 * i + 1] * x[1] + A[3 * i + 2] * x[2];
+}
+
+}  // namespace
+
+// grid = nb filters, block = one wave.  MARG: after the retraction, the variable of idx marg[b] (a window clone) leaves the table (its
+// slot becomes free, the window list closes up) and every variable behind it moves 6 columns down.
+template <bool MARG>
+__global__ __launch_bounds__(64) void k_nominal_update(NomTable t, const double* __restrict__ dx, int ldx, const int* __restrict__ marg, int b0)
+{
+    const int b = b0 + blockIdx.x, lane = threadIdx.x;
+    int* I = t.ih + (size_t)b * t.ir;
+    int* var = I + NOM_IH;
+    double* D = t.dv + (size_t)b * t.dr + NOM_DH;
+    const double* d = dx + (size_t)b * ldx;
+    const int nv = I[NOM_N_VAR];
+    for (int v = lane; v < nv; v += 64) {
+        const int kind = var[4 * v], idx = var[4 * v + 1];
+        double* x = D + (size_t)v * NOM_VD;
+        if (kind == NOM_KIND_SE23 || kind == NOM_KIND_SE3) {             // PoseState.cpp:174-186 / :79-88
+            double G0[9], G1[9], R[9], t1[3], t2[3];
+            gamma01(d + idx, G0, G1);
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) R[3 * i + j] = G0[3 * i] * x[j] + G0[3 * i + 1] * x[3 + j] + G0[3 * i + 2] * x[6 + j];
+            mulv(G0, x + 9, t1); mulv(G1, d + idx + 3, t2);
+            for (int i = 0; i < 9; ++i) x[i] = R[i];
+            for (int i = 0; i < 3; ++i) x[9 + i] = t1[i] + t2[i];
+            if (kind == NOM_KIND_SE23) {
+                mulv(G0, x + 12, t1); mulv(G1, d + idx + 6, t2);
+                for (int i = 0; i < 3; ++i) x[12 + i] = t1[i] + t2[i];
+            }
+        } else if (kind == NOM_KIND_VEC3) {                             // VecState.cpp:25-29
+            for (int i = 0; i < 3; ++i) x[9 + i] = x[9 + i] + d[idx + i];
+        } else if (kind == NOM_KIND_SCALAR) {                           // VecState.cpp:40-44
+            x[9] = x[9] + d[idx];
+        } else if (kind == NOM_KIND_LM) {                               // AnchoredLandmark.cpp:227-243: the anchor's d_theta
+            const int as = var[4 * v + 2], a = as >= 0 ? var[4 * as + 1] : -1;
+            if (a < 0) {                                                 // no live anchor: p + delta_p (AnchoredLandmark.cpp:238-242)
+                for (int i = 0; i < 3; ++i) x[9 + i] = x[9 + i] + d[idx + i];
+                continue;
+            }
+            double G0[9], G1[9], t1[3], t2[3];
+            gamma01(d + a, G0, G1);
+            mulv(G0, x + 9, t1); mulv(G1, d + idx, t2);
+            for (int i = 0; i < 3; ++i) x[9 + i] = t1[i] + t2[i];
+        }
+    }
+    if (!MARG) return;
+    const int m = marg[b];
+    if (m < 0) return;
+    __shared__ int s_drop;
+    if (lane == 0) {                                                     // the window list closes up over the clone that leaves
+        const int nc = I[NOM_N_CLONES];
+        int w = 0, drop = -1;
+        for (int q = 0; q < nc; ++q) {
+            const int s = I[NOM_CLONES + q];
+            if (drop < 0 && var[4 * s + 1] == m) { drop = s; continue; }
+            I[NOM_CLONES + w++] = s;
+        }
+        I[NOM_N_CLONES] = w;
+        s_drop = drop;
+    }
+    __syncthreads();
+    const int drop = s_drop;
+    for (int v = lane; v < nv; v += 64) {
+        if (var[4 * v] == NOM_KIND_NONE) continue;
+        if (v == drop) { var[4 * v] = NOM_KIND_NONE; var[4 * v + 1] = -1; var[4 * v + 2] = -1; }
+        else if (var[4 * v + 1] > m) var[4 * v + 1] -= 6;
+    }
+}
+
+void launch_nominal_update(const NomTable& t, const double* dx, int ldx, const int* marg, int b0, int nb, hipStream_t st)
+{
+    if (marg) hipLaunchKernelGGL(k_nominal_update<true>, dim3(nb), dim3(64), 0, st, t, dx, ldx, marg, b0);
+    else hipLaunchKernelGGL(k_nominal_update<false>, dim3(nb), dim3(64), 0, st, t, dx, ldx, marg, b0);
+}

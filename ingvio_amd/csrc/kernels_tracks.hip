@@ -13,6 +13,8 @@
 //     k_imu_steps      ImuPropagator::stateAndCovTransition (ImuPropagator.cpp:98-162) for the k samples: Phi, G, dt, the clone rotation
 //     k_tracks_apply   the delta on the store
 //     k_tracks_gather  FrameView arrays (uv, mask, pf, anchor, dof, clone table) of the listed tracks
+// With the device-resident nominal state (ingvio_frame_stage_tracks_nominal) the <true> instantiations of k_imu_steps and
+// k_tracks_gather read the start state and the clone poses from the filter's table and append the new clone to it.
 // gfx950 only.
 #include <hip/hip_runtime.h>
 
@@ -141,7 +143,11 @@ __device__ __forceinline__ void put(double* M, int r0, int c0, const M3& B)     
 // imu [k][7] = gyro (3), accel (3), dt; st0 [24] = R (9, row-major), p, v, bg, ba, gravity.  Writes Phi [k][225], G [k][180], dt [k]
 // of the filter's input slot (kst steps per filter, k its own count from the header) and the IMU rotation at clone time R_out [9]
 // (StateManager::augmentSlidingWindowPose reads it).
-__global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, int b0, int nb, int kst, double* __restrict__ PhiAll, double* __restrict__ GAll,
+// NOM (device-resident nominal state): the start state comes from the filter's table instead of the stage (pose variable R p v,
+// the bias variables, gravity), and lane 0 writes the end state back into the pose variable together with the new clone's pose
+// T_i2w * T_cl2i (StateManager.cpp:263-272) at the variable slot and idx the host reserved in the header (TRK_NOM_*).
+template <bool NOM>
+__global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, NomTable nt, int b0, int nb, int kst, double* __restrict__ PhiAll, double* __restrict__ GAll,
                                                   double* __restrict__ dtAll, double* __restrict__ Rall)
 {
     __shared__ double sm[IMU_STEPS_CH * 405];                          // [IMU_STEPS_CH][405]: Phi | G of samples c0 .. c0 + 15
@@ -152,8 +158,18 @@ __global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, int b0, int nb,
     const double* imu = d + h[TRK_D_IMU];
     const double* s0 = d + h[TRK_D_STATE];
     M3 R; V3 p, v, bg, ba, g;
-    for (int i = 0; i < 9; ++i) R.m[i] = s0[i];
-    for (int i = 0; i < 3; ++i) { p.v[i] = s0[9 + i]; v.v[i] = s0[12 + i]; bg.v[i] = s0[15 + i]; ba.v[i] = s0[18 + i]; g.v[i] = s0[21 + i]; }
+    if constexpr (NOM) {
+        const int* I = nt.ih + (size_t)(b0 + bl) * nt.ir;
+        const double* D = nt.dv + (size_t)(b0 + bl) * nt.dr;
+        const double* xs = D + NOM_DH + (size_t)I[NOM_V_POSE] * NOM_VD;
+        const double* xg = D + NOM_DH + (size_t)I[NOM_V_BG] * NOM_VD;
+        const double* xa = D + NOM_DH + (size_t)I[NOM_V_BA] * NOM_VD;
+        for (int i = 0; i < 9; ++i) R.m[i] = xs[i];
+        for (int i = 0; i < 3; ++i) { p.v[i] = xs[9 + i]; v.v[i] = xs[12 + i]; bg.v[i] = xg[9 + i]; ba.v[i] = xa[9 + i]; g.v[i] = D[i]; }
+    } else {
+        for (int i = 0; i < 9; ++i) R.m[i] = s0[i];
+        for (int i = 0; i < 3; ++i) { p.v[i] = s0[9 + i]; v.v[i] = s0[12 + i]; bg.v[i] = s0[15 + i]; ba.v[i] = s0[18 + i]; g.v[i] = s0[21 + i]; }
+    }
     const M3 I3 = m3_eye();
     const int mine = lane < k ? lane : k - 1;                          // lanes beyond k shadow the last sample
     // the cheap recursion, the SAME k iterations on every lane (no divergence); a lane keeps the state in front of its own sample
@@ -216,6 +232,28 @@ __global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, int b0, int nb,
     if (lane == 0) {                                                  // every lane's recursion ended behind the last sample
         double* Ro = Rall + (size_t)(b0 + bl) * 9;
         for (int i = 0; i < 9; ++i) Ro[i] = R.m[i];
+        if constexpr (NOM) {
+            int* I = nt.ih + (size_t)(b0 + bl) * nt.ir;
+            double* D = nt.dv + (size_t)(b0 + bl) * nt.dr + NOM_DH;
+            double* xs = D + (size_t)I[NOM_V_POSE] * NOM_VD;
+            for (int i = 0; i < 9; ++i) xs[i] = R.m[i];
+            for (int i = 0; i < 3; ++i) { xs[9 + i] = p.v[i]; xs[12 + i] = v.v[i]; }
+            const double* xe = D + (size_t)I[NOM_V_EXT] * NOM_VD;
+            M3 Re; V3 pe;
+            for (int i = 0; i < 9; ++i) Re.m[i] = xe[i];
+            for (int i = 0; i < 3; ++i) pe.v[i] = xe[9 + i];
+            const int slot = h[TRK_NOM_SLOT], ncl = h[TRK_N_CLONES];
+            double* xc = D + (size_t)slot * NOM_VD;
+            const M3 Rc = R * Re;
+            const V3 pc = R * pe + p;
+            for (int i = 0; i < 9; ++i) xc[i] = Rc.m[i];
+            for (int i = 0; i < 3; ++i) { xc[9 + i] = pc.v[i]; xc[12 + i] = 0.0; }
+            int* vc = I + NOM_IH + 4 * slot;
+            vc[0] = NOM_KIND_SE3; vc[1] = h[TRK_NOM_IDX]; vc[2] = -1; vc[3] = 0;
+            I[NOM_CLONES + ncl - 1] = slot;
+            I[NOM_N_CLONES] = ncl;
+            I[NOM_N_VAR] = h[TRK_NOM_NVAR];
+        }
     }
 }
 
@@ -279,7 +317,9 @@ __global__ __launch_bounds__(256) void k_tracks_apply(TrackStage ts, TrackStore 
 // One workgroup per filter: the staged frame (FrameView arrays of the context's current input set) of the listed tracks.
 // feat word = track | anchor slot << 16 | dof << 24; sel [n_feat] optional u64 masks ANDed onto the stored ones (the
 // Selected-timestamp updates, SwMargUpdate.cpp:236-257).
-__global__ __launch_bounds__(256) void k_tracks_gather(TrackStage ts, TrackStore st, FrameOut fv, int b0, int* __restrict__ idx_marg, int* __restrict__ gnss_idx)
+// NOM: the window's clone table comes from the device-resident nominal state (after k_imu_steps<true> appended the new clone).
+template <bool NOM>
+__global__ __launch_bounds__(256) void k_tracks_gather(TrackStage ts, TrackStore st, FrameOut fv, NomTable nt, int b0, int* __restrict__ idx_marg, int* __restrict__ gnss_idx)
 {
     const int bl = blockIdx.x, b = b0 + bl, tid = threadIdx.x;
     const int* h = ts.hdr + (size_t)bl * TRK_HDR;
@@ -296,9 +336,17 @@ __global__ __launch_bounds__(256) void k_tracks_gather(TrackStage ts, TrackStore
         idx_marg[b] = h[TRK_MARG];
     }
     if (tid < 5) gnss_idx[(size_t)b * 5 + tid] = ip[h[TRK_I_GNSS] + tid];
-    for (int q = tid; q < Cn; q += 256) fv.clone_idx[(size_t)b * fv.cmax + q] = cidx[q];
-    for (int q = tid; q < Cn * 9; q += 256) fv.clone_R[(size_t)b * fv.cmax * 9 + q] = cR[q];
-    for (int q = tid; q < Cn * 3; q += 256) fv.clone_p[(size_t)b * fv.cmax * 3 + q] = cp[q];
+    if constexpr (NOM) {
+        const int* I = nt.ih + (size_t)b * nt.ir;
+        const double* D = nt.dv + (size_t)b * nt.dr + NOM_DH;
+        for (int q = tid; q < Cn; q += 256) fv.clone_idx[(size_t)b * fv.cmax + q] = I[NOM_IH + 4 * I[NOM_CLONES + q] + 1];
+        for (int q = tid; q < Cn * 9; q += 256) fv.clone_R[(size_t)b * fv.cmax * 9 + q] = D[(size_t)I[NOM_CLONES + q / 9] * NOM_VD + q % 9];
+        for (int q = tid; q < Cn * 3; q += 256) fv.clone_p[(size_t)b * fv.cmax * 3 + q] = D[(size_t)I[NOM_CLONES + q / 3] * NOM_VD + 9 + q % 3];
+    } else {
+        for (int q = tid; q < Cn; q += 256) fv.clone_idx[(size_t)b * fv.cmax + q] = cidx[q];
+        for (int q = tid; q < Cn * 9; q += 256) fv.clone_R[(size_t)b * fv.cmax * 9 + q] = cR[q];
+        for (int q = tid; q < Cn * 3; q += 256) fv.clone_p[(size_t)b * fv.cmax * 3 + q] = cp[q];
+    }
     const double* uvB = st.uv + (size_t)b * T * C * 4;
     const unsigned long long* mkB = st.mask + (size_t)b * T;
     const double* pfB = st.pf + (size_t)b * T * 3;
@@ -323,15 +371,18 @@ __global__ __launch_bounds__(256) void k_tracks_gather(TrackStage ts, TrackStore
     }
 }
 
-void launch_imu_steps(const TrackStage& ts, int b0, int nb, int kst, double* Phi, double* G, double* dt, double* R, hipStream_t st)
+void launch_imu_steps(const TrackStage& ts, int b0, int nb, int kst, double* Phi, double* G, double* dt, double* R, hipStream_t st, const NomTable* nom)
 {
-    hipLaunchKernelGGL(k_imu_steps, dim3(nb), dim3(64), 0, st, ts, b0, nb, kst, Phi, G, dt, R);
+    if (nom) hipLaunchKernelGGL(k_imu_steps<true>, dim3(nb), dim3(64), 0, st, ts, *nom, b0, nb, kst, Phi, G, dt, R);
+    else hipLaunchKernelGGL(k_imu_steps<false>, dim3(nb), dim3(64), 0, st, ts, NomTable{}, b0, nb, kst, Phi, G, dt, R);
 }
 void launch_tracks_apply(const TrackStage& ts, const TrackStore& store, int b0, int nb, hipStream_t st)
 {
     hipLaunchKernelGGL(k_tracks_apply, dim3(nb), dim3(256), 0, st, ts, store, b0);
 }
-void launch_tracks_gather(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st)
+void launch_tracks_gather(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st,
+                          const NomTable* nom)
 {
-    hipLaunchKernelGGL(k_tracks_gather, dim3(nb), dim3(256), 0, st, ts, store, fv, b0, idx_marg, gnss_idx);
+    if (nom) hipLaunchKernelGGL(k_tracks_gather<true>, dim3(nb), dim3(256), 0, st, ts, store, fv, *nom, b0, idx_marg, gnss_idx);
+    else hipLaunchKernelGGL(k_tracks_gather<false>, dim3(nb), dim3(256), 0, st, ts, store, fv, NomTable{}, b0, idx_marg, gnss_idx);
 }

@@ -1,0 +1,24 @@
+// launch_nominal.h — host-side descriptor of the device-resident nominal state (kernels_nominal.hip, ingvio_nominal_* in capi.hip).
+#pragma once
+#include "dev_common.h"
+
+// Per filter b, two records:
+//   ints    ih + b * ir:  [NOM_N_VAR] slots in use, [NOM_N_CLONES], [NOM_V_EXT], [NOM_V_POSE], [NOM_V_BG], [NOM_V_BA],
+//                         [NOM_CLONES + q] variable slot of window clone q (ascending time), then [v_max][4] = {kind, idx, anchor slot, 0}
+//   doubles dv + b * dr:  gravity (3) + pad, then [v_max][16] = R (9, row-major), p (3), v (3), pad; a Vec3 in p, a Scalar in p[0],
+//                         a landmark's world position (AnchoredLandmark::valuePosXyz) in p
+enum { NOM_N_VAR, NOM_N_CLONES, NOM_V_EXT, NOM_V_POSE, NOM_V_BG, NOM_V_BA, NOM_CLONES = 8, NOM_IH = NOM_CLONES + 64 };
+enum { NOM_KIND_NONE = -1, NOM_KIND_SE23 = 0, NOM_KIND_SE3 = 1, NOM_KIND_VEC3 = 2, NOM_KIND_SCALAR = 3, NOM_KIND_LM = 4 };
+#define NOM_DH 4           // doubles in front of the variables' values (gravity)
+#define NOM_VD 16          // doubles per variable
+
+struct NomTable {
+    int* ih;
+    double* dv;
+    int vmax;
+    int ir, dr;            // record lengths: NOM_IH + 4 vmax ints, NOM_DH + NOM_VD vmax doubles
+};
+
+// StateManager::boxPlus (StateManager.cpp:244-251) of filters [b0, b0 + nb) with dx [b][ldx] (row b of the batch); marg != nullptr: then
+// drop the variable whose idx is marg[b] (a window clone, >= 0) and shift every later idx by 6 (StateManager.cpp:155-192)
+void launch_nominal_update(const NomTable& t, const double* dx, int ldx, const int* marg, int b0, int nb, hipStream_t st);

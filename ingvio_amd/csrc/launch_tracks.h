@@ -1,6 +1,7 @@
 // launch_tracks.h — host-side descriptors of kernels_tracks.hip (device-resident track store + per-frame delta hand-over).
 #pragma once
 #include "dev_common.h"
+#include "launch_nominal.h"
 
 // Per-filter header of a staged delta (ints).  Offsets TRK_OFF_* are positions of the filter's slice in the three upload pools
 // (ints / doubles / 64-bit masks); TRK_I_* / TRK_D_* are positions INSIDE that slice.
@@ -9,6 +10,7 @@ enum {
     TRK_OFF_I, TRK_OFF_D, TRK_OFF_M,
     TRK_I_DROP, TRK_I_FREE, TRK_I_OBS, TRK_I_PF, TRK_I_CIDX, TRK_I_FEAT, TRK_I_GNSS,
     TRK_D_OBS, TRK_D_PF, TRK_D_CR, TRK_D_CP, TRK_D_IMU, TRK_D_STATE,
+    TRK_NOM_SLOT, TRK_NOM_IDX, TRK_NOM_NVAR,      // device nominal stage: the new clone's variable slot and idx, the table's slots in use after it
     TRK_HDR_USED, TRK_HDR = 32
 };
 
@@ -31,6 +33,9 @@ struct FrameOut {                       // FrameView with writable pointers (the
     double* uv; int* dof; int cmax, fmax;
 };
 
-void launch_imu_steps(const TrackStage& ts, int b0, int nb, int kst, double* Phi, double* G, double* dt, double* R, hipStream_t st);
+// nom != nullptr: the device-resident nominal state variants (k_imu_steps<true>, k_tracks_gather<true>)
+void launch_imu_steps(const TrackStage& ts, int b0, int nb, int kst, double* Phi, double* G, double* dt, double* R, hipStream_t st,
+                      const NomTable* nom = nullptr);
 void launch_tracks_apply(const TrackStage& ts, const TrackStore& store, int b0, int nb, hipStream_t st);
-void launch_tracks_gather(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st);
+void launch_tracks_gather(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st,
+                          const NomTable* nom = nullptr);

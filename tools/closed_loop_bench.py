@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""What closing the filter loop costs: a batch of filters (default 512, 150 features x 11 clones, k = 10) runs the same
+closed loop of frames twice,
+  host loop    per frame: ingvio_frame_stage_tracks with the host's nominal values, ingvio_frame_run, ingvio_frame_fetch, then boxPlus,
+               the marginalisation's index shift and the IMU nominal integration on the host (ingvio_amd/closed_loop.py: the C oracle's
+               functions, one call per variable - the Python reference, not an optimised host)
+  device loop  the nominal state on the device (ingvio_frame_stage_tracks_nominal), pipelined:
+               run(i); stage_async(i+1); fetch_begin(i); run(i+1); fetch_end(i)
+and reports ms per frame (the host loop split into its phases), the bytes one filter's frame hand-over takes in each mode, and whether
+the two loops agree.  --device-only runs the device loop alone (the rocprofv3 --kernel-trace --stats run for the kernels' times).
+Writes $RESULTS/closed_loop_bench.json (RESULTS defaults to results/) and prints one JSON line.
+usage: python tools/closed_loop_bench.py [--batch 512] [--features 150] [--window 11] [--k 10] [--frames 30] [--warmup 5] [--device-only]"""
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def stage_bytes(cases, f, k, host):
+    """bytes of frame f's upload slab, by the layout frame_stage_tracks_impl (capi.hip) gives it: the [B][32]-int headers, then the int,
+    mask and double pools, each padded to 64 bytes.  Per filter: drop / free / obs / pf tracks, the clone table (host values only: the
+    window with the new clone), the features and 5 clock indices as ints; obs uv (4), points (3), clone poses (12, host values only), IMU
+    samples (7 k) and the start state (24, host values only) as doubles, rounded up to 4"""
+    def pad(b):
+        return (b + 63) & ~63
+    ni = nd = 0
+    for c in cases:
+        d = c["frames"][f]["delta"]
+        nct = c["C"] if host else 0
+        n_obs, n_pf = len(d.get("obs_track", [])), len(d.get("pf_track", []))
+        ni += len(d.get("drop", [])) + len(d.get("free", [])) + n_obs + n_pf + nct + len(d["feat_track"]) + 5
+        od = 4 * n_obs + 3 * n_pf + 12 * nct + 7 * k + (24 if host else 0)
+        nd += (od + 3) & ~3
+    return pad(4 * len(cases) * 32) + pad(4 * ni) + pad(8 * nd)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--features", type=int, default=150)
+    ap.add_argument("--window", type=int, default=11)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--frames", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--device-only", action="store_true")
+    a = ap.parse_args()
+    from oracle import oracle as orc
+    from ingvio_amd import closed_loop as cl
+    B, F, NF, W = a.batch, a.features, a.frames, a.warmup
+    t0 = time.perf_counter()
+    cases = cl.make_loop(B, NF, F=F, ks=(a.k,), windows=(a.window,))
+    out = dict(batch=B, features=F, window=a.window, k=a.k, frames_timed=NF - W, setup_s=round(time.perf_counter() - t0, 1))
+
+    # device loop, pipelined
+    ctx = cl.loop_ctx(cases, F, c_max=a.window + 1)
+    ctx.nominal_create(64)
+    ctx.nominal_set(0, [c["table"].as_dict() for c in cases])
+    calls = [cl.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
+    calls[0]()
+    ctx.frame_run()
+    dev_res = []
+    for f in range(NF):
+        if f == W:
+            ctx.sync()
+            t0 = time.perf_counter()
+        if f + 1 < NF:
+            calls[f + 1]()
+            ctx.frame_fetch_begin()
+            ctx.frame_run()
+            dev_res.append(ctx.frame_fetch_end())
+        else:
+            dev_res.append(ctx.frame_fetch())
+    out["device_loop_ms_per_frame"] = round(1e3 * (time.perf_counter() - t0) / (NF - W), 4)
+    dev_nom = ctx.nominal_get()
+    ctx.close()
+    timed = range(W, NF)
+    out["bytes_per_filter_host"] = round(sum(stage_bytes(cases, f, a.k, True) for f in timed) / (len(timed) * B), 1)
+    out["bytes_per_filter_device"] = round(sum(stage_bytes(cases, f, a.k, False) for f in timed) / (len(timed) * B), 1)
+    if a.device_only:
+        print(json.dumps(out))
+        return
+
+    # host loop, phase by phase
+    ctx = cl.loop_ctx(cases, F, c_max=a.window + 1)
+    tabs = [copy.deepcopy(c["table"]) for c in cases]
+    opts_frame, sigma, eg, scb, srw = cl.stage_args(cases)
+    ph = dict(host_imu=0.0, stage=0.0, run_fetch=0.0, host_box_plus=0.0)
+    worst = 0.0
+    for f in range(NF):
+        timed = f >= W
+        t = time.perf_counter()
+        steps, tfs = [], []
+        for c, tb in zip(cases, tabs):
+            fr = c["frames"][f]
+            e, bg, ba = tb.slots[tb.v_pose], tb.slots[tb.v_bg], tb.slots[tb.v_ba]
+            raw = dict(imu=fr["imu"], R=e["R"], p=e["p"], v=e["v"], bg=bg["p"], ba=ba["p"], gravity=tb.gravity)
+            R, p, v = e["R"], e["p"], e["v"]
+            for q in range(fr["imu"].shape[0]):
+                R, p, v, _, _ = orc.imu_transition(R, p, v, bg["p"], ba["p"], fr["imu"][q, :3], fr["imu"][q, 3:6], tb.gravity, fr["imu"][q, 6])
+            e["R"], e["p"], e["v"] = R, p, v
+            tb.append_clone(fr["new_idx"])
+            steps.append(dict(raw=raw, gnss_idx=c["step"]["gnss_idx"], marg_idx=fr["marg"]))
+            clo = [tb.slots[s] for s in tb.clones]
+            tfs.append(dict(fr["delta"], clone_idx=[s["idx"] for s in clo], clone_R=np.stack([s["R"] for s in clo]),
+                            clone_p=np.stack([s["p"] for s in clo])))
+        t1 = time.perf_counter()
+        ctx.frame_stage_tracks_prepare(0, steps, tfs, opts_frame, sigma, eg, scb, srw)()
+        t2 = time.perf_counter()
+        ctx.frame_run()
+        dx, acc, rows = ctx.frame_fetch()
+        t3 = time.perf_counter()
+        for b, (c, tb) in enumerate(zip(cases, tabs)):
+            tb.box_plus(dx[b])
+            tb.marginalize(c["frames"][f]["marg"])
+        t4 = time.perf_counter()
+        if timed:
+            ph["host_imu"] += t1 - t; ph["stage"] += t2 - t1; ph["run_fetch"] += t3 - t2; ph["host_box_plus"] += t4 - t3
+        d = dev_res[f][0]
+        worst = max(worst, float(np.max(np.abs(d - dx)) / max(np.max(np.abs(dx)), 1e-300)))
+    ctx.close()
+    for key in ph:
+        out["host_loop_ms_" + key] = round(1e3 * ph[key] / (NF - W), 3)
+    out["host_loop_ms_per_frame"] = round(sum(out["host_loop_ms_" + key] for key in ph), 3)
+    out["max_rel_dx_device_vs_host"] = worst
+    out["max_rel_pose_device_vs_host"] = max(float(np.max(np.abs(dev_nom[b]["val"][tabs[b].v_pose] - tabs[b].as_dict()["val"][tabs[b].v_pose])))
+                                             for b in range(B))
+    res_dir = os.environ.get("RESULTS", os.path.join(ROOT, "results"))
+    os.makedirs(res_dir, exist_ok=True)
+    with open(os.path.join(res_dir, "closed_loop_bench.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
