@@ -531,6 +531,43 @@ typedef struct {
 int ingvio_frame_stage_tracks_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,
                                       const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double sigma_cb, double sigma_rw,
                                       int async);
+/* ---- GNSS epochs in the device-resident closed loop ------------------------------------------------------------
+ * Names the GNSS scalars of filters [b0, b0 + nb)'s tables: slots [nb][6] = the table slots of the clock biases GPS, GLO, GAL, BDS, then
+ * FS, then YOF (State::GNSSType order, State.h:75); -1: not in the state.  From then on
+ *   - ingvio_frame_stage_tracks_nominal with enable_gnss != 0 advances every registered clock with the frequency shift at each IMU sample,
+ *     cb_s += dt_q * fs in the samples' order (ImuPropagator.cpp:139-148: _enable_gnss, the clock and FS in the state), on the device;
+ *   - ingvio_gnss_front_stage_nominal reads the receiver state from the table.
+ * The slots are part of the table's integer record: cleared by ingvio_nominal_create and by an ingvio_nominal_set of the filter, copied by
+ * ingvio_cov_snapshot / _restore.  INGVIO_E_ARG, nothing changed: no table, a slot out of range, named twice or not an INGVIO_NOM_SCALAR,
+ * a frame or a GNSS epoch staged from the table that has not run.  A filter that never registers runs exactly as before. */
+int ingvio_nominal_set_gnss(ingvio_ctx* ctx, int b0, int nb, const int* slots /* [nb][6] */);
+int ingvio_nominal_get_gnss(ingvio_ctx* ctx, int b0, int nb, int* slots /* [nb][6] */);
+/* ingvio_gnss_front_stage with the receiver taken from the device table: the epoch carries only what the host owns.  p_w, v_w
+ * (State::_extended_pose), the clock biases, FS and YOF (GnssUpdate.cpp:98-122 reads them from the state) and every Type::idx() come
+ * from the filter's table as the frame that has just run left it - IngvioFilter.cpp:329-362 runs after :276-327 and after margSwPose,
+ * so the idx are the shifted ones - on the context's stream, without a host round trip; the host-side checks of ingvio_gnss_front_stage
+ * (INGVIO_E_NOT_IN_STATE, the capacity checks) are made on the host mirror of the table.  n_sat = 0: no epoch for that filter.
+ * The following ingvio_gnss_run (same range, once: a second one is INGVIO_E_ARG) ends with StateManager::boxPlus of the update's dx on
+ * the table, on the device (StateManager.cpp:244-251 after GnssUpdate.cpp:290), and keeps its dx / row count / status apart from the
+ * frame's, so that ingvio_frame_fetch(_begin / _end) of the same frame is valid before or after it.  ingvio_gnss_fetch is optional.
+ *   run(i); fetch_begin(i); gnss_front_stage_nominal(i); gnss_run(i); stage_tracks_nominal(i + 1, async); run(i + 1); fetch_end(i)
+ * is a closed loop without a host synchronisation.
+ * The stage replaces whatever GNSS rows the context holds staged and not yet run, of any range (one GNSS stage at a time).  If the run
+ * itself is refused (INGVIO_E_NOT_IN_STATE, INGVIO_E_CAPACITY of the row gate: both before its first launch) the epoch stays staged.
+ * Refused before anything changes: no table (whatever the epochs hold, also when none has a satellite), no registered scalars for a
+ * filter with n_sat > 0, a frame staged from the table that has not run (INGVIO_E_ARG); opts->in_frame (INGVIO_E_UNSUPPORTED); the extended pose, YOF or FS not in the table with n_sat > 0
+ * (INGVIO_E_NOT_IN_STATE).  While such an epoch is staged and has not run, ingvio_frame_stage_tracks_nominal, ingvio_nominal_set /
+ * _box_plus / _set_gnss and ingvio_cov_snapshot return INGVIO_E_ARG; ingvio_cov_restore abandons it. */
+typedef struct {
+    int n_sat;                                /* <= INGVIO_GNSS_MAX_SAT; 0: no epoch                                   */
+    const double* eph;                        /* [n_sat][INGVIO_EPH_N]                                                 */
+    const double* obs;                        /* [n_sat][INGVIO_OBS_N]                                                 */
+    const double* ion;                        /* [8] Klobuchar parameters or NULL                                      */
+    double doy;
+    double R_enu2ecef[9], anchor_ecef[3];     /* GvioAligner::getRenu2ecef (row-major), translation of getTenu2ecef    */
+    double psr_noise_amp, dopp_noise_amp;     /* GnssUpdate::_psr_noise_amp / _dopp_noise_amp                          */
+} ingvio_gnss_epoch_nominal;
+int ingvio_gnss_front_stage_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_gnss_epoch_nominal* epochs, const ingvio_gnss_opts* opts);
 int ingvio_frame_run(ingvio_ctx* ctx, int restore_prior);
 /* Throughput batches (round 6, an experiment kept selectable): ingvio_frame_run deals the batch to `parts` slices of filters, each
  * on its own HIP stream; the slices' throughput-bound segments (gate + Gram, apply) are chained by events so that only ONE runs at a

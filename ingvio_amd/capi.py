@@ -33,6 +33,7 @@ EXPORTS = [
     "ingvio_info_reduce", "ingvio_info_commit", "ingvio_gnss_sat_eval",
     "ingvio_chi2_gamma_multi", "ingvio_ekf_update_batch", "ingvio_add_variable_delayed_invertible", "ingvio_add_variable_delayed", "ingvio_replace_var_linear",
     "ingvio_nominal_create", "ingvio_nominal_set", "ingvio_nominal_get", "ingvio_nominal_box_plus", "ingvio_frame_stage_tracks_nominal",
+    "ingvio_nominal_set_gnss", "ingvio_nominal_get_gnss", "ingvio_gnss_front_stage_nominal",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -60,6 +61,12 @@ class GnssEpoch(C.Structure):
                 ("doy", C.c_double), ("p_w", C.c_double * 3), ("v_w", C.c_double * 3), ("cb", C.c_double * 4), ("fs", C.c_double),
                 ("yaw_offset", C.c_double), ("R_enu2ecef", C.c_double * 9), ("anchor_ecef", C.c_double * 3), ("idx_se23", C.c_int),
                 ("idx_yof", C.c_int), ("idx_fs", C.c_int), ("idx_cb", C.c_int * 4), ("psr_noise_amp", C.c_double),
+                ("dopp_noise_amp", C.c_double)]
+
+
+class GnssEpochNominal(C.Structure):
+    _fields_ = [("n_sat", C.c_int), ("eph", C.POINTER(C.c_double)), ("obs", C.POINTER(C.c_double)), ("ion", C.POINTER(C.c_double)),
+                ("doy", C.c_double), ("R_enu2ecef", C.c_double * 9), ("anchor_ecef", C.c_double * 3), ("psr_noise_amp", C.c_double),
                 ("dopp_noise_amp", C.c_double)]
 
 
@@ -463,12 +470,49 @@ class Context:
     def gnss_front_stage(self, b0, epochs, chi2_table, gate_rows=True, strong_reject=False):
         """epochs: per filter a dict(eph [ns,25], obs [ns,6], ion [8] or None, doy, p_w, v_w, cb [4], fs, yaw_offset, R_enu2ecef [3,3],
         anchor_ecef, idx_se23, idx_yof, idx_fs, idx_cb [4], psr_amp, dopp_amp): raw GNSS epochs -> candidate rows on the device."""
+        self.gnss_front_stage_prepare(b0, epochs, chi2_table, gate_rows, strong_reject)()
+
+    def gnss_front_stage_prepare(self, b0, epochs, chi2_table, gate_rows=True, strong_reject=False):
+        """builds the C arguments of gnss_front_stage once and returns a callable that issues the stage"""
         nb = len(epochs)
         arr, keep = self._gnss_epochs(epochs)
         tab = f64(chi2_table)
         o = GnssOpts(); o.gate_rows = int(gate_rows); o.strong_reject = int(strong_reject); o.chi2_table = _d(tab); o.chi2_len = len(tab)
-        self._chk(self.L.ingvio_gnss_front_stage(self.h, b0, nb, arr, C.byref(o)))
-        self._gnss_range = (b0, nb)
+
+        def call(_keep=(keep, tab, arr, o)):
+            self._chk(self.L.ingvio_gnss_front_stage(self.h, b0, nb, arr, C.byref(o)))
+            self._gnss_range = (b0, nb)
+        return call
+
+    def gnss_front_stage_nominal_prepare(self, b0, epochs, chi2_table, gate_rows=True, strong_reject=False, in_frame=False):
+        """ingvio_gnss_front_stage_nominal: epochs per filter a dict(eph, obs, ion, doy, R_enu2ecef, anchor_ecef, psr_amp, dopp_amp) or None
+        (no epoch: n_sat = 0); the receiver state comes from the device nominal table.  Returns a callable that issues the stage."""
+        nb = len(epochs)
+        arr = (GnssEpochNominal * nb)(); keep = []
+        for i, e in enumerate(epochs):
+            a = arr[i]
+            if e is None:
+                a.n_sat = 0
+                continue
+            eph, obs = f64(e["eph"]), f64(e["obs"])
+            ion = f64(e["ion"]) if e.get("ion") is not None else None
+            keep.append((eph, obs, ion))
+            a.n_sat = eph.shape[0]; a.eph = _d(eph); a.obs = _d(obs); a.ion = _d(ion) if ion is not None else None
+            a.doy = float(e["doy"])
+            a.R_enu2ecef = (C.c_double * 9)(*np.asarray(e["R_enu2ecef"], dtype=np.float64).reshape(9))
+            a.anchor_ecef = (C.c_double * 3)(*e["anchor_ecef"])
+            a.psr_noise_amp = float(e.get("psr_amp", 1.0)); a.dopp_noise_amp = float(e.get("dopp_amp", 1.0))
+        tab = f64(chi2_table)
+        o = GnssOpts(); o.gate_rows = int(gate_rows); o.strong_reject = int(strong_reject); o.chi2_table = _d(tab); o.chi2_len = len(tab)
+        o.in_frame = int(in_frame)
+
+        def call(_keep=(keep, tab, arr, o)):
+            self._chk(self.L.ingvio_gnss_front_stage_nominal(self.h, int(b0), nb, arr, C.byref(o)))
+            self._gnss_range = (b0, nb)
+        return call
+
+    def gnss_front_stage_nominal(self, b0, epochs, chi2_table, gate_rows=True, strong_reject=False, in_frame=False):
+        self.gnss_front_stage_nominal_prepare(b0, epochs, chi2_table, gate_rows, strong_reject, in_frame)()
 
     def gnss_front_fetch(self, b0=None, nb=None):
         """-> [nb, 64, 20]: res_pos, res_vel, los (3), az, el, ion, tro, usable, then the SatState: pos (3), vel (3), dt, ddt, tgd, ttx"""
@@ -737,6 +781,17 @@ class Context:
                             clone_var=bf["clone_var"][:c].copy(), v_ext=q.v_ext, v_pose=q.v_pose, v_bg=q.v_bg, v_ba=q.v_ba,
                             gravity=np.array(q.gravity[:])))
         return out
+
+    def nominal_set_gnss(self, b0, slots):
+        """slots [nb][6]: table slots of the clock biases GPS, GLO, GAL, BDS, then FS, then YOF; -1: not in the state (ingvio_nominal_set_gnss)"""
+        sl = i32(np.asarray(slots, dtype=np.int32).reshape(-1, 6))
+        self._chk(self.L.ingvio_nominal_set_gnss(self.h, int(b0), sl.shape[0], _i(sl)))
+
+    def nominal_get_gnss(self, b0=0, nb=None):
+        nb = self.batch if nb is None else nb
+        sl = np.zeros((nb, 6), dtype=np.int32)
+        self._chk(self.L.ingvio_nominal_get_gnss(self.h, int(b0), nb, _i(sl)))
+        return sl
 
     def nominal_box_plus(self, b0, dx):
         """StateManager::boxPlus on the device: dx [nb][ldp] in the live index space (ingvio_nominal_box_plus)"""

@@ -125,6 +125,14 @@ struct ingvio_ctx {
         int nc_max = 0;
         double *W = nullptr, *Yf = nullptr, *dxf = nullptr;
         int *mf = nullptr, *ncf = nullptr;
+        // stage from the device nominal state (ingvio_gnss_front_stage_nominal): its run keeps row count, column count, dx
+        // AND status apart from the frame's (stf [B]), ends with the retraction of the table and therefore runs once
+        // own_status: the status words of the update that ran last are in stf, not in the frame's d_status.  Set by the nominal
+        // ingvio_gnss_run and kept after it, so that ingvio_gnss_fetch reads the right words for as long as those results are the
+        // current ones; cleared by the next stage of any form (ingvio_gnss_stage, both front stages).
+        bool nominal = false, nom_pending = false, own_status = false;
+        int nom_b0 = 0, nom_nb = 0;
+        int* stf = nullptr;
     } gn;
     // dense-H update workspace (kernels_lmbatch.hip + kernels_chol.hip): the batched landmark update and generic updates whose S
     // does not fit in LDS.  Rows live in Hd [m_cap][n_ld] per filter, the sweep in X / Y [ldx][m_cap].
@@ -324,6 +332,14 @@ int nom_mark(ingvio_ctx* c)
     return 0;
 }
 NomTable nom_table(ingvio_ctx* c) { return NomTable{ c->nom.ih, c->nom.dv, c->nom.vmax, c->nom.ir, c->nom.dr }; }
+// a GNSS epoch staged from the table (ingvio_gnss_front_stage_nominal) whose update has not run: its rows are linearised at the table's
+// present values, so nothing else may move the table or the covariance's bookkeeping in between
+int gnss_nom_busy(ingvio_ctx* c, const char* who)
+{
+    if (!c || !c->gn.nom_pending) return 0;
+    c->err = std::string(who) + ": a GNSS epoch staged from the device nominal state has not run yet";
+    return 1;
+}
 
 // the marginalisation on the host mirror of filter b's integer record, exactly as k_nominal_update<true> does it on the device
 void nom_mirror_marg(ingvio_ctx* c, int b, int m)
@@ -1175,6 +1191,7 @@ int ingvio_cov_snapshot(ingvio_ctx* c)
     if (phase_busy(c)) return INGVIO_E_ARG;
     if (!c) return INGVIO_E_ARG;
     if (c->nom.pending) { c->err = "ingvio_cov_snapshot: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, "ingvio_cov_snapshot")) return INGVIO_E_ARG;
     launch_snapshot(view(c), c->d.n_max, c->Psnap, c->d_n_snap, c->st);
     c->h_n_snap = c->h_n;
     c->has_snap = true;
@@ -1205,6 +1222,7 @@ int ingvio_cov_restore(ingvio_ctx* c)
         auto& m = c->nom;
         if (m.pending) { c->staged = false; m.pending = false; }      // the staged frame's clone is not in the restored table
         m.frame = false;
+        if (c->gn.nom_pending) { c->gn.nom_pending = false; c->gn.staged = false; }      // rows linearised at the abandoned table
         if (wait_inputs(c)) return INGVIO_E_HIP;                     // an asynchronous stage from the table must land before it is overwritten
         HIPCHK(c, hipMemcpyAsync(m.ih, m.ih_snap, sizeof(int) * (size_t)c->d.batch * m.ir, hipMemcpyDeviceToDevice, c->st));
         HIPCHK(c, hipMemcpyAsync(m.dv, m.dv_snap, sizeof(double) * (size_t)c->d.batch * m.dr, hipMemcpyDeviceToDevice, c->st));
@@ -1627,6 +1645,7 @@ int ingvio_gnss_stage(ingvio_ctx* c, int b0, int nb, const ingvio_update_block* 
     g.in_frame = o->in_frame != 0;
     g.fused_last = false;
     g.results = false;
+    g.nominal = false; g.nom_pending = false; g.own_status = false;
     if (g.in_frame && !g.W) {
         const size_t B = c->d.batch, ws = (size_t)c->ldp * 16;
         if (dalloc(c, &g.W, B * ws) | dalloc(c, &g.Yf, B * ws) | dalloc(c, &g.dxf, B * (size_t)c->ldp) | dalloc(c, &g.mf, B) | dalloc(c, &g.ncf, B)) return INGVIO_E_HIP;
@@ -1641,9 +1660,10 @@ int ingvio_gnss_stage(ingvio_ctx* c, int b0, int nb, const ingvio_update_block* 
 static int gnss_run_separate(ingvio_ctx* c, int b0, int nb, bool own_slots = false);
 
 // raw GNSS epochs -> candidate rows, on the device (kernels_gnss.hip)
-int ingvio_gnss_front_stage(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epoch* ep, const ingvio_gnss_opts* o)
+// nominal: the receiver state and the idx_* the kernel uses come from the device nominal table (the epochs' idx_* are the host mirror's, for
+// the checks below; p_w, v_w, cb, fs, yaw_offset are not read)
+static int gnss_front_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epoch* ep, const ingvio_gnss_opts* o, bool nominal)
 {
-    ENTER(c);
     static_assert(GNSS_FRONT_NCW == GNSS_NCW, "column stride of the staged rows");
     if (check_range(c, b0, nb) || !ep || !o) return INGVIO_E_ARG;
     if ((o->gate_rows || o->strong_reject) && (!o->chi2_table || o->chi2_len < 2 || o->chi2_len > CHI2_CAP)) return INGVIO_E_ARG;
@@ -1667,6 +1687,13 @@ int ingvio_gnss_front_stage(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epo
     if (!g.front) {
         rc |= dalloc(c, &g.feph, B * INGVIO_GNSS_MAX_SAT * GE_N); rc |= dalloc(c, &g.fobs, B * INGVIO_GNSS_MAX_SAT * GO_N);
         rc |= dalloc(c, &g.frcv, B * GR_N); rc |= dalloc(c, &g.front, B * 64 * GF_N);
+        if (rc) return INGVIO_E_HIP;
+    }
+    if (nominal) {                                  // the run's own result slots (shared with an in-frame stage) and status words
+        if (!g.dxf) rc |= dalloc(c, &g.dxf, B * (size_t)c->ldp);
+        if (!g.mf) rc |= dalloc(c, &g.mf, B);
+        if (!g.ncf) rc |= dalloc(c, &g.ncf, B);
+        if (!g.stf) rc |= dalloc(c, &g.stf, B);
         if (rc) return INGVIO_E_HIP;
     }
     const size_t S = INGVIO_GNSS_MAX_SAT;
@@ -1707,18 +1734,75 @@ int ingvio_gnss_front_stage(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epo
     L.front = g.front + (size_t)b0 * 64 * GF_N;
     L.H = g.H + (size_t)b0 * hs; L.res = g.res + (size_t)b0 * mld; L.noise = g.noise + (size_t)b0 * mld;
     L.m = g.m + b0; L.nc = g.nc + b0; L.colmap = g.colmap + (size_t)b0 * GNSS_NCW; L.mld = c->mld; L.hstride = (int)hs;
-    launch_gnss_front(L, nb, c->st);
+    const NomTable nt = nom_table(c);
+    launch_gnss_front(L, nb, c->st, nominal ? &nt : nullptr, b0);
     for (int i = 0; i < nb; ++i) g.hi[b0 + i] = his[i];
     g.gate_rows = o->gate_rows ? 1 : 0; g.strong = o->strong_reject ? 1 : 0;
     g.thr1 = o->gate_rows ? o->chi2_table[1] : __builtin_inf();
-    const int m_cap = 2 * smax;
+    int m_cap = 2 * smax;
+    // its own stage, never merged with an earlier one: GNSS rows of any range staged before and not yet run are dropped (documented in
+    // the header); no satellite anywhere: no rows
+    if (nominal) {
+        g.staged = false;
+        bool any = false;
+        for (int i = 0; i < nb; ++i) if (ep[i].n_sat > 0) any = true;
+        if (!any) m_cap = 0;
+    }
     if (!g.staged || m_cap > g.m_cap) g.m_cap = m_cap;
     // the front builds the reference's var_order [SE23, YOF, <= 4 clocks, FS] = at most 15 columns; a front-staged update is applied
     // by ingvio_gnss_run (the flags of an earlier in-frame ingvio_gnss_stage must not leak into this stage)
     if (o->in_frame) { c->err = "ingvio_gnss_front_stage: in_frame is not supported (stage the rows with ingvio_gnss_stage)"; return INGVIO_E_UNSUPPORTED; }
     g.in_frame = false; g.nc_max = 15; g.fused_last = false; g.results = false;
+    g.nominal = nominal; g.nom_pending = nominal; g.own_status = false; g.nom_b0 = b0; g.nom_nb = nb;
     g.staged = true;
     return last_launch(c);
+}
+
+int ingvio_gnss_front_stage(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epoch* ep, const ingvio_gnss_opts* o)
+{
+    ENTER(c);
+    return gnss_front_stage_impl(c, b0, nb, ep, o, false);
+}
+
+// the host mirror of filter b's integer record: idx of the variable in slot `slot` (-1: none)
+static int nom_idx_of(const ingvio_ctx* c, int b, int slot)
+{
+    return slot >= 0 ? c->nom.h_ih[(size_t)b * c->nom.ir + NOM_IH + 4 * slot + 1] : -1;
+}
+
+int ingvio_gnss_front_stage_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epoch_nominal* ep, const ingvio_gnss_opts* o)
+{
+    ENTER(c);
+    if (phase_busy(c) || check_range(c, b0, nb) || !ep || !o) return INGVIO_E_ARG;
+    if (o->in_frame) { c->err = "ingvio_gnss_front_stage_nominal: in_frame is not supported"; return INGVIO_E_UNSUPPORTED; }
+    auto& m = c->nom;
+    // without a table there is nothing the kernel could read, whatever the epochs hold (also when none has a satellite)
+    if (!m.vmax) { c->err = "ingvio_gnss_front_stage_nominal without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = "ingvio_gnss_front_stage_nominal: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    // the receiver's variables, from the host mirror of the table (no device round trip): what ingvio_gnss_front_stage checks on the
+    // epoch's idx_* is checked on these
+    std::vector<ingvio_gnss_epoch> full((size_t)nb);
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_gnss_epoch_nominal& e = ep[i];
+        ingvio_gnss_epoch& f = full[i];
+        memset(&f, 0, sizeof f);
+        f.n_sat = e.n_sat; f.eph = e.eph; f.obs = e.obs; f.ion = e.ion; f.doy = e.doy;
+        memcpy(f.R_enu2ecef, e.R_enu2ecef, sizeof f.R_enu2ecef); memcpy(f.anchor_ecef, e.anchor_ecef, sizeof f.anchor_ecef);
+        f.psr_noise_amp = e.psr_noise_amp; f.dopp_noise_amp = e.dopp_noise_amp;
+        f.idx_se23 = f.idx_yof = f.idx_fs = -1;
+        for (int s = 0; s < 4; ++s) f.idx_cb[s] = -1;
+        if (e.n_sat <= 0) continue;                 // (n_sat < 0 is refused below; 0: no epoch for this filter)
+        const int b = b0 + i;
+        const int* I = &m.h_ih[(size_t)b * m.ir];
+        bool reg = false;
+        for (int s = 0; s < 6; ++s) if (I[NOM_GNSS + s] >= 0) reg = true;
+        if (!reg) { c->err = "ingvio_gnss_front_stage_nominal: no GNSS scalars registered for the filter (ingvio_nominal_set_gnss)"; return INGVIO_E_ARG; }
+        f.idx_se23 = nom_idx_of(c, b, I[NOM_V_POSE]);
+        f.idx_yof = nom_idx_of(c, b, I[NOM_GNSS + NOM_G_YOF]);
+        f.idx_fs = nom_idx_of(c, b, I[NOM_GNSS + NOM_G_FS]);
+        for (int s = 0; s < 4; ++s) f.idx_cb[s] = nom_idx_of(c, b, I[NOM_GNSS + s]);
+    }
+    return gnss_front_stage_impl(c, b0, nb, full.data(), o, true);
 }
 
 // gnss_comm::sat_states + psr_res + dopp_res for an arbitrary list of epochs, detached from the filters of the context and from
@@ -1791,7 +1875,29 @@ int ingvio_gnss_run(ingvio_ctx* c, int b0, int nb)
     if (phase_busy(c)) return INGVIO_E_ARG;
     if (check_range(c, b0, nb) || !c->gn.staged) return INGVIO_E_ARG;
     if (c->gn.in_frame) { c->err = "the staged GNSS update is in-frame: ingvio_frame_run applies it"; return INGVIO_E_ARG; }
-    return gnss_run_separate(c, b0, nb);
+    if (!c->gn.nominal) return gnss_run_separate(c, b0, nb);
+    // ---- staged from the device nominal state: the update, then StateManager::boxPlus of its dx on the table, once ----
+    auto& g = c->gn;
+    if (b0 != g.nom_b0 || nb != g.nom_nb) { c->err = "ingvio_gnss_run: a stage from the device nominal state runs on the range it was staged for"; return INGVIO_E_ARG; }
+    if (c->nom.pending) { c->err = "ingvio_gnss_run: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    for (int i = 0; i < nb; ++i) if (g.hi[b0 + i] > c->h_n[b0 + i]) return INGVIO_E_NOT_IN_STATE;      // before anything changes
+    HIPCHK(c, hipMemsetAsync(g.dxf + (size_t)b0 * c->ldp, 0, 8 * (size_t)nb * c->ldp, c->st));       // dx = 0 beyond the live n and without rows
+    HIPCHK(c, hipMemsetAsync(g.stf + b0, 0, sizeof(int) * (size_t)nb, c->st));
+    HIPCHK(c, hipMemsetAsync(g.mf + b0, 0, sizeof(int) * (size_t)nb, c->st));
+    // a refusal of the pass below (INGVIO_E_CAPACITY of the row gate's LDS check) comes before its first launch: the stage then stays
+    // pending with its rows and the table is untouched (the stage's own result slots have been cleared: nothing to fetch)
+    const bool own_before = g.own_status, fused_before = g.fused_last, results_before = g.results;
+    g.own_status = true;
+    if (int rc = gnss_run_separate(c, b0, nb, true)) {
+        if (rc != INGVIO_E_HIP) { g.own_status = own_before; g.fused_last = fused_before; g.results = results_before; }
+        return rc;
+    }
+    g.nom_pending = false; g.staged = false;       // consumed: the table moves with this run, a second one is refused
+    if (g.m_cap > 0) {                              // rejected block / no epoch: dx = 0, the retraction's small-angle branch is the identity
+        launch_nominal_update(nom_table(c), g.dxf, c->ldp, nullptr, b0, nb, c->st);
+        if (int rc = last_launch(c)) return rc;
+    }
+    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
 }
 
 // own_slots: called by ingvio_frame_run for an in-frame stage - row count, column count and dx go to the stage's own buffers (the
@@ -1823,7 +1929,7 @@ static int gnss_run_separate(ingvio_ctx* c, int b0, int nb, bool own_slots)
     E.colmap = c->d_colmap + (size_t)b0 * GNSS_NCW; E.m = (own_slots ? g.mf : c->d_m) + b0; E.nc = (own_slots ? g.ncf : c->d_nc) + b0;
     E.noise = c->d_noiseB + (size_t)b0 * mld; E.r_kind = INGVIO_R_DIAG; E.mld = c->mld; E.hstride = (int)hs; E.cstride = GNSS_NCW;
     E.nstride = c->mld; E.Y = c->d_Y + (size_t)b0 * c->ystride; E.ystride = c->ystride; E.dx = own_slots ? g.dxf : c->d_dx;
-    E.status = c->d_status; E.m_cap = g.m_cap; E.nc_cap = GNSS_NCW;
+    E.status = g.own_status ? g.stf : c->d_status; E.m_cap = g.m_cap; E.nc_cap = GNSS_NCW;
     if (g.strong) { E.chi2 = g.chi2; E.chi2_len = g.chi2_len; E.gate_max_rows = 14; }      // GnssUpdate.cpp:286
     RowsGateIn in{ g.H + (size_t)b0 * hs, g.res + (size_t)b0 * mld, g.noise + (size_t)b0 * mld, g.m + b0, g.colmap + (size_t)b0 * GNSS_NCW,
                    g.nc + b0, (int)hs, GNSS_NCW };
@@ -1848,7 +1954,7 @@ int ingvio_gnss_fetch(ingvio_ctx* c, int b0, int nb, double* dx_out, int* rows_o
     if (rows_out) HIPCHK(c, hipMemcpyAsync(rows_out, (fz ? c->gn.mf : c->d_m) + b0, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, c->st));
     if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, c->gn.keep + (size_t)b0 * mld, sizeof(int) * (size_t)nb * mld, hipMemcpyDeviceToHost, c->st));
     if (gamma_out) HIPCHK(c, hipMemcpyAsync(gamma_out, c->gn.gamma + (size_t)b0 * mld, 8 * (size_t)nb * mld, hipMemcpyDeviceToHost, c->st));
-    if (down_sync(c, status.data(), c->d_status + b0, sizeof(int) * (size_t)nb)) return INGVIO_E_HIP;
+    if (down_sync(c, status.data(), (c->gn.own_status ? c->gn.stf : c->d_status) + b0, sizeof(int) * (size_t)nb)) return INGVIO_E_HIP;
     int rc = last_launch(c);
     if (rc) return rc;
     int soft = INGVIO_OK;
@@ -2682,7 +2788,7 @@ static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_f
         h[TRK_N_DROP] = f.n_drop; h[TRK_APPEND] = f.append_slot; h[TRK_N_OBS] = f.n_obs; h[TRK_N_FREE] = f.n_free; h[TRK_N_PF] = f.n_pf;
         h[TRK_N_CLONES] = f.n_clones; h[TRK_N_FEAT] = f.n_feat; h[TRK_K] = s.k; h[TRK_HAS_SEL] = f.feat_sel ? 1 : 0; h[TRK_MARG] = s.marg_idx;
         h[TRK_OFF_I] = (int)ni; h[TRK_OFF_D] = (int)nd; h[TRK_OFF_M] = (int)nm;
-        if (plan) { h[TRK_NOM_SLOT] = plan[4 * i]; h[TRK_NOM_IDX] = plan[4 * i + 1]; h[TRK_NOM_NVAR] = plan[4 * i + 3]; }
+        if (plan) { h[TRK_NOM_SLOT] = plan[4 * i]; h[TRK_NOM_IDX] = plan[4 * i + 1]; h[TRK_NOM_NVAR] = plan[4 * i + 3]; h[TRK_NOM_CLK] = enable_gnss ? 1 : 0; }
         int oi = 0, od = 0;
         h[TRK_I_DROP] = oi; oi += f.n_drop;
         h[TRK_I_FREE] = oi; oi += f.n_free;
@@ -2870,6 +2976,7 @@ int ingvio_nominal_create(ingvio_ctx* c, int v_max)
     for (size_t b = 0; b < B; ++b) {
         int* I = &m.h_ih[b * m.ir];
         I[NOM_V_EXT] = I[NOM_V_POSE] = I[NOM_V_BG] = I[NOM_V_BA] = -1;
+        for (int s = 0; s < 6; ++s) I[NOM_GNSS + s] = -1;
         for (int v = 0; v < v_max; ++v) { I[NOM_IH + 4 * v] = NOM_KIND_NONE; I[NOM_IH + 4 * v + 1] = -1; I[NOM_IH + 4 * v + 2] = -1; }
     }
     HIPCHK(c, hipMemcpyAsync(m.ih, m.h_ih.data(), sizeof(int) * m.h_ih.size(), hipMemcpyHostToDevice, c->st));
@@ -2878,6 +2985,7 @@ int ingvio_nominal_create(ingvio_ctx* c, int v_max)
     m.has_snap = false;
     if (m.pending) { c->staged = false; m.pending = false; }
     m.frame = false;
+    if (c->gn.nom_pending) { c->gn.nom_pending = false; c->gn.staged = false; }
     return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
 }
 
@@ -2888,6 +2996,7 @@ int ingvio_nominal_set(ingvio_ctx* c, int b0, int nb, const ingvio_nominal* nom)
     auto& m = c->nom;
     if (!m.vmax) { c->err = "ingvio_nominal_set without ingvio_nominal_create"; return INGVIO_E_ARG; }
     if (m.pending) { c->err = "ingvio_nominal_set: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, "ingvio_nominal_set")) return INGVIO_E_ARG;
     // ---- validation of every filter before anything is written ----
     for (int i = 0; i < nb; ++i) {
         const ingvio_nominal& q = nom[i];
@@ -2917,6 +3026,7 @@ int ingvio_nominal_set(ingvio_ctx* c, int b0, int nb, const ingvio_nominal* nom)
         double* D = &dv[(size_t)i * m.dr];
         I[NOM_N_VAR] = q.n_var; I[NOM_N_CLONES] = q.n_clones;
         I[NOM_V_EXT] = q.v_ext; I[NOM_V_POSE] = q.v_pose; I[NOM_V_BG] = q.v_bg; I[NOM_V_BA] = q.v_ba;
+        for (int s = 0; s < 6; ++s) I[NOM_GNSS + s] = -1;                  // a new table: the GNSS scalars are registered again
         for (int a = 0; a < q.n_clones; ++a) I[NOM_CLONES + a] = q.clone_var[a];
         for (int v = 0; v < m.vmax; ++v) {
             const bool used = v < q.n_var && q.kind[v] != NOM_KIND_NONE;
@@ -2971,6 +3081,7 @@ int ingvio_nominal_box_plus(ingvio_ctx* c, int b0, int nb, const double* dx)
     auto& m = c->nom;
     if (!m.vmax) { c->err = "ingvio_nominal_box_plus without ingvio_nominal_create"; return INGVIO_E_ARG; }
     if (m.pending) { c->err = "ingvio_nominal_box_plus: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, "ingvio_nominal_box_plus")) return INGVIO_E_ARG;
     const size_t bytes = 8 * (size_t)nb * c->ldp;
     Uploader upl{ c };
     if (int rc = upl.begin(bytes + 64)) return rc;
@@ -2981,6 +3092,48 @@ int ingvio_nominal_box_plus(ingvio_ctx* c, int b0, int nb, const double* dx)
     launch_nominal_update(nom_table(c), m.dx, c->ldp, nullptr, b0, nb, c->st);
     if (int rc = last_launch(c)) return rc;
     return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
+}
+
+// the table slots of the GNSS scalars (State::GNSSType order: clock GPS, GLO, GAL, BDS, FS, YOF); they live in the integer record
+int ingvio_nominal_set_gnss(ingvio_ctx* c, int b0, int nb, const int* slots)
+{
+    ENTER(c);
+    if (phase_busy(c) || check_range(c, b0, nb) || !slots) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    if (!m.vmax) { c->err = "ingvio_nominal_set_gnss without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = "ingvio_nominal_set_gnss: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, "ingvio_nominal_set_gnss")) return INGVIO_E_ARG;
+    for (int i = 0; i < nb; ++i) {
+        const int* I = &m.h_ih[(size_t)(b0 + i) * m.ir];
+        for (int s = 0; s < 6; ++s) {
+            const int v = slots[6 * i + s];
+            if (v == -1) continue;
+            if (v < 0 || v >= I[NOM_N_VAR] || I[NOM_IH + 4 * v] != NOM_KIND_SCALAR) {
+                c->err = "ingvio_nominal_set_gnss: a slot is out of range or holds no Scalar"; return INGVIO_E_ARG;
+            }
+            for (int t = 0; t < s; ++t) if (slots[6 * i + t] == v) { c->err = "ingvio_nominal_set_gnss: a slot is named twice"; return INGVIO_E_ARG; }
+        }
+    }
+    // behind the kernels that read the record (the stream orders the copies); the six ints of a filter are contiguous
+    Uploader upl{ c };
+    if (int rc = upl.begin(pad64(sizeof(int) * 6 * (size_t)nb) + 64)) return rc;
+    int* h = upl.take<int>(6 * (size_t)nb);
+    memcpy(h, slots, sizeof(int) * 6 * (size_t)nb);
+    // (no frame is staged from the table here - refused above - so nothing on the copy stream reads the record)
+    upl.copy_rows(m.ih + (size_t)b0 * m.ir + NOM_GNSS, (size_t)m.ir, h, (size_t)6, (size_t)6, (size_t)nb);
+    if (int rc = upl.end()) return rc;
+    for (int i = 0; i < nb; ++i) memcpy(&m.h_ih[(size_t)(b0 + i) * m.ir + NOM_GNSS], slots + 6 * (size_t)i, sizeof(int) * 6);
+    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
+}
+
+int ingvio_nominal_get_gnss(ingvio_ctx* c, int b0, int nb, int* slots)
+{
+    ENTER(c);
+    if (check_range(c, b0, nb) || !slots) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    if (!m.vmax) { c->err = "ingvio_nominal_get_gnss without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    for (int i = 0; i < nb; ++i) memcpy(slots + 6 * (size_t)i, &m.h_ih[(size_t)(b0 + i) * m.ir + NOM_GNSS], sizeof(int) * 6);      // the mirror is the record
+    return INGVIO_OK;
 }
 
 int ingvio_frame_stage_tracks_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,
@@ -2994,6 +3147,7 @@ int ingvio_frame_stage_tracks_nominal(ingvio_ctx* c, int b0, int nb, const ingvi
     // staged from the table is the whole batch's
     if (b0 != 0 || nb != c->d.batch) { c->err = "ingvio_frame_stage_tracks_nominal stages the whole batch (b0 = 0, nb = batch)"; return INGVIO_E_ARG; }
     if (m.pending) { c->err = "a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, "ingvio_frame_stage_tracks_nominal")) return INGVIO_E_ARG;
     if ((c->gn.staged && c->gn.in_frame) || (c->lm.staged && c->lm.in_frame)) {
         c->err = "the device nominal state does not take an in-frame GNSS or landmark stage";
         return INGVIO_E_UNSUPPORTED;

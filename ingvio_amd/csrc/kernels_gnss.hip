@@ -165,7 +165,8 @@ __constant__ double kNmf[9][5] = {
     { 5.8021897E-4, 5.6794847E-4, 5.8118019E-4, 5.9727542E-4, 6.1641693E-4 }, { 1.4275268E-3, 1.5138625E-3, 1.4572752E-3, 1.5007428E-3, 1.7599082E-3 },
     { 4.3472961E-2, 4.6729510E-2, 4.3908931E-2, 4.4626982E-2, 5.4736038E-2 } };
 
-__device__ double trop_delay(double doy, const double lla[3], double el)      // calculate_trop_delay :841-863 + nmf :797-839
+// (inlined by hand: with two instantiations of the kernel the compiler would make it a function call with a register spill)
+__device__ __forceinline__ double trop_delay(double doy, const double lla[3], double el)      // calculate_trop_delay :841-863 + nmf :797-839
 {
     if (lla[2] < -100.0 || 1E4 < lla[2] || el <= 0) return 0.0;
     const double hgt = lla[2] < 0.0 ? 0.0 : lla[2];
@@ -203,17 +204,55 @@ __device__ double iono_delay(double tow, const double* __restrict__ ion, const d
 }
 
 // grid = nb, 64 threads: lane = satellite.  Writes the per-satellite results (front [B][64][GF_N]) and the candidate rows.
-__global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L)
+// NOM (ingvio_gnss_front_stage_nominal): the receiver state - p_w, v_w of the extended pose, the clock biases, FS, YOF and
+// every Type::idx() - comes from filter b0 + bl's device-resident nominal table (the posterior of the frame that has just run, idx
+// after its marginalisation shift) instead of the receiver record, which then carries only what the host owns (n_sat, doy, ionosphere,
+// R_enu2ecef, anchor, noise amplitudes).  The table loads are wave-uniform and two levels deep (slot, then value / idx): they are issued
+// here at the top around the lane's first satellite loads, so that all of them are in flight together; from there on both variants run
+// the same arithmetic on the same values.
+template <bool NOM>
+__global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L, NomTable nt, int b0)
 {
     const int bl = blockIdx.x, i = threadIdx.x;
     const double* rc = L.rcv + (size_t)bl * GR_N;
     const int ns = (int)rc[GR_NSAT];
     __shared__ int sCbCol[4];
     __shared__ int sIdx[4];
+    double pw[3], vw[3], cb4[4] = { 0.0, 0.0, 0.0, 0.0 }, fs_v, yaw_v;
+    int ix_se23, ix_yof, ix_fs, ix_cb = -1;                           // ix_cb: lane s < 4 holds clock s's idx
+    double hd_sys = -1.0, hd_tow = 0.0, hd_psr = 0.0, hd_freq = -1.0;  // the satellite's first loads (NOM: issued with the table's)
+    if constexpr (NOM) {
+        const int* I = nt.ih + (size_t)(b0 + bl) * nt.ir;
+        const int* var = I + NOM_IH;
+        const double* D = nt.dv + (size_t)(b0 + bl) * nt.dr + NOM_DH;
+        const int vp = I[NOM_V_POSE];
+        int sl[6];
+        for (int q = 0; q < 6; ++q) sl[q] = I[NOM_GNSS + q];
+        {
+            const int j = i < ns ? i : 0;
+            const double* ep = L.eph + ((size_t)bl * L.smax + j) * GE_N;
+            const double* ob = L.obs + ((size_t)bl * L.smax + j) * GO_N;
+            hd_sys = ep[GE_SYS]; hd_tow = ob[GO_TOW]; hd_psr = ob[GO_PSR]; hd_freq = ob[GO_FREQ];
+        }
+        const double* xs = D + (size_t)(vp >= 0 ? vp : 0) * NOM_VD;
+        for (int q = 0; q < 3; ++q) { pw[q] = xs[9 + q]; vw[q] = xs[12 + q]; }
+        for (int q = 0; q < 4; ++q) cb4[q] = sl[q] >= 0 ? D[(size_t)sl[q] * NOM_VD + 9] : 0.0;
+        fs_v = sl[NOM_G_FS] >= 0 ? D[(size_t)sl[NOM_G_FS] * NOM_VD + 9] : 0.0;
+        yaw_v = sl[NOM_G_YOF] >= 0 ? D[(size_t)sl[NOM_G_YOF] * NOM_VD + 9] : 0.0;
+        ix_se23 = vp >= 0 ? var[4 * vp + 1] : -1;
+        ix_yof = sl[NOM_G_YOF] >= 0 ? var[4 * sl[NOM_G_YOF] + 1] : -1;
+        ix_fs = sl[NOM_G_FS] >= 0 ? var[4 * sl[NOM_G_FS] + 1] : -1;
+        if (i < 4) { const int sq = I[NOM_GNSS + i]; ix_cb = sq >= 0 ? var[4 * sq + 1] : -1; }
+    } else {
+        for (int q = 0; q < 3; ++q) { pw[q] = rc[GR_PW + q]; vw[q] = rc[GR_VW + q]; }
+        fs_v = rc[GR_FS]; yaw_v = rc[GR_YAW];
+        ix_se23 = (int)rc[GR_IDX_SE23]; ix_yof = (int)rc[GR_IDX_YOF]; ix_fs = (int)rc[GR_IDX_FS];
+        if (i < 4) ix_cb = (int)rc[GR_IDX_CB + i];
+    }
     double* H = L.H ? L.H + (size_t)bl * L.hstride : nullptr;
     if (H) { for (int e = i; e < L.mld * GNSS_FRONT_NCW; e += 64) H[e] = 0.0; }
     // receiver in ECEF: rcv = R_enu2ecef Rz(yaw) p_w + anchor (GnssUpdate.cpp:102), same rotation for the velocity (:108)
-    const double cy = cos(rc[GR_YAW]), sy = sin(rc[GR_YAW]);
+    const double cy = cos(yaw_v), sy = sin(yaw_v);
     double Rw[9];                                                     // R_w2ecef = R_enu2ecef Rz(yaw), row-major (:141)
     for (int r = 0; r < 3; ++r) {
         Rw[3 * r] = rc[GR_RENU + 3 * r] * cy + rc[GR_RENU + 3 * r + 1] * sy;
@@ -222,8 +261,8 @@ __global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L)
     }
     double xyz[3], vel[3];
     for (int r = 0; r < 3; ++r) {
-        xyz[r] = Rw[3 * r] * rc[GR_PW] + Rw[3 * r + 1] * rc[GR_PW + 1] + Rw[3 * r + 2] * rc[GR_PW + 2] + rc[GR_ANCHOR + r];
-        vel[r] = Rw[3 * r] * rc[GR_VW] + Rw[3 * r + 1] * rc[GR_VW + 1] + Rw[3 * r + 2] * rc[GR_VW + 2];
+        xyz[r] = Rw[3 * r] * pw[0] + Rw[3 * r + 1] * pw[1] + Rw[3 * r + 2] * pw[2] + rc[GR_ANCHOR + r];
+        vel[r] = Rw[3 * r] * vw[0] + Rw[3 * r + 1] * vw[1] + Rw[3 * r + 2] * vw[2];
     }
     double lla[3];
     ecef2geo(xyz, lla);
@@ -235,10 +274,11 @@ __global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L)
     if (i < ns) {
         const double* ep = L.eph + ((size_t)bl * L.smax + i) * GE_N;
         const double* ob = L.obs + ((size_t)bl * L.smax + i) * GO_N;
-        sys = (int)ep[GE_SYS];
-        if (sys >= 0 && sys <= 3 && ob[GO_FREQ] >= 0) {
+        if constexpr (!NOM) { hd_sys = ep[GE_SYS]; hd_tow = ob[GO_TOW]; hd_psr = ob[GO_PSR]; hd_freq = ob[GO_FREQ]; }
+        sys = (int)hd_sys;
+        if (sys >= 0 && sys <= 3 && hd_freq >= 0) {
             // sat_states (gnss_spp.cpp:50-98)
-            double ttx = ob[GO_TOW] - ob[GO_PSR] / kC;
+            double ttx = hd_tow - hd_psr / kC;
             double sp[3], sv[3], dts, ddts, tgd;
             if (sys == 1) {                                           // GLONASS (:72-79): SatState::tgd keeps its default 0
                 ttx -= geph2svdt(ttx, ep);
@@ -264,9 +304,12 @@ __global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L)
                 ion_d = rc[GR_HAVE_ION] != 0.0 ? iono_delay(ttx, rc + GR_ION, lla, az, el) : 0.0;
             }
             const double sag = kOmgGps * (sp[0] * xyz[1] - sp[1] * xyz[0]) / kC;
-            res_pos = range + sag + rc[GR_CB + sys] - dts * kC + tro_d + ion_d + tgd * kC - ob[GO_PSR];      // :132-139
+            double cbs;                                               // the receiver clock bias of the satellite's constellation
+            if constexpr (NOM) cbs = sys == 0 ? cb4[0] : (sys == 1 ? cb4[1] : (sys == 2 ? cb4[2] : cb4[3]));
+            else cbs = rc[GR_CB + sys];
+            res_pos = range + sag + cbs - dts * kC + tro_d + ion_d + tgd * kC - ob[GO_PSR];      // :132-139
             const double sagd = kOmgGps / kC * (sv[0] * xyz[1] + sp[0] * vel[1] - sv[1] * xyz[0] - sp[1] * vel[0]);
-            res_vel = (sv[0] - vel[0]) * u[0] + (sv[1] - vel[1]) * u[1] + (sv[2] - vel[2]) * u[2] + rc[GR_FS] + sagd - ddts * kC
+            res_vel = (sv[0] - vel[0]) * u[0] + (sv[1] - vel[1]) * u[1] + (sv[2] - vel[2]) * u[2] + fs_v + sagd - ddts * kC
                       + ob[GO_DOPP] * (kC / ob[GO_FREQ]);                                                                  // :267-277
             double se = sin(el);
             if (fabs(se) < 1e-6) se = 1e-6;
@@ -281,7 +324,7 @@ __global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L)
     for (int c = 0; c < 10; ++c) fr[10 + c] = st[c];
     if (!H) return;                                                   // satellite evaluation only (ingvio_gnss_sat_eval)
     // ---- candidate rows of updateTrackedSys (GnssUpdate.cpp:148-272): only constellations whose clock is in the state ----
-    if (i < 4) sIdx[i] = (int)rc[GR_IDX_CB + i];
+    if (i < 4) sIdx[i] = ix_cb;
     __syncthreads();
     const bool in_state = usable && sIdx[(sys < 0 || sys > 3) ? 0 : sys] >= 0;
     const unsigned long long mk = __ballot(in_state);
@@ -289,16 +332,16 @@ __global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L)
     if (i == 0) {
         int col = 10;
         int* cm = L.colmap + (size_t)bl * GNSS_FRONT_NCW;
-        const int i0 = (int)rc[GR_IDX_SE23];
+        const int i0 = ix_se23;
         for (int c = 0; c < 9; ++c) cm[c] = i0 + c;                   // var_order: SE23, YOF, clock biases in order of first appearance, FS
-        cm[9] = (int)rc[GR_IDX_YOF];
+        cm[9] = ix_yof;
         for (int s = 0; s < 4; ++s) sCbCol[s] = -1;
         for (int j = 0; j < ns; ++j) {
             if (!((mk >> j) & 1ULL)) continue;
             const int s = (int)L.eph[((size_t)bl * L.smax + j) * GE_N + GE_SYS];
             if (sCbCol[s] < 0) { sCbCol[s] = col; cm[col] = sIdx[s]; ++col; }
         }
-        cm[col] = (int)rc[GR_IDX_FS];
+        cm[col] = ix_fs;
         L.nc[bl] = nrow ? col + 1 : 0;
         L.m[bl] = 2 * nrow;
     }
@@ -306,7 +349,7 @@ __global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L)
     if (in_state) {
         int fs_col = 10;
         for (int s = 0; s < 4; ++s) if (sCbCol[s] >= 0) ++fs_col;
-        const double p[3] = { rc[GR_PW], rc[GR_PW + 1], rc[GR_PW + 2] }, v[3] = { rc[GR_VW], rc[GR_VW + 1], rc[GR_VW + 2] };
+        const double p[3] = { pw[0], pw[1], pw[2] }, v[3] = { vw[0], vw[1], vw[2] };
         double uR[3];                                                  // u^T R_w2ecef
         for (int c = 0; c < 3; ++c) uR[c] = u[0] * Rw[c] + u[1] * Rw[3 + c] + u[2] * Rw[6 + c];
         // u^T R [x]_x = (uR x x)^T:  row vector w^T [x]_x = (x cross ... ) -> (w^T [x]x)_c = sum_r w_r skew(x)[r][c]
@@ -330,7 +373,8 @@ __global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L)
 
 }  // namespace
 
-void launch_gnss_front(const GnssFrontLaunch& L, int nb, hipStream_t st)
+void launch_gnss_front(const GnssFrontLaunch& L, int nb, hipStream_t st, const NomTable* nom, int b0)
 {
-    hipLaunchKernelGGL(k_gnss_front, dim3(nb), dim3(64), 0, st, L);
+    if (nom) hipLaunchKernelGGL(k_gnss_front<true>, dim3(nb), dim3(64), 0, st, L, *nom, b0);
+    else hipLaunchKernelGGL(k_gnss_front<false>, dim3(nb), dim3(64), 0, st, L, NomTable{}, 0);
 }

@@ -145,7 +145,8 @@ __device__ __forceinline__ void put(double* M, int r0, int c0, const M3& B)     
 // (StateManager::augmentSlidingWindowPose reads it).
 // NOM (device-resident nominal state): the start state comes from the filter's table instead of the stage (pose variable R p v,
 // the bias variables, gravity), and lane 0 writes the end state back into the pose variable together with the new clone's pose
-// T_i2w * T_cl2i (StateManager.cpp:263-272) at the variable slot and idx the host reserved in the header (TRK_NOM_*).
+// T_i2w * T_cl2i (StateManager.cpp:263-272) at the variable slot and idx the host reserved in the header (TRK_NOM_*); with
+// TRK_NOM_CLK the registered receiver clocks advance with the frequency shift (lanes 1..4, see below).
 template <bool NOM>
 __global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, NomTable nt, int b0, int nb, int kst, double* __restrict__ PhiAll, double* __restrict__ GAll,
                                                   double* __restrict__ dtAll, double* __restrict__ Rall)
@@ -229,6 +230,29 @@ __global__ __launch_bounds__(64) void k_imu_steps(TrackStage ts, NomTable nt, in
         }
     }
     if (lane < k) dtAll[(size_t)(b0 + bl) * kst + lane] = imu[7 * lane + 6];
+    if constexpr (NOM) {
+        // receiver clocks (ImuPropagator.cpp:139-148: cb_s += dt * fs per sample when GNSS is enabled, the clock and FS are in the state):
+        // lanes 1..4 take one registered clock each (ingvio_nominal_set_gnss), lanes that have nothing to do in the write-back tail.
+        // Lane 0's own dependency chain is unchanged, but this is a divergent region of the same wave: it executes IN FRONT of lane
+        // 0's write-back, not beside it, so a registered filter pays k loads of dt (cached: every lane read them above) and k
+        // dependent multiply-adds once (measured 36.3 -> 37.2 us per 512 filters at k = 10).  Folding the sum into the recursion loop
+        // above would hide it, but that loop already sits at the 256-VGPR limit and would be paid by unregistered filters too.
+        // fs is constant over the frame.  The compiler may contract cb + dt * fs to one FMA where the host rounds twice (below 1e-14
+        // relative over 64 samples).  The condition is wave-uniform: a filter without registered scalars, or a frame staged without
+        // enable_gnss, branches over all of it (two uniform loads).
+        const int* Ig = nt.ih + (size_t)(b0 + bl) * nt.ir + NOM_GNSS;
+        const int sfs = Ig[NOM_G_FS];
+        if (h[TRK_NOM_CLK] != 0 && sfs >= 0 && lane >= 1 && lane <= 4) {
+            const int sc = Ig[lane - 1];
+            if (sc >= 0) {
+                double* D = nt.dv + (size_t)(b0 + bl) * nt.dr + NOM_DH;
+                const double fs = D[(size_t)sfs * NOM_VD + 9];
+                double cb = D[(size_t)sc * NOM_VD + 9];
+                for (int s = 0; s < k; ++s) cb = cb + imu[7 * s + 6] * fs;
+                D[(size_t)sc * NOM_VD + 9] = cb;
+            }
+        }
+    }
     if (lane == 0) {                                                  // every lane's recursion ended behind the last sample
         double* Ro = Rall + (size_t)(b0 + bl) * 9;
         for (int i = 0; i < 9; ++i) Ro[i] = R.m[i];

@@ -1,6 +1,7 @@
 // launch_gnss.h — host-side launch descriptor of kernels_gnss.hip.
 #pragma once
 #include "dev_common.h"
+#include "launch_nominal.h"
 
 // flat records (doubles), the same layout as include/ingvio_hip.h documents for ingvio_gnss_epoch
 enum { GE_SYS = 0, GE_PRN, GE_TOE, GE_TOE_SYS, GE_TOC, GE_A, GE_E, GE_I0, GE_OMG, GE_OMG0, GE_M0, GE_DELTA_N, GE_OMG_DOT, GE_I_DOT,
@@ -26,4 +27,6 @@ struct GnssFrontLaunch {
     int mld, hstride;
 };
 
-void launch_gnss_front(const GnssFrontLaunch& L, int nb, hipStream_t st);
+// nom != nullptr (k_gnss_front<true>): p_w, v_w, cb, fs, yaw_offset and the idx_* of filter b0 + i come from its device-resident nominal
+// table (extended pose + the scalars registered with ingvio_nominal_set_gnss); those fields of the receiver record are not read
+void launch_gnss_front(const GnssFrontLaunch& L, int nb, hipStream_t st, const NomTable* nom = nullptr, int b0 = 0);

@@ -4,10 +4,13 @@
 
 // Per filter b, two records:
 //   ints    ih + b * ir:  [NOM_N_VAR] slots in use, [NOM_N_CLONES], [NOM_V_EXT], [NOM_V_POSE], [NOM_V_BG], [NOM_V_BA],
+//                         [NOM_GNSS + s] variable slot of the GNSS scalars (ingvio_nominal_set_gnss): clock bias GPS, GLO, GAL, BDS, then FS,
+//                         then YOF (State::GNSSType order, State.h:75); -1: not in the state / not registered,
 //                         [NOM_CLONES + q] variable slot of window clone q (ascending time), then [v_max][4] = {kind, idx, anchor slot, 0}
 //   doubles dv + b * dr:  gravity (3) + pad, then [v_max][16] = R (9, row-major), p (3), v (3), pad; a Vec3 in p, a Scalar in p[0],
 //                         a landmark's world position (AnchoredLandmark::valuePosXyz) in p
-enum { NOM_N_VAR, NOM_N_CLONES, NOM_V_EXT, NOM_V_POSE, NOM_V_BG, NOM_V_BA, NOM_CLONES = 8, NOM_IH = NOM_CLONES + 64 };
+enum { NOM_N_VAR, NOM_N_CLONES, NOM_V_EXT, NOM_V_POSE, NOM_V_BG, NOM_V_BA, NOM_GNSS, NOM_CLONES = NOM_GNSS + 6, NOM_IH = NOM_CLONES + 64 };
+enum { NOM_G_FS = 4, NOM_G_YOF = 5 };      // positions behind NOM_GNSS (0..3: the clock biases)
 enum { NOM_KIND_NONE = -1, NOM_KIND_SE23 = 0, NOM_KIND_SE3 = 1, NOM_KIND_VEC3 = 2, NOM_KIND_SCALAR = 3, NOM_KIND_LM = 4 };
 #define NOM_DH 4           // doubles in front of the variables' values (gravity)
 #define NOM_VD 16          // doubles per variable

@@ -11,6 +11,7 @@ enum {
     TRK_I_DROP, TRK_I_FREE, TRK_I_OBS, TRK_I_PF, TRK_I_CIDX, TRK_I_FEAT, TRK_I_GNSS,
     TRK_D_OBS, TRK_D_PF, TRK_D_CR, TRK_D_CP, TRK_D_IMU, TRK_D_STATE,
     TRK_NOM_SLOT, TRK_NOM_IDX, TRK_NOM_NVAR,      // device nominal stage: the new clone's variable slot and idx, the table's slots in use after it
+    TRK_NOM_CLK,                                  // device nominal stage: != 0 - the frame is staged with enable_gnss (the registered clocks advance)
     TRK_HDR_USED, TRK_HDR = 32
 };
 

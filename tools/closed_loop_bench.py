@@ -8,8 +8,21 @@ closed loop of frames twice,
                run(i); stage_async(i+1); fetch_begin(i); run(i+1); fetch_end(i)
 and reports ms per frame (the host loop split into its phases), the bytes one filter's frame hand-over takes in each mode, and whether
 the two loops agree.  --device-only runs the device loop alone (the rocprofv3 --kernel-trace --stats run for the kernels' times).
+--gnss: every filter also takes a raw GNSS epoch (the 11 usable satellites of tests/golden/gnss_front.npz) per frame, and two forms of the
+device loop are timed on the same build,
+  device form      run(i); fetch_begin(i); gnss_front_stage_nominal(i); gnss_run(i); stage_async(i+1); run(i+1); fetch_end(i)
+  round-trip form  the epoch through the host: ingvio_nominal_get, ingvio_gnss_front_stage with the table's values, ingvio_gnss_run,
+                   ingvio_gnss_fetch, ingvio_nominal_box_plus (three synchronisations per epoch)
+Both forms run the same way - a context synchronisation at the end of every frame, so that a frame's time is its own - and both are
+reported twice: *_abi_ms_per_frame, the time spent INSIDE the library's calls (what a compiled host would pay), and
+*_wall_ms_per_frame with this harness' Python between the calls (for the round-trip form mostly the conversion of 512 fetched tables
+into epoch structures).  device_loop_ms_per_frame is the device form free-running, without the per-frame synchronisation.  The GNSS
+modes write $RESULTS/closed_loop_bench_gnss.json.
+--register-only: the loop without epochs but with the GNSS scalars registered, i.e. the clock recursion of k_imu_steps<true> switched on
+(against the plain run: that kernel's time with and without registered clocks).
 Writes $RESULTS/closed_loop_bench.json (RESULTS defaults to results/) and prints one JSON line.
-usage: python tools/closed_loop_bench.py [--batch 512] [--features 150] [--window 11] [--k 10] [--frames 30] [--warmup 5] [--device-only]"""
+usage: python tools/closed_loop_bench.py [--batch 512] [--features 150] [--window 11] [--k 10] [--frames 30] [--warmup 5] [--device-only]
+                                         [--gnss | --register-only]"""
 import argparse
 import copy
 import json
@@ -41,6 +54,133 @@ def stage_bytes(cases, f, k, host):
     return pad(4 * len(cases) * 32) + pad(4 * ni) + pad(8 * nd)
 
 
+class TimedLib:
+    """the loaded library with the time spent inside its calls summed up (the round-trip form's figure: ABI calls only)"""
+
+    def __init__(self, lib):
+        self._lib, self.t = lib, 0.0
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*args):
+            t0 = time.perf_counter()
+            r = fn(*args)
+            self.t += time.perf_counter() - t0
+            return r
+        return call
+
+
+def main_gnss(a):
+    from ingvio_amd import synth
+    from ingvio_amd import closed_loop as cl
+    from ingvio_amd import closed_loop_gnss as cg
+    B, F, NF, W = a.batch, a.features, a.frames, a.warmup
+    z = np.load(os.path.join(ROOT, "tests", "golden", "gnss_front.npz"))
+    t0 = time.perf_counter()
+    cases = cg.make_gnss_loop(z, B, NF, F=F, every=0, ks=(a.k,), windows=(a.window,))
+    table = synth.chi2_table()
+    out = dict(batch=B, features=F, window=a.window, k=a.k, frames_timed=NF - W, gnss=bool(a.gnss), setup_s=round(time.perf_counter() - t0, 1))
+
+    def fresh():
+        ctx = cl.loop_ctx(cases, F, c_max=a.window + 1)
+        ctx.nominal_create(64)
+        ctx.nominal_set(0, [c["table"].as_dict() for c in cases])
+        ctx.nominal_set_gnss(0, [c["gnss_slots"] for c in cases])
+        return ctx
+
+    # device form
+    ctx = fresh()
+    stages = [cg.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
+    gst = [cg.gnss_stage_call(ctx, cases, f, table) for f in range(NF)] if a.gnss else None
+    stages[0]()
+    ctx.frame_run()
+    for f in range(NF):
+        if f == W:
+            ctx.sync()
+            t0 = time.perf_counter()
+        ctx.frame_fetch_begin()
+        if a.gnss:
+            gst[f]()
+            ctx.gnss_run()
+        if f + 1 < NF:
+            stages[f + 1]()
+            ctx.frame_run()
+        ctx.frame_fetch_end()
+    ctx.sync()
+    out["device_loop_ms_per_frame"] = round(1e3 * (time.perf_counter() - t0) / (NF - W), 4)
+    if a.gnss:
+        g = ctx.gnss_fetch()
+        out["last_epoch_rows_mean"] = float(g[1].mean()); out["last_epoch_ok"] = int((g[4] == 0).sum())
+    dev_nom = ctx.nominal_get()
+    ctx.close()
+    if a.gnss and not a.device_only:
+        # device form once more, measured exactly as the round-trip form below: synchronised per frame, time inside the calls and wall
+        ctx = fresh()
+        stages = [cg.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
+        gst = [cg.gnss_stage_call(ctx, cases, f, table) for f in range(NF)]
+        stages[0]()
+        ctx.frame_run()
+        ctx.L = TimedLib(ctx.L)
+        wall = 0.0
+        for f in range(NF):
+            ctx.sync()
+            if f == W:
+                ctx.L.t = 0.0
+            t1 = time.perf_counter()
+            ctx.frame_fetch_begin()
+            gst[f]()
+            ctx.gnss_run()
+            if f + 1 < NF:
+                stages[f + 1]()
+                ctx.frame_run()
+            ctx.frame_fetch_end()
+            ctx.sync()
+            if f >= W:
+                wall += time.perf_counter() - t1
+        out["device_abi_ms_per_frame"] = round(1e3 * ctx.L.t / (NF - W), 4)
+        out["device_wall_ms_per_frame"] = round(1e3 * wall / (NF - W), 4)
+        ctx.L = ctx.L._lib
+        ctx.close()
+        # round-trip form
+        ctx = fresh()
+        stages = [cg.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
+        stages[0]()
+        ctx.frame_run()
+        ctx.L = TimedLib(ctx.L)
+        wall = 0.0
+        for f in range(NF):
+            ctx.sync()
+            if f == W:
+                ctx.L.t = 0.0
+            t1 = time.perf_counter()
+            ctx.frame_fetch_begin()
+            nom = ctx.nominal_get()                                      # synchronises both streams
+            ctx.gnss_front_stage_prepare(0, cg.table_epochs(nom, cases, f), table, gate_rows=True, strong_reject=True)()
+            ctx.gnss_run()
+            g = ctx.gnss_fetch()                                         # synchronises
+            ctx.nominal_box_plus(0, g[0])
+            if f + 1 < NF:
+                stages[f + 1]()
+                ctx.frame_run()
+            ctx.frame_fetch_end()
+            ctx.sync()
+            if f >= W:
+                wall += time.perf_counter() - t1
+        abi = ctx.L.t
+        ctx.L = ctx.L._lib
+        out["roundtrip_abi_ms_per_frame"] = round(1e3 * abi / (NF - W), 4)
+        out["roundtrip_wall_ms_per_frame"] = round(1e3 * wall / (NF - W), 4)
+        rt_nom = ctx.nominal_get()
+        ctx.close()
+        out["max_abs_pose_device_vs_roundtrip"] = max(float(np.max(np.abs(dev_nom[b]["val"][0] - rt_nom[b]["val"][0]))) for b in range(B))
+    res_dir = os.environ.get("RESULTS", os.path.join(ROOT, "results"))
+    os.makedirs(res_dir, exist_ok=True)
+    with open(os.path.join(res_dir, "closed_loop_bench_gnss.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=512)
@@ -50,7 +190,11 @@ def main():
     ap.add_argument("--frames", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--device-only", action="store_true")
+    ap.add_argument("--gnss", action="store_true")
+    ap.add_argument("--register-only", action="store_true", help="the loop without epochs, the GNSS scalars registered (clock recursion on)")
     a = ap.parse_args()
+    if a.gnss or a.register_only:
+        return main_gnss(a)
     from oracle import oracle as orc
     from ingvio_amd import closed_loop as cl
     B, F, NF, W = a.batch, a.features, a.frames, a.warmup
