@@ -243,7 +243,8 @@ int ingvio_info_commit(ingvio_ctx* ctx, int b);
  * (calcResJacobianSingleLandmark*, :521-572 / :619-686, as written), the per-landmark chi^2 gate on the prior (:98-99), the
  * accepted rows stacked, one ekfUpdate (:146) - rows, gates, stacking and the update on the device for a range of filters, with
  * S = H P H^T + s^2 I factorised outside LDS (up to INGVIO_LM_MAX landmarks = 256 stereo rows per filter).
- * The nominal values are the host's: it hands over the CURRENT pose / extrinsics / landmark positions and applies dx itself. */
+ * The nominal values are the host's: it hands over the CURRENT pose / extrinsics / landmark positions and applies dx itself -
+ * or, with the device-resident nominal state, the table's (ingvio_landmark_stage_nominal below: only the observations travel). */
 #define INGVIO_LM_MAX 64
 typedef struct {
     double R_i2w[9], p_i2w[3];    /* extended pose (row-major rotation, position)                          */
@@ -516,10 +517,11 @@ int ingvio_nominal_box_plus(ingvio_ctx* ctx, int b0, int nb, const double* dx);
  * frame enqueued last, so run(i); stage(i+1, async); fetch_begin(i); run(i+1); fetch_end(i) is a closed loop.
  * Refused before anything changes: no table (INGVIO_E_ARG), a range other than the whole batch (b0 != 0 or nb != batch: the post-frame
  * step covers every filter, INGVIO_E_ARG), a frame staged from the table that has not run yet (INGVIO_E_ARG), an
- * in-frame GNSS or landmark stage or frame_parts > 1 (INGVIO_E_UNSUPPORTED), marg_idx not a window clone (INGVIO_E_NOT_IN_STATE), a
+ * in-frame GNSS or host-fed landmark stage or frame_parts > 1 (INGVIO_E_UNSUPPORTED), marg_idx not a window clone (INGVIO_E_NOT_IN_STATE), a
  * landmark anchored to the clone that leaves (INGVIO_E_ARG), no free slot or a full window (INGVIO_E_CAPACITY).  While such a frame is
  * staged and has not run, ingvio_frame_stage(_async), ingvio_frame_stage_tracks, ingvio_nominal_set / _box_plus, ingvio_cov_snapshot
- * and ingvio_frame_run(restore_prior != 0) return INGVIO_E_ARG and ingvio_frame_run_phase INGVIO_E_UNSUPPORTED.  ingvio_cov_snapshot /
+ * and ingvio_frame_run(restore_prior != 0) return INGVIO_E_ARG and ingvio_frame_run_phase INGVIO_E_UNSUPPORTED.  The ONE stage accepted
+ * while such a frame is pending is ingvio_landmark_stage_nominal with opts->in_frame != 0: the frame's own landmark update.  ingvio_cov_snapshot /
  * ingvio_cov_restore copy the table with the covariance (restore abandons such a staged frame); a restore whose snapshot was taken
  * before ingvio_nominal_create holds no table and is refused (INGVIO_E_ARG). */
 typedef struct {
@@ -568,6 +570,37 @@ typedef struct {
     double psr_noise_amp, dopp_noise_amp;     /* GnssUpdate::_psr_noise_amp / _dopp_noise_amp                          */
 } ingvio_gnss_epoch_nominal;
 int ingvio_gnss_front_stage_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_gnss_epoch_nominal* epochs, const ingvio_gnss_opts* opts);
+/* ---- in-state landmarks in the device-resident closed loop -------------------------------------------------------
+ * ingvio_landmark_stage with the nominal values taken from the device table: per filter only the observations and the table slots of the
+ * landmarks they belong to.  R_i2w, p_i2w (the table's extended pose), R_cl2i, p_c2i (its extrinsics), idx_epose, idx_ext and per
+ * landmark lm_idx, anchor_idx (the idx of the slot and of its anchor's slot) and pf (its value) are read on the device at the moment the
+ * rows are formed; the checks ingvio_landmark_stage makes on them are made on the host mirror of the table.
+ *   opts->in_frame == 0: ingvio_landmark_run of the same range (once: a second one is INGVIO_E_ARG) forms the rows from the table as it
+ *     stands, updates the covariance and ends with StateManager::boxPlus of its dx on the table (LandmarkUpdate.cpp:146-147).  While it is
+ *     staged and has not run, ingvio_frame_stage_tracks_nominal, ingvio_nominal_set / _box_plus / _set_gnss, ingvio_cov_snapshot and
+ *     ingvio_gnss_front_stage_nominal return INGVIO_E_ARG; ingvio_cov_restore abandons it.
+ *   opts->in_frame != 0: called AFTER ingvio_frame_stage_tracks_nominal of the frame it belongs to and before its ingvio_frame_run, for
+ *     the whole batch.  That run then follows IngvioFilter.cpp:277-324 on the device: MSCKF update -> boxPlus of the frame's dx on the
+ *     table -> landmark rows at the UPDATED values -> per-landmark gates -> one stacked update -> boxPlus of the landmark dx (index space
+ *     of the update, new clone included) -> drop of the marginalised clone and index shift.  The stage is consumed by the run;
+ *     ingvio_cov_restore abandons it with the frame.  The upload is ordered behind the frame enqueued last, so
+ *       run(i); stage_tracks_nominal(i + 1, async); landmark_stage_nominal(i + 1); fetch_begin(i); run(i + 1); fetch_end(i)
+ *     is a closed loop without a host synchronisation.
+ * ingvio_landmark_fetch returns dx / rows / accept / gamma / status as for the host-fed stage; the frame's own dx, row counts and accept
+ * masks stay valid for ingvio_frame_fetch(_begin / _end) of the same frame.
+ * Refused before anything changes: no table, a table without extended pose or extrinsics, a slot that is free, out of range, named twice
+ * or not an INGVIO_NOM_LANDMARK, in_frame != 0 without a pending frame from the table or for a range other than the whole batch,
+ * in_frame == 0 with such a frame pending, a GNSS epoch staged from the table that has not run (INGVIO_E_ARG); n_lm > INGVIO_LM_MAX
+ * (INGVIO_E_CAPACITY); a variable beyond the live state (INGVIO_E_NOT_IN_STATE).  Still refused with a frame from the table: the host-fed
+ * ingvio_landmark_stage with in_frame != 0 and any in-frame GNSS stage (INGVIO_E_UNSUPPORTED). */
+typedef struct {
+    int n_lm;                       /* <= INGVIO_LM_MAX; 0: no landmark update for this filter                 */
+    const int* lm_var;              /* [n_lm] table slots, each of kind INGVIO_NOM_LANDMARK, no duplicates      */
+    const double* uv;               /* [n_lm][4] current observation u0 v0 u1 v1 (mono: first two)              */
+    const unsigned char* tracked;   /* [n_lm] 1 = observed in this frame (0: the landmark is skipped)           */
+} ingvio_landmark_frame_nominal;
+int ingvio_landmark_stage_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_landmark_frame_nominal* frames,
+                                  const ingvio_landmark_opts* opts);
 int ingvio_frame_run(ingvio_ctx* ctx, int restore_prior);
 /* Throughput batches (round 6, an experiment kept selectable): ingvio_frame_run deals the batch to `parts` slices of filters, each
  * on its own HIP stream; the slices' throughput-bound segments (gate + Gram, apply) are chained by events so that only ONE runs at a

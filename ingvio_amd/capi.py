@@ -33,7 +33,7 @@ EXPORTS = [
     "ingvio_info_reduce", "ingvio_info_commit", "ingvio_gnss_sat_eval",
     "ingvio_chi2_gamma_multi", "ingvio_ekf_update_batch", "ingvio_add_variable_delayed_invertible", "ingvio_add_variable_delayed", "ingvio_replace_var_linear",
     "ingvio_nominal_create", "ingvio_nominal_set", "ingvio_nominal_get", "ingvio_nominal_box_plus", "ingvio_frame_stage_tracks_nominal",
-    "ingvio_nominal_set_gnss", "ingvio_nominal_get_gnss", "ingvio_gnss_front_stage_nominal",
+    "ingvio_nominal_set_gnss", "ingvio_nominal_get_gnss", "ingvio_gnss_front_stage_nominal", "ingvio_landmark_stage_nominal",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -75,6 +75,10 @@ class LandmarkFrame(C.Structure):
                 ("idx_epose", C.c_int), ("idx_ext", C.c_int), ("n_lm", C.c_int), ("lm_idx", C.POINTER(C.c_int)),
                 ("anchor_idx", C.POINTER(C.c_int)), ("pf", C.POINTER(C.c_double)), ("uv", C.POINTER(C.c_double)),
                 ("tracked", C.POINTER(C.c_ubyte))]
+
+
+class LandmarkFrameNominal(C.Structure):
+    _fields_ = [("n_lm", C.c_int), ("lm_var", C.POINTER(C.c_int)), ("uv", C.POINTER(C.c_double)), ("tracked", C.POINTER(C.c_ubyte))]
 
 
 class LandmarkOpts(C.Structure):
@@ -560,6 +564,33 @@ class Context:
         o.in_frame = int(bool(in_frame))
         self._chk(self.L.ingvio_landmark_stage(self.h, b0, nb, arr, C.byref(o)))
         self._lm_range = (b0, nb)
+
+    def landmark_stage_nominal_prepare(self, b0, frames, stereo, noise, chi2_thr, R_cl2cr=None, t_cl2cr=None, in_frame=False):
+        """ingvio_landmark_stage_nominal: frames per filter a dict(lm_var [L] table slots, uv [L,4], tracked [L]) or None (n_lm = 0);
+        everything else comes from the device nominal table.  Returns a callable that issues the stage."""
+        nb = len(frames)
+        arr = (LandmarkFrameNominal * nb)(); keep = []
+        for i, f in enumerate(frames):
+            a = arr[i]
+            if f is None or len(f["lm_var"]) == 0:
+                a.n_lm = 0
+                continue
+            lv = np.ascontiguousarray(f["lm_var"], dtype=np.int32); uv = f64(f["uv"]).reshape(-1, 4)
+            tr = np.ascontiguousarray(f.get("tracked", np.ones(len(lv))), dtype=np.uint8)
+            keep.append((lv, uv, tr))
+            a.n_lm = len(lv); a.lm_var = _i(lv); a.uv = _d(uv); a.tracked = tr.ctypes.data_as(C.POINTER(C.c_ubyte))
+        o = LandmarkOpts(); o.stereo = int(bool(stereo)); o.noise = float(noise); o.chi2_thr = float(chi2_thr)
+        o.R_cl2cr = (C.c_double * 9)(*f64(np.eye(3) if R_cl2cr is None else R_cl2cr).reshape(9))
+        o.t_cl2cr = (C.c_double * 3)(*f64(np.zeros(3) if t_cl2cr is None else t_cl2cr).reshape(3))
+        o.in_frame = int(bool(in_frame))
+
+        def call(_keep=(keep, arr, o)):
+            self._chk(self.L.ingvio_landmark_stage_nominal(self.h, int(b0), nb, arr, C.byref(o)))
+            self._lm_range = (b0, nb)
+        return call
+
+    def landmark_stage_nominal(self, b0, frames, stereo, noise, chi2_thr, R_cl2cr=None, t_cl2cr=None, in_frame=False):
+        self.landmark_stage_nominal_prepare(b0, frames, stereo, noise, chi2_thr, R_cl2cr, t_cl2cr, in_frame)()
 
     def landmark_run(self, b0=None, nb=None):
         b0, nb = (self._lm_range if b0 is None else (b0, nb))

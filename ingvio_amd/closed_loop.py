@@ -70,7 +70,7 @@ class HostTable:
 KS = (1, 9, 10, 33)
 
 
-def make_loop(B, n_frames, F=24, seed=5, ks=KS, windows=None):
+def make_loop(B, n_frames, F=24, seed=5, ks=KS, windows=None, n_landmarks=2, lm_sigma=1.0):
     """B filters of ragged windows; per frame and filter the raw IMU samples, the track delta and the marginalised clone (always the
     window's second clone: the first one anchors the landmarks).  Only integers of the state enter the inputs, so they are prepared
     in advance; the host reference keeps the values."""
@@ -79,7 +79,8 @@ def make_loop(B, n_frames, F=24, seed=5, ks=KS, windows=None):
     cases = []
     for b in range(B):
         C = 5 + b % 7 if windows is None else windows[b % len(windows)]
-        flt, step, frame, info = synth.build_case(lambda P: orc.Cov(P, ld=160), orc.imu_transition, seed=seed + b, F=8, C=C, n_gnss=6, n_landmarks=2)
+        flt, step, frame, info = synth.build_case(lambda P: orc.Cov(P, ld=160), orc.imu_transition, seed=seed + b, F=8, C=C, n_gnss=6, n_landmarks=n_landmarks,
+                                                  lm_sigma=lm_sigma)
         P = flt.cov.P() if callable(flt.cov.P) else flt.cov.P
         raw = step["raw"]
         slots = []

@@ -148,6 +148,12 @@ struct ingvio_ctx {
         LmOpts op;
         int l_hi = 0, in_frame = 0;
         bool alloc = false, staged = false;
+        // stage from the device nominal state (ingvio_landmark_stage_nominal): only uv / tracked / n_lm and the landmarks'
+        // table slots are uploaded; pose, idx, lm_idx, anchor_idx and pf are filled from the table when the rows are formed
+        // (launch_nominal_gather).  nom_pending: the stand-alone form, staged and not yet run (it runs once: its run moves the table)
+        int* slot = nullptr;            // [B][LM_MAX]
+        bool nominal = false, nom_pending = false;
+        int nom_b0 = 0, nom_nb = 0;
         std::vector<int> hi;            // per filter: one past the highest state index the staged rows name (re-checked against the live n at run time)
     } lm;
     char* d_multi = nullptr;            // ingvio_chi2_gamma_multi: packed blocks (grown on demand)
@@ -334,10 +340,12 @@ int nom_mark(ingvio_ctx* c)
 NomTable nom_table(ingvio_ctx* c) { return NomTable{ c->nom.ih, c->nom.dv, c->nom.vmax, c->nom.ir, c->nom.dr }; }
 // a GNSS epoch staged from the table (ingvio_gnss_front_stage_nominal) whose update has not run: its rows are linearised at the table's
 // present values, so nothing else may move the table or the covariance's bookkeeping in between
+// (the same holds for a stand-alone landmark update staged from the table, ingvio_landmark_stage_nominal)
 int gnss_nom_busy(ingvio_ctx* c, const char* who)
 {
-    if (!c || !c->gn.nom_pending) return 0;
-    c->err = std::string(who) + ": a GNSS epoch staged from the device nominal state has not run yet";
+    if (!c || (!c->gn.nom_pending && !c->lm.nom_pending)) return 0;
+    c->err = std::string(who) + (c->gn.nom_pending ? ": a GNSS epoch staged from the device nominal state has not run yet"
+                                                   : ": a landmark update staged from the device nominal state has not run yet");
     return 1;
 }
 
@@ -1078,7 +1086,7 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
                      c->gn.H, c->gn.res, c->gn.noise, c->gn.gamma, c->gn.chi2, c->gn.m, c->gn.nc, c->gn.colmap, c->gn.keep,
                      c->gn.feph, c->gn.fobs, c->gn.frcv, c->gn.front,
                      c->dw.Hd, c->dw.X, c->dw.Y, c->dw.Tb, c->dw.noise, c->dw.noiseB, c->dw.m, c->dw.cidx, c->lm.pose, c->lm.pf, c->lm.uv, c->lm.gamma, c->lm.idx, c->lm.n_lm,
-                     c->lm.lm_idx, c->lm.anchor_idx, c->lm.tracked, c->lm.accept, c->lm.dx, c->d_xchg, c->dw.U, c->dw.rowmap, c->d_zero_idx,
+                     c->lm.lm_idx, c->lm.anchor_idx, c->lm.tracked, c->lm.accept, c->lm.slot, c->lm.dx, c->d_xchg, c->dw.U, c->dw.rowmap, c->d_zero_idx,
                      c->d_Asum, c->d_used_sum, c->d_Tflat, c->d_imu, c->d_tri_mask, c->d_prm };
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& sl : c->pin) { if (sl.p) hipHostFree(sl.p); if (sl.ev) hipEventDestroy(sl.ev); }
@@ -1223,6 +1231,7 @@ int ingvio_cov_restore(ingvio_ctx* c)
         if (m.pending) { c->staged = false; m.pending = false; }      // the staged frame's clone is not in the restored table
         m.frame = false;
         if (c->gn.nom_pending) { c->gn.nom_pending = false; c->gn.staged = false; }      // rows linearised at the abandoned table
+        if (c->lm.nominal && c->lm.staged) { c->lm.nom_pending = false; c->lm.staged = false; }      // either form: its slots name the abandoned table
         if (wait_inputs(c)) return INGVIO_E_HIP;                     // an asynchronous stage from the table must land before it is overwritten
         HIPCHK(c, hipMemcpyAsync(m.ih, m.ih_snap, sizeof(int) * (size_t)c->d.batch * m.ir, hipMemcpyDeviceToDevice, c->st));
         HIPCHK(c, hipMemcpyAsync(m.dv, m.dv_snap, sizeof(double) * (size_t)c->d.batch * m.dr, hipMemcpyDeviceToDevice, c->st));
@@ -1779,6 +1788,7 @@ int ingvio_gnss_front_stage_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_
     // without a table there is nothing the kernel could read, whatever the epochs hold (also when none has a satellite)
     if (!m.vmax) { c->err = "ingvio_gnss_front_stage_nominal without ingvio_nominal_create"; return INGVIO_E_ARG; }
     if (m.pending) { c->err = "ingvio_gnss_front_stage_nominal: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (c->lm.nom_pending) { c->err = "ingvio_gnss_front_stage_nominal: a landmark update staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
     // the receiver's variables, from the host mirror of the table (no device round trip): what ingvio_gnss_front_stage checks on the
     // epoch's idx_* is checked on these
     std::vector<ingvio_gnss_epoch> full((size_t)nb);
@@ -2414,6 +2424,34 @@ static int landmark_update_launch(ingvio_ctx* c, int b0, int nb, const int* marg
     return run_dense_update(c, b0, nb, s.op.var, -1, nullptr, 0, s.dx, true, rowmap, marg_idx, marg_size, marg_fused);
 }
 
+static int landmark_stage_alloc(ingvio_ctx* c, int l_hi)
+{
+    auto& s = c->lm;
+    const int B = c->d.batch;
+    if (!s.alloc) {
+        int rc = dalloc(c, &s.pose, (size_t)B * 24) | dalloc(c, &s.pf, (size_t)B * LM_MAX * 3) | dalloc(c, &s.uv, (size_t)B * LM_MAX * 4)
+               | dalloc(c, &s.gamma, (size_t)B * LM_MAX) | dalloc(c, &s.idx, (size_t)B * 2) | dalloc(c, &s.n_lm, (size_t)B)
+               | dalloc(c, &s.lm_idx, (size_t)B * LM_MAX) | dalloc(c, &s.anchor_idx, (size_t)B * LM_MAX) | dalloc(c, &s.tracked, (size_t)B * LM_MAX)
+               | dalloc(c, &s.accept, (size_t)B * LM_MAX) | dalloc(c, &s.dx, (size_t)B * c->ldp);
+        if (rc) return INGVIO_E_HIP;
+        s.alloc = true;
+    }
+    if (c->nom.vmax && !s.slot && dalloc(c, &s.slot, (size_t)B * LM_MAX)) return INGVIO_E_HIP;
+    s.l_hi = std::max(s.l_hi, l_hi);
+    return dense_ws_alloc(c, std::max(32, 4 * s.l_hi));
+}
+
+static void landmark_stage_commit(ingvio_ctx* c, int b0, int nb, const ingvio_landmark_opts* o, const std::vector<int>& hi_new)
+{
+    auto& s = c->lm;
+    memcpy(s.op.R_lr, o->R_cl2cr, 72); memcpy(s.op.t_lr, o->t_cl2cr, 24);
+    s.op.var = o->noise * o->noise; s.op.chi2_thr = o->chi2_thr; s.op.stereo = o->stereo ? 1 : 0;
+    s.in_frame = o->in_frame ? 1 : 0;
+    if ((int)s.hi.size() != c->d.batch) s.hi.assign(c->d.batch, 0);
+    for (int i = 0; i < nb; ++i) s.hi[b0 + i] = hi_new[i];
+    s.staged = true;
+}
+
 int ingvio_landmark_stage(ingvio_ctx* c, int b0, int nb, const ingvio_landmark_frame* fr, const ingvio_landmark_opts* o)
 {
     ENTER(c);
@@ -2437,16 +2475,7 @@ int ingvio_landmark_stage(ingvio_ctx* c, int b0, int nb, const ingvio_landmark_f
         l_hi = std::max(l_hi, f.n_lm);
     }
     const int B = c->d.batch;
-    if (!s.alloc) {
-        int rc = dalloc(c, &s.pose, (size_t)B * 24) | dalloc(c, &s.pf, (size_t)B * LM_MAX * 3) | dalloc(c, &s.uv, (size_t)B * LM_MAX * 4)
-               | dalloc(c, &s.gamma, (size_t)B * LM_MAX) | dalloc(c, &s.idx, (size_t)B * 2) | dalloc(c, &s.n_lm, (size_t)B)
-               | dalloc(c, &s.lm_idx, (size_t)B * LM_MAX) | dalloc(c, &s.anchor_idx, (size_t)B * LM_MAX) | dalloc(c, &s.tracked, (size_t)B * LM_MAX)
-               | dalloc(c, &s.accept, (size_t)B * LM_MAX) | dalloc(c, &s.dx, (size_t)B * c->ldp);
-        if (rc) return INGVIO_E_HIP;
-        s.alloc = true;
-    }
-    s.l_hi = std::max(s.l_hi, l_hi);
-    if (int rc = dense_ws_alloc(c, std::max(32, 4 * s.l_hi))) return rc;
+    if (int rc = landmark_stage_alloc(c, l_hi)) return rc;
     Uploader upl{ c };
     if (int rc = upl.begin(pad64(8 * (size_t)nb * (24 + 7 * LM_MAX)) + pad64(4 * (size_t)nb * (3 + 3 * LM_MAX)) + 1024)) return rc;
     double* hp = upl.take<double>((size_t)nb * 24);
@@ -2477,13 +2506,89 @@ int ingvio_landmark_stage(ingvio_ctx* c, int b0, int nb, const ingvio_landmark_f
     upl.copy(s.anchor_idx + (size_t)b0 * LM_MAX, ha, (size_t)nb * LM_MAX);
     upl.copy(s.tracked + (size_t)b0 * LM_MAX, ht, (size_t)nb * LM_MAX);
     if (int rc = upl.end()) return rc;
-    memcpy(s.op.R_lr, o->R_cl2cr, 72); memcpy(s.op.t_lr, o->t_cl2cr, 24);
-    s.op.var = o->noise * o->noise; s.op.chi2_thr = o->chi2_thr; s.op.stereo = o->stereo ? 1 : 0;
-    s.in_frame = o->in_frame ? 1 : 0;
-    if ((int)s.hi.size() != B) s.hi.assign(B, 0);
-    for (int i = 0; i < nb; ++i) s.hi[b0 + i] = hi_new[i];
-    s.staged = true;
+    landmark_stage_commit(c, b0, nb, o, hi_new);
+    s.nominal = false; s.nom_pending = false;      // (replaces a stage from the device nominal state that has not run)
     return INGVIO_OK;
+}
+
+// ingvio_landmark_stage with everything but the observations taken from the device nominal table.  Validated on the host
+// mirror of the table's integer records, before anything changes; the upload (uv, tracked, n_lm, the table slots) goes to the compute
+// stream, behind the kernels of the frame enqueued last that still read the staged arrays.
+int ingvio_landmark_stage_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_landmark_frame_nominal* fr, const ingvio_landmark_opts* o)
+{
+    ENTER(c);
+    if (phase_busy(c) || check_range(c, b0, nb) || !fr || !o || !(o->noise > 0.0)) return INGVIO_E_ARG;
+    auto& s = c->lm;
+    auto& m = c->nom;
+    const int B = c->d.batch;
+    if (!m.vmax) { c->err = "ingvio_landmark_stage_nominal without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (o->in_frame) {
+        if (!m.pending) { c->err = "ingvio_landmark_stage_nominal(in_frame): no frame staged from the device nominal state is waiting to run"; return INGVIO_E_ARG; }
+        if (b0 != 0 || nb != B) { c->err = "ingvio_landmark_stage_nominal(in_frame) stages the whole batch (b0 = 0, nb = batch)"; return INGVIO_E_ARG; }
+    } else if (m.pending) {
+        c->err = "ingvio_landmark_stage_nominal: a frame staged from the device nominal state has not run yet (in_frame = 0)"; return INGVIO_E_ARG;
+    }
+    if (c->gn.nom_pending) { c->err = "ingvio_landmark_stage_nominal: a GNSS epoch staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    int l_hi = 0;
+    std::vector<int> hi_new(nb, 0);
+    for (int i = 0; i < nb; ++i) {
+        const auto& f = fr[i];
+        const int b = b0 + i;
+        if (f.n_lm < 0 || f.n_lm > LM_MAX) return INGVIO_E_CAPACITY;
+        if (f.n_lm && (!f.lm_var || !f.uv || !f.tracked)) return INGVIO_E_ARG;
+        const int* I = &m.h_ih[(size_t)b * m.ir];
+        const int* var = I + NOM_IH;
+        if (I[NOM_V_POSE] < 0 || I[NOM_V_EXT] < 0) { c->err = "ingvio_landmark_stage_nominal: the table names no extended pose or extrinsics"; return INGVIO_E_ARG; }
+        // (in_frame: the stage of the frame has already put the new clone into the mirror, its 6 columns are appended by the run)
+        const int n_lim = std::min(c->d.n_max, c->h_n[b] + (o->in_frame ? 6 : 0));
+        const int ie = var[4 * I[NOM_V_POSE] + 1], ix = var[4 * I[NOM_V_EXT] + 1];
+        if (ie < 0 || ie + 9 > n_lim || ix < 0 || ix + 6 > n_lim) return INGVIO_E_NOT_IN_STATE;
+        int hi = f.n_lm ? std::max(ie + 9, ix + 6) : 0;
+        for (int l = 0; l < f.n_lm; ++l) {
+            const int v = f.lm_var[l];
+            if (v < 0 || v >= I[NOM_N_VAR] || var[4 * v] != NOM_KIND_LM) { c->err = "ingvio_landmark_stage_nominal: a slot is free or holds no landmark"; return INGVIO_E_ARG; }
+            for (int t = 0; t < l; ++t) if (f.lm_var[t] == v) { c->err = "ingvio_landmark_stage_nominal: a slot is named twice"; return INGVIO_E_ARG; }
+            const int as = var[4 * v + 2], il = var[4 * v + 1], ia = as >= 0 && as < I[NOM_N_VAR] ? var[4 * as + 1] : -1;
+            if (il < 0 || il + 3 > n_lim || ia < 0 || ia + 6 > n_lim) return INGVIO_E_NOT_IN_STATE;
+            hi = std::max(hi, std::max(il + 3, ia + 6));
+        }
+        hi_new[i] = hi;
+        l_hi = std::max(l_hi, f.n_lm);
+    }
+    if (int rc = landmark_stage_alloc(c, l_hi)) return rc;
+    Uploader upl{ c };
+    if (int rc = upl.begin(pad64(8 * (size_t)nb * 4 * LM_MAX) + pad64(4 * (size_t)nb * (1 + 2 * LM_MAX)) + 1024)) return rc;
+    double* huv = upl.take<double>((size_t)nb * LM_MAX * 4);
+    int* hn = upl.take<int>((size_t)nb);
+    int* hs = upl.take<int>((size_t)nb * LM_MAX);
+    int* ht = upl.take<int>((size_t)nb * LM_MAX);
+    for (int i = 0; i < nb; ++i) {
+        const auto& f = fr[i];
+        hn[i] = f.n_lm;
+        for (int l = 0; l < LM_MAX; ++l) {
+            const bool on = l < f.n_lm;
+            hs[i * LM_MAX + l] = on ? f.lm_var[l] : -1; ht[i * LM_MAX + l] = on ? f.tracked[l] : 0;
+            for (int k = 0; k < 4; ++k) huv[((size_t)i * LM_MAX + l) * 4 + k] = on ? ((o->stereo || k < 2) ? f.uv[4 * l + k] : 0.0) : 0.0;
+        }
+    }
+    upl.copy(s.uv + (size_t)b0 * LM_MAX * 4, huv, (size_t)nb * LM_MAX * 4);
+    upl.copy(s.n_lm + b0, hn, (size_t)nb);
+    upl.copy(s.slot + (size_t)b0 * LM_MAX, hs, (size_t)nb * LM_MAX);
+    upl.copy(s.tracked + (size_t)b0 * LM_MAX, ht, (size_t)nb * LM_MAX);
+    if (int rc = upl.end()) return rc;
+    landmark_stage_commit(c, b0, nb, o, hi_new);
+    s.nominal = true; s.nom_pending = !o->in_frame; s.nom_b0 = b0; s.nom_nb = nb;
+    return INGVIO_OK;
+}
+
+// the staged arrays' pose / idx / lm_idx / anchor_idx / pf from the table (dx != nullptr: after boxPlus of dx, in the same launch)
+static void landmark_gather_launch(ingvio_ctx* c, const double* dx, int b0, int nb)
+{
+    auto& s = c->lm;
+    NomGather g;
+    g.n_lm = s.n_lm; g.slot = s.slot; g.lmax = LM_MAX;
+    g.pose = s.pose; g.idx = s.idx; g.lm_idx = s.lm_idx; g.anchor_idx = s.anchor_idx; g.pf = s.pf;
+    launch_nominal_gather(nom_table(c), dx, c->ldp, g, b0, nb, c->st);
 }
 
 // The staged landmark rows name state columns: a marginalisation between stage and run may have shrunk or shifted the state,
@@ -2501,9 +2606,22 @@ int ingvio_landmark_run(ingvio_ctx* c, int b0, int nb)
     ENTER(c);
     if (phase_busy(c)) return INGVIO_E_ARG;
     if (check_range(c, b0, nb) || !c->lm.staged) return INGVIO_E_ARG;
+    auto& s = c->lm;
+    if (s.nominal) {                               // staged from the device nominal state: the range it was staged for, once
+        if (s.in_frame) { c->err = "ingvio_landmark_run: the stage belongs to a frame staged from the device nominal state (ingvio_frame_run applies it)"; return INGVIO_E_ARG; }
+        if (!s.nom_pending || b0 != s.nom_b0 || nb != s.nom_nb) { c->err = "ingvio_landmark_run: a stage from the device nominal state runs once, on the range it was staged for"; return INGVIO_E_ARG; }
+        if (c->nom.pending) { c->err = "ingvio_landmark_run: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    }
     if (int rc = landmark_in_state(c, b0, nb, c->h_n, 0)) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_status + b0, 0, sizeof(int) * (size_t)nb, c->st));
-    return landmark_update_launch(c, b0, nb);
+    if (!s.nominal) return landmark_update_launch(c, b0, nb);
+    // rows at the table as it stands, the update, then StateManager::boxPlus of its dx on the table (LandmarkUpdate.cpp:146-147)
+    s.nom_pending = false; s.staged = false;       // consumed: the table moves with this run, a second one is refused
+    landmark_gather_launch(c, nullptr, b0, nb);
+    if (int rc = landmark_update_launch(c, b0, nb)) return rc;
+    launch_nominal_update(nom_table(c), s.dx, c->ldp, nullptr, b0, nb, c->st);
+    if (int rc = last_launch(c)) return rc;
+    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
 }
 
 int ingvio_landmark_fetch(ingvio_ctx* c, int b0, int nb, double* dx, int* rows, int* accept, double* gamma, int* status)
@@ -2986,6 +3104,7 @@ int ingvio_nominal_create(ingvio_ctx* c, int v_max)
     if (m.pending) { c->staged = false; m.pending = false; }
     m.frame = false;
     if (c->gn.nom_pending) { c->gn.nom_pending = false; c->gn.staged = false; }
+    if (c->lm.nominal && c->lm.staged) { c->lm.nom_pending = false; c->lm.staged = false; }
     return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
 }
 
@@ -3311,9 +3430,12 @@ static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
         if (!c->nom.pending) { c->err = "the frame staged from the device nominal state has already run"; return INGVIO_E_ARG; }
         if (phase) { c->err = "the split step does not take a frame staged from the device nominal state"; return INGVIO_E_UNSUPPORTED; }
         if (restore_prior) { c->err = "restore_prior with a frame staged from the device nominal state (restore with ingvio_cov_restore before the stage)"; return INGVIO_E_ARG; }
-        if ((c->gn.staged && c->gn.in_frame) || (c->lm.staged && c->lm.in_frame) || c->parts_req > 1) {
-            c->err = "the device nominal state takes no in-frame GNSS / landmark stage and frame_parts = 1 only"; return INGVIO_E_UNSUPPORTED;
+        // (the one in-frame stage it takes is the landmark stage from the table itself, ingvio_landmark_stage_nominal)
+        if ((c->gn.staged && c->gn.in_frame) || (c->lm.staged && c->lm.in_frame && !c->lm.nominal) || c->parts_req > 1) {
+            c->err = "the device nominal state takes no in-frame GNSS / host-fed landmark stage and frame_parts = 1 only"; return INGVIO_E_UNSUPPORTED;
         }
+    } else if (c->lm.staged && c->lm.in_frame && c->lm.nominal) {
+        c->err = "an in-frame landmark stage from the device nominal state needs a frame staged from it"; return INGVIO_E_ARG;
     }
     if (phase && c->method != 1) return INGVIO_E_UNSUPPORTED;             // the split needs the information form's [A | b]
     // protocol of the split step: 1 -> (ingvio_debug_msckf_info / ingvio_info_set) -> 2, exactly once each; the accepted-feature
@@ -3436,6 +3558,10 @@ static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
         if (!c->apply_flipped) launch_post_marg(view(c), 0, B, c->d_zero_idx, 0, c->st);
         for (int b = 0; b < B; ++b) c->h_cur[b] ^= 1;
     }
+    // landmarks staged from the device nominal state: boxPlus of the MSCKF dx on the table (no drop, no shift) and, in the same launch,
+    // the landmark inputs from the values just retracted - the rows are formed at the state after the MSCKF update (IngvioFilter.cpp:283-289)
+    const bool lm_nom = with_lm && c->lm.nominal;
+    if (lm_nom) landmark_gather_launch(c, c->d_dx, 0, B);
     bool lm_fused = false;
     if (with_lm) { rc = landmark_update_launch(c, 0, B, c->d_idx, 6, &lm_fused); if (rc) return rc; }
     if (!(fuse && c->apply_flipped)) {             // (the write-back of the fused step has flipped the halves itself: no launch, no profile slot)
@@ -3449,7 +3575,8 @@ static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
     bool all_marg = true;
     for (int b = 0; b < B; ++b) { if (c->st_marg[b] >= 0) { c->h_n[b] -= 6; c->h_cur[b] ^= 1; } else all_marg = false; }
     if (c->nom.pending) {                          // device nominal state: boxPlus with the frame's dx, drop + shift, behind the marginalisation
-        launch_nominal_update(nom_table(c), c->d_dx, c->ldp, c->d_idx, 0, B, c->st);
+        // (with landmarks from the table the frame's dx is on the table already: the LANDMARK update's dx, in the same index space)
+        launch_nominal_update(nom_table(c), lm_nom ? c->lm.dx : c->d_dx, c->ldp, c->d_idx, 0, B, c->st);
         if (int rc2 = last_launch(c)) return rc2;
         for (int b = 0; b < B; ++b) nom_mirror_marg(c, b, c->st_marg[b]);
         c->nom.pending = false;

@@ -45,8 +45,11 @@ __device__ __forceinline__ void mulv(const double A[9], const double* x, double 
 
 // grid = nb filters, block = one wave.  MARG: after the retraction, the variable of idx marg[b] (a window clone) leaves the table (its
 // slot becomes free, the window list closes up) and every variable behind it moves 6 columns down.
-template <bool MARG>
-__global__ __launch_bounds__(64) void k_nominal_update(NomTable t, const double* __restrict__ dx, int ldx, const int* __restrict__ marg, int b0)
+// GATHER (never with MARG): after the retraction (skipped when dx is absent) the wave copies what the landmark update reads - pose,
+// extrinsics, the staged landmarks' positions and every idx - from the table into the staged SoA (NomGather).  A lane is a staged
+// landmark there, not a table slot: it reads back what the wave has just written, behind the barrier.
+template <bool MARG, bool GATHER = false>
+__global__ __launch_bounds__(64) void k_nominal_update(NomTable t, const double* __restrict__ dx, int ldx, const int* __restrict__ marg, int b0, NomGather g)
 {
     const int b = b0 + blockIdx.x, lane = threadIdx.x;
     int* I = t.ih + (size_t)b * t.ir;
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(64) void k_nominal_update(NomTable t, const double*
     double* D = t.dv + (size_t)b * t.dr + NOM_DH;
     const double* d = dx + (size_t)b * ldx;
     const int nv = I[NOM_N_VAR];
-    for (int v = lane; v < nv; v += 64) {
+    for (int v = lane; v < ((GATHER && !dx) ? 0 : nv); v += 64) {
         const int kind = var[4 * v], idx = var[4 * v + 1];
         double* x = D + (size_t)v * NOM_VD;
         if (kind == NOM_KIND_SE23 || kind == NOM_KIND_SE3) {             // PoseState.cpp:174-186 / :79-88
@@ -85,6 +88,22 @@ __global__ __launch_bounds__(64) void k_nominal_update(NomTable t, const double*
             for (int i = 0; i < 3; ++i) x[9 + i] = t1[i] + t2[i];
         }
     }
+    if (GATHER) {
+        __syncthreads();                                                 // the values the other lanes have just retracted
+        const int vp = I[NOM_V_POSE], vx = I[NOM_V_EXT];
+        if (lane < 24) g.pose[(size_t)b * 24 + lane] = D[(size_t)(lane < 12 ? vp : vx) * NOM_VD + (lane < 12 ? lane : lane - 12)];
+        if (lane < 2) g.idx[2 * b + lane] = var[4 * (lane ? vx : vp) + 1];
+        const int nl = min(g.n_lm[b], g.lmax);
+        for (int l = lane; l < nl; l += 64) {
+            const size_t o = (size_t)b * g.lmax + l;
+            const int s = g.slot[o];
+            const bool ok = s >= 0 && s < nv && var[4 * s] == NOM_KIND_LM;
+            const int as = ok ? var[4 * s + 2] : -1;
+            g.lm_idx[o] = ok ? var[4 * s + 1] : -1;
+            g.anchor_idx[o] = (as >= 0 && as < nv) ? var[4 * as + 1] : -1;
+            for (int i = 0; i < 3; ++i) g.pf[3 * o + i] = ok ? D[(size_t)s * NOM_VD + 9 + i] : 0.0;
+        }
+    }
     if (!MARG) return;
     const int m = marg[b];
     if (m < 0) return;
@@ -111,6 +130,11 @@ __global__ __launch_bounds__(64) void k_nominal_update(NomTable t, const double*
 
 void launch_nominal_update(const NomTable& t, const double* dx, int ldx, const int* marg, int b0, int nb, hipStream_t st)
 {
-    if (marg) hipLaunchKernelGGL(k_nominal_update<true>, dim3(nb), dim3(64), 0, st, t, dx, ldx, marg, b0);
-    else hipLaunchKernelGGL(k_nominal_update<false>, dim3(nb), dim3(64), 0, st, t, dx, ldx, marg, b0);
+    if (marg) hipLaunchKernelGGL(k_nominal_update<true>, dim3(nb), dim3(64), 0, st, t, dx, ldx, marg, b0, NomGather{});
+    else hipLaunchKernelGGL(k_nominal_update<false>, dim3(nb), dim3(64), 0, st, t, dx, ldx, marg, b0, NomGather{});
+}
+
+void launch_nominal_gather(const NomTable& t, const double* dx, int ldx, const NomGather& g, int b0, int nb, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_nominal_update<false, true>), dim3(nb), dim3(64), 0, st, t, dx, ldx, (const int*)nullptr, b0, g);
 }

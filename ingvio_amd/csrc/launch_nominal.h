@@ -25,3 +25,14 @@ struct NomTable {
 // StateManager::boxPlus (StateManager.cpp:244-251) of filters [b0, b0 + nb) with dx [b][ldx] (row b of the batch); marg != nullptr: then
 // drop the variable whose idx is marg[b] (a window clone, >= 0) and shift every later idx by 6 (StateManager.cpp:155-192)
 void launch_nominal_update(const NomTable& t, const double* dx, int ldx, const int* marg, int b0, int nb, hipStream_t st);
+
+// The landmark update's staged inputs (LmView, launch_lmbatch.h) filled from the table: per filter the extended pose and the extrinsics
+// into pose [B][24] and their idx into idx [B][2], and for each of the n_lm[b] staged landmarks (slot [B][lmax]: its table slot)
+// lm_idx = idx[slot], anchor_idx = idx[anchor[slot]] (-1: no live anchor), pf = p[slot].  Indexed by the ABSOLUTE filter b.
+struct NomGather {
+    const int* n_lm; const int* slot; int lmax;
+    double* pose; int* idx; int* lm_idx; int* anchor_idx; double* pf;
+};
+// launch_nominal_update without drop and shift, then the gather above from the values it has just retracted, in ONE launch (the
+// landmark rows of a frame are formed at the state after the MSCKF update's boxPlus, IngvioFilter.cpp:283-289).  dx == nullptr: gather only.
+void launch_nominal_gather(const NomTable& t, const double* dx, int ldx, const NomGather& g, int b0, int nb, hipStream_t st);

@@ -20,9 +20,16 @@ into epoch structures).  device_loop_ms_per_frame is the device form free-runnin
 modes write $RESULTS/closed_loop_bench_gnss.json.
 --register-only: the loop without epochs but with the GNSS scalars registered, i.e. the clock recursion of k_imu_steps<true> switched on
 (against the plain run: that kernel's time with and without registered clocks).
+--landmarks L: every filter carries L in-state landmarks that are observed in every frame (ingvio_amd/closed_loop_lm.py), two forms on
+the same build,
+  device form      run(i); stage_async(i+1); landmark_stage_nominal(i+1, in_frame); fetch_begin(i); run(i+1); fetch_end(i) - the
+                   landmark update inside ingvio_frame_run, its inputs from the table
+  round-trip form  the plain frame, then ingvio_nominal_get, ingvio_landmark_stage with the table's values, ingvio_landmark_run,
+                   ingvio_landmark_fetch, ingvio_nominal_box_plus
+measured and reported as the GNSS forms are; writes $RESULTS/closed_loop_bench_lm.json.
 Writes $RESULTS/closed_loop_bench.json (RESULTS defaults to results/) and prints one JSON line.
 usage: python tools/closed_loop_bench.py [--batch 512] [--features 150] [--window 11] [--k 10] [--frames 30] [--warmup 5] [--device-only]
-                                         [--gnss | --register-only]"""
+                                         [--gnss | --register-only | --landmarks L]"""
 import argparse
 import copy
 import json
@@ -181,6 +188,109 @@ def main_gnss(a):
     print(json.dumps(out))
 
 
+def main_landmarks(a):
+    from ingvio_amd import closed_loop as cl
+    from ingvio_amd import closed_loop_lm as clm
+    B, F, NF, W, L = a.batch, a.features, a.frames, a.warmup, a.landmarks
+    t0 = time.perf_counter()
+    cases = clm.make_lm_loop(B, NF, L=L, F=F, ks=(a.k,), windows=(a.window,))
+    opts = clm.lm_opts()
+    out = dict(batch=B, features=F, window=a.window, k=a.k, frames_timed=NF - W, landmarks=L, setup_s=round(time.perf_counter() - t0, 1))
+
+    def fresh():
+        ctx = cl.loop_ctx(cases, F, c_max=a.window + 1)
+        ctx.nominal_create(max(64, 32 + L))
+        ctx.nominal_set(0, [c["table"].as_dict() for c in cases])
+        return ctx
+
+    def device_form(ctx, timed_lib):
+        stages = [cl.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
+        lms = [clm.lm_stage_call(ctx, cases, f, opts) for f in range(NF)]
+        stages[0](); lms[0]()
+        ctx.frame_run()
+        if timed_lib:
+            ctx.L = TimedLib(ctx.L)
+        wall, t0 = 0.0, 0.0
+        for f in range(NF):
+            if timed_lib or f == W:
+                ctx.sync()
+            if f == W:
+                t0 = time.perf_counter()
+                if timed_lib:
+                    ctx.L.t = 0.0
+            t1 = time.perf_counter()
+            if f + 1 < NF:
+                stages[f + 1](); lms[f + 1]()
+                ctx.frame_fetch_begin()
+                ctx.frame_run()
+                ctx.frame_fetch_end()
+            else:
+                ctx.frame_fetch()
+            if timed_lib:
+                ctx.sync()
+                if f >= W:
+                    wall += time.perf_counter() - t1
+        ctx.sync()
+        free = time.perf_counter() - t0
+        abi = ctx.L.t if timed_lib else 0.0
+        if timed_lib:
+            ctx.L = ctx.L._lib
+        return free, abi, wall
+
+    ctx = fresh()
+    free, _, _ = device_form(ctx, False)
+    out["device_loop_ms_per_frame"] = round(1e3 * free / (NF - W), 4)
+    lm = ctx.landmark_fetch()
+    out["last_frame_lm_rows_mean"] = float(lm[1].mean()); out["last_frame_lm_ok"] = int((lm[4] == 0).sum())
+    dev_nom = ctx.nominal_get()
+    ctx.close()
+    if not a.device_only:
+        ctx = fresh()
+        _, abi, wall = device_form(ctx, True)
+        out["device_abi_ms_per_frame"] = round(1e3 * abi / (NF - W), 4)
+        out["device_wall_ms_per_frame"] = round(1e3 * wall / (NF - W), 4)
+        ctx.close()
+        # round-trip form
+        ctx = fresh()
+        stages = [cl.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
+        stages[0]()
+        ctx.frame_run()
+        ctx.L = TimedLib(ctx.L)
+        wall = 0.0
+        for f in range(NF):
+            ctx.sync()
+            if f == W:
+                ctx.L.t = 0.0
+            t1 = time.perf_counter()
+            ctx.frame_fetch_begin()
+            nom = ctx.nominal_get()                                      # synchronises both streams
+            ctx.landmark_stage(0, clm.table_frames(nom, cases, f), opts["stereo"], opts["noise"], opts["chi2_thr"], opts["R_cl2cr"], opts["t_cl2cr"])
+            ctx.landmark_run()
+            lm = ctx.landmark_fetch()                                    # synchronises
+            ctx.nominal_box_plus(0, lm[0])
+            if f + 1 < NF:
+                stages[f + 1]()
+                ctx.frame_run()
+            ctx.frame_fetch_end()
+            ctx.sync()
+            if f >= W:
+                wall += time.perf_counter() - t1
+        abi = ctx.L.t
+        ctx.L = ctx.L._lib
+        out["roundtrip_abi_ms_per_frame"] = round(1e3 * abi / (NF - W), 4)
+        out["roundtrip_wall_ms_per_frame"] = round(1e3 * wall / (NF - W), 4)
+        rt_nom = ctx.nominal_get()
+        ctx.close()
+        # (the two forms differ by design: the round trip updates the landmarks after the frame's marginalisation, with rows at the
+        # values the frame left; the device form inside the frame, in the reference's order)
+        out["max_abs_pose_device_vs_roundtrip"] = max(float(np.max(np.abs(dev_nom[b]["val"][0] - rt_nom[b]["val"][0]))) for b in range(B))
+    res_dir = os.environ.get("RESULTS", os.path.join(ROOT, "results"))
+    os.makedirs(res_dir, exist_ok=True)
+    with open(os.path.join(res_dir, "closed_loop_bench_lm.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=512)
@@ -192,7 +302,10 @@ def main():
     ap.add_argument("--device-only", action="store_true")
     ap.add_argument("--gnss", action="store_true")
     ap.add_argument("--register-only", action="store_true", help="the loop without epochs, the GNSS scalars registered (clock recursion on)")
+    ap.add_argument("--landmarks", type=int, default=0, help="L in-state landmarks per filter, updated in every frame")
     a = ap.parse_args()
+    if a.landmarks > 0:
+        return main_landmarks(a)
     if a.gnss or a.register_only:
         return main_gnss(a)
     from oracle import oracle as orc
