@@ -253,6 +253,34 @@ def make_step_raw(step):
     return s, keep
 
 
+def _gnss_opts(chi2_table, gate_rows, strong_reject, in_frame=False):
+    """-> (GnssOpts, the table it points into)"""
+    tab = f64(chi2_table)
+    o = GnssOpts(); o.gate_rows = int(gate_rows); o.strong_reject = int(strong_reject); o.chi2_table = _d(tab); o.chi2_len = len(tab)
+    o.in_frame = int(in_frame)
+    return o, tab
+
+
+def _landmark_opts(stereo, noise, chi2_thr, R_cl2cr, t_cl2cr, in_frame):
+    o = LandmarkOpts(); o.stereo = int(bool(stereo)); o.noise = float(noise); o.chi2_thr = float(chi2_thr)
+    o.R_cl2cr = (C.c_double * 9)(*f64(np.eye(3) if R_cl2cr is None else R_cl2cr).reshape(9))
+    o.t_cl2cr = (C.c_double * 3)(*f64(np.zeros(3) if t_cl2cr is None else t_cl2cr).reshape(3))
+    o.in_frame = int(bool(in_frame))
+    return o
+
+
+def _epoch_host_fields(a, e):
+    """the host-owned part of a raw epoch into a GnssEpoch / GnssEpochNominal; -> the arrays it points into"""
+    eph, obs = f64(e["eph"]), f64(e["obs"])
+    ion = f64(e["ion"]) if e.get("ion") is not None else None
+    a.n_sat = eph.shape[0]; a.eph = _d(eph); a.obs = _d(obs); a.ion = _d(ion) if ion is not None else None
+    a.doy = float(e["doy"])
+    a.R_enu2ecef = (C.c_double * 9)(*np.asarray(e["R_enu2ecef"], dtype=np.float64).reshape(9))
+    a.anchor_ecef = (C.c_double * 3)(*e["anchor_ecef"])
+    a.psr_noise_amp = float(e.get("psr_amp", 1.0)); a.dopp_noise_amp = float(e.get("dopp_amp", 1.0))
+    return eph, obs, ion
+
+
 class Context:
     """A batch of independent filters on one GPU (ingvio_ctx)."""
 
@@ -437,9 +465,7 @@ class Context:
         """blocks: per filter (vidx, vsize, H [m, nc] candidate rows, res [m], Rdiag [m]) or None.  in_frame: applied by frame_run
         right after the frame's MSCKF update, in the same sweep over P (no gnss_run)."""
         arr, keep = self._update_blocks(blocks)
-        tab = f64(chi2_table)
-        o = GnssOpts(); o.gate_rows = int(gate_rows); o.strong_reject = int(strong_reject); o.chi2_table = _d(tab); o.chi2_len = len(tab)
-        o.in_frame = int(in_frame)
+        o, tab = _gnss_opts(chi2_table, gate_rows, strong_reject, in_frame)
         self._chk(self.L.ingvio_gnss_stage(self.h, b0, len(blocks), arr, C.byref(o)))
         self._gnss_range = (b0, len(blocks))
 
@@ -448,18 +474,12 @@ class Context:
         nb = len(epochs)
         arr = (GnssEpoch * nb)(); keep = []
         for i, e in enumerate(epochs):
-            eph, obs = f64(e["eph"]), f64(e["obs"])
-            ion = f64(e["ion"]) if e.get("ion") is not None else None
-            keep.append((eph, obs, ion))
             a = arr[i]
-            a.n_sat = eph.shape[0]; a.eph = _d(eph); a.obs = _d(obs); a.ion = _d(ion) if ion is not None else None
-            a.doy = float(e["doy"]); a.p_w = (C.c_double * 3)(*e["p_w"]); a.v_w = (C.c_double * 3)(*e["v_w"])
+            keep.append(_epoch_host_fields(a, e))
+            a.p_w = (C.c_double * 3)(*e["p_w"]); a.v_w = (C.c_double * 3)(*e["v_w"])
             a.cb = (C.c_double * 4)(*e["cb"]); a.fs = float(e["fs"]); a.yaw_offset = float(e["yaw_offset"])
-            a.R_enu2ecef = (C.c_double * 9)(*np.asarray(e["R_enu2ecef"], dtype=np.float64).reshape(9))
-            a.anchor_ecef = (C.c_double * 3)(*e["anchor_ecef"])
             a.idx_se23 = int(e["idx_se23"]); a.idx_yof = int(e["idx_yof"]); a.idx_fs = int(e["idx_fs"])
             a.idx_cb = (C.c_int * 4)(*[int(x) for x in e["idx_cb"]])
-            a.psr_noise_amp = float(e.get("psr_amp", 1.0)); a.dopp_noise_amp = float(e.get("dopp_amp", 1.0))
         return arr, keep
 
     def gnss_sat_eval(self, epochs):
@@ -480,8 +500,7 @@ class Context:
         """builds the C arguments of gnss_front_stage once and returns a callable that issues the stage"""
         nb = len(epochs)
         arr, keep = self._gnss_epochs(epochs)
-        tab = f64(chi2_table)
-        o = GnssOpts(); o.gate_rows = int(gate_rows); o.strong_reject = int(strong_reject); o.chi2_table = _d(tab); o.chi2_len = len(tab)
+        o, tab = _gnss_opts(chi2_table, gate_rows, strong_reject)
 
         def call(_keep=(keep, tab, arr, o)):
             self._chk(self.L.ingvio_gnss_front_stage(self.h, b0, nb, arr, C.byref(o)))
@@ -498,17 +517,8 @@ class Context:
             if e is None:
                 a.n_sat = 0
                 continue
-            eph, obs = f64(e["eph"]), f64(e["obs"])
-            ion = f64(e["ion"]) if e.get("ion") is not None else None
-            keep.append((eph, obs, ion))
-            a.n_sat = eph.shape[0]; a.eph = _d(eph); a.obs = _d(obs); a.ion = _d(ion) if ion is not None else None
-            a.doy = float(e["doy"])
-            a.R_enu2ecef = (C.c_double * 9)(*np.asarray(e["R_enu2ecef"], dtype=np.float64).reshape(9))
-            a.anchor_ecef = (C.c_double * 3)(*e["anchor_ecef"])
-            a.psr_noise_amp = float(e.get("psr_amp", 1.0)); a.dopp_noise_amp = float(e.get("dopp_amp", 1.0))
-        tab = f64(chi2_table)
-        o = GnssOpts(); o.gate_rows = int(gate_rows); o.strong_reject = int(strong_reject); o.chi2_table = _d(tab); o.chi2_len = len(tab)
-        o.in_frame = int(in_frame)
+            keep.append(_epoch_host_fields(a, e))
+        o, tab = _gnss_opts(chi2_table, gate_rows, strong_reject, in_frame)
 
         def call(_keep=(keep, tab, arr, o)):
             self._chk(self.L.ingvio_gnss_front_stage_nominal(self.h, int(b0), nb, arr, C.byref(o)))
@@ -558,10 +568,7 @@ class Context:
             a.R_cl2i = (C.c_double * 9)(*f64(f["R_cl2i"]).reshape(9)); a.p_c2i = (C.c_double * 3)(*f64(f["p_c2i"]).reshape(3))
             a.idx_epose = int(f["idx_epose"]); a.idx_ext = int(f["idx_ext"]); a.n_lm = len(li)
             a.lm_idx = _i(li); a.anchor_idx = _i(ai); a.pf = _d(pf); a.uv = _d(uv); a.tracked = tr.ctypes.data_as(C.POINTER(C.c_ubyte))
-        o = LandmarkOpts(); o.stereo = int(bool(stereo)); o.noise = float(noise); o.chi2_thr = float(chi2_thr)
-        o.R_cl2cr = (C.c_double * 9)(*f64(np.eye(3) if R_cl2cr is None else R_cl2cr).reshape(9))
-        o.t_cl2cr = (C.c_double * 3)(*f64(np.zeros(3) if t_cl2cr is None else t_cl2cr).reshape(3))
-        o.in_frame = int(bool(in_frame))
+        o = _landmark_opts(stereo, noise, chi2_thr, R_cl2cr, t_cl2cr, in_frame)
         self._chk(self.L.ingvio_landmark_stage(self.h, b0, nb, arr, C.byref(o)))
         self._lm_range = (b0, nb)
 
@@ -579,10 +586,7 @@ class Context:
             tr = np.ascontiguousarray(f.get("tracked", np.ones(len(lv))), dtype=np.uint8)
             keep.append((lv, uv, tr))
             a.n_lm = len(lv); a.lm_var = _i(lv); a.uv = _d(uv); a.tracked = tr.ctypes.data_as(C.POINTER(C.c_ubyte))
-        o = LandmarkOpts(); o.stereo = int(bool(stereo)); o.noise = float(noise); o.chi2_thr = float(chi2_thr)
-        o.R_cl2cr = (C.c_double * 9)(*f64(np.eye(3) if R_cl2cr is None else R_cl2cr).reshape(9))
-        o.t_cl2cr = (C.c_double * 3)(*f64(np.zeros(3) if t_cl2cr is None else t_cl2cr).reshape(3))
-        o.in_frame = int(bool(in_frame))
+        o = _landmark_opts(stereo, noise, chi2_thr, R_cl2cr, t_cl2cr, in_frame)
 
         def call(_keep=(keep, arr, o)):
             self._chk(self.L.ingvio_landmark_stage_nominal(self.h, int(b0), nb, arr, C.byref(o)))
@@ -744,15 +748,7 @@ class Context:
     # ---- whole-batch frame (bench) ------------------------------------------------------------
     def frame_stage(self, b0, steps, frames, sigma, enable_gnss=0, sigma_cb=0.0, sigma_rw=0.0, max_accept=0,
                     compress_rule=1, selected_variant=0):
-        nb = len(steps)
-        sa = (FrameStep * nb)(); fa = (MsckfFrame * nb)()
-        keeps = []
-        for i in range(nb):
-            s, k1 = make_step(steps[i]); f, k2 = make_frame(frames[i])
-            sa[i] = s; fa[i] = f; keeps.append((k1, k2))
-        o, chi2 = make_opts(frames[0], max_accept, compress_rule, selected_variant)
-        self._chk(self.L.ingvio_frame_stage(self.h, b0, nb, sa, fa, C.byref(o), _d(f64(sigma)), int(enable_gnss),
-                                            C.c_double(sigma_cb), C.c_double(sigma_rw)))
+        self.frame_stage_prepare(b0, steps, frames, sigma, enable_gnss, sigma_cb, sigma_rw, max_accept, compress_rule, selected_variant)()
 
     def tracks_create(self, t_max):
         """allocates / clears the device-resident track store (ingvio_tracks_create)"""

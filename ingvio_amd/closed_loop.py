@@ -1,7 +1,8 @@
 """Closed-loop batches of the device-resident nominal state (ingvio_nominal_*) - harness code shared by
-tests/test_gpu_nominal_state.py and tools/closed_loop_bench.py: inputs of a loop of frames (raw IMU samples, track deltas, the
-marginalised clone), the host reference that keeps the nominal values with the C oracle's functions and the Var semantics of
-oracle/stream_filter.py, and the two ways to drive a context (host loop, device loop)."""
+tests/test_gpu_nominal_*.py and tools/closed_loop_bench.py: inputs of a loop of frames (raw IMU samples, track deltas, the
+marginalised clone), the pieces of the host reference that keeps the nominal values with the C oracle's functions and the Var semantics
+of oracle/stream_filter.py, and DeviceLoop, the one driver of the device loop.  closed_loop_gnss.py and closed_loop_lm.py add their
+inputs, their host reference step and their Form of the driver."""
 import numpy as np
 
 
@@ -73,7 +74,8 @@ KS = (1, 9, 10, 33)
 def make_loop(B, n_frames, F=24, seed=5, ks=KS, windows=None, n_landmarks=2, lm_sigma=1.0):
     """B filters of ragged windows; per frame and filter the raw IMU samples, the track delta and the marginalised clone (always the
     window's second clone: the first one anchors the landmarks).  Only integers of the state enter the inputs, so they are prepared
-    in advance; the host reference keeps the values."""
+    in advance; the host reference keeps the values.  Per frame also "gnss_idx", the clock indices k_propagate takes: the scalars lie
+    in front of the clones here, so they never shift."""
     from oracle import oracle as orc
     from ingvio_amd import synth
     cases = []
@@ -142,7 +144,7 @@ def make_loop(B, n_frames, F=24, seed=5, ks=KS, windows=None, n_landmarks=2, lm_
                      feat_dof=[nobs - 1] * F if nobs >= 3 else [])
             if f == 0:
                 d.update(pf_track=list(range(F)), pf=pf_true)
-            frames.append(dict(delta=d, imu=imus[f], marg=marg, new_idx=n))
+            frames.append(dict(delta=d, imu=imus[f], marg=marg, new_idx=n, gnss_idx=step["gnss_idx"]))
             cidx = [c - 6 if c > marg else c for c in cidx if c != marg]
         cases.append(dict(P=P, table=table, frames=frames, step=step, frame=frame, C=C))
     return cases
@@ -165,17 +167,18 @@ def stage_args(cases):
     return c0["frame"], st["sigma"], st["enable_gnss"], st["sigma_cb"], st["sigma_rw"]
 
 
-def nominal_stage(ctx, cases, f, use_async=False):
+def nominal_stage(ctx, cases, f, use_async=False, enable_gnss=None):
     opts_frame, sigma, eg, scb, srw = stage_args(cases)
-    steps = [dict(imu=c["frames"][f]["imu"], gnss_idx=c["step"]["gnss_idx"], marg_idx=c["frames"][f]["marg"]) for c in cases]
-    return ctx.frame_stage_tracks_nominal_prepare(0, steps, [c["frames"][f]["delta"] for c in cases], opts_frame, sigma, eg, scb, srw,
-                                                  use_async=use_async)
+    steps = [dict(imu=c["frames"][f]["imu"], gnss_idx=c["frames"][f]["gnss_idx"], marg_idx=c["frames"][f]["marg"]) for c in cases]
+    return ctx.frame_stage_tracks_nominal_prepare(0, steps, [c["frames"][f]["delta"] for c in cases], opts_frame, sigma,
+                                                  eg if enable_gnss is None else enable_gnss, scb, srw, use_async=use_async)
 
 
-def host_step(ctx, cases, tabs, f):
-    """the reference loop: ingvio_frame_stage_tracks with host nominal values (oracle.imu_transition), then boxPlus / drop / shift"""
+# ---- the host reference: the pieces every host step is made of ---------------------------------------------------------------------
+def host_propagate(cases, tabs, f, marg=True):
+    """the host half of a frame: IMU nominal integration (oracle.imu_transition) and the new clone on the host tables; -> (steps, track
+    frames) of ingvio_frame_stage_tracks.  marg=False: the frame does not marginalise (the caller does, after its own updates)"""
     from oracle import oracle as orc
-    opts_frame, sigma, eg, scb, srw = stage_args(cases)
     steps, tfs = [], []
     for c, t in zip(cases, tabs):
         fr = c["frames"][f]
@@ -186,37 +189,122 @@ def host_step(ctx, cases, tabs, f):
             R, p, v, _, _ = orc.imu_transition(R, p, v, bg["p"], ba["p"], fr["imu"][q, :3], fr["imu"][q, 3:6], t.gravity, fr["imu"][q, 6])
         e["R"], e["p"], e["v"] = R, p, v
         t.append_clone(fr["new_idx"])
-        steps.append(dict(raw=raw, gnss_idx=c["step"]["gnss_idx"], marg_idx=fr["marg"]))
+        steps.append(dict(raw=raw, gnss_idx=fr["gnss_idx"], marg_idx=fr["marg"] if marg else -1))
         cl = [t.slots[s] for s in t.clones]
         tfs.append(dict(fr["delta"], clone_idx=[s["idx"] for s in cl], clone_R=np.stack([s["R"] for s in cl]), clone_p=np.stack([s["p"] for s in cl])))
-    ctx.frame_stage_tracks_prepare(0, steps, tfs, opts_frame, sigma, eg, scb, srw)()
-    ctx.frame_run()
-    dx, acc, rows = ctx.frame_fetch()
+    return steps, tfs
+
+
+def host_stage(ctx, cases, steps, tfs):
+    ctx.frame_stage_tracks_prepare(0, steps, tfs, *stage_args(cases))()
+
+
+def host_tail(cases, tabs, f, dx, drop=True):
+    """boxPlus with an update's dx, then (drop) the marginalised clone's drop and index shift"""
     for b, (c, t) in enumerate(zip(cases, tabs)):
         t.box_plus(dx[b])
-        t.marginalize(c["frames"][f]["marg"])
-    return dx, acc, rows
+        if drop:
+            t.marginalize(c["frames"][f]["marg"])
 
 
-
-def device_loop(ctx, cases, frames, pipelined):
-    out = []
-    if not pipelined:
-        for f in frames:
-            nominal_stage(ctx, cases, f)()
-            ctx.frame_run()
-            out.append(ctx.frame_fetch())
-        return out
-    nominal_stage(ctx, cases, frames[0], use_async=True)()
+def host_step(ctx, cases, tabs, f):
+    """the reference loop: ingvio_frame_stage_tracks with host nominal values, run, fetch, then boxPlus / drop / shift"""
+    host_stage(ctx, cases, *host_propagate(cases, tabs, f))
     ctx.frame_run()
-    for i, f in enumerate(frames):
-        if i + 1 < len(frames):
-            nominal_stage(ctx, cases, frames[i + 1], use_async=True)()
+    res = ctx.frame_fetch()
+    host_tail(cases, tabs, f, res[0])
+    return res
+
+
+# ---- the device loop -----------------------------------------------------------------------------------------------------------------
+class Form:
+    """What a form of the loop adds to the frame stage / run / fetch of DeviceLoop; this one, the plain loop, adds nothing.
+    late: the form's work on frame i follows that frame's run (after), and the table must see it before frame i + 1 is staged."""
+    late = False
+
+    def prepare(self, ctx, cases, f):
+        """the form's own stage of frame f as a callable, or None"""
+        return None
+
+    def staged(self, loop, i):
+        """right after the frame stage of frames[i]"""
+
+    def after(self, loop, i):
+        """behind the run of frames[i]: serial after its fetch, pipelined right after its fetch_begin"""
+
+    def collect(self, ctx):
+        """the form's results of the frame, or None"""
+        return None
+
+
+class DeviceLoop:
+    """The device loop of every form, driven frame by frame: start(), then frame(i) for i = 0 .. len(frames) - 1; run() does both.
+    The nominal stages refuse when issued out of turn, so the order of the calls is this class and nowhere else:
+      serial            stage(i) staged(i) run(i) fetch(i) after(i) collect(i)
+      pipelined         start: stage(0) staged(0) run(0), then per frame
+                        stage(i+1) staged(i+1) fetch_begin(i) collect(i) run(i+1) fetch_end(i)      (the last frame: fetch(i) collect(i))
+      pipelined, late   fetch_begin(i) after(i) stage(i+1) staged(i+1) run(i+1) fetch_end(i) collect(i)
+    fetch_end(i) is issued after run(i + 1) and still returns frame i's results.  prepare() builds every stage callable ahead of
+    the loop (otherwise each is built when it is due), collect=False leaves the form's results unfetched: what the bench tool times.
+    sync_every_call (serial): a context synchronisation after every call that only enqueues."""
+
+    def __init__(self, ctx, cases, frames, form=None, pipelined=True, sync_every_call=False, collect=True):
+        self.ctx, self.cases, self.frames, self.form, self.pipelined = ctx, cases, list(frames), form or Form(), pipelined
+        self.sync = ctx.sync if sync_every_call and not pipelined else (lambda: None)
+        self.collect = self.form.collect if collect else (lambda ctx: None)
+        self.stages, self.form_calls = {}, {}
+
+    def prepare(self):
+        for i, f in enumerate(self.frames):
+            self.stages[i] = nominal_stage(self.ctx, self.cases, f, use_async=self.pipelined)
+            self.form_calls[i] = self.form.prepare(self.ctx, self.cases, f)
+        return self
+
+    def form_call(self, i):
+        return self.form_calls[i] if i in self.form_calls else self.form.prepare(self.ctx, self.cases, self.frames[i])
+
+    def stage(self, i):
+        (self.stages.get(i) or nominal_stage(self.ctx, self.cases, self.frames[i], use_async=self.pipelined))()
+        self.sync()
+        self.form.staged(self, i)
+
+    def start(self):
+        if self.pipelined:
+            self.stage(0)
+            self.ctx.frame_run()
+
+    def frame(self, i):
+        """-> frame i's (dx, accept, rows), with a form that collects: (that, the form's results)"""
+        ctx, form, last = self.ctx, self.form, i + 1 == len(self.frames)
+        if self.pipelined and not form.late and not last:
+            self.stage(i + 1)
             ctx.frame_fetch_begin()
+            res = self.collect(ctx)                                      # after stage i + 1: its upload leaves frame i's results alone
             ctx.frame_run()
-            out.append(ctx.frame_fetch_end())
+            fr = ctx.frame_fetch_end()
+            return fr if res is None else (fr, res)
+        if not self.pipelined:
+            self.stage(i)
+            ctx.frame_run()
+            self.sync()
+            fr = ctx.frame_fetch()
+            form.after(self, i)
+        elif form.late:
+            ctx.frame_fetch_begin()
+            form.after(self, i)
+            if not last:
+                self.stage(i + 1)
+                ctx.frame_run()
+            fr = ctx.frame_fetch_end()                                   # issued after run(i + 1): still frame i's results
         else:
-            out.append(ctx.frame_fetch())
-    return out
+            fr = ctx.frame_fetch()
+        res = self.collect(ctx)
+        return fr if res is None else (fr, res)
+
+    def run(self):
+        self.start()
+        return [self.frame(i) for i in range(len(self.frames))]
 
 
+def device_loop(ctx, cases, frames, pipelined, form=None, sync_every_call=False):
+    return DeviceLoop(ctx, cases, frames, form, pipelined, sync_every_call).run()

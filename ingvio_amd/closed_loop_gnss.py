@@ -1,7 +1,8 @@
 """GNSS epochs in the closed loop of the device-resident nominal state (ingvio_nominal_set_gnss, ingvio_gnss_front_stage_nominal, DESIGN
 4.11) - harness code beside ingvio_amd/closed_loop.py, shared by tests/test_gpu_nominal_gnss.py and tools/closed_loop_bench.py --gnss:
 the loop inputs of closed_loop.make_loop with receiver clocks in the table and one raw GNSS epoch per filter and frame, the host
-reference (clock recursion of ImuPropagator.cpp:139-148, host-fed front, host boxPlus) and the device loop.
+reference (clock recursion of ImuPropagator.cpp:139-148, host-fed front, host boxPlus) and the loop's two forms for
+closed_loop.DeviceLoop (epochs from the table, epochs through the host).
 
 The satellite data is one recorded instant (tests/golden/gnss_front.npz) while the synthetic trajectory moves, so every epoch is made
 consistent with the filter's TRUE state of its frame: the anchor maps the true position onto the fixture's evaluation point (plus a few
@@ -9,7 +10,8 @@ metres), and pseudo-ranges / Dopplers are shifted by the difference between the 
 velocity, clocks that drift with the true frequency shift) and at the fixture's own true state - the fixture's measurement noise stays."""
 import numpy as np
 
-from ingvio_amd.closed_loop import SCALAR, make_loop, stage_args
+from ingvio_amd.closed_loop import SCALAR, Form, device_loop, host_step, make_loop
+from ingvio_amd.closed_loop import nominal_stage  # noqa: F401  (the GNSS loop's stage is the plain one: it reads the frame's own clock indices)
 
 C_LIGHT = 2.99792458e8
 LAT, LON = np.deg2rad(31.0), np.deg2rad(121.4)
@@ -115,25 +117,18 @@ def host_clocks(t, slots, imu, enable_gnss=1):
         t.slots[slots[s]]["p"] = np.array([cb, 0.0, 0.0])
 
 
-def host_epoch(t, slots, ep):
-    """the epoch ingvio_gnss_front_stage takes: the host-owned part plus the receiver state of the host table"""
-    if ep is None:
-        return dict(eph=NO_EPH, obs=NO_OBS, ion=None, doy=0.0, p_w=np.zeros(3), v_w=np.zeros(3), cb=np.zeros(4), fs=0.0, yaw_offset=0.0,
-                    R_enu2ecef=np.eye(3), anchor_ecef=np.zeros(3), idx_se23=-1, idx_yof=-1, idx_fs=-1, idx_cb=[-1] * 4)
-    e = t.slots[t.v_pose]
-    val = lambda s: float(t.slots[s]["p"][0]) if s >= 0 else 0.0
-    idx = lambda s: int(t.slots[s]["idx"]) if s >= 0 else -1
-    return dict(ep, p_w=e["p"], v_w=e["v"], cb=[val(s) for s in slots[:4]], fs=val(slots[4]), yaw_offset=val(slots[5]), idx_se23=e["idx"],
-                idx_yof=idx(slots[5]), idx_fs=idx(slots[4]), idx_cb=[idx(s) for s in slots[:4]])
+NO_EPOCH = dict(eph=NO_EPH, obs=NO_OBS, ion=None, doy=0.0, p_w=np.zeros(3), v_w=np.zeros(3), cb=np.zeros(4), fs=0.0, yaw_offset=0.0,
+                R_enu2ecef=np.eye(3), anchor_ecef=np.zeros(3), idx_se23=-1, idx_yof=-1, idx_fs=-1, idx_cb=[-1] * 4)
 
 
 def table_epochs(nominal, cases, f):
-    """host-fed epochs from what ingvio_nominal_get returned (the round-trip form)"""
+    """the epochs ingvio_gnss_front_stage takes: the host-owned part plus the receiver state of the tables, given in the layout of
+    ingvio_nominal_get / HostTable.as_dict()"""
     out = []
     for nm, c in zip(nominal, cases):
         ep, sl = c["epochs"][f], c["gnss_slots"]
         if ep is None:
-            out.append(host_epoch(None, sl, None))
+            out.append(NO_EPOCH)
             continue
         vp = nm["v_pose"]
         val = lambda s: float(nm["val"][s, 9]) if s >= 0 else 0.0
@@ -143,38 +138,8 @@ def table_epochs(nominal, cases, f):
     return out
 
 
-def nominal_stage(ctx, cases, f, use_async=False, enable_gnss=None):
-    """closed_loop.nominal_stage with the frame's own clock indices"""
-    opts_frame, sigma, eg, scb, srw = stage_args(cases)
-    steps = [dict(imu=c["frames"][f]["imu"], gnss_idx=c["frames"][f]["gnss_idx"], marg_idx=c["frames"][f]["marg"]) for c in cases]
-    return ctx.frame_stage_tracks_nominal_prepare(0, steps, [c["frames"][f]["delta"] for c in cases], opts_frame, sigma,
-                                                  eg if enable_gnss is None else enable_gnss, scb, srw, use_async=use_async)
-
-
-def host_step(ctx, cases, tabs, f):
-    """closed_loop.host_step with the frame's own clock indices"""
-    from oracle import oracle as orc
-    opts_frame, sigma, eg, scb, srw = stage_args(cases)
-    steps, tfs = [], []
-    for c, t in zip(cases, tabs):
-        fr = c["frames"][f]
-        e, bg, ba = t.slots[t.v_pose], t.slots[t.v_bg], t.slots[t.v_ba]
-        raw = dict(imu=fr["imu"], R=e["R"], p=e["p"], v=e["v"], bg=bg["p"], ba=ba["p"], gravity=t.gravity)
-        R, p, v = e["R"], e["p"], e["v"]
-        for q in range(fr["imu"].shape[0]):
-            R, p, v, _, _ = orc.imu_transition(R, p, v, bg["p"], ba["p"], fr["imu"][q, :3], fr["imu"][q, 3:6], t.gravity, fr["imu"][q, 6])
-        e["R"], e["p"], e["v"] = R, p, v
-        t.append_clone(fr["new_idx"])
-        steps.append(dict(raw=raw, gnss_idx=fr["gnss_idx"], marg_idx=fr["marg"]))
-        cl = [t.slots[s] for s in t.clones]
-        tfs.append(dict(fr["delta"], clone_idx=[s["idx"] for s in cl], clone_R=np.stack([s["R"] for s in cl]), clone_p=np.stack([s["p"] for s in cl])))
-    ctx.frame_stage_tracks_prepare(0, steps, tfs, opts_frame, sigma, eg, scb, srw)()
-    ctx.frame_run()
-    dx, acc, rows = ctx.frame_fetch()
-    for b, (c, t) in enumerate(zip(cases, tabs)):
-        t.box_plus(dx[b])
-        t.marginalize(c["frames"][f]["marg"])
-    return dx, acc, rows
+def host_epochs(tabs, cases, f):
+    return table_epochs([t.as_dict() for t in tabs], cases, f)
 
 
 def host_step_gnss(ctx, cases, tabs, f, chi2_table, enable_gnss=1):
@@ -183,8 +148,7 @@ def host_step_gnss(ctx, cases, tabs, f, chi2_table, enable_gnss=1):
     for c, t in zip(cases, tabs):
         host_clocks(t, c["gnss_slots"], c["frames"][f]["imu"], enable_gnss)
     frame = host_step(ctx, cases, tabs, f)
-    ctx.gnss_front_stage(0, [host_epoch(t, c["gnss_slots"], c["epochs"][f]) for c, t in zip(cases, tabs)], chi2_table, gate_rows=True,
-                         strong_reject=True)
+    ctx.gnss_front_stage(0, host_epochs(tabs, cases, f), chi2_table, gate_rows=True, strong_reject=True)
     ctx.gnss_run()
     g = ctx.gnss_fetch()
     for b, t in enumerate(tabs):
@@ -197,30 +161,46 @@ def gnss_stage_call(ctx, cases, f, chi2_table):
     return ctx.gnss_front_stage_nominal_prepare(0, [c["epochs"][f] for c in cases], chi2_table, gate_rows=True, strong_reject=True)
 
 
-def device_loop_gnss(ctx, cases, frames, chi2_table, pipelined, sync_every_call=False):
-    """the device loop with GNSS epochs; -> [(frame results, GNSS results)] per frame.  pipelined:
-    run(i); fetch_begin(i); gnss_front_stage_nominal(i); gnss_run(i); stage_tracks_nominal(i + 1, async); run(i + 1); fetch_end(i)
-    (the GNSS results are fetched after that, which is optional for the loop)"""
-    out = []
-    sync = ctx.sync if sync_every_call else (lambda: None)
-    if not pipelined:
-        for f in frames:
-            nominal_stage(ctx, cases, f)(); sync()
-            ctx.frame_run(); sync()
-            fr = ctx.frame_fetch()
-            gnss_stage_call(ctx, cases, f, chi2_table)(); sync()
-            ctx.gnss_run(); sync()
-            out.append((fr, ctx.gnss_fetch()))
-        return out
-    nominal_stage(ctx, cases, frames[0], use_async=True)()
-    ctx.frame_run()
-    for i, f in enumerate(frames):
-        ctx.frame_fetch_begin()
-        gnss_stage_call(ctx, cases, f, chi2_table)()
+class GnssForm(Form):
+    """the epoch of frame i from the table, behind that frame's run: gnss_front_stage_nominal(i); gnss_run(i).  Its boxPlus must
+    reach the table before frame i + 1 is staged (late); the GNSS results are fetched last, which is optional for the loop.
+    epochs=False: no epochs, the late order alone (the loop with registered clocks)"""
+    late = True
+
+    def __init__(self, chi2_table, epochs=True):
+        self.chi2_table, self.epochs = chi2_table, epochs
+
+    def prepare(self, ctx, cases, f):
+        return gnss_stage_call(ctx, cases, f, self.chi2_table) if self.epochs else None
+
+    def after(self, loop, i):
+        if self.epochs:
+            loop.form_call(i)()
+            loop.sync()
+            loop.ctx.gnss_run()
+            loop.sync()
+
+    def collect(self, ctx):
+        return ctx.gnss_fetch() if self.epochs else None
+
+
+class GnssRoundTrip(Form):
+    """the epoch through the host: ingvio_nominal_get, ingvio_gnss_front_stage with the table's values, ingvio_gnss_run,
+    ingvio_gnss_fetch, ingvio_nominal_box_plus (three synchronisations per epoch)"""
+    late = True
+
+    def __init__(self, chi2_table):
+        self.chi2_table = chi2_table
+
+    def after(self, loop, i):
+        ctx = loop.ctx
+        nom = ctx.nominal_get()                                          # synchronises both streams
+        ctx.gnss_front_stage_prepare(0, table_epochs(nom, loop.cases, loop.frames[i]), self.chi2_table, gate_rows=True, strong_reject=True)()
         ctx.gnss_run()
-        if i + 1 < len(frames):
-            nominal_stage(ctx, cases, frames[i + 1], use_async=True)()
-            ctx.frame_run()
-        fr = ctx.frame_fetch_end()                                       # issued after gnss_run(i): still frame i's MSCKF results
-        out.append((fr, ctx.gnss_fetch()))
-    return out
+        g = ctx.gnss_fetch()                                             # synchronises
+        ctx.nominal_box_plus(0, g[0])
+
+
+def device_loop_gnss(ctx, cases, frames, chi2_table, pipelined, sync_every_call=False):
+    """the device loop with GNSS epochs; -> [(frame results, GNSS results)] per frame"""
+    return device_loop(ctx, cases, frames, pipelined, GnssForm(chi2_table), sync_every_call)

@@ -1,7 +1,8 @@
 """In-state SLAM landmarks in the closed loop of the device-resident nominal state (ingvio_landmark_stage_nominal) -
 harness code beside ingvio_amd/closed_loop.py, shared by tests/test_gpu_nominal_landmarks.py and tools/closed_loop_bench.py --landmarks:
 the loop inputs of closed_loop.make_loop with L real landmarks per filter that stay in view over all frames, the host reference loop in
-the reference's order (IngvioFilter.cpp:277-324) built from the host-fed entry points, and the device loop.
+the reference's order (IngvioFilter.cpp:277-324) built from the host-fed entry points, and the loop's two forms for
+closed_loop.DeviceLoop (the in-frame stage from the table, the update through the host).
 
 The landmarks are points seen from the TRUE camera poses of every frame (synth.make_features over the loop's frame times), anchored to
 the window's first clone (make_loop never marginalises it); the table holds their positions with a small error, the prior their 3 x 3
@@ -9,7 +10,7 @@ blocks.  Every `outlier_every`-th landmark is grossly off in every third frame (
 in some frames."""
 import numpy as np
 
-from ingvio_amd.closed_loop import LM, make_loop, nominal_stage, stage_args
+from ingvio_amd.closed_loop import LM, Form, device_loop, host_propagate, host_stage, host_tail, make_loop
 
 CHI2_4, CHI2_2 = 9.487729036781154, 5.991464547107979      # quantile(chi_squared(4 | 2), 0.95), Update.cpp:98-100
 LM_NOISE = 0.02
@@ -52,55 +53,40 @@ def lm_opts(stereo=True, noise=LM_NOISE):
     return dict(stereo=stereo, noise=noise, chi2_thr=CHI2_4 if stereo else CHI2_2, R_cl2cr=Rlr, t_cl2cr=tlr)
 
 
-def host_frames(tabs, cases, f):
-    """what ingvio_landmark_stage takes, from the host tables' present values"""
-    out = []
-    for c, t in zip(cases, tabs):
-        e, x = t.slots[t.v_pose], t.slots[t.v_ext]
-        lm = [t.slots[s] for s in c["lm_slots"]]
-        out.append(dict(R_i2w=e["R"], p_i2w=e["p"], R_cl2i=x["R"], p_c2i=x["p"], idx_epose=e["idx"], idx_ext=x["idx"],
-                        lm_idx=[s["idx"] for s in lm], anchor_idx=[t.slots[s["anchor"]]["idx"] for s in lm],
-                        pf=np.stack([s["p"] for s in lm]) if lm else np.zeros((0, 3)), uv=c["frames"][f]["lm_uv"],
-                        tracked=c["frames"][f]["lm_tracked"]))
-    return out
-
-
-def table_frames(nominal, cases, f, slots=None, uv=None, tracked=None):
-    """the same from what ingvio_nominal_get returned (the round-trip form)"""
-    out = []
-    for b, (nm, c) in enumerate(zip(nominal, cases)):
-        sl = c["lm_slots"] if slots is None else slots[b]
-        vp, vx = nm["v_pose"], nm["v_ext"]
-        out.append(dict(R_i2w=nm["val"][vp, 0:9].reshape(3, 3), p_i2w=nm["val"][vp, 9:12], R_cl2i=nm["val"][vx, 0:9].reshape(3, 3),
-                        p_c2i=nm["val"][vx, 9:12], idx_epose=int(nm["idx"][vp]), idx_ext=int(nm["idx"][vx]),
-                        lm_idx=[int(nm["idx"][s]) for s in sl], anchor_idx=[int(nm["idx"][nm["anchor"][s]]) for s in sl],
-                        pf=nm["val"][sl, 9:12].reshape(-1, 3), uv=c["frames"][f]["lm_uv"] if uv is None else uv[b],
-                        tracked=c["frames"][f]["lm_tracked"] if tracked is None else tracked[b]))
-    return out
-
-
 def nominal_frames(cases, f):
     """what ingvio_landmark_stage_nominal takes: slots, observations, tracked flags"""
     return [dict(lm_var=c["lm_slots"], uv=c["frames"][f]["lm_uv"], tracked=c["frames"][f]["lm_tracked"]) for c in cases]
 
 
-def host_propagate(cases, tabs, f, marg):
-    """IMU nominal integration and the new clone on the host tables; -> (steps, track frames) of ingvio_frame_stage_tracks"""
-    from oracle import oracle as orc
-    steps, tfs = [], []
-    for c, t in zip(cases, tabs):
-        fr = c["frames"][f]
-        e, bg, ba = t.slots[t.v_pose], t.slots[t.v_bg], t.slots[t.v_ba]
-        raw = dict(imu=fr["imu"], R=e["R"], p=e["p"], v=e["v"], bg=bg["p"], ba=ba["p"], gravity=t.gravity)
-        R, p, v = e["R"], e["p"], e["v"]
-        for q in range(fr["imu"].shape[0]):
-            R, p, v, _, _ = orc.imu_transition(R, p, v, bg["p"], ba["p"], fr["imu"][q, :3], fr["imu"][q, 3:6], t.gravity, fr["imu"][q, 6])
-        e["R"], e["p"], e["v"] = R, p, v
-        t.append_clone(fr["new_idx"])
-        steps.append(dict(raw=raw, gnss_idx=c["step"]["gnss_idx"], marg_idx=fr["marg"] if marg else -1))
-        cl = [t.slots[s] for s in t.clones]
-        tfs.append(dict(fr["delta"], clone_idx=[s["idx"] for s in cl], clone_R=np.stack([s["R"] for s in cl]), clone_p=np.stack([s["p"] for s in cl])))
-    return steps, tfs
+def staged_frames(nominal, staged):
+    """what ingvio_landmark_stage takes, from tables in the layout of ingvio_nominal_get / HostTable.as_dict() and what
+    ingvio_landmark_stage_nominal takes (nominal_frames; None: a filter that stages nothing)"""
+    out = []
+    for nm, s in zip(nominal, staged):
+        sl = [] if s is None else list(s["lm_var"])
+        vp, vx = nm["v_pose"], nm["v_ext"]
+        out.append(dict(R_i2w=nm["val"][vp, 0:9].reshape(3, 3), p_i2w=nm["val"][vp, 9:12], R_cl2i=nm["val"][vx, 0:9].reshape(3, 3),
+                        p_c2i=nm["val"][vx, 9:12], idx_epose=int(nm["idx"][vp]), idx_ext=int(nm["idx"][vx]),
+                        lm_idx=[int(nm["idx"][v]) for v in sl], anchor_idx=[int(nm["idx"][nm["anchor"][v]]) for v in sl],
+                        pf=nm["val"][sl, 9:12].reshape(-1, 3), uv=np.zeros((0, 4)) if s is None else s["uv"],
+                        tracked=np.zeros(0, dtype=np.uint8) if s is None else s["tracked"]))
+    return out
+
+
+def table_frames(nominal, cases, f, slots=None, uv=None, tracked=None):
+    """staged_frames for frame f of the loop; slots / uv / tracked [B]: other landmarks or observations than the loop's"""
+    staged = nominal_frames(cases, f)
+    for b, s in enumerate(staged):
+        s.update({k: v[b] for k, v in (("lm_var", slots), ("uv", uv), ("tracked", tracked)) if v is not None})
+    return staged_frames(nominal, staged)
+
+
+def host_frames(tabs, cases, f):
+    return table_frames([t.as_dict() for t in tabs], cases, f)
+
+
+def host_lm_stage(ctx, frames, opts, in_frame=False):
+    ctx.landmark_stage(0, frames, opts["stereo"], opts["noise"], opts["chi2_thr"], opts["R_cl2cr"], opts["t_cl2cr"], in_frame=in_frame)
 
 
 def host_step_lm(ctx, cases, tabs, f, opts):
@@ -108,31 +94,24 @@ def host_step_lm(ctx, cases, tabs, f, opts):
     host, ingvio_frame_stage_tracks with host values and NO marginalisation -> run -> fetch -> host boxPlus -> ingvio_landmark_stage with
     the updated values -> run -> fetch -> host boxPlus -> ingvio_marginalize of the frame's clone -> the host table's drop and shift.
     -> ((dx, accept, rows) of the MSCKF update, (dx, rows, accept, gamma, status) of the landmark update)"""
-    opts_frame, sigma, eg, scb, srw = stage_args(cases)
-    steps, tfs = host_propagate(cases, tabs, f, marg=False)
-    ctx.frame_stage_tracks_prepare(0, steps, tfs, opts_frame, sigma, eg, scb, srw)()
+    host_stage(ctx, cases, *host_propagate(cases, tabs, f, marg=False))
     ctx.frame_run()
     frame = ctx.frame_fetch()
-    for b, t in enumerate(tabs):
-        t.box_plus(frame[0][b])
-    ctx.landmark_stage(0, host_frames(tabs, cases, f), opts["stereo"], opts["noise"], opts["chi2_thr"], opts["R_cl2cr"], opts["t_cl2cr"])
+    host_tail(cases, tabs, f, frame[0], drop=False)
+    host_lm_stage(ctx, host_frames(tabs, cases, f), opts)
     ctx.landmark_run()
     lm = ctx.landmark_fetch()
-    for b, (c, t) in enumerate(zip(cases, tabs)):
-        t.box_plus(lm[0][b])
+    for b, c in enumerate(cases):
         ctx.marginalize(b, c["frames"][f]["marg"], 6)
-        t.marginalize(c["frames"][f]["marg"])
+    host_tail(cases, tabs, f, lm[0])
     return frame, lm
 
 
 def host_step_lm_prestaged(ctx, cases, tabs, f, opts):
     """the host-fed IN-FRAME landmark stage: the rows are staged before ingvio_frame_run, i.e. linearised at the values the host has
     BEFORE the frame's MSCKF update (not the reference's order).  The host tables are left propagated, not updated."""
-    opts_frame, sigma, eg, scb, srw = stage_args(cases)
-    steps, tfs = host_propagate(cases, tabs, f, marg=True)
-    ctx.frame_stage_tracks_prepare(0, steps, tfs, opts_frame, sigma, eg, scb, srw)()
-    ctx.landmark_stage(0, host_frames(tabs, cases, f), opts["stereo"], opts["noise"], opts["chi2_thr"], opts["R_cl2cr"], opts["t_cl2cr"],
-                       in_frame=True)
+    host_stage(ctx, cases, *host_propagate(cases, tabs, f))
+    host_lm_stage(ctx, host_frames(tabs, cases, f), opts, in_frame=True)
     ctx.frame_run()
     return ctx.frame_fetch(), ctx.landmark_fetch()
 
@@ -142,29 +121,40 @@ def lm_stage_call(ctx, cases, f, opts, in_frame=True):
                                               opts["t_cl2cr"], in_frame=in_frame)
 
 
+class LmForm(Form):
+    """the in-frame landmark stage from the table, right behind the frame stage it belongs to; the frame's run applies it.  The
+    landmark results of frame i are fetched between fetch_begin(i) and run(i + 1) (optional for the loop; it synchronises)."""
+
+    def __init__(self, opts):
+        self.opts = opts
+
+    def prepare(self, ctx, cases, f):
+        return lm_stage_call(ctx, cases, f, self.opts)
+
+    def staged(self, loop, i):
+        loop.form_call(i)()
+
+    def collect(self, ctx):
+        return ctx.landmark_fetch()
+
+
+class LmRoundTrip(Form):
+    """the plain frame, then the update through the host: ingvio_nominal_get, ingvio_landmark_stage with the table's values,
+    ingvio_landmark_run, ingvio_landmark_fetch, ingvio_nominal_box_plus"""
+    late = True
+
+    def __init__(self, opts):
+        self.opts = opts
+
+    def after(self, loop, i):
+        ctx = loop.ctx
+        nom = ctx.nominal_get()                                          # synchronises both streams
+        host_lm_stage(ctx, table_frames(nom, loop.cases, loop.frames[i]), self.opts)
+        ctx.landmark_run()
+        lm = ctx.landmark_fetch()                                        # synchronises
+        ctx.nominal_box_plus(0, lm[0])
+
+
 def device_loop_lm(ctx, cases, frames, opts, pipelined):
-    """the device loop with the in-frame landmark stage; -> [(frame results, landmark results)] per frame.  pipelined:
-    run(i); stage_tracks_nominal(i + 1, async); landmark_stage_nominal(i + 1); fetch_begin(i); run(i + 1); fetch_end(i)
-    The landmark results of frame i are fetched between fetch_begin(i) and run(i + 1) (optional for the loop; it synchronises)."""
-    out = []
-    if not pipelined:
-        for f in frames:
-            nominal_stage(ctx, cases, f)()
-            lm_stage_call(ctx, cases, f, opts)()
-            ctx.frame_run()
-            out.append((ctx.frame_fetch(), ctx.landmark_fetch()))
-        return out
-    nominal_stage(ctx, cases, frames[0], use_async=True)()
-    lm_stage_call(ctx, cases, frames[0], opts)()
-    ctx.frame_run()
-    for i, f in enumerate(frames):
-        if i + 1 < len(frames):
-            nominal_stage(ctx, cases, frames[i + 1], use_async=True)()
-            lm_stage_call(ctx, cases, frames[i + 1], opts)()
-            ctx.frame_fetch_begin()
-            lm = ctx.landmark_fetch()                                    # after stage i + 1: its upload leaves frame i's results alone
-            ctx.frame_run()
-            out.append((ctx.frame_fetch_end(), lm))
-        else:
-            out.append((ctx.frame_fetch(), ctx.landmark_fetch()))
-    return out
+    """the device loop with the in-frame landmark stage; -> [(frame results, landmark results)] per frame"""
+    return device_loop(ctx, cases, frames, pipelined, LmForm(opts))

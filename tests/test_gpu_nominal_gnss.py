@@ -13,44 +13,20 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from ingvio_amd.closed_loop import NONE, loop_ctx
-from ingvio_amd.closed_loop_gnss import (R_ENU, device_loop_gnss, gnss_stage_call, host_step_gnss, make_gnss_loop, nominal_stage, rot_z,
-                                          table_epochs)
+from conftest import rel_err as rel
+from ingvio_amd.closed_loop import loop_ctx, nominal_stage
+from ingvio_amd.closed_loop_gnss import R_ENU, device_loop_gnss, gnss_stage_call, host_step_gnss, make_gnss_loop, rot_z, table_epochs
+from nominal_helpers import TABLE_KEYS, assert_table, refused, same_state, table_ctx
+from nominal_helpers import device_state as state
 
 pytestmark = pytest.mark.gpu
 
 F = 24
-TABLE_KEYS = ("kind", "idx", "anchor", "val", "clone_var")
-
-
-def rel(a, b):
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
 def chi2():
     from ingvio_amd import synth
     return synth.chi2_table()
-
-
-def new_ctx(cases, register=True):
-    ctx = loop_ctx(cases, F)
-    ctx.nominal_create(48)
-    ctx.nominal_set(0, [c["table"].as_dict() for c in cases])
-    if register:
-        ctx.nominal_set_gnss(0, [c["gnss_slots"] for c in cases])
-    return ctx
-
-
-def state(ctx, B):
-    return ctx.nominal_get(), [ctx.cov_get(b) for b in range(B)]
-
-
-def same_state(s0, s1, what=""):
-    for b in range(len(s0[1])):
-        for key in TABLE_KEYS:
-            assert np.array_equal(s0[0][b][key], s1[0][b][key]), (what, b, key)
-        assert np.array_equal(s0[1][b], s1[1][b]), (what, b)
 
 
 def same_gnss(cases, f, ga, gb, ns, what=""):
@@ -74,7 +50,7 @@ def test_clock_recursion_matches_the_sequential_host_sum():
     no_fs = [sl[:4] + [-1, sl[5]] for sl in full]
 
     def staged(slots, eg):
-        ctx = new_ctx(cases, register=False)
+        ctx = table_ctx(cases, F)
         if slots is not None:
             ctx.nominal_set_gnss(0, slots)
             assert np.array_equal(ctx.nominal_get_gnss(), np.array(slots))
@@ -128,7 +104,7 @@ def test_front_from_the_table_equals_the_host_fed_front_and_the_oracle(orc):
     table = chi2()
     res = []
     for nominal in (True, False):
-        ctx = new_ctx(cases)
+        ctx = table_ctx(cases, F, gnss=True)
         nominal_stage(ctx, cases, 0)()
         ctx.frame_run()
         ctx.frame_fetch()
@@ -173,24 +149,12 @@ def loop_cases():
     return make_gnss_loop(load_golden("gnss_front"), 24, 13)
 
 
-def assert_table(dev, host, tol, what):
-    h = host.as_dict()
-    n = len(h["kind"])
-    assert list(dev["kind"][:n]) == list(h["kind"]) and all(k == NONE for k in dev["kind"][n:]), what
-    for i in range(n):
-        if h["kind"][i] == NONE:
-            continue
-        assert dev["idx"][i] == h["idx"][i] and dev["anchor"][i] == h["anchor"][i], (what, i)
-        assert rel(dev["val"][i], h["val"][i]) <= tol, (what, i, rel(dev["val"][i], h["val"][i]))
-    assert list(dev["clone_var"]) == list(h["clone_var"]), what
-
-
 def test_closed_loop_with_gnss_device_equals_host(loop_cases):
     from ingvio_amd import capi
     cases = loop_cases
     B, ns = len(cases), 12
     table = chi2()
-    ch, cd = loop_ctx(cases, F), new_ctx(cases)
+    ch, cd = loop_ctx(cases, F), table_ctx(cases, F, gnss=True)
     tabs = [copy.deepcopy(c["table"]) for c in cases]
     epochs = ok = 0
     for f in range(len(cases[0]["frames"])):
@@ -228,7 +192,7 @@ def test_pipelined_gnss_loop_equals_serial_loop(loop_cases):
     table = chi2()
     res = []
     for pipelined in (False, True):
-        ctx = new_ctx(cases)
+        ctx = table_ctx(cases, F, gnss=True)
         out = device_loop_gnss(ctx, cases, list(range(len(cases[0]["frames"]))), table, pipelined, sync_every_call=not pipelined)
         res.append((out, state(ctx, B)))
         ctx.close()
@@ -246,7 +210,7 @@ def test_snapshot_restore_replays_the_gnss_loop_bit_for_bit(loop_cases):
     cases = loop_cases
     B, N = len(cases), 6
     table = chi2()
-    ctx = new_ctx(cases)
+    ctx = table_ctx(cases, F, gnss=True)
     ctx.snapshot()
     runs = []
     for rep in range(2):
@@ -273,13 +237,6 @@ def test_refusals_leave_table_covariance_and_staged_rows_unchanged(loop_cases):
     table = chi2()
     slots = [c["gnss_slots"] for c in cases]
     tabs = [c["table"].as_dict() for c in cases]
-
-    def refused(ctx, fn, code):
-        s0 = state(ctx, B)
-        with pytest.raises(capi.IngvioError) as e:
-            fn()
-        assert e.value.code == code, (e.value.code, code)
-        same_state(s0, state(ctx, B))
 
     # -- ingvio_nominal_set_gnss
     ctx = loop_ctx(cases, F)

@@ -10,45 +10,17 @@ import copy
 import numpy as np
 import pytest
 
+from conftest import rel_err as rel
 from ingvio_amd import closed_loop as cl
 from ingvio_amd import closed_loop_lm as clm
-from ingvio_amd.closed_loop import LM, NONE, SE23, SE3, VEC3, HostTable
+from ingvio_amd.closed_loop import LM, SE23, SE3, VEC3, HostTable
+from nominal_helpers import assert_table, device_state, same_state
+from nominal_helpers import refused as refused_on
+from nominal_helpers import table_ctx as fresh
 
 pytestmark = pytest.mark.gpu
 
 L_LOOP = 6
-KEYS = ("kind", "idx", "anchor", "val", "clone_var")
-
-
-def rel(a, b):
-    a, b = np.asarray(a, dtype=float), np.asarray(b, dtype=float)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-def assert_table(dev, host, tol, what):
-    h = host.as_dict()
-    n = len(h["kind"])
-    assert list(dev["kind"][:n]) == list(h["kind"]) and all(k == NONE for k in dev["kind"][n:]), what
-    worst = 0.0
-    for i in range(n):
-        if h["kind"][i] == NONE:
-            continue
-        assert dev["idx"][i] == h["idx"][i] and dev["anchor"][i] == h["anchor"][i], (what, i)
-        worst = max(worst, rel(dev["val"][i], h["val"][i]))
-        assert rel(dev["val"][i], h["val"][i]) <= tol, (what, i, rel(dev["val"][i], h["val"][i]))
-    assert list(dev["clone_var"]) == list(h["clone_var"]), what
-    return worst
-
-
-def device_state(ctx, B):
-    return ctx.nominal_get(), [ctx.cov_get(b) for b in range(B)]
-
-
-def same_state(s0, s1, B, keys=KEYS):
-    for b in range(B):
-        for key in keys:
-            assert np.array_equal(s0[0][b][key], s1[0][b][key]), (b, key)
-        assert np.array_equal(s0[1][b], s1[1][b]), b
 
 
 def same_results(o0, o1, cases):
@@ -137,19 +109,6 @@ def standalone_ctx(flt, with_table=True):
     return ctx
 
 
-def host_fed_frames(nom, staged):
-    out = []
-    for nm, s in zip(nom, staged):
-        sl = [] if s is None else list(s["lm_var"])
-        vp, vx = nm["v_pose"], nm["v_ext"]
-        out.append(dict(R_i2w=nm["val"][vp, 0:9].reshape(3, 3), p_i2w=nm["val"][vp, 9:12], R_cl2i=nm["val"][vx, 0:9].reshape(3, 3),
-                        p_c2i=nm["val"][vx, 9:12], idx_epose=int(nm["idx"][vp]), idx_ext=int(nm["idx"][vx]),
-                        lm_idx=[int(nm["idx"][v]) for v in sl], anchor_idx=[int(nm["idx"][nm["anchor"][v]]) for v in sl],
-                        pf=nm["val"][sl, 9:12].reshape(-1, 3), uv=np.zeros((0, 4)) if s is None else s["uv"],
-                        tracked=np.zeros(0, dtype=np.uint8) if s is None else s["tracked"]))
-    return out
-
-
 # (True, 60, 10): states of 267 ... 285 rows, beyond the fused landmark front (256 rows) - the k_lm_build route
 @pytest.mark.parametrize("stereo,L,C", [(True, 9, 5), (False, 9, 5), (True, 60, 10)])
 def test_standalone_equals_host_fed_stage_bit_for_bit(stereo, L, C):
@@ -161,7 +120,7 @@ def test_standalone_equals_host_fed_stage_bit_for_bit(stereo, L, C):
     cd.landmark_stage_nominal(0, staged, stereo, 0.02, thr, flt[0]["Rlr"], flt[0]["tlr"])
     cd.landmark_run()
     rd = cd.landmark_fetch()
-    ch.landmark_stage(0, host_fed_frames(nom, staged), stereo, 0.02, thr, flt[0]["Rlr"], flt[0]["tlr"])
+    ch.landmark_stage(0, clm.staged_frames(nom, staged), stereo, 0.02, thr, flt[0]["Rlr"], flt[0]["tlr"])
     ch.landmark_run()
     rh = ch.landmark_fetch()
     for name, x, y in zip(("dx", "rows", "accept", "gamma", "status"), rd, rh):
@@ -216,7 +175,7 @@ def test_standalone_against_the_oracle(stereo, L, C):
     cd.landmark_run()
     dx, rows, acc, gam, st = cd.landmark_fetch()
     assert not st.any()
-    frames = host_fed_frames([f["table"].as_dict() for f in flt], staged)
+    frames = clm.staged_frames([f["table"].as_dict() for f in flt], staged)
     seen = set()
     for b, (f, fr) in enumerate(zip(flt, frames)):
         n, nl = f["P"].shape[0], len(fr["lm_idx"])
@@ -238,13 +197,6 @@ def test_standalone_against_the_oracle(stereo, L, C):
 @pytest.fixture(scope="module")
 def lm_cases():
     return clm.make_lm_loop(24, 13, L=L_LOOP)
-
-
-def fresh(cases, F=24):
-    ctx = cl.loop_ctx(cases, F)
-    ctx.nominal_create(48)
-    ctx.nominal_set(0, [c["table"].as_dict() for c in cases])
-    return ctx
 
 
 def device_frame(ctx, cases, f, opts):
@@ -336,7 +288,7 @@ def test_pipelined_loop_equals_serial_loop(lm_cases):
     for f, ((fa, la), (fb, lb)) in enumerate(zip(o0, o1)):
         for x, y in zip(fa + la, fb + lb):
             assert np.array_equal(x, y), f
-    same_state(s0, s1, B)
+    same_state(s0, s1)
     assert sum(int(la[1].sum()) for _, la in o0) > 0
 
 
@@ -353,7 +305,7 @@ def test_snapshot_restore_replays_bit_for_bit(lm_cases):
         out = clm.device_loop_lm(ctx, cases, list(range(N)), opts, False)
         runs.append((out, device_state(ctx, B)))
     same_results(runs[0][0], runs[1][0], cases)
-    same_state(runs[0][1], runs[1][1], B, keys=("kind", "idx", "val", "clone_var"))
+    same_state(runs[0][1], runs[1][1], keys=("kind", "idx", "val", "clone_var"))
     ctx.close()
 
 
@@ -376,7 +328,7 @@ def test_frames_without_a_landmark_stage_run_as_before(lm_cases):
         for i, c in enumerate(cases):
             nf = len(c["frames"][f]["delta"]["feat_track"])
             assert np.array_equal(a[1][i, :nf], b[1][i, :nf]), (f, i)
-    same_state(want_state, device_state(ctx, B), B, keys=("kind", "idx", "val", "clone_var"))
+    same_state(want_state, device_state(ctx, B), keys=("kind", "idx", "val", "clone_var"))
     ctx.close()
     # without a restore in between: frame 0 with the stage, frame 1 without, against the host loops of the same order
     ch, cd = cl.loop_ctx(cases, F), fresh(cases)
@@ -409,13 +361,7 @@ def test_refusals_leave_the_state_unchanged(lm_cases):
         return device_state(ctx, B), [ctx.n(b) for b in range(B)]
 
     def refused(fn, code):
-        s0 = state()
-        with pytest.raises(capi.IngvioError) as e:
-            fn()
-        assert e.value.code == code, (e.value.code, code, str(e.value))
-        s1 = state()
-        same_state(s0[0], s1[0], B)
-        assert s0[1] == s1[1]
+        refused_on(ctx, fn, code, sizes=True)
 
     def stage(frames, in_frame, b0=0):
         return ctx.landmark_stage_nominal_prepare(b0, frames, opts["stereo"], opts["noise"], opts["chi2_thr"], opts["R_cl2cr"], opts["t_cl2cr"],
@@ -462,7 +408,7 @@ def test_refusals_leave_the_state_unchanged(lm_cases):
     ctx.restore()
     ctx.tracks_create(F)
     s1 = state()
-    same_state(s0[0], s1[0], B)
+    same_state(s0[0], s1[0])
     refused(lambda: ctx.landmark_run(0, B), capi.E_ARG)
 
     # with a frame staged from the table and not yet run
@@ -490,7 +436,7 @@ def test_refusals_leave_the_state_unchanged(lm_cases):
     ctx = fresh(cases)
     want = [device_frame(ctx, cases, f, opts) for f in range(3)]
     same_results(want, got, cases)
-    same_state(device_state(ctx, B), got_state, B)
+    same_state(device_state(ctx, B), got_state)
     ctx.close()
 
     # a table without extrinsics

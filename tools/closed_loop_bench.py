@@ -78,9 +78,76 @@ class TimedLib:
         return call
 
 
+def free_run(out, ctx, cases, form, NF, W):
+    """the pipelined device loop free-running, every stage prepared beforehand -> device_loop_ms_per_frame"""
+    from ingvio_amd.closed_loop import DeviceLoop
+    loop = DeviceLoop(ctx, cases, range(NF), form, collect=False).prepare()
+    loop.start()
+    for f in range(NF):
+        if f == W:
+            ctx.sync()
+            t0 = time.perf_counter()
+        loop.frame(f)
+    ctx.sync()
+    out["device_loop_ms_per_frame"] = round(1e3 * (time.perf_counter() - t0) / (NF - W), 4)
+
+
+def synced_run(out, name, ctx, cases, form, NF, W):
+    """the same loop with a context synchronisation at the end of every frame -> <name>_abi_ms_per_frame, the time inside the
+    library's calls, and <name>_wall_ms_per_frame"""
+    from ingvio_amd.closed_loop import DeviceLoop
+    loop = DeviceLoop(ctx, cases, range(NF), form, collect=False).prepare()
+    loop.start()
+    ctx.L = TimedLib(ctx.L)
+    wall = 0.0
+    for f in range(NF):
+        ctx.sync()
+        if f == W:
+            ctx.L.t = 0.0
+        t1 = time.perf_counter()
+        loop.frame(f)
+        ctx.sync()
+        if f >= W:
+            wall += time.perf_counter() - t1
+    out[name + "_abi_ms_per_frame"] = round(1e3 * ctx.L.t / (NF - W), 4)
+    out[name + "_wall_ms_per_frame"] = round(1e3 * wall / (NF - W), 4)
+    ctx.L = ctx.L._lib
+
+
+def synced_forms(out, fresh, cases, device_form, roundtrip_form, NF, W, dev_nom):
+    """the device and the round-trip form, measured the same way, and how far apart they leave the pose"""
+    ctx = fresh()
+    synced_run(out, "device", ctx, cases, device_form, NF, W)
+    ctx.close()
+    ctx = fresh()
+    synced_run(out, "roundtrip", ctx, cases, roundtrip_form, NF, W)
+    rt_nom = ctx.nominal_get()
+    ctx.close()
+    out["max_abs_pose_device_vs_roundtrip"] = max(float(np.max(np.abs(d["val"][0] - r["val"][0]))) for d, r in zip(dev_nom, rt_nom))
+
+
+def finish(out, name=None):
+    if name:
+        res_dir = os.environ.get("RESULTS", os.path.join(ROOT, "results"))
+        os.makedirs(res_dir, exist_ok=True)
+        with open(os.path.join(res_dir, name), "w") as fh:
+            json.dump(out, fh, indent=1)
+    print(json.dumps(out))
+
+
+def fresh_ctx(a, cases, v_max=64, gnss=False, table=True):
+    from ingvio_amd import closed_loop as cl
+    ctx = cl.loop_ctx(cases, a.features, c_max=a.window + 1)
+    if table:
+        ctx.nominal_create(v_max)
+        ctx.nominal_set(0, [c["table"].as_dict() for c in cases])
+    if gnss:
+        ctx.nominal_set_gnss(0, [c["gnss_slots"] for c in cases])
+    return ctx
+
+
 def main_gnss(a):
     from ingvio_amd import synth
-    from ingvio_amd import closed_loop as cl
     from ingvio_amd import closed_loop_gnss as cg
     B, F, NF, W = a.batch, a.features, a.frames, a.warmup
     z = np.load(os.path.join(ROOT, "tests", "golden", "gnss_front.npz"))
@@ -88,207 +155,38 @@ def main_gnss(a):
     cases = cg.make_gnss_loop(z, B, NF, F=F, every=0, ks=(a.k,), windows=(a.window,))
     table = synth.chi2_table()
     out = dict(batch=B, features=F, window=a.window, k=a.k, frames_timed=NF - W, gnss=bool(a.gnss), setup_s=round(time.perf_counter() - t0, 1))
-
-    def fresh():
-        ctx = cl.loop_ctx(cases, F, c_max=a.window + 1)
-        ctx.nominal_create(64)
-        ctx.nominal_set(0, [c["table"].as_dict() for c in cases])
-        ctx.nominal_set_gnss(0, [c["gnss_slots"] for c in cases])
-        return ctx
-
-    # device form
+    fresh = lambda: fresh_ctx(a, cases, gnss=True)
     ctx = fresh()
-    stages = [cg.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
-    gst = [cg.gnss_stage_call(ctx, cases, f, table) for f in range(NF)] if a.gnss else None
-    stages[0]()
-    ctx.frame_run()
-    for f in range(NF):
-        if f == W:
-            ctx.sync()
-            t0 = time.perf_counter()
-        ctx.frame_fetch_begin()
-        if a.gnss:
-            gst[f]()
-            ctx.gnss_run()
-        if f + 1 < NF:
-            stages[f + 1]()
-            ctx.frame_run()
-        ctx.frame_fetch_end()
-    ctx.sync()
-    out["device_loop_ms_per_frame"] = round(1e3 * (time.perf_counter() - t0) / (NF - W), 4)
+    free_run(out, ctx, cases, cg.GnssForm(table, epochs=a.gnss), NF, W)
     if a.gnss:
         g = ctx.gnss_fetch()
         out["last_epoch_rows_mean"] = float(g[1].mean()); out["last_epoch_ok"] = int((g[4] == 0).sum())
     dev_nom = ctx.nominal_get()
     ctx.close()
     if a.gnss and not a.device_only:
-        # device form once more, measured exactly as the round-trip form below: synchronised per frame, time inside the calls and wall
-        ctx = fresh()
-        stages = [cg.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
-        gst = [cg.gnss_stage_call(ctx, cases, f, table) for f in range(NF)]
-        stages[0]()
-        ctx.frame_run()
-        ctx.L = TimedLib(ctx.L)
-        wall = 0.0
-        for f in range(NF):
-            ctx.sync()
-            if f == W:
-                ctx.L.t = 0.0
-            t1 = time.perf_counter()
-            ctx.frame_fetch_begin()
-            gst[f]()
-            ctx.gnss_run()
-            if f + 1 < NF:
-                stages[f + 1]()
-                ctx.frame_run()
-            ctx.frame_fetch_end()
-            ctx.sync()
-            if f >= W:
-                wall += time.perf_counter() - t1
-        out["device_abi_ms_per_frame"] = round(1e3 * ctx.L.t / (NF - W), 4)
-        out["device_wall_ms_per_frame"] = round(1e3 * wall / (NF - W), 4)
-        ctx.L = ctx.L._lib
-        ctx.close()
-        # round-trip form
-        ctx = fresh()
-        stages = [cg.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
-        stages[0]()
-        ctx.frame_run()
-        ctx.L = TimedLib(ctx.L)
-        wall = 0.0
-        for f in range(NF):
-            ctx.sync()
-            if f == W:
-                ctx.L.t = 0.0
-            t1 = time.perf_counter()
-            ctx.frame_fetch_begin()
-            nom = ctx.nominal_get()                                      # synchronises both streams
-            ctx.gnss_front_stage_prepare(0, cg.table_epochs(nom, cases, f), table, gate_rows=True, strong_reject=True)()
-            ctx.gnss_run()
-            g = ctx.gnss_fetch()                                         # synchronises
-            ctx.nominal_box_plus(0, g[0])
-            if f + 1 < NF:
-                stages[f + 1]()
-                ctx.frame_run()
-            ctx.frame_fetch_end()
-            ctx.sync()
-            if f >= W:
-                wall += time.perf_counter() - t1
-        abi = ctx.L.t
-        ctx.L = ctx.L._lib
-        out["roundtrip_abi_ms_per_frame"] = round(1e3 * abi / (NF - W), 4)
-        out["roundtrip_wall_ms_per_frame"] = round(1e3 * wall / (NF - W), 4)
-        rt_nom = ctx.nominal_get()
-        ctx.close()
-        out["max_abs_pose_device_vs_roundtrip"] = max(float(np.max(np.abs(dev_nom[b]["val"][0] - rt_nom[b]["val"][0]))) for b in range(B))
-    res_dir = os.environ.get("RESULTS", os.path.join(ROOT, "results"))
-    os.makedirs(res_dir, exist_ok=True)
-    with open(os.path.join(res_dir, "closed_loop_bench_gnss.json"), "w") as fh:
-        json.dump(out, fh, indent=1)
-    print(json.dumps(out))
+        synced_forms(out, fresh, cases, cg.GnssForm(table), cg.GnssRoundTrip(table), NF, W, dev_nom)
+    finish(out, "closed_loop_bench_gnss.json")
 
 
 def main_landmarks(a):
-    from ingvio_amd import closed_loop as cl
     from ingvio_amd import closed_loop_lm as clm
     B, F, NF, W, L = a.batch, a.features, a.frames, a.warmup, a.landmarks
     t0 = time.perf_counter()
     cases = clm.make_lm_loop(B, NF, L=L, F=F, ks=(a.k,), windows=(a.window,))
     opts = clm.lm_opts()
     out = dict(batch=B, features=F, window=a.window, k=a.k, frames_timed=NF - W, landmarks=L, setup_s=round(time.perf_counter() - t0, 1))
-
-    def fresh():
-        ctx = cl.loop_ctx(cases, F, c_max=a.window + 1)
-        ctx.nominal_create(max(64, 32 + L))
-        ctx.nominal_set(0, [c["table"].as_dict() for c in cases])
-        return ctx
-
-    def device_form(ctx, timed_lib):
-        stages = [cl.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
-        lms = [clm.lm_stage_call(ctx, cases, f, opts) for f in range(NF)]
-        stages[0](); lms[0]()
-        ctx.frame_run()
-        if timed_lib:
-            ctx.L = TimedLib(ctx.L)
-        wall, t0 = 0.0, 0.0
-        for f in range(NF):
-            if timed_lib or f == W:
-                ctx.sync()
-            if f == W:
-                t0 = time.perf_counter()
-                if timed_lib:
-                    ctx.L.t = 0.0
-            t1 = time.perf_counter()
-            if f + 1 < NF:
-                stages[f + 1](); lms[f + 1]()
-                ctx.frame_fetch_begin()
-                ctx.frame_run()
-                ctx.frame_fetch_end()
-            else:
-                ctx.frame_fetch()
-            if timed_lib:
-                ctx.sync()
-                if f >= W:
-                    wall += time.perf_counter() - t1
-        ctx.sync()
-        free = time.perf_counter() - t0
-        abi = ctx.L.t if timed_lib else 0.0
-        if timed_lib:
-            ctx.L = ctx.L._lib
-        return free, abi, wall
-
+    fresh = lambda: fresh_ctx(a, cases, v_max=max(64, 32 + L))
     ctx = fresh()
-    free, _, _ = device_form(ctx, False)
-    out["device_loop_ms_per_frame"] = round(1e3 * free / (NF - W), 4)
+    free_run(out, ctx, cases, clm.LmForm(opts), NF, W)
     lm = ctx.landmark_fetch()
     out["last_frame_lm_rows_mean"] = float(lm[1].mean()); out["last_frame_lm_ok"] = int((lm[4] == 0).sum())
     dev_nom = ctx.nominal_get()
     ctx.close()
     if not a.device_only:
-        ctx = fresh()
-        _, abi, wall = device_form(ctx, True)
-        out["device_abi_ms_per_frame"] = round(1e3 * abi / (NF - W), 4)
-        out["device_wall_ms_per_frame"] = round(1e3 * wall / (NF - W), 4)
-        ctx.close()
-        # round-trip form
-        ctx = fresh()
-        stages = [cl.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
-        stages[0]()
-        ctx.frame_run()
-        ctx.L = TimedLib(ctx.L)
-        wall = 0.0
-        for f in range(NF):
-            ctx.sync()
-            if f == W:
-                ctx.L.t = 0.0
-            t1 = time.perf_counter()
-            ctx.frame_fetch_begin()
-            nom = ctx.nominal_get()                                      # synchronises both streams
-            ctx.landmark_stage(0, clm.table_frames(nom, cases, f), opts["stereo"], opts["noise"], opts["chi2_thr"], opts["R_cl2cr"], opts["t_cl2cr"])
-            ctx.landmark_run()
-            lm = ctx.landmark_fetch()                                    # synchronises
-            ctx.nominal_box_plus(0, lm[0])
-            if f + 1 < NF:
-                stages[f + 1]()
-                ctx.frame_run()
-            ctx.frame_fetch_end()
-            ctx.sync()
-            if f >= W:
-                wall += time.perf_counter() - t1
-        abi = ctx.L.t
-        ctx.L = ctx.L._lib
-        out["roundtrip_abi_ms_per_frame"] = round(1e3 * abi / (NF - W), 4)
-        out["roundtrip_wall_ms_per_frame"] = round(1e3 * wall / (NF - W), 4)
-        rt_nom = ctx.nominal_get()
-        ctx.close()
         # (the two forms differ by design: the round trip updates the landmarks after the frame's marginalisation, with rows at the
         # values the frame left; the device form inside the frame, in the reference's order)
-        out["max_abs_pose_device_vs_roundtrip"] = max(float(np.max(np.abs(dev_nom[b]["val"][0] - rt_nom[b]["val"][0]))) for b in range(B))
-    res_dir = os.environ.get("RESULTS", os.path.join(ROOT, "results"))
-    os.makedirs(res_dir, exist_ok=True)
-    with open(os.path.join(res_dir, "closed_loop_bench_lm.json"), "w") as fh:
-        json.dump(out, fh, indent=1)
-    print(json.dumps(out))
+        synced_forms(out, fresh, cases, clm.LmForm(opts), clm.LmRoundTrip(opts), NF, W, dev_nom)
+    finish(out, "closed_loop_bench_lm.json")
 
 
 def main():
@@ -308,7 +206,6 @@ def main():
         return main_landmarks(a)
     if a.gnss or a.register_only:
         return main_gnss(a)
-    from oracle import oracle as orc
     from ingvio_amd import closed_loop as cl
     B, F, NF, W = a.batch, a.features, a.frames, a.warmup
     t0 = time.perf_counter()
@@ -316,24 +213,15 @@ def main():
     out = dict(batch=B, features=F, window=a.window, k=a.k, frames_timed=NF - W, setup_s=round(time.perf_counter() - t0, 1))
 
     # device loop, pipelined
-    ctx = cl.loop_ctx(cases, F, c_max=a.window + 1)
-    ctx.nominal_create(64)
-    ctx.nominal_set(0, [c["table"].as_dict() for c in cases])
-    calls = [cl.nominal_stage(ctx, cases, f, use_async=True) for f in range(NF)]
-    calls[0]()
-    ctx.frame_run()
+    ctx = fresh_ctx(a, cases)
+    loop = cl.DeviceLoop(ctx, cases, range(NF)).prepare()
+    loop.start()
     dev_res = []
     for f in range(NF):
         if f == W:
             ctx.sync()
             t0 = time.perf_counter()
-        if f + 1 < NF:
-            calls[f + 1]()
-            ctx.frame_fetch_begin()
-            ctx.frame_run()
-            dev_res.append(ctx.frame_fetch_end())
-        else:
-            dev_res.append(ctx.frame_fetch())
+        dev_res.append(loop.frame(f))
     out["device_loop_ms_per_frame"] = round(1e3 * (time.perf_counter() - t0) / (NF - W), 4)
     dev_nom = ctx.nominal_get()
     ctx.close()
@@ -341,43 +229,25 @@ def main():
     out["bytes_per_filter_host"] = round(sum(stage_bytes(cases, f, a.k, True) for f in timed) / (len(timed) * B), 1)
     out["bytes_per_filter_device"] = round(sum(stage_bytes(cases, f, a.k, False) for f in timed) / (len(timed) * B), 1)
     if a.device_only:
-        print(json.dumps(out))
-        return
+        return finish(out)
 
     # host loop, phase by phase
-    ctx = cl.loop_ctx(cases, F, c_max=a.window + 1)
+    ctx = fresh_ctx(a, cases, table=False)
     tabs = [copy.deepcopy(c["table"]) for c in cases]
-    opts_frame, sigma, eg, scb, srw = cl.stage_args(cases)
     ph = dict(host_imu=0.0, stage=0.0, run_fetch=0.0, host_box_plus=0.0)
     worst = 0.0
     for f in range(NF):
-        timed = f >= W
         t = time.perf_counter()
-        steps, tfs = [], []
-        for c, tb in zip(cases, tabs):
-            fr = c["frames"][f]
-            e, bg, ba = tb.slots[tb.v_pose], tb.slots[tb.v_bg], tb.slots[tb.v_ba]
-            raw = dict(imu=fr["imu"], R=e["R"], p=e["p"], v=e["v"], bg=bg["p"], ba=ba["p"], gravity=tb.gravity)
-            R, p, v = e["R"], e["p"], e["v"]
-            for q in range(fr["imu"].shape[0]):
-                R, p, v, _, _ = orc.imu_transition(R, p, v, bg["p"], ba["p"], fr["imu"][q, :3], fr["imu"][q, 3:6], tb.gravity, fr["imu"][q, 6])
-            e["R"], e["p"], e["v"] = R, p, v
-            tb.append_clone(fr["new_idx"])
-            steps.append(dict(raw=raw, gnss_idx=c["step"]["gnss_idx"], marg_idx=fr["marg"]))
-            clo = [tb.slots[s] for s in tb.clones]
-            tfs.append(dict(fr["delta"], clone_idx=[s["idx"] for s in clo], clone_R=np.stack([s["R"] for s in clo]),
-                            clone_p=np.stack([s["p"] for s in clo])))
+        steps, tfs = cl.host_propagate(cases, tabs, f)
         t1 = time.perf_counter()
-        ctx.frame_stage_tracks_prepare(0, steps, tfs, opts_frame, sigma, eg, scb, srw)()
+        cl.host_stage(ctx, cases, steps, tfs)
         t2 = time.perf_counter()
         ctx.frame_run()
         dx, acc, rows = ctx.frame_fetch()
         t3 = time.perf_counter()
-        for b, (c, tb) in enumerate(zip(cases, tabs)):
-            tb.box_plus(dx[b])
-            tb.marginalize(c["frames"][f]["marg"])
+        cl.host_tail(cases, tabs, f, dx)
         t4 = time.perf_counter()
-        if timed:
+        if f >= W:
             ph["host_imu"] += t1 - t; ph["stage"] += t2 - t1; ph["run_fetch"] += t3 - t2; ph["host_box_plus"] += t4 - t3
         d = dev_res[f][0]
         worst = max(worst, float(np.max(np.abs(d - dx)) / max(np.max(np.abs(dx)), 1e-300)))
@@ -388,11 +258,7 @@ def main():
     out["max_rel_dx_device_vs_host"] = worst
     out["max_rel_pose_device_vs_host"] = max(float(np.max(np.abs(dev_nom[b]["val"][tabs[b].v_pose] - tabs[b].as_dict()["val"][tabs[b].v_pose])))
                                              for b in range(B))
-    res_dir = os.environ.get("RESULTS", os.path.join(ROOT, "results"))
-    os.makedirs(res_dir, exist_ok=True)
-    with open(os.path.join(res_dir, "closed_loop_bench.json"), "w") as fh:
-        json.dump(out, fh, indent=1)
-    print(json.dumps(out))
+    finish(out, "closed_loop_bench.json")
 
 
 if __name__ == "__main__":
