@@ -304,6 +304,45 @@ int ingvio_add_variable_delayed(ingvio_ctx* ctx, int b, const int* vidx, const i
                                 const double* H_old, int ldh, const double* H_new, int ldn, int m, int s,
                                 const double* res, double noise, double chi2_mult, int do_chi2, double chi2_check,
                                 double* dx_out, int* added, int* new_idx, double* chi2_out);
+/* addVariableDelayed for filters [b0, b0 + nb) with several candidate variables per filter, in one call and ONE stream
+ * synchronisation (kernels_delayed.hip).  Per filter the candidates are tried in order, each against the covariance the
+ * previous one left (the appended variable included), exactly as the reference's loops over new landmarks do
+ * (LandmarkUpdate.cpp:399-421, :892-956): Givens rotations, chi2 of the lower m - s rows on the prior marginal, refusal
+ * when chi2 > chi2_mult * chi2_check && do_chi2, otherwise addVariableDelayedInvertible and the ekfUpdate with the lower
+ * rows.  The verdicts are taken on the device; the host sees nothing between the candidates.
+ *   added / new_idx / chi2 [nb][cand_cap]: candidate j of filter b0 + i at [i * cand_cap + j].  A candidate with m <= s is
+ *     skipped (added = 0, chi2 = 0); a refused or skipped candidate leaves that filter's P and n untouched bit for bit.
+ *     new_idx = the filter's live N at the append (-1 when not added).  var_old_order must lie inside the state the
+ *     filter has when the call starts (new variables go to the end, so the indices hold over the rounds).
+ *   dx [nb][cand_cap][ldp] (may be NULL): K res of candidate j in the index space after its own append, zero when it was
+ *     not added; boxPlus is the caller's (ingvio_nominal_box_plus or the host).
+ *   status [nb] (may be NULL): INGVIO_OK / INGVIO_NEG_DIAG / INGVIO_E_NOT_PD per filter, as ingvio_ekf_update_batch;
+ *     after a trailing update whose S was not positive definite the filter's remaining candidates are not tried.
+ *     The worst of these codes is also the call's return value; the outputs and every filter's n are valid with it.
+ * One noise (sigma, R = noise^2 I) for the call.  The call never touches the device nominal table: entering the new
+ * variable there stays ingvio_nominal_get / _set.
+ * Refused before anything changes: INGVIO_E_ARG (range, NULL where data is needed, s outside 1..6, ldh / ldn < m,
+ * n_cand > cand_cap, a split frame step pending, or a frame / GNSS epoch / landmark stage from the nominal table that
+ * has not run - as ingvio_nominal_box_plus); INGVIO_E_NOT_IN_STATE (an (idx, size) beyond the filter's n);
+ * INGVIO_E_CAPACITY (n + sum of the filter's s > n_max, m > ingvio_mld, more columns than the context holds, the
+ * trailing update's S beyond LDS, the single-filter gate's bound 8 (nc (m-s) + (m-s+1)^2) <= 150 KB, or the front's own:
+ * it keeps the rows AND T = Pcc H^T in LDS, 8 ((2 nc + 1)(m | 1) + 3 s m + (m-s+1)^2) + 4 nc + 1.3 KB <= 160 KB - tighter
+ * than the single-filter call for wide windows, e.g. m = 64 rows on 16 clones fit, m = 84 on 21 clones do not). */
+typedef struct {
+    const int* vidx; const int* vsize; int k;   /* var_old_order as (idx, size)[k]                       */
+    const double* H_old; int ldh;               /* m x sum(vsize), column-major                          */
+    const double* H_new; int ldn;               /* m x s                                                 */
+    const double* res;                          /* [m]                                                   */
+    int m, s;                                   /* s <= 6                                                */
+    double chi2_check;                          /* quantile(chi_squared(m), 0.95), supplied by the caller */
+} ingvio_delayed_cand;
+typedef struct {
+    int n_cand;                                 /* 0: nothing for this filter                            */
+    const ingvio_delayed_cand* cand;            /* [n_cand], tried in this order                         */
+} ingvio_delayed_block;
+int ingvio_add_variable_delayed_batch(ingvio_ctx* ctx, int b0, int nb, const ingvio_delayed_block* blocks,
+                                      double noise, double chi2_mult, int do_chi2, int cand_cap,
+                                      int* added, int* new_idx, double* chi2, double* dx, int* status);
 /* replaceVarLinear (StateManager.cpp:639-693): the target variable (tidx, tsize <= 6) becomes H * [dependence
  * variables]: its rows/columns <- P H^T, its diagonal block <- H Pcc H^T.  H tsize x sum(vsize) (ldh). */
 int ingvio_replace_var_linear(ingvio_ctx* ctx, int b, int tidx, int tsize, const int* vidx, const int* vsize, int k,

@@ -31,7 +31,7 @@ EXPORTS = [
     "ingvio_landmark_fetch", "ingvio_frame_run_phase", "ingvio_info_set", "ingvio_debug_read", "ingvio_triangulate",
     "ingvio_gnss_front_stage", "ingvio_gnss_front_fetch", "ingvio_gnss_update_batch", "ingvio_gnss_stage", "ingvio_gnss_run", "ingvio_gnss_fetch", "ingvio_mld", "ingvio_debug_msckf_info", "ingvio_debug_info_solution",
     "ingvio_info_reduce", "ingvio_info_commit", "ingvio_gnss_sat_eval",
-    "ingvio_chi2_gamma_multi", "ingvio_ekf_update_batch", "ingvio_add_variable_delayed_invertible", "ingvio_add_variable_delayed", "ingvio_replace_var_linear",
+    "ingvio_chi2_gamma_multi", "ingvio_ekf_update_batch", "ingvio_add_variable_delayed_invertible", "ingvio_add_variable_delayed", "ingvio_add_variable_delayed_batch", "ingvio_replace_var_linear",
     "ingvio_nominal_create", "ingvio_nominal_set", "ingvio_nominal_get", "ingvio_nominal_box_plus", "ingvio_frame_stage_tracks_nominal",
     "ingvio_nominal_set_gnss", "ingvio_nominal_get_gnss", "ingvio_gnss_front_stage_nominal", "ingvio_landmark_stage_nominal",
 ]
@@ -49,6 +49,46 @@ class GateBlock(C.Structure):
 class UpdateBlock(C.Structure):
     _fields_ = [("vidx", C.POINTER(C.c_int)), ("vsize", C.POINTER(C.c_int)), ("k", C.c_int), ("H", C.POINTER(C.c_double)),
                 ("ldh", C.c_int), ("m", C.c_int), ("res", C.POINTER(C.c_double)), ("R", C.POINTER(C.c_double))]
+
+
+class DelayedCand(C.Structure):
+    _fields_ = [("vidx", C.POINTER(C.c_int)), ("vsize", C.POINTER(C.c_int)), ("k", C.c_int), ("H_old", C.POINTER(C.c_double)),
+                ("ldh", C.c_int), ("H_new", C.POINTER(C.c_double)), ("ldn", C.c_int), ("res", C.POINTER(C.c_double)),
+                ("m", C.c_int), ("s", C.c_int), ("chi2_check", C.c_double)]
+
+
+class DelayedBlock(C.Structure):
+    _fields_ = [("n_cand", C.c_int), ("cand", C.POINTER(DelayedCand))]
+
+
+def make_delayed_blocks(blocks):
+    """blocks: per filter a list of candidates (vidx, vsize, H_old [m, nc], H_new [m, s], res [m][, chi2_check]); chi2_check defaults to
+    quantile(chi2(m), 0.95) (scipy).  Returns (ingvio_delayed_block array, cand_cap, objects that own the memory the array points to)."""
+    nb = len(blocks)
+    arr = (DelayedBlock * max(nb, 1))(); keep = []
+    cand_cap = max([len(cs) for cs in blocks] + [1])
+    for g, cands in enumerate(blocks):
+        arr[g].n_cand = len(cands)
+        if not cands:
+            continue
+        ca = (DelayedCand * len(cands))()
+        for j, cd in enumerate(cands):
+            vidx, vsize, H_old, H_new, res = cd[:5]
+            H_old = np.asfortranarray(np.atleast_2d(H_old), dtype=np.float64)
+            H_new = np.asfortranarray(np.atleast_2d(H_new), dtype=np.float64)
+            m, s = H_new.shape
+            if len(cd) > 5 and cd[5] is not None:
+                chk = float(cd[5])
+            else:
+                from scipy.stats import chi2 as _chi2
+                chk = float(_chi2.ppf(0.95, m)) if m > 0 else 0.0
+            vi, vs, r = i32(vidx), i32(vsize), f64(res)
+            keep.append((H_old, H_new, vi, vs, r))
+            ca[j].vidx = _i(vi); ca[j].vsize = _i(vs); ca[j].k = len(vi); ca[j].H_old = _d(H_old); ca[j].ldh = max(m, 1)
+            ca[j].H_new = _d(H_new); ca[j].ldn = max(m, 1); ca[j].res = _d(r); ca[j].m = m; ca[j].s = s; ca[j].chi2_check = chk
+        keep.append(ca)
+        arr[g].cand = ca
+    return arr, cand_cap, keep
 
 
 class GnssOpts(C.Structure):
@@ -681,6 +721,30 @@ class Context:
                                                      1 if do_chi2 else 0, C.c_double(chi2_check), _d(dx), C.byref(added),
                                                      C.byref(idx), C.byref(chi2)))
         return bool(added.value), (dx if added.value else None), chi2.value, idx.value
+
+    def add_variable_delayed_batch(self, b0, blocks, noise, chi2_mult=1.0, do_chi2=True, want_dx=True):
+        """addVariableDelayed for filters b0, b0+1, ..., several candidates each (make_delayed_blocks), one synchronisation.
+        Returns per filter (added [bool], new_idx [int], chi2 [float], dx [array of the state after the append, or None]), one
+        entry per candidate; self.delayed_status holds the per-filter status codes of the call (OK, NEG_DIAG or E_NOT_PD: after a trailing
+        update whose S is not positive definite the variable stays appended, its dx is zero and the filter's later candidates are not tried)."""
+        nb = len(blocks)
+        arr, cap, keep = make_delayed_blocks(blocks)
+        added = np.zeros((nb, cap), dtype=np.int32); idx = np.full((nb, cap), -1, dtype=np.int32); chi2 = np.zeros((nb, cap))
+        dx = np.zeros((nb, cap, self.ldp)) if want_dx else None
+        st = np.zeros(nb, dtype=np.int32)
+        rc = self.L.ingvio_add_variable_delayed_batch(self.h, b0, nb, arr, C.c_double(noise), C.c_double(chi2_mult), 1 if do_chi2 else 0,
+                                                      cap, _i(added), _i(idx), _d(chi2), _d(dx) if want_dx else None, _i(st))
+        # NEG_DIAG / E_NOT_PD of a trailing update come back AFTER the state has grown: they are reported per filter in
+        # delayed_status beside the results, never raised; everything else negative is a refusal that changed nothing
+        if rc != E_NOT_PD:
+            self._chk(rc)
+        self.delayed_status = st
+        out = []
+        for g, cands in enumerate(blocks):
+            k = len(cands)
+            dxs = [(dx[g, j, :idx[g, j] + arr[g].cand[j].s].copy() if want_dx and added[g, j] else None) for j in range(k)]
+            out.append(([bool(a) for a in added[g, :k]], [int(v) for v in idx[g, :k]], [float(v) for v in chi2[g, :k]], dxs))
+        return out
 
     def replace_var_linear(self, b, tidx, tsize, vidx, vsize, H):
         H = np.asfortranarray(np.atleast_2d(H), dtype=np.float64)

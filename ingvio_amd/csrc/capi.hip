@@ -9,6 +9,7 @@
 #include "launch_tri.h"
 #include "launch_tracks.h"
 #include "launch_lm.h"
+#include "launch_delayed.h"
 #include "launch_qr.h"
 #include "launch_chol.h"
 #include "launch_gnss.h"
@@ -157,6 +158,9 @@ struct ingvio_ctx {
         std::vector<int> hi;            // per filter: one past the highest state index the staged rows name (re-checked against the live n at run time)
     } lm;
     char* d_multi = nullptr;            // ingvio_chi2_gamma_multi: packed blocks (grown on demand)
+    // ingvio_add_variable_delayed_batch (kernels_delayed.hip), grown on demand: the packed candidates of a call, the rows / row
+    // counts its fronts hand to the update kernels, and the results of every round with their pinned mirror
+    struct DelayedWs { char *in = nullptr, *wk = nullptr, *out = nullptr, *h_out = nullptr; size_t in_cap = 0, wk_cap = 0, out_cap = 0; } dl;
     size_t multi_cap = 0;
     // staged frame state
     int st_stereo, st_enable_gnss, st_fmax_used;
@@ -1089,6 +1093,8 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
                      c->lm.lm_idx, c->lm.anchor_idx, c->lm.tracked, c->lm.accept, c->lm.slot, c->lm.dx, c->d_xchg, c->dw.U, c->dw.rowmap, c->d_zero_idx,
                      c->d_Asum, c->d_used_sum, c->d_Tflat, c->d_imu, c->d_tri_mask, c->d_prm };
     for (void* p : ptrs) if (p) hipFree(p);
+    for (void* p : { (void*)c->dl.in, (void*)c->dl.wk, (void*)c->dl.out }) if (p) hipFree(p);
+    if (c->dl.h_out) hipHostFree(c->dl.h_out);
     for (auto& sl : c->pin) { if (sl.p) hipHostFree(sl.p); if (sl.ev) hipEventDestroy(sl.ev); }
     if (c->h_result) hipHostFree(c->h_result);
     if (c->qr.exec) hipGraphExecDestroy(c->qr.exec);
@@ -2252,6 +2258,164 @@ int ingvio_add_variable_delayed(ingvio_ctx* c, int b, const int* vidx, const int
     rc = last_launch(c);
     if (rc) return rc;
     return (status & 4) ? INGVIO_E_NOT_PD : ((status & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
+}
+
+// ---- addVariableDelayed for filters [b0, b0 + nb), several candidates per filter (kernels_delayed.hip) --------------------------
+// Round j = candidate j of every filter that has one: k_delayed_front (rotations, gate, verdict, append) + the batched
+// k_ekf_core / k_downdate on the row counts the front wrote.  Nothing comes back to the host between the rounds.
+static int dl_grow(ingvio_ctx* c, char** p, size_t* cap, size_t need)
+{
+    if (*cap >= need) return 0;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (*p) hipFree(*p);
+    *p = nullptr; *cap = 0;
+    const size_t bytes = (need + (1u << 20)) & ~((size_t)(1u << 20) - 1);
+    if (dalloc(c, p, bytes)) return INGVIO_E_HIP;
+    *cap = bytes;
+    return 0;
+}
+
+int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvio_delayed_block* blocks, double noise, double chi2_mult,
+                                      int do_chi2, int cand_cap, int* added, int* new_idx, double* chi2, double* dx, int* status)
+{
+    ENTER(c);
+    if (phase_busy(c)) return INGVIO_E_ARG;
+    if (check_range(c, b0, nb) || !blocks || cand_cap < 1 || !added || !new_idx) return INGVIO_E_ARG;
+    if (c->nom.pending) { c->err = "ingvio_add_variable_delayed_batch: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, "ingvio_add_variable_delayed_batch")) return INGVIO_E_ARG;
+    // ---- everything that can be wrong, before anything changes ----
+    int R = 0, mu_cap = 0, nc_cap = 0, n_cap = 0;
+    size_t lds = 0, dtot = 0;
+    for (int i = 0; i < nb; ++i) if (blocks[i].n_cand > R) R = blocks[i].n_cand;      // rounds (a wrong n_cand is refused below)
+    if (R > cand_cap) return INGVIO_E_ARG;
+    const size_t RN = (size_t)R * nb;
+    std::vector<int> ncs(RN, 0);                  // [round][filter]: columns of the candidate, 0 = none / skipped
+    std::vector<size_t> offs(RN, 0);
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_delayed_block& blk = blocks[i];
+        const int b = b0 + i;
+        if (blk.n_cand < 0 || (blk.n_cand > 0 && !blk.cand)) return INGVIO_E_ARG;
+        int grow = 0;
+        for (int j = 0; j < blk.n_cand; ++j) {
+            const ingvio_delayed_cand& q = blk.cand[j];
+            if (q.s < 1 || q.s > 6 || q.m < 0) return INGVIO_E_ARG;
+            if (q.m <= q.s) continue;                                                   // StateManager.cpp:574-578: skipped
+            if (!q.vidx || !q.vsize || !q.H_old || !q.H_new || !q.res || q.k < 1 || q.ldh < q.m || q.ldn < q.m) return INGVIO_E_ARG;
+            int nc = 0;
+            for (int t = 0; t < q.k; ++t) {
+                if (q.vidx[t] < 0 || q.vsize[t] < 0 || q.vidx[t] + q.vsize[t] > c->h_n[b]) return INGVIO_E_NOT_IN_STATE;      // checkSubOrder
+                nc += q.vsize[t];
+            }
+            if (nc < 1) return INGVIO_E_ARG;
+            const int mu = q.m - q.s;
+            if (q.m > c->mld || nc > c->nc_cap || !ekf_core_fits(mu, nc)) return INGVIO_E_CAPACITY;
+            if ((size_t)8 * ((size_t)nc * mu + (size_t)(mu + 1) * (mu + 1)) > 150 * 1024) return INGVIO_E_CAPACITY;      // the single-filter gate's bound
+            const size_t l = delayed_front_lds(q.m, q.s, nc);
+            if (l > 160 * 1024) return INGVIO_E_CAPACITY;                               // the front's own: rows and T stay in LDS
+            if (l > lds) lds = l;
+            if (mu > mu_cap) mu_cap = mu;
+            if (nc > nc_cap) nc_cap = nc;
+            grow += q.s;
+            ncs[(size_t)j * nb + i] = nc;
+            offs[(size_t)j * nb + i] = dtot;
+            dtot += (size_t)q.m * (nc + q.s + 1);
+        }
+        if (c->h_n[b] + grow > c->d.n_max) return INGVIO_E_CAPACITY;                    // every candidate of the filter may be added
+        if (c->h_n[b] + grow > n_cap) n_cap = c->h_n[b] + grow;
+    }
+    const size_t CC = (size_t)nb * cand_cap;
+    for (size_t e = 0; e < CC; ++e) { added[e] = 0; new_idx[e] = -1; if (chi2) chi2[e] = 0.0; }
+    if (dx) memset(dx, 0, 8 * CC * c->ldp);
+    if (status) for (int i = 0; i < nb; ++i) status[i] = INGVIO_OK;
+    if (R == 0 || nc_cap == 0) return INGVIO_OK;                                        // nothing to try anywhere
+    // ---- one slab up: [m | s | nc | colmap | offsets | thresholds | var | rows] ----
+    const size_t cs = nc_cap;
+    const size_t o_m = 0, o_s = o_m + pad64(4 * RN), o_nc = o_s + pad64(4 * RN), o_cm = o_nc + pad64(4 * RN), o_off = o_cm + pad64(4 * RN * cs),
+                 o_thr = o_off + pad64(8 * RN), o_var = o_thr + pad64(8 * RN), o_d = o_var + 64, in_bytes = o_d + pad64(8 * dtot);
+    const int mldu = (mu_cap + 15) & ~15;
+    const size_t hsu = (size_t)mldu * nc_cap;
+    const size_t w_res = pad64(8 * (size_t)nb * hsu), w_mu = w_res + pad64(8 * (size_t)nb * mldu), wk_bytes = w_mu + pad64(4 * (size_t)nb);
+    const size_t B = c->d.batch;
+    const size_t r_idx = pad64(4 * RN), r_st = r_idx + pad64(4 * RN), r_chi = r_st + pad64(4 * B), r_dx = r_chi + pad64(8 * RN),
+                 out_bytes = r_dx + (dx ? 8 * RN * c->ldp : 0);
+    auto& w = c->dl;
+    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
+    if (int rc = dl_grow(c, &w.wk, &w.wk_cap, wk_bytes)) return rc;
+    if (w.out_cap < out_bytes && w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; }      // the pinned mirror grows with the device slab
+    if (int rc = dl_grow(c, &w.out, &w.out_cap, out_bytes)) return rc;
+    if (!w.h_out) HIPCHK(c, hipHostMalloc((void**)&w.h_out, w.out_cap, hipHostMallocDefault));
+    Uploader upl{ c };
+    if (int rc = upl.begin(in_bytes + 64)) return rc;
+    char* h = upl.take<char>(in_bytes);
+    memset(h, 0, o_d);
+    int *hm = (int*)(h + o_m), *hs = (int*)(h + o_s), *hnc = (int*)(h + o_nc), *hcm = (int*)(h + o_cm);
+    size_t* hoff = (size_t*)(h + o_off);
+    double *hthr = (double*)(h + o_thr), *hd = (double*)(h + o_d);
+    *(double*)(h + o_var) = noise * noise;
+    parallel_for(nb, [=, &ncs, &offs](int i) {
+        const ingvio_delayed_block& blk = blocks[i];
+        for (int j = 0; j < blk.n_cand; ++j) {
+            const size_t e = (size_t)j * nb + i;
+            const int nc = ncs[e];
+            if (!nc) continue;
+            const ingvio_delayed_cand& q = blk.cand[j];
+            hm[e] = q.m; hs[e] = q.s; hnc[e] = nc; hoff[e] = offs[e]; hthr[e] = chi2_mult * q.chi2_check;
+            int* cm = hcm + e * cs;
+            int wr = 0;
+            for (int t = 0; t < q.k; ++t) for (int u = 0; u < q.vsize[t]; ++u) cm[wr++] = q.vidx[t] + u;
+            double* d = hd + offs[e];
+            for (int cc = 0; cc < nc; ++cc) memcpy(d + (size_t)cc * q.m, q.H_old + (size_t)cc * q.ldh, 8 * (size_t)q.m);
+            d += (size_t)nc * q.m;
+            for (int cc = 0; cc < q.s; ++cc) memcpy(d + (size_t)cc * q.m, q.H_new + (size_t)cc * q.ldn, 8 * (size_t)q.m);
+            memcpy(d + (size_t)q.s * q.m, q.res, 8 * (size_t)q.m);
+        }
+    });
+    upl.copy(w.in, h, in_bytes);
+    if (int rc = upl.end()) return rc;
+    int* d_st = (int*)(w.out + r_st);
+    HIPCHK(c, hipMemsetAsync(d_st + b0, 0, sizeof(int) * (size_t)nb, c->st));
+    HIPCHK(c, hipMemsetAsync(c->d_dx + (size_t)b0 * c->ldp, 0, 8 * (size_t)nb * c->ldp, c->st));      // entries past a filter's n stay zero
+    const CovView cv = view(c);
+    for (int j = 0; j < R; ++j) {
+        const size_t r0 = (size_t)j * nb;
+        DelayedFront F;
+        memset(&F, 0, sizeof F);
+        F.cv = cv; F.b0 = b0; F.nb = nb; F.dbuf = (const double*)(w.in + o_d); F.doff = (const size_t*)(w.in + o_off) + r0;
+        F.m = (const int*)(w.in + o_m) + r0; F.s = (const int*)(w.in + o_s) + r0; F.nc = (const int*)(w.in + o_nc) + r0;
+        F.colmap = (const int*)(w.in + o_cm) + r0 * cs; F.cs = (int)cs; F.thr = (const double*)(w.in + o_thr) + r0;
+        F.do_chi2 = do_chi2 ? 1 : 0; F.var = noise * noise;
+        F.Hu = (double*)w.wk; F.resu = (double*)(w.wk + w_res); F.mldu = mldu; F.hsu = hsu; F.mu = (int*)(w.wk + w_mu);
+        F.Y = c->d_Y + (size_t)b0 * c->ystride; F.ystride = (size_t)c->ystride; F.status = d_st;
+        F.added = (int*)w.out + r0; F.new_idx = (int*)(w.out + r_idx) + r0; F.chi2 = (double*)(w.out + r_chi) + r0;
+        if (launch_delayed_front(F, lds, c->st)) return INGVIO_E_CAPACITY;
+        EkfLaunch E;                                                                    // :623-624 ekfUpdate with the lower rows on the extended state
+        memset(&E, 0, sizeof E);
+        E.cv = cv; E.b0 = b0; E.nb = nb; E.H = F.Hu; E.res = F.resu; E.colmap = F.colmap; E.m = F.mu; E.nc = F.nc;
+        E.noise = (const double*)(w.in + o_var); E.r_kind = 0; E.mld = mldu; E.hstride = (int)hsu; E.cstride = (int)cs; E.nstride = 0;
+        E.Y = c->d_Y + (size_t)b0 * c->ystride; E.ystride = c->ystride; E.dx = c->d_dx; E.status = d_st; E.m_cap = mu_cap; E.nc_cap = nc_cap;
+        { ProfScope p(c, PF_EKF_CORE); launch_ekf_core(E, c->st); }
+        { ProfScope p(c, PF_DOWNDATE); launch_downdate(E, n_cap, c->st); }
+        if (dx) HIPCHK(c, hipMemcpyAsync(w.out + r_dx + 8 * r0 * c->ldp, c->d_dx + (size_t)b0 * c->ldp, 8 * (size_t)nb * c->ldp, hipMemcpyDeviceToDevice, c->st));
+    }
+    HIPCHK(c, hipMemcpyAsync(w.h_out, w.out, out_bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (int rc = last_launch(c)) return rc;
+    const int *ra = (const int*)w.h_out, *ri = (const int*)(w.h_out + r_idx), *rs = (const int*)(w.h_out + r_st) + b0;
+    const double *rc2 = (const double*)(w.h_out + r_chi), *rdx = (const double*)(w.h_out + r_dx);
+    int soft = INGVIO_OK;
+    for (int i = 0; i < nb; ++i) {
+        for (int j = 0; j < blocks[i].n_cand; ++j) {
+            const size_t e = (size_t)j * nb + i, o = (size_t)i * cand_cap + j;
+            added[o] = ra[e]; new_idx[o] = ri[e];
+            if (chi2) chi2[o] = rc2[e];
+            if (ra[e]) c->h_n[b0 + i] += blocks[i].cand[j].s;
+            if (dx && ra[e]) memcpy(dx + o * c->ldp, rdx + e * c->ldp, 8 * (size_t)c->ldp);
+        }
+        const int st = (rs[i] & 4) ? INGVIO_E_NOT_PD : ((rs[i] & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
+        if (status) status[i] = st;
+        if (st != INGVIO_OK) soft = st;
+    }
+    return soft;
 }
 
 int ingvio_replace_var_linear(ingvio_ctx* c, int b, int tidx, int tsize, const int* vidx, const int* vsize, int k, const double* H, int ldh)
