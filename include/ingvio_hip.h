@@ -320,7 +320,8 @@ int ingvio_add_variable_delayed(ingvio_ctx* ctx, int b, const int* vidx, const i
  *     after a trailing update whose S was not positive definite the filter's remaining candidates are not tried.
  *     The worst of these codes is also the call's return value; the outputs and every filter's n are valid with it.
  * One noise (sigma, R = noise^2 I) for the call.  The call never touches the device nominal table: entering the new
- * variable there stays ingvio_nominal_get / _set.
+ * variable there stays ingvio_nominal_get / _set (ingvio_landmark_init_nominal below forms the rows of new landmarks on the
+ * device and enters them itself).
  * Refused before anything changes: INGVIO_E_ARG (range, NULL where data is needed, s outside 1..6, ldh / ldn < m,
  * n_cand > cand_cap, a split frame step pending, or a frame / GNSS epoch / landmark stage from the nominal table that
  * has not run - as ingvio_nominal_box_plus); INGVIO_E_NOT_IN_STATE (an (idx, size) beyond the filter's n);
@@ -640,6 +641,60 @@ typedef struct {
 } ingvio_landmark_frame_nominal;
 int ingvio_landmark_stage_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_landmark_frame_nominal* frames,
                                   const ingvio_landmark_opts* opts);
+/* ---- landmark initialisation in the device-resident closed loop ------------------------------------------------
+ * LandmarkUpdate::initNewLandmark{Mono,Stereo} (LandmarkUpdate.cpp:399-421, :928-955) for filters [b0, b0 + nb) from what the device
+ * already holds: the observations and the 64-bit mask of the track store, the clone poses of the nominal table.  Per filter the
+ * candidates are tried in order; for each one
+ *   - the rows of calcResJacobianSingleFeatAll{Mono,Stereo}Obs (:426-500, :803-890) are formed on the device at the table's CURRENT clone
+ *     poses, for every stored observation of `track` whose store column is not in drop_cols (the reference's
+ *     sw_poses.find(time) == end() -> continue).  A store column maps to a window position by the count of dropped columns below it.
+ *     var_old_order = the window's clones in ascending time, six columns each; s = 3; two rows per observation (mono) or four
+ *     (opts->stereo, R_cl2cr, t_cl2cr), in ascending window position; the anchor's theta block is minus the observer's and both are
+ *     absent when the observer is the anchor.  m = rows per observation x observations used;
+ *   - addVariableDelayed as one round of ingvio_add_variable_delayed_batch with noise = opts->noise and the threshold
+ *     chi2_mult * opts->chi2_table[m] (the quantile at dof m, StateManager.cpp:610-612);
+ *   - on acceptance the landmark is entered into the table ON THE DEVICE: kind INGVIO_NOM_LANDMARK, idx = the live n, anchor = the
+ *     table slot of window clone `anchor`, p = pf, in the slot the host reserved - candidate j of a filter gets the j-th lowest free
+ *     slot of the table at the call's start, a refused candidate leaves its slot free - and then StateManager::boxPlus of the
+ *     candidate's trailing dx runs on the table, the new landmark included.  The next candidate's rows are formed after that, as the
+ *     reference forms them (ingvio_add_variable_delayed_batch takes every candidate's rows up front).
+ * The host takes no decision between the candidates and synchronises once, at the end; then the live sizes and its mirror of the table
+ * follow the verdicts.  40 bytes per candidate travel.
+ *   added / new_idx / chi2 [nb][cand_cap], dx [nb][cand_cap][ldp] (may be NULL), status [nb] (may be NULL) and the soft
+ *     INGVIO_NEG_DIAG / INGVIO_E_NOT_PD return with the stop of that filter's sequence: as ingvio_add_variable_delayed_batch.
+ *   slot [nb][cand_cap]: the table slot of the new landmark, -1 when not added.
+ *   A candidate whose used observations give m <= 3 is skipped on the device (added = 0, chi2 = 0, state untouched): only the device
+ *     knows the mask.  A refused or skipped candidate leaves P, n and the table untouched.
+ * Refused before anything changes, from the host mirror only: INGVIO_E_ARG (no table, no track store, range, NULL where data is
+ * needed, n_cand > cand_cap, a track outside the store, an anchor outside the window, drop_cols not ascending or outside c_max, window
+ * size + n_drop > c_max, chi2_table shorter than rows per observation x window size + 1, a split frame step pending, or a frame / GNSS
+ * epoch / landmark stage from the table that has not run); INGVIO_E_NOT_IN_STATE (a window clone beyond the filter's n);
+ * INGVIO_E_CAPACITY (fewer free table slots than candidates, n + 3 n_cand > n_max, the worst-case m - every window clone observing -
+ * beyond ingvio_mld, more columns than the context holds, and the three LDS bounds of ingvio_add_variable_delayed_batch taken at that
+ * worst-case m: the trailing update's S, the single-filter gate's 150 KB, the front's 160 KB - e.g. a stereo candidate on 20 clones).
+ * Not reproduced: the reference's hasNaN skip of an observation (:479, :866) - a point on a camera's z = 0 plane gives a non-finite
+ * chi2 and is refused (with do_chi2 != 0).  The call runs where ingvio_add_variable_delayed_batch runs: between frames, on the window the
+ * table holds then; it is not part of ingvio_frame_run.  Which tracks to try, triangulation, the max_landmarks cap and the MapServer's
+ * _ftype flag stay the host's. */
+typedef struct {
+    int track;        /* track-store track of the feature                                                      */
+    int anchor;       /* window position (ascending time, AFTER the pending drops) of getAnchoredPose()        */
+    double pf[3];     /* _landmark->valuePosXyz() after triangulation                                          */
+} ingvio_lm_init_cand;
+typedef struct {
+    int n_cand; const ingvio_lm_init_cand* cand;      /* tried in this order                                    */
+    int n_drop; const int* drop_cols;                 /* store columns whose clone has left the table's window but whose drop has not
+                                                         reached the store yet (what the next frame's drop_slots will be), ascending */
+} ingvio_lm_init_block;
+int ingvio_landmark_init_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_lm_init_block* blocks, const ingvio_msckf_opts* opts,
+                                 double chi2_mult, int do_chi2, int cand_cap,
+                                 int* added, int* new_idx, int* slot, double* chi2, double* dx, int* status);
+/* parity hook (tests): the row formation of ingvio_landmark_init_nominal alone for filter b and one candidate; nothing changes, so
+ * neither a free table slot nor room for three more columns is asked for (every other refusal as above).
+ * H_old [m x 6 C] and H_new [m x 3] column-major with leading dimension *m_out, res [m]; the caller provides room for
+ * m = rows per observation x window size. */
+int ingvio_debug_landmark_init_rows(ingvio_ctx* ctx, int b, const ingvio_lm_init_cand* cand, const ingvio_msckf_opts* opts,
+                                    int n_drop, const int* drop_cols, double* H_old, double* H_new, double* res, int* m_out);
 int ingvio_frame_run(ingvio_ctx* ctx, int restore_prior);
 /* Throughput batches (round 6, an experiment kept selectable): ingvio_frame_run deals the batch to `parts` slices of filters, each
  * on its own HIP stream; the slices' throughput-bound segments (gate + Gram, apply) are chained by events so that only ONE runs at a

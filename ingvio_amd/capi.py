@@ -34,6 +34,7 @@ EXPORTS = [
     "ingvio_chi2_gamma_multi", "ingvio_ekf_update_batch", "ingvio_add_variable_delayed_invertible", "ingvio_add_variable_delayed", "ingvio_add_variable_delayed_batch", "ingvio_replace_var_linear",
     "ingvio_nominal_create", "ingvio_nominal_set", "ingvio_nominal_get", "ingvio_nominal_box_plus", "ingvio_frame_stage_tracks_nominal",
     "ingvio_nominal_set_gnss", "ingvio_nominal_get_gnss", "ingvio_gnss_front_stage_nominal", "ingvio_landmark_stage_nominal",
+    "ingvio_landmark_init_nominal", "ingvio_debug_landmark_init_rows",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -86,6 +87,35 @@ def make_delayed_blocks(blocks):
             keep.append((H_old, H_new, vi, vs, r))
             ca[j].vidx = _i(vi); ca[j].vsize = _i(vs); ca[j].k = len(vi); ca[j].H_old = _d(H_old); ca[j].ldh = max(m, 1)
             ca[j].H_new = _d(H_new); ca[j].ldn = max(m, 1); ca[j].res = _d(r); ca[j].m = m; ca[j].s = s; ca[j].chi2_check = chk
+        keep.append(ca)
+        arr[g].cand = ca
+    return arr, cand_cap, keep
+
+
+class LmInitCand(C.Structure):
+    _fields_ = [("track", C.c_int), ("anchor", C.c_int), ("pf", C.c_double * 3)]
+
+
+class LmInitBlock(C.Structure):
+    _fields_ = [("n_cand", C.c_int), ("cand", C.POINTER(LmInitCand)), ("n_drop", C.c_int), ("drop_cols", C.POINTER(C.c_int))]
+
+
+def make_lm_init_blocks(blocks):
+    """blocks: per filter a dict(cands=[(track, anchor window position, pf [3]), ...], drop=[pending drop columns of the store]).
+    Returns (ingvio_lm_init_block array, cand_cap, objects that own the memory the array points to)."""
+    nb = len(blocks)
+    arr = (LmInitBlock * max(nb, 1))(); keep = []
+    cand_cap = max([len(bk["cands"]) for bk in blocks] + [1])
+    for g, bk in enumerate(blocks):
+        cands, drop = bk["cands"], i32(bk.get("drop", []))
+        arr[g].n_cand = len(cands); arr[g].n_drop = len(drop)
+        if len(drop):
+            arr[g].drop_cols = _i(drop); keep.append(drop)
+        if not cands:
+            continue
+        ca = (LmInitCand * len(cands))()
+        for j, (track, anchor, pf) in enumerate(cands):
+            ca[j].track = int(track); ca[j].anchor = int(anchor); ca[j].pf = (C.c_double * 3)(*f64(pf).reshape(3))
         keep.append(ca)
         arr[g].cand = ca
     return arr, cand_cap, keep
@@ -745,6 +775,43 @@ class Context:
             dxs = [(dx[g, j, :idx[g, j] + arr[g].cand[j].s].copy() if want_dx and added[g, j] else None) for j in range(k)]
             out.append(([bool(a) for a in added[g, :k]], [int(v) for v in idx[g, :k]], [float(v) for v in chi2[g, :k]], dxs))
         return out
+
+    def landmark_init_nominal(self, b0, blocks, opts_frame, chi2_mult=1.0, do_chi2=True, want_dx=True):
+        """ingvio_landmark_init_nominal for filters b0, b0+1, ...: blocks as make_lm_init_blocks takes them, opts_frame a dict with
+        stereo / R_cl2cr / t_cl2cr / noise / chi2_table (make_opts).  Returns per filter (added [bool], new_idx [int], chi2 [float],
+        dx [array of the state after the append, or None], slot [int]), one entry per candidate; self.delayed_status as
+        add_variable_delayed_batch leaves it."""
+        nb = len(blocks)
+        arr, cap, keep = make_lm_init_blocks(blocks)
+        o, tab = make_opts(opts_frame)
+        added = np.zeros((nb, cap), dtype=np.int32); idx = np.full((nb, cap), -1, dtype=np.int32); slot = np.full((nb, cap), -1, dtype=np.int32)
+        chi2 = np.zeros((nb, cap)); dx = np.zeros((nb, cap, self.ldp)) if want_dx else None
+        st = np.zeros(nb, dtype=np.int32)
+        rc = self.L.ingvio_landmark_init_nominal(self.h, int(b0), nb, arr, C.byref(o), C.c_double(chi2_mult), 1 if do_chi2 else 0, cap,
+                                                 _i(added), _i(idx), _i(slot), _d(chi2), _d(dx) if want_dx else None, _i(st))
+        if rc != E_NOT_PD:
+            self._chk(rc)
+        self.delayed_status = st
+        out = []
+        for g, bk in enumerate(blocks):
+            k = len(bk["cands"])
+            dxs = [(dx[g, j, :idx[g, j] + 3].copy() if want_dx and added[g, j] else None) for j in range(k)]
+            out.append(([bool(a) for a in added[g, :k]], [int(v) for v in idx[g, :k]], [float(v) for v in chi2[g, :k]], dxs,
+                        [int(v) for v in slot[g, :k]]))
+        return out
+
+    def debug_landmark_init_rows(self, b, cand, opts_frame, n_clones, drop=()):
+        """the rows ingvio_landmark_init_nominal forms for filter b (its table's window holds n_clones clones) and the candidate
+        (track, anchor, pf): (H_old [m, 6 n_clones], H_new [m, 3], res [m])"""
+        o, tab = make_opts(opts_frame)
+        ca = LmInitCand(); ca.track = int(cand[0]); ca.anchor = int(cand[1]); ca.pf = (C.c_double * 3)(*f64(cand[2]).reshape(3))
+        drop = i32(list(drop))
+        mw, nc = (4 if o.stereo else 2) * self.c_max, 6 * self.c_max
+        H_old = np.zeros(mw * nc); H_new = np.zeros(mw * 3); res = np.zeros(mw); m = C.c_int(0)
+        self._chk(self.L.ingvio_debug_landmark_init_rows(self.h, int(b), C.byref(ca), C.byref(o), len(drop), _i(drop) if len(drop) else None,
+                                                         _d(H_old), _d(H_new), _d(res), C.byref(m)))
+        m, nc = m.value, 6 * int(n_clones)
+        return (H_old[:m * nc].reshape(nc, m).T.copy(), H_new[:3 * m].reshape(3, m).T.copy(), res[:m].copy())
 
     def replace_var_linear(self, b, tidx, tsize, vidx, vsize, H):
         H = np.asfortranarray(np.atleast_2d(H), dtype=np.float64)

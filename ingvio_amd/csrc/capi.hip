@@ -2418,6 +2418,238 @@ int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvi
     return soft;
 }
 
+// ---- LandmarkUpdate::initNewLandmark{Mono,Stereo} (LandmarkUpdate.cpp:363-424, :892-956) from the track store and the nominal table ----
+// The rounds of ingvio_add_variable_delayed_batch with the rows formed by the front itself (k_delayed_front<true>) at the clone poses
+// the table holds when the round starts, the accepted landmark entered into the table by the front, and boxPlus of the round's dx on
+// the table behind the trailing update: candidate j + 1 is linearised where the reference linearises it.  Validation on the host
+// mirror only, no decision between the rounds, one synchronisation.
+struct LmInitPlan {
+    int R = 0, mu_cap = 0, nc_cap = 0, n_cap = 0, per = 2;
+    size_t lds = 0;
+    std::vector<int> slots;             // [round][filter] reserved table slot (-1: no candidate)
+    std::vector<unsigned long long> dropm;
+};
+
+// rows_only: the parity hook - it appends nothing, so neither a free table slot nor room in the state is asked for
+static int lm_init_validate(ingvio_ctx* c, const char* who, int b0, int nb, const ingvio_lm_init_block* blocks, const ingvio_msckf_opts* o, int cand_cap,
+                            LmInitPlan& pl, bool rows_only = false)
+{
+    auto& m = c->nom;
+    if (phase_busy(c)) return INGVIO_E_ARG;
+    if (check_range(c, b0, nb) || !blocks || !o || cand_cap < 1) return INGVIO_E_ARG;
+    if (!m.vmax) { c->err = std::string(who) + " without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (!c->trk.t_max) { c->err = std::string(who) + " without ingvio_tracks_create"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = std::string(who) + ": a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, who)) return INGVIO_E_ARG;
+    if (!(o->noise > 0.0) || !o->chi2_table || o->chi2_len < 1) return INGVIO_E_ARG;
+    const int cm = c->d.c_max, per = o->stereo ? 4 : 2;
+    pl.per = per;
+    for (int i = 0; i < nb; ++i) if (blocks[i].n_cand > pl.R) pl.R = blocks[i].n_cand;
+    if (pl.R > cand_cap) return INGVIO_E_ARG;
+    pl.slots.assign((size_t)pl.R * nb, -1);
+    pl.dropm.assign((size_t)nb, 0ULL);
+    int cap_err = 0;
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_lm_init_block& blk = blocks[i];
+        const int b = b0 + i;
+        const int* I = &m.h_ih[(size_t)b * m.ir];
+        const int* var = I + NOM_IH;
+        const int cw = I[NOM_N_CLONES];
+        if (blk.n_cand < 0 || (blk.n_cand > 0 && !blk.cand) || blk.n_drop < 0 || (blk.n_drop > 0 && !blk.drop_cols)) return INGVIO_E_ARG;
+        for (int q = 0; q < blk.n_drop; ++q) {
+            if (blk.drop_cols[q] < 0 || blk.drop_cols[q] >= cm || (q && blk.drop_cols[q] <= blk.drop_cols[q - 1])) {
+                c->err = std::string(who) + ": drop_cols is not ascending or names a column outside c_max"; return INGVIO_E_ARG;
+            }
+            pl.dropm[i] |= 1ULL << blk.drop_cols[q];
+        }
+        if (cw + blk.n_drop > cm) { c->err = std::string(who) + ": the window and the pending drops exceed c_max"; return INGVIO_E_ARG; }
+        if (blk.n_cand == 0) continue;
+        for (int j = 0; j < blk.n_cand; ++j) {
+            const ingvio_lm_init_cand& q = blk.cand[j];
+            if (q.track < 0 || q.track >= c->trk.t_max) { c->err = std::string(who) + ": a track lies outside the store"; return INGVIO_E_ARG; }
+            if (q.anchor < 0 || q.anchor >= cw) { c->err = std::string(who) + ": an anchor lies outside the window"; return INGVIO_E_ARG; }
+        }
+        if (o->chi2_len < per * cw + 1) { c->err = std::string(who) + ": chi2_table is shorter than the widest candidate needs"; return INGVIO_E_ARG; }
+        for (int q = 0; q < cw; ++q) {
+            const int ix = var[4 * I[NOM_CLONES + q] + 1];
+            if (ix < 0 || ix + 6 > c->h_n[b]) return INGVIO_E_NOT_IN_STATE;
+        }
+        // capacity (reported after every argument of the call has been looked at)
+        int got = 0;
+        for (int v = 0; v < m.vmax && got < blk.n_cand; ++v) if (var[4 * v] == NOM_KIND_NONE) pl.slots[(size_t)(got++) * nb + i] = v;
+        const int mw = per * cw, nc = 6 * cw, mu = mw - 3;
+        if (!rows_only && (got < blk.n_cand || c->h_n[b] + 3 * blk.n_cand > c->d.n_max)) { cap_err = 1; continue; }
+        if (mw > c->mld || nc > c->nc_cap) { cap_err = 1; continue; }
+        if (mu > 0) {
+            const size_t l = delayed_front_lds(mw, 3, nc);
+            if (l > 160 * 1024 || !ekf_core_fits(mu, nc)) { cap_err = 1; continue; }
+            if ((size_t)8 * ((size_t)nc * mu + (size_t)(mu + 1) * (mu + 1)) > 150 * 1024) { cap_err = 1; continue; }      // as ingvio_add_variable_delayed_batch
+            if (l > pl.lds) pl.lds = l;
+            if (mu > pl.mu_cap) pl.mu_cap = mu;
+        }
+        if (nc > pl.nc_cap) pl.nc_cap = nc;
+        if (c->h_n[b] + 3 * blk.n_cand > pl.n_cap) pl.n_cap = c->h_n[b] + 3 * blk.n_cand;
+    }
+    return cap_err ? INGVIO_E_CAPACITY : INGVIO_OK;
+}
+
+static void lm_init_rows_common(ingvio_ctx* c, const ingvio_msckf_opts* o, double chi2_mult, DelayedRows& Rw)
+{
+    Rw.nt = nom_table(c);
+    Rw.ts = TrackStore{ c->trk.uv, c->trk.mask, c->trk.pf, c->trk.t_max, c->d.c_max };
+    Rw.chi2_mult = chi2_mult; Rw.stereo = o->stereo ? 1 : 0;
+    memcpy(Rw.R_lr, o->R_cl2cr, 72); memcpy(Rw.t_lr, o->t_cl2cr, 24);
+}
+
+int ingvio_landmark_init_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_lm_init_block* blocks, const ingvio_msckf_opts* o, double chi2_mult,
+                                 int do_chi2, int cand_cap, int* added, int* new_idx, int* slot, double* chi2, double* dx, int* status)
+{
+    ENTER(c);
+    if (!c) return INGVIO_E_ARG;
+    if (!added || !new_idx || !slot) return INGVIO_E_ARG;
+    LmInitPlan pl;
+    if (int rc = lm_init_validate(c, "ingvio_landmark_init_nominal", b0, nb, blocks, o, cand_cap, pl)) return rc;
+    const int R = pl.R;
+    const size_t RN = (size_t)R * nb, CC = (size_t)nb * cand_cap;
+    for (size_t e = 0; e < CC; ++e) { added[e] = 0; new_idx[e] = -1; slot[e] = -1; if (chi2) chi2[e] = 0.0; }
+    if (dx) memset(dx, 0, 8 * CC * c->ldp);
+    if (status) for (int i = 0; i < nb; ++i) status[i] = INGVIO_OK;
+    if (R == 0 || pl.mu_cap == 0) return INGVIO_OK;                                    // nothing to try anywhere (or no window wider than m <= 3)
+    // ---- one slab up: 40 bytes per candidate, the pending drops, the chi2 table ----
+    const size_t ntab = (size_t)pl.mu_cap + 4;                                          // chi2_table[0 .. widest m]
+    const size_t o_tr = 0, o_an = o_tr + pad64(4 * RN), o_sl = o_an + pad64(4 * RN), o_pf = o_sl + pad64(4 * RN), o_dm = o_pf + pad64(24 * RN),
+                 o_tab = o_dm + pad64(8 * (size_t)nb), o_var = o_tab + pad64(8 * ntab), in_bytes = o_var + 64;
+    const int mldu = (pl.mu_cap + 15) & ~15;
+    const size_t cs = pl.nc_cap, hsu = (size_t)mldu * pl.nc_cap;
+    const size_t w_res = pad64(8 * (size_t)nb * hsu), w_mu = w_res + pad64(8 * (size_t)nb * mldu), w_nc = w_mu + pad64(4 * (size_t)nb),
+                 w_cm = w_nc + pad64(4 * (size_t)nb), wk_bytes = w_cm + pad64(4 * (size_t)nb * cs);
+    const size_t B = c->d.batch;
+    const size_t r_idx = pad64(4 * RN), r_st = r_idx + pad64(4 * RN), r_chi = r_st + pad64(4 * B), r_sl = r_chi + pad64(8 * RN), r_dx = r_sl + pad64(4 * RN),
+                 out_bytes = r_dx + (dx ? 8 * RN * c->ldp : 0);
+    auto& w = c->dl;
+    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
+    if (int rc = dl_grow(c, &w.wk, &w.wk_cap, wk_bytes)) return rc;
+    if (w.out_cap < out_bytes && w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; }
+    if (int rc = dl_grow(c, &w.out, &w.out_cap, out_bytes)) return rc;
+    if (!w.h_out) HIPCHK(c, hipHostMalloc((void**)&w.h_out, w.out_cap, hipHostMallocDefault));
+    Uploader upl{ c };
+    if (int rc = upl.begin(in_bytes + 64)) return rc;
+    char* h = upl.take<char>(in_bytes);
+    memset(h, 0, in_bytes);
+    int *htr = (int*)(h + o_tr), *han = (int*)(h + o_an), *hsl = (int*)(h + o_sl);
+    double* hpf = (double*)(h + o_pf);
+    for (size_t e = 0; e < RN; ++e) htr[e] = -1;
+    for (int i = 0; i < nb; ++i)
+        for (int j = 0; j < blocks[i].n_cand; ++j) {
+            const size_t e = (size_t)j * nb + i;
+            const ingvio_lm_init_cand& q = blocks[i].cand[j];
+            htr[e] = q.track; han[e] = q.anchor; hsl[e] = pl.slots[e];
+            memcpy(hpf + 3 * e, q.pf, 24);
+        }
+    memcpy(h + o_dm, pl.dropm.data(), 8 * (size_t)nb);
+    memcpy(h + o_tab, o->chi2_table, 8 * ntab);
+    const double var = o->noise * o->noise;
+    *(double*)(h + o_var) = var;
+    upl.copy(w.in, h, in_bytes);
+    if (int rc = upl.end()) return rc;
+    if (wait_inputs(c)) return INGVIO_E_HIP;                                            // the store's last delta may have travelled on the copy stream
+    int* d_st = (int*)(w.out + r_st);
+    HIPCHK(c, hipMemsetAsync(d_st + b0, 0, sizeof(int) * (size_t)nb, c->st));
+    HIPCHK(c, hipMemsetAsync(c->d_dx + (size_t)b0 * c->ldp, 0, 8 * (size_t)nb * c->ldp, c->st));
+    const CovView cv = view(c);
+    DelayedRows Rw;
+    memset(&Rw, 0, sizeof Rw);
+    lm_init_rows_common(c, o, chi2_mult, Rw);
+    Rw.dropm = (const unsigned long long*)(w.in + o_dm); Rw.chi2 = (const double*)(w.in + o_tab);
+    Rw.nc_out = (int*)(w.wk + w_nc); Rw.colmap_out = (int*)(w.wk + w_cm);
+    for (int j = 0; j < R; ++j) {
+        const size_t r0 = (size_t)j * nb;
+        DelayedFront F;
+        memset(&F, 0, sizeof F);
+        F.cv = cv; F.b0 = b0; F.nb = nb; F.cs = (int)cs; F.do_chi2 = do_chi2 ? 1 : 0; F.var = var;
+        F.Hu = (double*)w.wk; F.resu = (double*)(w.wk + w_res); F.mldu = mldu; F.hsu = hsu; F.mu = (int*)(w.wk + w_mu);
+        F.Y = c->d_Y + (size_t)b0 * c->ystride; F.ystride = (size_t)c->ystride; F.status = d_st;
+        F.added = (int*)w.out + r0; F.new_idx = (int*)(w.out + r_idx) + r0; F.chi2 = (double*)(w.out + r_chi) + r0;
+        Rw.track = (const int*)(w.in + o_tr) + r0; Rw.anchor = (const int*)(w.in + o_an) + r0; Rw.slot = (const int*)(w.in + o_sl) + r0;
+        Rw.pf = (const double*)(w.in + o_pf) + 3 * r0; Rw.slot_out = (int*)(w.out + r_sl) + r0;
+        if (launch_delayed_front_rows(F, Rw, pl.lds, c->st)) return INGVIO_E_CAPACITY;
+        EkfLaunch E;                                                                    // :623-624 ekfUpdate with the lower rows on the extended state
+        memset(&E, 0, sizeof E);
+        E.cv = cv; E.b0 = b0; E.nb = nb; E.H = F.Hu; E.res = F.resu; E.colmap = Rw.colmap_out; E.m = F.mu; E.nc = Rw.nc_out;
+        E.noise = (const double*)(w.in + o_var); E.r_kind = 0; E.mld = mldu; E.hstride = (int)hsu; E.cstride = (int)cs; E.nstride = 0;
+        E.Y = c->d_Y + (size_t)b0 * c->ystride; E.ystride = c->ystride; E.dx = c->d_dx; E.status = d_st; E.m_cap = pl.mu_cap; E.nc_cap = pl.nc_cap;
+        { ProfScope p(c, PF_EKF_CORE); launch_ekf_core(E, c->st); }
+        { ProfScope p(c, PF_DOWNDATE); launch_downdate(E, pl.n_cap, c->st); }
+        // boxPlus of the round's dx (zero where nothing was added) on the table, the new landmark included (stream_filter.py:772-775)
+        launch_nominal_update(nom_table(c), c->d_dx, c->ldp, nullptr, b0, nb, c->st);
+        if (dx) HIPCHK(c, hipMemcpyAsync(w.out + r_dx + 8 * r0 * c->ldp, c->d_dx + (size_t)b0 * c->ldp, 8 * (size_t)nb * c->ldp, hipMemcpyDeviceToDevice, c->st));
+    }
+    HIPCHK(c, hipMemcpyAsync(w.h_out, w.out, out_bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (int rc = last_launch(c)) return rc;
+    const int *ra = (const int*)w.h_out, *ri = (const int*)(w.h_out + r_idx), *rs = (const int*)(w.h_out + r_st) + b0, *rl = (const int*)(w.h_out + r_sl);
+    const double *rc2 = (const double*)(w.h_out + r_chi), *rdx = (const double*)(w.h_out + r_dx);
+    int soft = INGVIO_OK;
+    for (int i = 0; i < nb; ++i) {
+        int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
+        for (int j = 0; j < blocks[i].n_cand; ++j) {
+            const size_t e = (size_t)j * nb + i, oo = (size_t)i * cand_cap + j;
+            added[oo] = ra[e]; new_idx[oo] = ri[e]; slot[oo] = ra[e] ? rl[e] : -1;
+            if (chi2) chi2[oo] = rc2[e];
+            if (dx && ra[e]) memcpy(dx + oo * c->ldp, rdx + e * c->ldp, 8 * (size_t)c->ldp);
+            if (!ra[e]) continue;
+            c->h_n[b0 + i] += 3;                                                        // the mirror follows the front's record
+            int* v = I + NOM_IH + 4 * rl[e];
+            v[0] = NOM_KIND_LM; v[1] = ri[e]; v[2] = I[NOM_CLONES + blocks[i].cand[j].anchor]; v[3] = 0;
+            if (rl[e] >= I[NOM_N_VAR]) I[NOM_N_VAR] = rl[e] + 1;
+        }
+        const int st = (rs[i] & 4) ? INGVIO_E_NOT_PD : ((rs[i] & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
+        if (status) status[i] = st;
+        if (st != INGVIO_OK) soft = st;
+    }
+    if (nom_mark(c)) return INGVIO_E_HIP;
+    return soft;
+}
+
+// parity hook (tests): the row stage of ingvio_landmark_init_nominal alone, for one filter and one candidate; changes nothing
+int ingvio_debug_landmark_init_rows(ingvio_ctx* c, int b, const ingvio_lm_init_cand* cand, const ingvio_msckf_opts* o, int n_drop, const int* drop_cols,
+                                    double* H_old, double* H_new, double* res, int* m_out)
+{
+    ENTER(c);
+    if (!c || !cand || !H_old || !H_new || !res || !m_out) return INGVIO_E_ARG;
+    ingvio_lm_init_block blk{ 1, cand, n_drop, drop_cols };
+    LmInitPlan pl;
+    if (int rc = lm_init_validate(c, "ingvio_debug_landmark_init_rows", b, 1, &blk, o, 1, pl, true)) return rc;
+    const int cw = c->nom.h_ih[(size_t)b * c->nom.ir + NOM_N_CLONES], mw = pl.per * cw, nc = 6 * cw;
+    const size_t rows = (size_t)mw * (nc + 4), o_pf = 64, o_dm = 128, in_bytes = 192, out_bytes = pad64(8 * rows) + 64;
+    auto& w = c->dl;
+    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
+    if (int rc = dl_grow(c, &w.wk, &w.wk_cap, out_bytes)) return rc;
+    char h[192];
+    memset(h, 0, sizeof h);
+    ((int*)h)[0] = cand->track; ((int*)h)[1] = cand->anchor;
+    memcpy(h + o_pf, cand->pf, 24); memcpy(h + o_dm, pl.dropm.data(), 8);
+    if (up(c, w.in, h, in_bytes)) return INGVIO_E_HIP;
+    if (wait_inputs(c)) return INGVIO_E_HIP;
+    DelayedRows Rw;
+    memset(&Rw, 0, sizeof Rw);
+    lm_init_rows_common(c, o, 1.0, Rw);
+    Rw.track = (const int*)w.in; Rw.anchor = (const int*)w.in + 1; Rw.pf = (const double*)(w.in + o_pf); Rw.dropm = (const unsigned long long*)(w.in + o_dm);
+    int* d_m = (int*)(w.wk + pad64(8 * rows));
+    const size_t lds = delayed_front_lds(mw > 0 ? mw : 1, 3, nc);
+    if (launch_delayed_rows_debug(Rw, b, (double*)w.wk, d_m, lds, c->st)) return INGVIO_E_CAPACITY;
+    std::vector<double> out(rows);
+    int m = 0;
+    HIPCHK(c, hipMemcpyAsync(out.data(), w.wk, 8 * rows, hipMemcpyDeviceToHost, c->st));
+    if (down_sync(c, &m, d_m, sizeof(int))) return INGVIO_E_HIP;
+    if (int rc = last_launch(c)) return rc;
+    *m_out = m;
+    memcpy(H_old, out.data(), 8 * (size_t)m * nc);
+    memcpy(H_new, out.data() + (size_t)m * nc, 8 * (size_t)m * 3);
+    memcpy(res, out.data() + (size_t)m * (nc + 3), 8 * (size_t)m);
+    return INGVIO_OK;
+}
+
 int ingvio_replace_var_linear(ingvio_ctx* c, int b, int tidx, int tsize, const int* vidx, const int* vsize, int k, const double* H, int ldh)
 {
     ENTER(c);

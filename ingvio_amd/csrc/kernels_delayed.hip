@@ -11,7 +11,12 @@
 //   5. chi2 > chi2_mult chi2_check && do_chi2 (:614-618): refused, nothing written but the verdict.  Otherwise
 //      addVariableDelayedInvertible with the upper s rows (:461-543, as k_delayed_add), n += s, and the lower rows go to the
 //      update's buffers from row 0 with their count in mu[bl]: k_ekf_core / k_downdate of the same round do the ekfUpdate.
+// k_delayed_front<true> (ingvio_landmark_init_nominal) replaces step 1: the rows are not loaded but FORMED in LDS, one lane per store
+// column of the candidate's track, from the track store's observations and the nominal table's clone poses
+// (calcResJacobianSingleFeatAll{Mono,Stereo}Obs, LandmarkUpdate.cpp:426-500 / :803-890); an accepted candidate is entered into the table.
 // No atomics, no global round trip inside the rotation loop.  FP64, gfx950 only.
+#include <type_traits>
+
 #include "dev_common.h"
 #include "launch_delayed.h"
 #include "lm_small.h"
@@ -40,16 +45,101 @@ __host__ __device__ inline DelayedLds delayed_carve(int m, int s, int nc)
     return L;
 }
 
-__global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a)
+struct NoRows {};
+
+// The store columns of a track whose rows are formed: a stored observation, not a pending drop, its window position (the count of
+// columns below it that are not dropped) inside the window of cw clones (and inside the store's cmax columns).  Uniform over the workgroup.
+__device__ __forceinline__ unsigned long long rows_used(unsigned long long mask, unsigned long long dm, int cw, int cmax)
+{
+    unsigned long long um = 0ULL;
+    int q = 0;
+    for (int c = 0; c < cmax && c < 64 && q < cw; ++c) {
+        if ((dm >> c) & 1ULL) continue;
+        um |= mask & (1ULL << c);
+        ++q;
+    }
+    return um;
+}
+
+// Lane c = store column c of filter b's candidate (entry bl of r's arrays): its two (mono) or four (stereo) rows of
+// [H_old | res] into sA (column stride ldA, residual in column nc) and of H_new into sHn (column stride m).  Only the non-zero
+// blocks are written: the observer's six columns, the anchor's theta block (minus the observer's; both absent when the observer is
+// the anchor, LandmarkUpdate.cpp:470-474) and H_new.  Rows in ascending window position.
+__device__ __forceinline__ void rows_form(const DelayedRows& r, int b, int bl, unsigned long long um, unsigned long long dm, int c, int m, int nc,
+                                          double* sA, int ldA, double* sHn)
+{
+    if (!((um >> c) & 1ULL)) return;
+    const unsigned long long below = (1ULL << c) - 1ULL;
+    const int q = c - __popcll(dm & below), row = (r.stereo ? 4 : 2) * __popcll(um & below), anc = r.anchor[bl];
+    const int* I = r.nt.ih + (size_t)b * r.nt.ir;
+    const double* x = r.nt.dv + (size_t)b * r.nt.dr + NOM_DH + (size_t)I[NOM_CLONES + q] * NOM_VD;
+    const double* pf = r.pf + 3 * (size_t)bl;
+    const double4 uv4 = *reinterpret_cast<const double4*>(r.ts.uv + (((size_t)b * r.ts.tmax + r.track[bl]) * r.ts.cmax + c) * 4);
+    const double uv[4] = { uv4.x, uv4.y, uv4.z, uv4.w };
+    double RT[9], A[9], pc[3];
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k) RT[3 * i + k] = x[3 * k + i];                          // R_cm2w^T
+    const double d[3] = { pf[0] - x[9], pf[1] - x[10], pf[2] - x[11] };
+    for (int i = 0; i < 3; ++i) {
+        pc[i] = RT[3 * i] * d[0] + RT[3 * i + 1] * d[1] + RT[3 * i + 2] * d[2];            // pf_cm
+        A[3 * i] = RT[3 * i + 1] * pf[2] - RT[3 * i + 2] * pf[1];                          // R_cm2w^T skew(pf_w)
+        A[3 * i + 1] = RT[3 * i + 2] * pf[0] - RT[3 * i] * pf[2];
+        A[3 * i + 2] = RT[3 * i] * pf[1] - RT[3 * i + 1] * pf[0];
+    }
+    for (int cam = 0; cam < (r.stereo ? 2 : 1); ++cam) {
+        double p[3], J[6];                                                                 // H_proj, for the right camera H_proj_r R_cl2cr
+        if (cam == 0) {
+            for (int i = 0; i < 3; ++i) p[i] = pc[i];
+            J[0] = 1.0 / p[2]; J[1] = 0.0; J[2] = -p[0] / (p[2] * p[2]);
+            J[3] = 0.0; J[4] = 1.0 / p[2]; J[5] = -p[1] / (p[2] * p[2]);
+        } else {
+            for (int i = 0; i < 3; ++i) p[i] = r.R_lr[3 * i] * pc[0] + r.R_lr[3 * i + 1] * pc[1] + r.R_lr[3 * i + 2] * pc[2] + r.t_lr[i];
+            const double h0 = 1.0 / p[2], h2 = -p[0] / (p[2] * p[2]), h5 = -p[1] / (p[2] * p[2]);
+            for (int k = 0; k < 3; ++k) { J[k] = h0 * r.R_lr[k] + h2 * r.R_lr[6 + k]; J[3 + k] = h0 * r.R_lr[3 + k] + h5 * r.R_lr[6 + k]; }
+        }
+        for (int rr = 0; rr < 2; ++rr) {
+            const int ro = row + 2 * cam + rr;
+            for (int j = 0; j < 3; ++j) {
+                const double ht = J[3 * rr] * A[j] + J[3 * rr + 1] * A[3 + j] + J[3 * rr + 2] * A[6 + j];
+                const double hf = J[3 * rr] * RT[j] + J[3 * rr + 1] * RT[3 + j] + J[3 * rr + 2] * RT[6 + j];
+                sHn[ro + j * m] = hf;
+                sA[ro + (size_t)(6 * q + 3 + j) * ldA] = -hf;
+                if (q != anc) { sA[ro + (size_t)(6 * q + j) * ldA] = ht; sA[ro + (size_t)(6 * anc + j) * ldA] = -ht; }
+            }
+            sA[ro + (size_t)nc * ldA] = uv[2 * cam + rr] - p[rr] / p[2];
+        }
+    }
+}
+
+template <bool ROWS>
+__global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a, std::conditional_t<ROWS, DelayedRows, NoRows> r)
 {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int bl = blockIdx.x, b = a.b0 + bl, tid = threadIdx.x;
-    const int m = a.m[bl];
-    if (m == 0 || (a.status[b] & 4)) {                       // nothing to try (or an update of this call failed on this filter)
-        if (tid == 0) { a.added[bl] = 0; a.new_idx[bl] = -1; a.chi2[bl] = 0.0; a.mu[bl] = 0; }
-        return;
+    int m_ = 0, s_ = 3, nc_ = 0;
+    unsigned long long um = 0ULL, dm = 0ULL;
+    if constexpr (ROWS) {
+        const int track = r.track[bl];
+        if (track >= 0 && !(a.status[b] & 4)) {
+            const int cw = r.nt.ih[(size_t)b * r.nt.ir + NOM_N_CLONES];
+            dm = r.dropm[bl];
+            um = rows_used(r.ts.mask[(size_t)b * r.ts.tmax + track], dm, cw, r.ts.cmax);
+            m_ = (r.stereo ? 4 : 2) * __popcll(um);
+            nc_ = 6 * cw;
+        }
+        if (m_ <= s_) {                                      // no candidate, a failed update before it, or m <= s (StateManager.cpp:571-575)
+            if (tid == 0) { a.added[bl] = 0; a.new_idx[bl] = -1; a.chi2[bl] = 0.0; a.mu[bl] = 0; r.slot_out[bl] = -1; }
+            return;
+        }
+    } else {
+        m_ = a.m[bl];
+        if (m_ == 0 || (a.status[b] & 4)) {                  // nothing to try (or an update of this call failed on this filter)
+            if (tid == 0) { a.added[bl] = 0; a.new_idx[bl] = -1; a.chi2[bl] = 0.0; a.mu[bl] = 0; }
+            return;
+        }
+        s_ = a.s[bl]; nc_ = a.nc[bl];
     }
-    const int s = a.s[bl], nc = a.nc[bl], mu = m - s;
+    const int m = m_, s = s_, nc = nc_, mu = m - s;
     const DelayedLds L = delayed_carve(m, s, nc);
     double* base = reinterpret_cast<double*>(smem_raw);
     double *sA = base + L.A, *sHn = base + L.Hn, *sCS = base + L.CS, *sS = base + L.S;
@@ -57,15 +147,28 @@ __global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a)
     int* sCol = reinterpret_cast<int*>(base + L.col);
     const int ldA = L.ldA, n = a.cv.n[b], ld = a.cv.ldp, LS = mu + 1;
     double* P = cov_ptr(a.cv, b);
-    const double* in = a.dbuf + a.doff[bl];
-    const double *Hin = in, *Hnin = in + (size_t)m * nc, *rin = Hnin + (size_t)m * s;
     double* sT = sA + (size_t)(nc + 1) * ldA;               // row c of T = column nc + 1 + c of sA
 
     // ---- 1. stage the rows --------------------------------------------------------------------------------------------
-    for (int e = tid; e < m * nc; e += DL_NT) sA[(e % m) + (size_t)(e / m) * ldA] = Hin[e];
-    for (int e = tid; e < m; e += DL_NT) sA[e + (size_t)nc * ldA] = rin[e];
-    for (int e = tid; e < s * m; e += DL_NT) sHn[e] = Hnin[e];
-    for (int c = tid; c < nc; c += DL_NT) sCol[c] = a.colmap[(size_t)bl * a.cs + c];
+    if constexpr (ROWS) {                                    // formed here: zero fill, then one lane per store column writes its blocks
+        for (int e = tid; e < (nc + 1) * ldA; e += DL_NT) sA[e] = 0.0;
+        for (int e = tid; e < s * m; e += DL_NT) sHn[e] = 0.0;
+        const int* I = r.nt.ih + (size_t)b * r.nt.ir;
+        for (int c = tid; c < nc; c += DL_NT) {              // var_old_order: the window's clones in ascending time
+            const int col = I[NOM_IH + 4 * I[NOM_CLONES + c / 6] + 1] + c % 6;
+            sCol[c] = col; r.colmap_out[(size_t)bl * a.cs + c] = col;
+        }
+        if (tid == 0) r.nc_out[bl] = nc;
+        __syncthreads();
+        if (tid < WAVE) rows_form(r, b, bl, um, dm, tid, m, nc, sA, ldA, sHn);
+    } else {
+        const double* in = a.dbuf + a.doff[bl];
+        const double *Hin = in, *Hnin = in + (size_t)m * nc, *rin = Hnin + (size_t)m * s;
+        for (int e = tid; e < m * nc; e += DL_NT) sA[(e % m) + (size_t)(e / m) * ldA] = Hin[e];
+        for (int e = tid; e < m; e += DL_NT) sA[e + (size_t)nc * ldA] = rin[e];
+        for (int e = tid; e < s * m; e += DL_NT) sHn[e] = Hnin[e];
+        for (int c = tid; c < nc; c += DL_NT) sCol[c] = a.colmap[(size_t)bl * a.cs + c];
+    }
     __syncthreads();
     // ---- 2. the rotation list (one lane) beside T = Pcc H_old^T (the other waves) --------------------------------------
     if (tid < WAVE) {
@@ -143,8 +246,14 @@ __global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a)
     }
     // ---- 5. the verdict (uniform: every thread reads the same LDS word) -------------------------------------------------
     const double chi2 = -sS[mu * LS + mu];
-    if (chi2 > a.thr[bl] && a.do_chi2) {
-        if (tid == 0) { a.added[bl] = 0; a.new_idx[bl] = -1; a.chi2[bl] = chi2; a.mu[bl] = 0; }
+    bool refuse;
+    if constexpr (ROWS) refuse = !(chi2 <= r.chi2_mult * r.chi2[m]);      // the quantile at dof m (StateManager.cpp:610-612); a non-finite chi2 is refused
+    else refuse = chi2 > a.thr[bl];
+    if (refuse && a.do_chi2) {
+        if (tid == 0) {
+            a.added[bl] = 0; a.new_idx[bl] = -1; a.chi2[bl] = chi2; a.mu[bl] = 0;
+            if constexpr (ROWS) r.slot_out[bl] = -1;
+        }
         return;
     }
     // the trailing update's rows, from row 0
@@ -205,6 +314,45 @@ __global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a)
         }
     }
     if (tid == 0) { a.cv.n[b] = n + s; a.added[bl] = 1; a.new_idx[bl] = n; a.chi2[bl] = chi2; a.mu[bl] = mu; }
+    if constexpr (ROWS) {
+        // the landmark's table record, in the slot the host reserved: the round's boxPlus (k_nominal_update<false>, behind the
+        // trailing update) retracts it with the rest (AnchoredLandmark.cpp:227-243)
+        if (tid == 0) {
+            int* I = r.nt.ih + (size_t)b * r.nt.ir;
+            const int slot = r.slot[bl];
+            int* v = I + NOM_IH + 4 * slot;
+            v[0] = NOM_KIND_LM; v[1] = n; v[2] = I[NOM_CLONES + r.anchor[bl]]; v[3] = 0;
+            double* x = r.nt.dv + (size_t)b * r.nt.dr + NOM_DH + (size_t)slot * NOM_VD;
+            for (int i = 0; i < NOM_VD; ++i) x[i] = (i == 0 || i == 4 || i == 8) ? 1.0 : 0.0;
+            for (int i = 0; i < 3; ++i) x[9 + i] = r.pf[3 * (size_t)bl + i];
+            if (slot >= I[NOM_N_VAR]) I[NOM_N_VAR] = slot + 1;
+            r.slot_out[bl] = slot;
+        }
+    }
+}
+
+// test hook (ingvio_debug_landmark_init_rows): the row stage of k_delayed_front<true> alone, one wave, dense rows to global memory
+__global__ __launch_bounds__(WAVE) void k_delayed_rows_debug(DelayedRows r, int b, double* __restrict__ out, int* __restrict__ m_out)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int tid = threadIdx.x;
+    const int cw = r.nt.ih[(size_t)b * r.nt.ir + NOM_N_CLONES], nc = 6 * cw, s = 3;
+    const unsigned long long dm = r.dropm[0];
+    const unsigned long long um = rows_used(r.ts.mask[(size_t)b * r.ts.tmax + r.track[0]], dm, cw, r.ts.cmax);
+    const int m = (r.stereo ? 4 : 2) * __popcll(um);
+    if (tid == 0) *m_out = m;
+    if (m == 0) return;
+    const DelayedLds L = delayed_carve(m, s, nc);
+    double* base = reinterpret_cast<double*>(smem_raw);
+    double *sA = base + L.A, *sHn = base + L.Hn;
+    for (int e = tid; e < (nc + 1) * L.ldA; e += WAVE) sA[e] = 0.0;
+    for (int e = tid; e < s * m; e += WAVE) sHn[e] = 0.0;
+    __syncthreads();
+    rows_form(r, b, 0, um, dm, tid, m, nc, sA, L.ldA, sHn);
+    __syncthreads();
+    for (int e = tid; e < m * nc; e += WAVE) out[e] = sA[(e % m) + (size_t)(e / m) * L.ldA];
+    for (int e = tid; e < s * m; e += WAVE) out[(size_t)m * nc + e] = sHn[e];
+    for (int e = tid; e < m; e += WAVE) out[(size_t)m * (nc + s) + e] = sA[e + (size_t)nc * L.ldA];
 }
 
 }  // namespace
@@ -214,7 +362,23 @@ size_t delayed_front_lds(int m, int s, int nc) { return delayed_carve(m, s, nc).
 int launch_delayed_front(const DelayedFront& L, size_t lds_bytes, hipStream_t st)
 {
     if (lds_bytes > 160 * 1024) return -1;
-    hipFuncSetAttribute((const void*)k_delayed_front, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL(k_delayed_front, dim3(L.nb), dim3(DL_NT), lds_bytes, st, L);
+    hipFuncSetAttribute((const void*)k_delayed_front<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(k_delayed_front<false>, dim3(L.nb), dim3(DL_NT), lds_bytes, st, L, NoRows{});
+    return 0;
+}
+
+int launch_delayed_front_rows(const DelayedFront& L, const DelayedRows& R, size_t lds_bytes, hipStream_t st)
+{
+    if (lds_bytes > 160 * 1024) return -1;
+    hipFuncSetAttribute((const void*)k_delayed_front<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(k_delayed_front<true>, dim3(L.nb), dim3(DL_NT), lds_bytes, st, L, R);
+    return 0;
+}
+
+int launch_delayed_rows_debug(const DelayedRows& R, int b, double* out, int* m_out, size_t lds_bytes, hipStream_t st)
+{
+    if (lds_bytes > 160 * 1024) return -1;
+    hipFuncSetAttribute((const void*)k_delayed_rows_debug, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(k_delayed_rows_debug, dim3(1), dim3(WAVE), lds_bytes, st, R, b, out, m_out);
     return 0;
 }

@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include "dev_common.h"
+#include "launch_tracks.h"
 
 // One round: workgroup bl works on candidate `round` of filter b0 + bl.  The per-candidate arrays are this round's slices, [nb] each.
 struct DelayedFront {
@@ -31,7 +32,32 @@ struct DelayedFront {
     double* chi2;               // [nb] out (0 where there was no candidate)
 };
 
+// The rows of a round formed on the device (ingvio_landmark_init_nominal): LandmarkUpdate::calcResJacobianSingleFeatAll{Mono,Stereo}Obs
+// (LandmarkUpdate.cpp:426-500, :803-890) of one track per filter, from the track store's observations and the nominal table's clone
+// poses as they stand when the round starts.  With it the front ignores dbuf / doff / m / s / nc / colmap / thr of DelayedFront.
+struct DelayedRows {
+    NomTable nt;
+    TrackStore ts;
+    const int* track;                   // [nb] track of the round's candidate, -1: none for this filter
+    const int* anchor;                  // [nb] window position of the anchor clone
+    const int* slot;                    // [nb] table slot reserved for the landmark
+    const double* pf;                   // [nb][3]
+    const unsigned long long* dropm;    // [nb] store columns whose clone has left the window (pending drops)
+    const double* chi2;                 // chi2_table[dof], at least rows per observation * window size + 1 entries
+    double chi2_mult;
+    int stereo;
+    double R_lr[9], t_lr[3];
+    int* nc_out;                        // [nb] out: 6 * window size (the trailing update's column count)
+    int* colmap_out;                    // [nb][cs] out: state column of every column of H_old (cs of DelayedFront)
+    int* slot_out;                      // [nb] out: the slot the landmark was entered at, -1 when not added
+};
+
 // dynamic LDS of one workgroup of k_delayed_front for a candidate (m, s, nc)
 size_t delayed_front_lds(int m, int s, int nc);
 // lds_bytes: the largest delayed_front_lds of the round's candidates.  -1: beyond the LDS of a CU
 int launch_delayed_front(const DelayedFront& L, size_t lds_bytes, hipStream_t st);
+// the same with the rows formed in LDS from the track store and the nominal table (template instantiation <true>); an accepted
+// candidate is also entered into the table.  lds_bytes: delayed_front_lds of the widest window with every clone observing
+int launch_delayed_front_rows(const DelayedFront& L, const DelayedRows& R, size_t lds_bytes, hipStream_t st);
+// test hook: the row formation alone for filter b (entry 0 of R's arrays) -> out = [H_old m x nc (ld m) | H_new m x 3 | res m], *m_out
+int launch_delayed_rows_debug(const DelayedRows& R, int b, double* out, int* m_out, size_t lds_bytes, hipStream_t st);
