@@ -497,7 +497,8 @@ int ingvio_frame_set_imu_noise(ingvio_ctx* ctx, int b0, int nb, const double* no
  *     (ImuPropagator.cpp:98-162, analytic branch) runs on the device (Phi, G, dt and the clone rotation never cross the bus);
  * about 7.6 KB per update for the same frame.  ingvio_frame_stage_tracks leaves the context exactly as ingvio_frame_stage(_async) does:
  * ingvio_frame_run / ingvio_frame_fetch follow.  Slot and track numbers are the CALLER's bookkeeping (the shim's MapServer); tracks
- * are numbered 0 .. t_max - 1 (t_max <= 65536), anchor slots and dof fit a byte. */
+ * are numbered 0 .. t_max - 1 (t_max <= 65536), anchor slots and dof fit a byte.  A track may appear once per delta in obs_track
+ * (one observation per track and frame): repeats are not checked, and two threads would then write one mask word. */
 typedef struct {
     int n_drop; const int* drop_slots;            /* window slots leaving the window, ascending (before the append)              */
     int n_free; const int* free_tracks;           /* erased features: the track's observations are forgotten                     */
@@ -721,6 +722,20 @@ int ingvio_debug_msckf_info(ingvio_ctx* ctx, int b, double* A_out, int* ncol_out
 /* parity hook (tests): [M | t] of filter b's last factored update as the solve kernel left it (MP x MP row-major + MP, MP = 6 * window class
  * rounded up to 4); count doubles are copied. */
 int ingvio_debug_info_solution(ingvio_ctx* ctx, int b, double* out, int count);
+
+/* parity hook (tests): filter b's slice of the track store, mask [t_max], uv [t_max][c_max][4], pf [t_max][3].  Waits for the context's
+ * stream and the copy stream (an asynchronous stage applies its delta there), copies, changes nothing; a NULL array is skipped.
+ * INGVIO_E_ARG for a b outside the batch or without a store.  Measurements are meaningful where the mask bit is set: closing a
+ * track's row up leaves the old values in the columns it vacates. */
+int ingvio_debug_tracks_read(ingvio_ctx* ctx, int b, unsigned long long* mask, double* uv, double* pf);
+
+/* parity hook (tests): filter b's arrays of the input set the NEXT ingvio_frame_run reads (after an asynchronous stage: the set just
+ * staged into), whichever of ingvio_frame_stage(_async) / ingvio_frame_stage_tracks(_nominal) filled it: n_clones [1], n_feat [1],
+ * clone_idx [c_max], clone_R [c_max][9], clone_p [c_max][3], anchor [f_max], dof [f_max], obs_mask [f_max], pf [f_max][3],
+ * uv [f_max][c_max][4].  Synchronises as ingvio_debug_tracks_read, changes nothing; a NULL array is skipped; INGVIO_E_ARG for a b
+ * outside the batch. */
+int ingvio_debug_staged_frame(ingvio_ctx* ctx, int b, int* n_clones, int* n_feat, int* clone_idx, double* clone_R, double* clone_p,
+                              int* anchor, int* dof, unsigned long long* obs_mask, double* pf, double* uv);
 
 /* debug: shader-clock stamps written by block (0,0) of the instrumented kernels (see dev_common.h) */
 int ingvio_debug_read(ingvio_ctx* ctx, long long* out, int n);

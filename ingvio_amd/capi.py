@@ -35,6 +35,7 @@ EXPORTS = [
     "ingvio_nominal_create", "ingvio_nominal_set", "ingvio_nominal_get", "ingvio_nominal_box_plus", "ingvio_frame_stage_tracks_nominal",
     "ingvio_nominal_set_gnss", "ingvio_nominal_get_gnss", "ingvio_gnss_front_stage_nominal", "ingvio_landmark_stage_nominal",
     "ingvio_landmark_init_nominal", "ingvio_debug_landmark_init_rows",
+    "ingvio_debug_tracks_read", "ingvio_debug_staged_frame",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -884,6 +885,26 @@ class Context:
     def tracks_create(self, t_max):
         """allocates / clears the device-resident track store (ingvio_tracks_create)"""
         self._chk(self.L.ingvio_tracks_create(self.h, int(t_max)))
+        self.t_max = int(t_max)
+
+    def debug_tracks_read(self, b):
+        """filter b's slice of the track store: (mask [t_max] uint64, uv [t_max, c_max, 4], pf [t_max, 3]) (ingvio_debug_tracks_read)"""
+        T = getattr(self, "t_max", 0)
+        mask = np.zeros(max(T, 1), dtype=np.uint64); uv = np.zeros((max(T, 1), self.c_max, 4)); pf = np.zeros((max(T, 1), 3))
+        self._chk(self.L.ingvio_debug_tracks_read(self.h, int(b), mask.ctypes.data_as(c_up), _d(uv), _d(pf)))
+        return mask, uv, pf
+
+    def debug_staged_frame(self, b):
+        """filter b's arrays of the input set the next frame_run reads (ingvio_debug_staged_frame): a dict n_clones, n_feat, clone_idx
+        [c_max], clone_R [c_max, 9], clone_p [c_max, 3], anchor [f_max], dof [f_max], obs_mask [f_max], pf [f_max, 3], uv [f_max, c_max, 4]"""
+        cm, fm = self.c_max, self.f_max
+        nc = C.c_int(0); nf = C.c_int(0)
+        o = dict(clone_idx=np.zeros(cm, dtype=np.int32), clone_R=np.zeros((cm, 9)), clone_p=np.zeros((cm, 3)), anchor=np.zeros(fm, dtype=np.int32),
+                 dof=np.zeros(fm, dtype=np.int32), obs_mask=np.zeros(fm, dtype=np.uint64), pf=np.zeros((fm, 3)), uv=np.zeros((fm, cm, 4)))
+        self._chk(self.L.ingvio_debug_staged_frame(self.h, int(b), C.byref(nc), C.byref(nf), _i(o["clone_idx"]), _d(o["clone_R"]), _d(o["clone_p"]),
+                                                   _i(o["anchor"]), _i(o["dof"]), o["obs_mask"].ctypes.data_as(c_up), _d(o["pf"]), _d(o["uv"])))
+        o["n_clones"] = nc.value; o["n_feat"] = nf.value
+        return o
 
     def frame_stage_tracks_prepare(self, b0, steps, track_frames, opts_frame, sigma, enable_gnss=0, sigma_cb=0.0, sigma_rw=0.0, max_accept=0,
                                    compress_rule=1, selected_variant=0, use_async=False):

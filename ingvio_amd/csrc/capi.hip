@@ -4179,6 +4179,50 @@ int ingvio_debug_info_solution(ingvio_ctx* c, int b, double* out, int count)
     return INGVIO_OK;
 }
 
+// both streams idle, then plain blocking copies: the hooks below read what the compute stream AND the copy stream (asynchronous
+// stages) have written, and leave every flag and event of the context as it was
+static int debug_quiesce(ingvio_ctx* c)
+{
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (c->st_copy) HIPCHK(c, hipStreamSynchronize(c->st_copy));
+    return 0;
+}
+static int debug_down(ingvio_ctx* c, void* dst, const void* src, size_t bytes)
+{
+    if (dst && bytes) HIPCHK(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// parity hook: filter b's slice of the track store
+int ingvio_debug_tracks_read(ingvio_ctx* c, int b, unsigned long long* mask, double* uv, double* pf)
+{
+    ENTER(c);
+    if (check_range(c, b, 1)) return INGVIO_E_ARG;
+    if (!c->trk.t_max) { c->err = "ingvio_debug_tracks_read without ingvio_tracks_create"; return INGVIO_E_ARG; }
+    if (debug_quiesce(c)) return INGVIO_E_HIP;
+    const size_t T = c->trk.t_max, C = c->d.c_max;
+    if (debug_down(c, mask, c->trk.mask + (size_t)b * T, 8 * T) || debug_down(c, uv, c->trk.uv + (size_t)b * T * C * 4, 8 * T * C * 4) ||
+        debug_down(c, pf, c->trk.pf + (size_t)b * T * 3, 8 * T * 3)) return INGVIO_E_HIP;
+    return INGVIO_OK;
+}
+
+// parity hook: filter b's arrays of the input set the next ingvio_frame_run reads (the d_* pointers: after an asynchronous stage the
+// set it staged into)
+int ingvio_debug_staged_frame(ingvio_ctx* c, int b, int* n_clones, int* n_feat, int* clone_idx, double* clone_R, double* clone_p, int* anchor, int* dof,
+                              unsigned long long* obs_mask, double* pf, double* uv)
+{
+    ENTER(c);
+    if (check_range(c, b, 1)) return INGVIO_E_ARG;
+    if (debug_quiesce(c)) return INGVIO_E_HIP;
+    const size_t cm = c->d.c_max, fm = c->d.f_max, B = b;
+    if (debug_down(c, n_clones, c->d_nclones + B, 4) || debug_down(c, n_feat, c->d_nfeat + B, 4) ||
+        debug_down(c, clone_idx, c->d_clone_idx + B * cm, 4 * cm) || debug_down(c, clone_R, c->d_clone_R + B * cm * 9, 8 * cm * 9) ||
+        debug_down(c, clone_p, c->d_clone_p + B * cm * 3, 8 * cm * 3) || debug_down(c, anchor, c->d_anchor + B * fm, 4 * fm) ||
+        debug_down(c, dof, c->d_dof + B * fm, 4 * fm) || debug_down(c, obs_mask, c->d_mask + B * fm, 8 * fm) ||
+        debug_down(c, pf, c->d_pf + B * fm * 3, 8 * fm * 3) || debug_down(c, uv, c->d_uv + B * fm * cm * 4, 8 * fm * cm * 4)) return INGVIO_E_HIP;
+    return INGVIO_OK;
+}
+
 int ingvio_debug_read(ingvio_ctx* c, long long* out, int n)
 {
     ENTER(c);

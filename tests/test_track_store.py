@@ -7,6 +7,8 @@ device's sin / cos instead of the host's (1-2 ulp), so the posterior is compared
 import numpy as np
 import pytest
 
+from track_store_model import ragged_observations
+
 pytestmark = pytest.mark.gpu
 
 
@@ -24,10 +26,8 @@ def build(nb, C, F, seed0, stereo=True):
                                                   n_gnss=6, n_landmarks=0, stereo=stereo)
         rng = np.random.default_rng(900 + b)
         mask = np.zeros(F, dtype=np.uint64); dof = np.zeros(F, dtype=np.int32)
-        for j in range(F):                                              # ragged tracks: every feature its own observation set
-            k = int(rng.integers(4, C + 1))
-            obs = np.sort(rng.choice(C, size=k, replace=False))
-            mask[j] = np.uint64(sum(1 << int(o) for o in obs)); dof[j] = k - 1
+        for j, obs in enumerate(ragged_observations(rng, F, C)):        # ragged tracks: every feature its own observation set
+            mask[j] = np.uint64(sum(1 << int(o) for o in obs)); dof[j] = len(obs) - 1
         frame = dict(frame); frame["obs_mask"] = mask; frame["dof"] = dof
         frame["anchor"] = np.array([int([o for o in range(C) if (int(mask[j]) >> o) & 1][j % 3]) for j in range(F)], dtype=np.int32)
         frame["uv"] = np.array(frame["uv"]) * ((mask[:, None] >> np.arange(C, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(float)[:, :, None]
