@@ -559,7 +559,7 @@ int ingvio_nominal_box_plus(ingvio_ctx* ctx, int b0, int nb, const double* dx);
  * Refused before anything changes: no table (INGVIO_E_ARG), a range other than the whole batch (b0 != 0 or nb != batch: the post-frame
  * step covers every filter, INGVIO_E_ARG), a frame staged from the table that has not run yet (INGVIO_E_ARG), an
  * in-frame GNSS or host-fed landmark stage or frame_parts > 1 (INGVIO_E_UNSUPPORTED), marg_idx not a window clone (INGVIO_E_NOT_IN_STATE), a
- * landmark anchored to the clone that leaves (INGVIO_E_ARG), no free slot or a full window (INGVIO_E_CAPACITY).  While such a frame is
+ * landmark anchored to the clone that leaves (INGVIO_E_ARG: stage with marg_idx = -1 and let ingvio_nominal_tail drop the clone), no free slot or a full window (INGVIO_E_CAPACITY).  While such a frame is
  * staged and has not run, ingvio_frame_stage(_async), ingvio_frame_stage_tracks, ingvio_nominal_set / _box_plus, ingvio_cov_snapshot
  * and ingvio_frame_run(restore_prior != 0) return INGVIO_E_ARG and ingvio_frame_run_phase INGVIO_E_UNSUPPORTED.  The ONE stage accepted
  * while such a frame is pending is ingvio_landmark_stage_nominal with opts->in_frame != 0: the frame's own landmark update.  ingvio_cov_snapshot /
@@ -585,6 +585,39 @@ int ingvio_frame_stage_tracks_nominal(ingvio_ctx* ctx, int b0, int nb, const ing
  * a frame or a GNSS epoch staged from the table that has not run.  A filter that never registers runs exactly as before. */
 int ingvio_nominal_set_gnss(ingvio_ctx* ctx, int b0, int nb, const int* slots /* [nb][6] */);
 int ingvio_nominal_get_gnss(ingvio_ctx* ctx, int b0, int nb, int* slots /* [nb][6] */);
+/* ---- the landmark tail of a frame on the device -----------------------------------------------------------------
+ * What callbackStereoFrame / callbackMonoFrame do behind the updates for the in-state landmarks, for filters [b0, b0 + nb) from what the
+ * device holds, per filter in the reference's order:
+ *   1. LandmarkUpdate::changeLandmarkAnchor (LandmarkUpdate.cpp:273-361): for every landmark of lm_slot, in that order, body = R_new^T
+ *      (p_f - p_new) from the table's current values.  body.z <= 0: verdict 0, the landmark is marginalised instead (:298-302).  Otherwise
+ *      verdict 1: FeatureInfoManager::changeAnchoredPose (MapServerManager.cpp:343-379), i.e. StateManager::replaceVarLinear
+ *      (StateManager.cpp:639-693) with H = [-[p_f]x 0 | [p_f]x 0 | I] over [old anchor, new anchor, landmark]; the table's anchor slot
+ *      becomes new_anchor, the world position stays (resetAnchoredPose(.., true)).
+ *   2. the verdict-0 landmarks, the erase_slot landmarks (margAnchoredLandmarkInState, StateManager.cpp:340-353) and the marg_slot
+ *      clones (margSwPose) are marginalised: P is compacted out of place into the other ping-pong half, n shrinks.
+ *   3. the table: freed slots take INGVIO_NOM_NONE, the window list closes up, every surviving idx (the GNSS scalars' included) moves down
+ *      by the size of what left below it; no value of a surviving variable changes.
+ * All landmarks of a filter are one congruence P' = T P T^T (replacing L_i writes row and column L_i only and no H_j reads another
+ * landmark), so P is read once and written once; the result equals the sequential reference up to rounding.  The diagonal blocks are
+ * symmetrised as ingvio_replace_var_linear does, P stays exactly symmetric.
+ * verdict [nb][lm_cap] (entry [i][e] for lm_slot[e] of filter b0 + i; the rest 0), status [nb] (may be NULL; INGVIO_OK).  The call
+ * synchronises once at the end - only the device knows the verdicts - and the host mirror of the table follows them.  A filter whose
+ * three lists are empty is untouched; a call in which every filter is empty launches nothing.  new_anchor is read only with
+ * n_reanchor > 0.
+ * Refused from the host mirror before anything changes: INGVIO_E_ARG (no table, range, NULL where data is needed, n_reanchor > lm_cap
+ * or > 64, a split frame step pending, a frame / GNSS epoch / landmark stage from the table that has not run, a slot named twice or in
+ * both landmark lists, new_anchor listed in marg_slot, a landmark already anchored to new_anchor, n_reanchor > 0 with fewer than two
+ * window clones, a landmark in neither list that would stay anchored to a marg_slot clone); INGVIO_E_NOT_IN_STATE (a listed slot that
+ * is free or holds no landmark, a marg_slot or new_anchor that is no window clone, a table variable beyond the filter's n);
+ * INGVIO_E_CAPACITY (a state too wide for the kernels' index maps).  Stage the frame with marg_idx = -1 when the tail drops its clone. */
+typedef struct {
+    int n_reanchor; const int* lm_slot;   /* table slots of landmarks whose anchor leaves, in the reference's visiting order */
+    int new_anchor;                       /* table slot of the target clone (the reference: the window's newest)            */
+    int n_erase;    const int* erase_slot;/* landmarks marginalised unconditionally (lost track)                             */
+    int n_marg;     const int* marg_slot; /* window clones that leave AFTER the anchor change (margSwPose; key-frame mode: two) */
+} ingvio_nominal_tail_block;
+int ingvio_nominal_tail(ingvio_ctx* ctx, int b0, int nb, const ingvio_nominal_tail_block* blocks, int lm_cap,
+                        int* verdict /* [nb][lm_cap] */, int* status /* [nb], may be NULL */);
 /* ingvio_gnss_front_stage with the receiver taken from the device table: the epoch carries only what the host owns.  p_w, v_w
  * (State::_extended_pose), the clock biases, FS and YOF (GnssUpdate.cpp:98-122 reads them from the state) and every Type::idx() come
  * from the filter's table as the frame that has just run left it - IngvioFilter.cpp:329-362 runs after :276-327 and after margSwPose,

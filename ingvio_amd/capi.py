@@ -34,7 +34,7 @@ EXPORTS = [
     "ingvio_chi2_gamma_multi", "ingvio_ekf_update_batch", "ingvio_add_variable_delayed_invertible", "ingvio_add_variable_delayed", "ingvio_add_variable_delayed_batch", "ingvio_replace_var_linear",
     "ingvio_nominal_create", "ingvio_nominal_set", "ingvio_nominal_get", "ingvio_nominal_box_plus", "ingvio_frame_stage_tracks_nominal",
     "ingvio_nominal_set_gnss", "ingvio_nominal_get_gnss", "ingvio_gnss_front_stage_nominal", "ingvio_landmark_stage_nominal",
-    "ingvio_landmark_init_nominal", "ingvio_debug_landmark_init_rows",
+    "ingvio_landmark_init_nominal", "ingvio_debug_landmark_init_rows", "ingvio_nominal_tail",
     "ingvio_debug_tracks_read", "ingvio_debug_staged_frame",
 ]
 
@@ -120,6 +120,11 @@ def make_lm_init_blocks(blocks):
         keep.append(ca)
         arr[g].cand = ca
     return arr, cand_cap, keep
+
+
+class NominalTailBlock(C.Structure):
+    _fields_ = [("n_reanchor", C.c_int), ("lm_slot", C.POINTER(C.c_int)), ("new_anchor", C.c_int), ("n_erase", C.c_int),
+                ("erase_slot", C.POINTER(C.c_int)), ("n_marg", C.c_int), ("marg_slot", C.POINTER(C.c_int))]
 
 
 class GnssOpts(C.Structure):
@@ -976,6 +981,28 @@ class Context:
         """StateManager::boxPlus on the device: dx [nb][ldp] in the live index space (ingvio_nominal_box_plus)"""
         d = f64(np.asarray(dx, dtype=np.float64).reshape(-1, self.ldp))
         self._chk(self.L.ingvio_nominal_box_plus(self.h, int(b0), d.shape[0], _d(d)))
+
+    def nominal_tail(self, b0, blocks, lm_cap=None):
+        """the landmark tail of a frame (ingvio_nominal_tail) for filters b0, b0+1, ...: blocks are dicts with lm_slot (landmarks to
+        re-anchor, the reference's visiting order), new_anchor, erase_slot, marg_slot (each optional).  Synchronises.  Returns
+        (verdict [nb][lm_cap]: 1 re-anchored, 0 behind the new anchor and marginalised; status [nb])."""
+        nb = len(blocks)
+        arr = (NominalTailBlock * max(nb, 1))(); keep = []
+        for i, bk in enumerate(blocks):
+            lm, er, mg = i32(bk.get("lm_slot", [])), i32(bk.get("erase_slot", [])), i32(bk.get("marg_slot", []))
+            keep.append((lm, er, mg))
+            arr[i].n_reanchor = len(lm); arr[i].n_erase = len(er); arr[i].n_marg = len(mg)
+            arr[i].new_anchor = int(bk.get("new_anchor", -1))
+            if len(lm):
+                arr[i].lm_slot = _i(lm)
+            if len(er):
+                arr[i].erase_slot = _i(er)
+            if len(mg):
+                arr[i].marg_slot = _i(mg)
+        cap = max([len(k[0]) for k in keep] + [1]) if lm_cap is None else int(lm_cap)
+        verdict = np.zeros((nb, max(cap, 1)), dtype=np.int32); status = np.zeros(max(nb, 1), dtype=np.int32)
+        self._chk(self.L.ingvio_nominal_tail(self.h, int(b0), nb, arr, cap, _i(verdict), _i(status)))
+        return verdict[:, :cap], status[:nb]
 
     def frame_stage_tracks_nominal_prepare(self, b0, steps, track_frames, opts_frame, sigma, enable_gnss=0, sigma_cb=0.0, sigma_rw=0.0, max_accept=0,
                                            compress_rule=1, selected_variant=0, use_async=False):

@@ -15,6 +15,7 @@
 #include "launch_gnss.h"
 #include "launch_lmbatch.h"
 #include "launch_nominal.h"
+#include "launch_tail.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -225,6 +226,9 @@ struct ingvio_ctx {
         bool frame = false;                                   // the staged frame came from the table (it runs once)
         hipEvent_t ev = nullptr; bool ev_valid = false;       // behind the post-frame kernel of the frame enqueued last
     } nom;
+    // ingvio_nominal_tail (kernels_tail.hip), grown on demand: the uploaded lists, the panel kernel's workspace (transient: nothing in it
+    // outlives the call, so a snapshot has nothing to copy) and the pinned mirror of the verdicts and the new dimensions
+    struct TailWs { char *in = nullptr, *ws = nullptr, *h_out = nullptr; size_t in_cap = 0, ws_cap = 0, out_cap = 0; } tl;
     // profiling
     bool prof;
     std::vector<ProfRec> recs;
@@ -1095,6 +1099,8 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
     for (void* p : ptrs) if (p) hipFree(p);
     for (void* p : { (void*)c->dl.in, (void*)c->dl.wk, (void*)c->dl.out }) if (p) hipFree(p);
     if (c->dl.h_out) hipHostFree(c->dl.h_out);
+    for (void* p : { (void*)c->tl.in, (void*)c->tl.ws }) if (p) hipFree(p);
+    if (c->tl.h_out) hipHostFree(c->tl.h_out);
     for (auto& sl : c->pin) { if (sl.p) hipHostFree(sl.p); if (sl.ev) hipEventDestroy(sl.ev); }
     if (c->h_result) hipHostFree(c->h_result);
     if (c->qr.exec) hipGraphExecDestroy(c->qr.exec);
@@ -3649,6 +3655,151 @@ int ingvio_nominal_get_gnss(ingvio_ctx* c, int b0, int nb, int* slots)
     if (!m.vmax) { c->err = "ingvio_nominal_get_gnss without ingvio_nominal_create"; return INGVIO_E_ARG; }
     for (int i = 0; i < nb; ++i) memcpy(slots + 6 * (size_t)i, &m.h_ih[(size_t)(b0 + i) * m.ir + NOM_GNSS], sizeof(int) * 6);      // the mirror is the record
     return INGVIO_OK;
+}
+
+// ---- the landmark tail of a frame on the device (kernels_tail.hip) ------------------------------------------------
+// changeLandmarkAnchor (LandmarkUpdate.cpp:273-361), margSwPose and margAnchoredLandmarkInState (StateManager.cpp:340-353) for filters
+// [b0, b0 + nb) in one sweep over P.  Everything is validated on the host mirror before the first launch; the verdicts of the depth test
+// come back with the one synchronisation at the end, and the mirror follows them.
+int ingvio_nominal_tail(ingvio_ctx* c, int b0, int nb, const ingvio_nominal_tail_block* blocks, int lm_cap, int* verdict, int* status)
+{
+    ENTER(c);
+    if (!c || phase_busy(c) || check_range(c, b0, nb) || !blocks || lm_cap < 0) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    const char* who = "ingvio_nominal_tail";
+    if (!m.vmax) { c->err = "ingvio_nominal_tail without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = "ingvio_nominal_tail: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, who)) return INGVIO_E_ARG;
+    auto fail = [&](int code, const char* what) { c->err = std::string(who) + ": " + what; return code; };
+    int kcap = 0, ecap = 0, mcap = 0, active = 0;
+    std::vector<char> mark((size_t)m.vmax);
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_nominal_tail_block& q = blocks[i];
+        const int b = b0 + i;
+        if (q.n_reanchor < 0 || q.n_erase < 0 || q.n_marg < 0) return fail(INGVIO_E_ARG, "a negative count");
+        if (q.n_reanchor > lm_cap || q.n_reanchor > TAIL_LM_MAX) return fail(INGVIO_E_ARG, "n_reanchor exceeds lm_cap or 64");
+        if ((q.n_reanchor && (!q.lm_slot || !verdict)) || (q.n_erase && !q.erase_slot) || (q.n_marg && !q.marg_slot)) return fail(INGVIO_E_ARG, "NULL where data is needed");
+        if (q.n_erase > m.vmax || q.n_marg > NOM_IH - NOM_CLONES) return fail(INGVIO_E_ARG, "more slots listed than the table holds");
+        if (q.n_reanchor + q.n_erase + q.n_marg == 0) continue;
+        ++active;
+        kcap = std::max(kcap, q.n_reanchor); ecap = std::max(ecap, q.n_erase); mcap = std::max(mcap, q.n_marg);
+        const int* I = &m.h_ih[(size_t)b * m.ir];
+        const int* var = I + NOM_IH;
+        const int nv = I[NOM_N_VAR], nc = I[NOM_N_CLONES], n = c->h_n[b];
+        auto in_window = [&](int sl) { for (int w = 0; w < nc; ++w) if (I[NOM_CLONES + w] == sl) return true; return false; };
+        auto is_marg = [&](int sl) { for (int e = 0; e < q.n_marg; ++e) if (q.marg_slot[e] == sl) return true; return false; };
+        // every column index the kernels form comes from the table: all of it has to lie inside the live state
+        for (int v = 0; v < nv; ++v)
+            if (var[4 * v] != NOM_KIND_NONE && (var[4 * v + 1] < 0 || var[4 * v + 1] + nom_size(var[4 * v]) > n)) return fail(INGVIO_E_NOT_IN_STATE, "a table variable lies beyond the filter's n");
+        std::fill(mark.begin(), mark.end(), 0);
+        for (int e = 0; e < q.n_reanchor + q.n_erase; ++e) {
+            const int sl = e < q.n_reanchor ? q.lm_slot[e] : q.erase_slot[e - q.n_reanchor];
+            if (sl < 0 || sl >= nv || var[4 * sl] != NOM_KIND_LM) return fail(INGVIO_E_NOT_IN_STATE, "a listed slot is free or holds no landmark");
+            if (mark[sl]) return fail(INGVIO_E_ARG, "a landmark slot is named twice");
+            mark[sl] = 1;
+        }
+        for (int e = 0; e < q.n_marg; ++e) {
+            const int sl = q.marg_slot[e];
+            if (sl < 0 || sl >= nv || var[4 * sl] != NOM_KIND_SE3 || !in_window(sl)) return fail(INGVIO_E_NOT_IN_STATE, "a marg_slot is no window clone");
+            for (int t = 0; t < e; ++t) if (q.marg_slot[t] == sl) return fail(INGVIO_E_ARG, "a marg_slot is named twice");
+        }
+        if (q.n_reanchor) {
+            const int na = q.new_anchor;
+            if (na < 0 || na >= nv || var[4 * na] != NOM_KIND_SE3 || !in_window(na)) return fail(INGVIO_E_NOT_IN_STATE, "new_anchor is no window clone");
+            if (is_marg(na)) return fail(INGVIO_E_ARG, "new_anchor is listed in marg_slot");
+            if (nc < 2) return fail(INGVIO_E_ARG, "an anchor change needs two window clones (MapServerManager.cpp:347)");
+            for (int e = 0; e < q.n_reanchor; ++e) {
+                const int an = var[4 * q.lm_slot[e] + 2];
+                if (an == na) return fail(INGVIO_E_ARG, "a landmark is already anchored to new_anchor");
+                if (an < 0 || an >= nv || var[4 * an] != NOM_KIND_SE3) return fail(INGVIO_E_ARG, "a landmark without a live anchor");
+            }
+        }
+        for (int v = 0; v < nv; ++v)
+            if (var[4 * v] == NOM_KIND_LM && !mark[v] && is_marg(var[4 * v + 2])) return fail(INGVIO_E_ARG, "a surviving landmark would stay anchored to a clone that leaves");
+    }
+    if (tail_panel_lds(c->ldp) > TAIL_LDS_MAX) return fail(INGVIO_E_CAPACITY, "the state is too wide for the panel kernel's index maps");
+    if (status) for (int i = 0; i < nb; ++i) status[i] = INGVIO_OK;
+    if (verdict) for (size_t e = 0; e < (size_t)nb * lm_cap; ++e) verdict[e] = 0;
+    if (!active) return INGVIO_OK;                                                      // nothing to do anywhere: nothing is launched
+    // ---- lists up, workspace ----
+    const int istride = TAIL_HDR + kcap + ecap + mcap, ld = c->ldp;
+    const size_t in_bytes = pad64(sizeof(int) * (size_t)nb * istride);
+    const size_t zstride = (size_t)ld * 3 * kcap;
+    const size_t w_ver = pad64(sizeof(int) * (size_t)nb), w_map = w_ver + pad64(sizeof(int) * (size_t)nb * std::max(kcap, 1)),
+                 w_tag = w_map + pad64(sizeof(int) * (size_t)nb * ld), w_Z = w_tag + pad64(sizeof(int) * (size_t)nb * ld),
+                 ws_bytes = w_Z + 8 * (size_t)nb * zstride + 64, out_bytes = w_map;      // nnew | verdict come back
+    auto& w = c->tl;
+    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
+    if (int rc = dl_grow(c, &w.ws, &w.ws_cap, ws_bytes)) return rc;
+    if (w.out_cap < out_bytes) {
+        if (w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; w.out_cap = 0; }
+        HIPCHK(c, hipHostMalloc((void**)&w.h_out, out_bytes + 4096, hipHostMallocDefault));
+        w.out_cap = out_bytes + 4096;
+    }
+    Uploader upl{ c };
+    if (int rc = upl.begin(in_bytes + 64)) return rc;
+    int* h = upl.take<int>(in_bytes / sizeof(int));
+    memset(h, 0, in_bytes);
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_nominal_tail_block& q = blocks[i];
+        int* r = h + (size_t)i * istride;
+        r[TAIL_N_RE] = q.n_reanchor; r[TAIL_NEW] = q.n_reanchor ? q.new_anchor : 0; r[TAIL_N_ER] = q.n_erase; r[TAIL_N_MG] = q.n_marg;
+        for (int e = 0; e < q.n_reanchor; ++e) r[TAIL_HDR + e] = q.lm_slot[e];
+        for (int e = 0; e < q.n_erase; ++e) r[TAIL_HDR + kcap + e] = q.erase_slot[e];
+        for (int e = 0; e < q.n_marg; ++e) r[TAIL_HDR + kcap + ecap + e] = q.marg_slot[e];
+    }
+    upl.copy((int*)w.in, h, in_bytes / sizeof(int));
+    if (int rc = upl.end()) return rc;
+    if (wait_inputs(c)) return INGVIO_E_HIP;                                            // nothing on the copy stream may still read the table
+    TailLaunch L;
+    L.cv = view(c); L.t = nom_table(c); L.b0 = b0; L.nb = nb;
+    L.in = (const int*)w.in; L.istride = istride; L.kcap = kcap; L.ecap = ecap; L.mcap = mcap;
+    L.nnew = (int*)w.ws; L.verdict = (int*)(w.ws + w_ver); L.map = (int*)(w.ws + w_map); L.tag = (int*)(w.ws + w_tag);
+    L.Z = (double*)(w.ws + w_Z); L.zstride = zstride;
+    if (launch_tail(L, c->d.n_max, c->st)) return fail(INGVIO_E_CAPACITY, "a workspace bound of the tail kernels does not hold");
+    HIPCHK(c, hipMemcpyAsync(w.h_out, w.ws, out_bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));                                             // only the device knows the verdicts
+    if (int rc = last_launch(c)) return rc;
+    // ---- the mirror follows the verdicts: the arithmetic of k_tail_panel's table pass on the host's copy ----
+    const int* h_nnew = (const int*)w.h_out;
+    const int* h_ver = (const int*)(w.h_out + w_ver);
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_nominal_tail_block& q = blocks[i];
+        if (q.n_reanchor + q.n_erase + q.n_marg == 0) continue;
+        const int b = b0 + i;
+        int* I = &m.h_ih[(size_t)b * m.ir];
+        int* var = I + NOM_IH;
+        const int nv = I[NOM_N_VAR];
+        std::fill(mark.begin(), mark.end(), 0);                                         // 1: the slot leaves
+        for (int e = 0; e < q.n_reanchor; ++e) {
+            const int v = h_ver[(size_t)i * kcap + e];
+            verdict[(size_t)i * lm_cap + e] = v;
+            if (v) var[4 * q.lm_slot[e] + 2] = q.new_anchor; else mark[q.lm_slot[e]] = 1;
+        }
+        for (int e = 0; e < q.n_erase; ++e) mark[q.erase_slot[e]] = 1;
+        for (int e = 0; e < q.n_marg; ++e) mark[q.marg_slot[e]] = 1;
+        int wq = 0;
+        for (int a = 0; a < I[NOM_N_CLONES]; ++a) if (!mark[I[NOM_CLONES + a]]) I[NOM_CLONES + wq++] = I[NOM_CLONES + a];
+        I[NOM_N_CLONES] = wq;
+        std::vector<int> nidx((size_t)nv, -1);
+        int gone = 0;
+        for (int v = 0; v < nv; ++v) {
+            if (var[4 * v] == NOM_KIND_NONE) continue;
+            if (mark[v]) { gone += nom_size(var[4 * v]); continue; }
+            int sh = 0;
+            for (int u = 0; u < nv; ++u) if (mark[u] && var[4 * u] != NOM_KIND_NONE && var[4 * u + 1] < var[4 * v + 1]) sh += nom_size(var[4 * u]);
+            nidx[v] = var[4 * v + 1] - sh;
+        }
+        for (int v = 0; v < nv; ++v) {
+            if (var[4 * v] == NOM_KIND_NONE) continue;
+            if (mark[v]) { var[4 * v] = NOM_KIND_NONE; var[4 * v + 1] = -1; var[4 * v + 2] = -1; }
+            else var[4 * v + 1] = nidx[v];
+        }
+        if (h_nnew[i] != c->h_n[b] - gone) return fail(INGVIO_E_HIP, "the device's dimension after the tail disagrees with the host mirror");
+        c->h_n[b] = h_nnew[i];
+        c->h_cur[b] ^= 1;
+    }
+    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
 }
 
 int ingvio_frame_stage_tracks_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,

@@ -27,9 +27,16 @@ the same build,
   round-trip form  the plain frame, then ingvio_nominal_get, ingvio_landmark_stage with the table's values, ingvio_landmark_run,
                    ingvio_landmark_fetch, ingvio_nominal_box_plus
 measured and reported as the GNSS forms are; writes $RESULTS/closed_loop_bench_lm.json.
+--tail: the loop with a real window policy (ingvio_amd/closed_loop_tail.py): the frame is staged without a marginalisation, every filter
+carries --landmarks L in-state landmarks (default 20) that are updated in every frame, and behind the frame the OLDEST clone leaves and
+ALL landmarks change their anchor to the newest clone, two forms on the same build,
+  device form      ... run(i); fetch_begin(i); nominal_tail(i); stage_async(i+1); landmark_stage_nominal(i+1, in_frame); run(i+1) ...
+  round-trip form  the tail through the host: ingvio_nominal_get, one ingvio_replace_var_linear per landmark and one ingvio_marginalize
+                   per variable and filter, ingvio_nominal_set
+measured and reported as the GNSS forms are; writes $RESULTS/closed_loop_bench_tail.json.
 Writes $RESULTS/closed_loop_bench.json (RESULTS defaults to results/) and prints one JSON line.
 usage: python tools/closed_loop_bench.py [--batch 512] [--features 150] [--window 11] [--k 10] [--frames 30] [--warmup 5] [--device-only]
-                                         [--gnss | --register-only | --landmarks L]"""
+                                         [--gnss | --register-only | --landmarks L | --tail [--landmarks L]]"""
 import argparse
 import copy
 import json
@@ -189,6 +196,26 @@ def main_landmarks(a):
     finish(out, "closed_loop_bench_lm.json")
 
 
+def main_tail(a):
+    from ingvio_amd import closed_loop_lm as clm
+    from ingvio_amd import closed_loop_tail as clt
+    B, F, NF, W, L = a.batch, a.features, a.frames, a.warmup, a.landmarks or 20
+    t0 = time.perf_counter()
+    cases = clt.make_tail_loop(B, NF, L=L, F=F, mode="sw", behind=False, erase=False, reanchor_all=True, ks=(a.k,), windows=(a.window,))
+    opts = clm.lm_opts()
+    out = dict(batch=B, features=F, window=a.window, k=a.k, frames_timed=NF - W, landmarks=L, tail=True, setup_s=round(time.perf_counter() - t0, 1))
+    fresh = lambda: fresh_ctx(a, cases, v_max=max(64, 32 + L))
+    ctx = fresh()
+    form = clt.TailForm(opts, cases, fetch_lm=False)
+    free_run(out, ctx, cases, form, NF, W)
+    out["last_frame_anchor_changes_mean"] = float(np.mean([sum(v) for v in form.out[1]]))
+    dev_nom = ctx.nominal_get()
+    ctx.close()
+    if not a.device_only:
+        synced_forms(out, fresh, cases, clt.TailForm(opts, cases, fetch_lm=False), clt.TailRoundTrip(opts, cases), NF, W, dev_nom)
+    finish(out, "closed_loop_bench_tail.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=512)
@@ -201,7 +228,10 @@ def main():
     ap.add_argument("--gnss", action="store_true")
     ap.add_argument("--register-only", action="store_true", help="the loop without epochs, the GNSS scalars registered (clock recursion on)")
     ap.add_argument("--landmarks", type=int, default=0, help="L in-state landmarks per filter, updated in every frame")
+    ap.add_argument("--tail", action="store_true", help="the oldest clone leaves and every landmark changes its anchor behind every frame")
     a = ap.parse_args()
+    if a.tail:
+        return main_tail(a)
     if a.landmarks > 0:
         return main_landmarks(a)
     if a.gnss or a.register_only:
