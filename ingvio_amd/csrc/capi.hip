@@ -321,6 +321,16 @@ int last_launch(ingvio_ctx* c)
     return 0;
 }
 
+// The input set a frame step has read may be refilled (ingvio_frame_stage_async) once the kernels enqueued on the compute stream so
+// far are done with it.
+int release_input_set(ingvio_ctx* c)
+{
+    if (!c->alt_ready) return 0;
+    HIPCHK(c, hipEventRecord(c->ev_free[c->set_id], c->st));
+    c->free_valid[c->set_id] = true;
+    return 0;
+}
+
 // Split frame step: the compute stream waits for the slices' streams (a device-side wait, the host does not block).  Called by every
 // entry point other than ingvio_frame_run itself before it touches the context.
 int join_parts(ingvio_ctx* c)
@@ -328,11 +338,7 @@ int join_parts(ingvio_ctx* c)
     if (!c->split_pending) return 0;
     for (int p = 0; p < c->parts_alloc; ++p) HIPCHK(c, hipStreamWaitEvent(c->st, c->part[p].ev_done, 0));
     c->split_pending = false;
-    if (c->alt_ready) {                            // the input set the slices read may be refilled once they are done with it
-        HIPCHK(c, hipEventRecord(c->ev_free[c->set_id], c->st));
-        c->free_valid[c->set_id] = true;
-    }
-    return 0;
+    return release_input_set(c);                   // the slices' input set, once they are done with it
 }
 #define ENTER(c) do { if ((c) && (c)->split_pending && join_parts(c)) return INGVIO_E_HIP; } while (0)
 
@@ -673,7 +679,6 @@ size_t frames_bytes(const ingvio_ctx* c, int nb)
            pad64(8 * n * fm * cm * 4) + pad64(8 * n * fm) + 1024;
 }
 
-// packs frames [b0, b0+nb) into the slab of `up` and enqueues the copies into the SoA device staging; max F in *fmax_used
 // Everything that can be wrong with the caller's frames, checked BEFORE any context state is touched.  `grow` = rows/columns
 // the state gains between now and the update (6: the clone ingvio_frame_run appends; 0: ingvio_msckf_update).
 int validate_frames(ingvio_ctx* c, int b0, int nb, const ingvio_msckf_frame* fr, int grow, int* fmax_used)
@@ -701,7 +706,8 @@ int validate_frames(ingvio_ctx* c, int b0, int nb, const ingvio_msckf_frame* fr,
     return 0;
 }
 
-// packs already VALIDATED frames: cannot fail
+// packs already VALIDATED frames [b0, b0+nb) into the slab of `up` and enqueues the copies into the SoA device staging; max F in
+// *fmax_used.  Cannot fail.
 int pack_frames(ingvio_ctx* c, Uploader& up, int b0, int nb, const ingvio_msckf_frame* fr, int* fmax_used)
 {
     const int cm = c->d.c_max, fm = c->d.f_max;
@@ -769,9 +775,9 @@ int stage_frames(ingvio_ctx* c, int b0, int nb, const ingvio_msckf_frame* fr, in
     return up.end();
 }
 
-int make_opts(ingvio_ctx* c, const ingvio_msckf_opts* o, MsckfOpts* op)
+// the caller's options as the kernels take them; the chi-square table itself is uploaded by whoever calls this
+void fill_opts(const ingvio_ctx* c, const ingvio_msckf_opts* o, MsckfOpts* op)
 {
-    if (!o || !o->chi2_table || o->chi2_len < 2 || o->chi2_len > CHI2_CAP) return INGVIO_E_ARG;
     memcpy(op->R_lr, o->R_cl2cr, 72);
     memcpy(op->t_lr, o->t_cl2cr, 24);
     op->var = o->noise * o->noise;
@@ -779,6 +785,12 @@ int make_opts(ingvio_ctx* c, const ingvio_msckf_opts* o, MsckfOpts* op)
     op->selected_variant = o->selected_variant;
     op->chi2 = c->d_chi2;
     op->chi2_len = o->chi2_len;
+}
+
+int make_opts(ingvio_ctx* c, const ingvio_msckf_opts* o, MsckfOpts* op)
+{
+    if (!o || !o->chi2_table || o->chi2_len < 2 || o->chi2_len > CHI2_CAP) return INGVIO_E_ARG;
+    fill_opts(c, o, op);
     if (wait_inputs(c)) return INGVIO_E_HIP;
     auto& u = c->upc;
     if (u.chi2_ok && (int)u.chi2.size() >= o->chi2_len && !memcmp(u.chi2.data(), o->chi2_table, 8 * (size_t)o->chi2_len)) return 0;      // already there
@@ -952,6 +964,135 @@ int fill_noise_scalar(ingvio_ctx* c, int b0, int nb, double var)
     u.noise_ok = true; u.b0 = b0; u.nb = nb; u.var = var;
     return 0;
 }
+
+// Per-filter IMU parameters of the staged frame.  Filter b propagates k_b steps from its own slot of d_Phi / d_G / d_dt (b * KMAX steps
+// in: partial stages never touch another filter's steps) with its own sigma / sigma_cb / sigma_rw, held in d_prm [b][8] and mirrored on
+// the host (st_prm).  A stage sets them for the filters it stages; the first stage after creation or after a failed stage sets them for
+// every filter (k and noise of its first step for the filters it does not stage).  Packs the blocks to upload into `blk` and returns
+// their first filter; *count = their number.
+template <class Step>
+int stage_imu_params(ingvio_ctx* c, int b0, int nb, const Step* steps, const double sigma[4], double scb, double srw, double* blk, int* count)
+{
+    const bool all = !c->staged;
+    const int lo = all ? 0 : b0, hi = all ? c->d.batch : b0 + nb;
+    for (int b = lo; b < hi; ++b) {
+        double* h = &c->st_prm[(size_t)b * 8];
+        h[0] = sigma[0]; h[1] = sigma[1]; h[2] = sigma[2]; h[3] = sigma[3]; h[4] = scb; h[5] = srw;
+        h[6] = (double)steps[b >= b0 && b < b0 + nb ? b - b0 : 0].k; h[7] = 0.0;
+        memcpy(blk + (size_t)(b - lo) * 8, h, 64);
+    }
+    *count = hi - lo;
+    return lo;
+}
+
+// ---- staging a frame: the one sequence under ingvio_frame_stage(_async), ingvio_frame_stage_tracks and .._tracks_nominal ------------
+//     refuse -> the form's validation -> begin -> the form's packing into the pinned slab -> commit -> the form's copies and launches,
+//     upload_imu / upload_gate among them -> finish
+// Nothing of the context changes before commit(): begin() only takes resources (the second input set, a pinned slab) and the slab is
+// scratch, so the packing may still refuse.  From commit() on only HIP runtime errors can occur; they leave through fail(), which
+// invalidates the staged frame.  Step: ingvio_frame_step or ingvio_frame_step_raw (k, gnss_idx, marg_idx).
+struct FrameStage {
+    ingvio_ctx* c; int b0, nb; const ingvio_msckf_opts* opts; const double* sigma; int enable_gnss; double scb, srw; bool async;
+    Uploader upl{ c };
+    // the refusals every form shares; inputs: the form's own pointers are there, tracks: the form needs the track store
+    int refuse(bool inputs, bool tracks) const
+    {
+        if (phase_busy(c)) return INGVIO_E_ARG;
+        if (c && c->nom.pending) { c->err = "a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+        if (check_range(c, b0, nb) || !inputs || !opts || !sigma) return INGVIO_E_ARG;
+        if (tracks && !c->trk.t_max) { c->err = "ingvio_frame_stage_tracks without ingvio_tracks_create"; return INGVIO_E_ARG; }
+        if (async && (b0 != 0 || nb != c->d.batch)) return INGVIO_E_ARG;      // a whole input set is replaced
+        if (!opts->chi2_table || opts->chi2_len < 2 || opts->chi2_len > CHI2_CAP) return INGVIO_E_ARG;
+        return 0;
+    }
+    // resources that may fail; bytes: the form's own share of the pinned slab
+    int begin(size_t bytes)
+    {
+        if (async) if (int rc = prepare_async_set(c)) return rc;
+        return upl.begin(bytes + pad64(8 * CHI2_CAP) + pad64(8 * (size_t)nb) + pad64(64 * (size_t)c->d.batch) + 1024);
+    }
+    int fail(int code)
+    {
+        hipStreamSynchronize(c->st);
+        if (c->st_copy) hipStreamSynchronize(c->st_copy);
+        c->staged = false; c->copy_pending = false;
+        return code;
+    }
+    template <class Step>
+    int commit(const Step* steps)
+    {
+        // new clock-state indices: the next restore is a full one (the strips the last step wrote are named by the OLD indices); a stage
+        // with the same indices - every frame of a running filter between two GNSS initialisations - keeps the partial restore valid
+        bool same = c->staged && enable_gnss == c->st_enable_gnss;
+        for (int i = 0; i < nb; ++i)
+            for (int g = 0; g < 5; ++g) {
+                int& old = c->st_gnss[(size_t)(b0 + i) * 5 + g];
+                if (old != steps[i].gnss_idx[g]) { same = false; old = steps[i].gnss_idx[g]; }
+            }
+        if (!same) c->strip_ok = false;
+        // an earlier asynchronous stage into this set must land before it is overwritten in-stream
+        if (!async) return wait_inputs(c) ? fail(INGVIO_E_HIP) : 0;
+        // the set about to be overwritten was last read two frames ago; its "free" event is on the compute stream
+        if (c->free_valid[c->set_id ^ 1] && hipStreamWaitEvent(c->st_copy, c->ev_free[c->set_id ^ 1], 0) != hipSuccess) return fail(INGVIO_E_HIP);
+        swap_input_sets(c);
+        upl.stream = c->st_copy;
+        return 0;
+    }
+    // the filters' IMU parameter blocks (stage_imu_params)
+    template <class Step>
+    void upload_imu(const Step* steps)
+    {
+        double* prm = upl.take<double>(8 * (size_t)c->d.batch);
+        int np = 0;
+        const int p0 = stage_imu_params(c, b0, nb, steps, sigma, scb, srw, prm, &np);
+        upl.copy(c->d_prm + (size_t)p0 * 8, prm, (size_t)np * 8);
+    }
+    // what the gate takes from the options: the chi-square table, the filters' measurement noise, st_op
+    void upload_gate()
+    {
+        double* chi2 = upl.take<double>(CHI2_CAP); double* nz = upl.take<double>(nb);
+        memcpy(chi2, opts->chi2_table, 8 * (size_t)opts->chi2_len);
+        fill_opts(c, opts, &c->st_op);
+        for (int i = 0; i < nb; ++i) nz[i] = c->st_op.var;
+        upl.copy(c->d_chi2, chi2, (size_t)opts->chi2_len);
+        upl.copy(c->d_noise + b0, nz, (size_t)nb);
+        c->upc.chi2_ok = false; c->upc.noise_ok = false;
+    }
+    // Frame: ingvio_msckf_frame or ingvio_track_frame (n_clones, clone_idx); fmx: the call's largest feature count; plan: as
+    // frame_stage_tracks_impl takes it
+    template <class Step, class Frame>
+    int finish(const Step* steps, const Frame* frames, int fmx, const int* plan = nullptr)
+    {
+        if (int rc = upl.end()) return fail(rc);
+        if (async) {
+            if (hipEventRecord(c->ev_copy, c->st_copy) != hipSuccess) return fail(INGVIO_E_HIP);
+            c->copy_pending = true;
+        }
+        for (int i = 0; i < nb; ++i) {
+            c->st_marg[b0 + i] = steps[i].marg_idx;
+            int hi = -1;
+            if (plan) hi = plan[4 * i + 1];
+            else for (int q = 0; q < frames[i].n_clones; ++q) if (frames[i].clone_idx[q] > hi) hi = frames[i].clone_idx[q];
+            c->st_cidx_hi[b0 + i] = hi;
+            c->h_nclones[b0 + i] = frames[i].n_clones;
+        }
+        if (plan) {                                   // the mirror follows what k_imu_steps<true> writes
+            for (int i = 0; i < nb; ++i) {
+                int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
+                const int slot = plan[4 * i], ncl = plan[4 * i + 2];
+                int* vc = I + NOM_IH + 4 * slot;
+                vc[0] = NOM_KIND_SE3; vc[1] = plan[4 * i + 1]; vc[2] = -1; vc[3] = 0;
+                I[NOM_CLONES + ncl - 1] = slot; I[NOM_N_CLONES] = ncl; I[NOM_N_VAR] = plan[4 * i + 3];
+            }
+            c->nom.pending = true;
+        }
+        c->nom.frame = plan != nullptr;                // a frame from the table is followed by the post-frame step
+        c->st_stereo = opts->stereo; c->st_enable_gnss = enable_gnss;
+        if (!c->staged || fmx > c->st_fmax_used) c->st_fmax_used = fmx;
+        c->staged = true;
+        return INGVIO_OK;
+    }
+};
 
 }  // namespace
 
@@ -3105,25 +3246,6 @@ int ingvio_qr_compress(ingvio_ctx* c, const double* H, int ldh, int m, int n, co
     }
 }
 
-// Per-filter IMU parameters of the staged frame.  Filter b propagates k_b steps from its own slot of d_Phi / d_G / d_dt (b * KMAX steps
-// in: partial stages never touch another filter's steps) with its own sigma / sigma_cb / sigma_rw, held in d_prm [b][8] and mirrored on
-// the host (st_prm).  A stage sets them for the filters it stages; the first stage after creation or after a failed stage sets them for
-// every filter (k and noise of its first step for the filters it does not stage).  Packs the blocks to upload into `blk` and returns
-// their first filter; *count = their number.
-static int stage_imu_params(ingvio_ctx* c, int b0, int nb, const int* ks, const double sigma[4], double scb, double srw, double* blk, int* count)
-{
-    const bool all = !c->staged;
-    const int lo = all ? 0 : b0, hi = all ? c->d.batch : b0 + nb;
-    for (int b = lo; b < hi; ++b) {
-        double* h = &c->st_prm[(size_t)b * 8];
-        h[0] = sigma[0]; h[1] = sigma[1]; h[2] = sigma[2]; h[3] = sigma[3]; h[4] = scb; h[5] = srw;
-        h[6] = (double)(b >= b0 && b < b0 + nb ? ks[b - b0] : ks[0]); h[7] = 0.0;
-        memcpy(blk + (size_t)(b - lo) * 8, h, 64);
-    }
-    *count = hi - lo;
-    return lo;
-}
-
 // launch_propagate's IMU arguments for filters [b0, b0 + nb): k and the noise as scalar kernel arguments when every filter of the launch
 // shares them (the headline case: k is then no memory round trip in front of the kernel), else prm = the filters' blocks (k_propagate<.., true>)
 struct ImuLaunch { int k; double sigma[4], scb, srw; const double* prm; };
@@ -3139,12 +3261,8 @@ static ImuLaunch imu_launch(const ingvio_ctx* c, int b0, int nb)
 static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step* steps, const ingvio_msckf_frame* frames,
                             const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, bool async)
 {
-    if (phase_busy(c)) return INGVIO_E_ARG;
-    if (c && c->nom.pending) { c->err = "a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
-    // ---- validation: nothing of the context is modified until every input has been accepted ---------------------------
-    if (check_range(c, b0, nb) || !steps || !frames || !opts || !sigma) return INGVIO_E_ARG;
-    if (async && (b0 != 0 || nb != c->d.batch)) return INGVIO_E_ARG;      // a whole input set is replaced
-    if (!opts->chi2_table || opts->chi2_len < 2 || opts->chi2_len > CHI2_CAP) return INGVIO_E_ARG;
+    FrameStage stage{ c, b0, nb, opts, sigma, enable_gnss, scb, srw, async };
+    if (int rc = stage.refuse(steps && frames, false)) return rc;
     int k = 0;                                                              // the call's largest step count: the slab's stride
     for (int i = 0; i < nb; ++i) {
         if (steps[i].k < 1 || steps[i].k > KMAX || !steps[i].Phi || !steps[i].G || !steps[i].dt) return INGVIO_E_ARG;
@@ -3153,56 +3271,16 @@ static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_st
     int fmx = 0;
     // clone indices are checked against the buffer only (grow < 0): the live size at run time depends on whether the run
     // restores the snapshot; ingvio_frame_run checks them against the live state before its first launch
-    int rc = validate_frames(c, b0, nb, frames, -1, &fmx);
-    if (rc) return rc;
-    // ---- resources that may fail, still without side effects on the staged state --------------------------------------
-    Uploader upl{ c };
+    if (int rc = validate_frames(c, b0, nb, frames, -1, &fmx)) return rc;
     const size_t n = nb;
-    if (async) {
-        rc = prepare_async_set(c);
-        if (rc) return rc;
-    }
-    rc = upl.begin(pad64(8 * n * k * 225) + pad64(8 * n * k * 180) + pad64(8 * n * k) + pad64(8 * n * 9) + pad64(4 * n * 5) + pad64(4 * n) +
-                   pad64(8 * CHI2_CAP) + pad64(8 * n) + pad64(64 * (size_t)c->d.batch) + frames_bytes(c, nb) + 1024);
-    if (rc) return rc;
-    // ---- from here on only HIP runtime errors can occur; they invalidate the staged frame -----------------------------
-    // new clock-state indices: the next restore is a full one (the strips the last step wrote are named by the OLD indices); a stage
-    // with the same indices - every frame of a running filter between two GNSS initialisations - keeps the partial restore valid
-    {
-        bool same = c->staged && enable_gnss == c->st_enable_gnss;
-        for (int i = 0; i < nb; ++i)
-            for (int g = 0; g < 5; ++g) {
-                int& old = c->st_gnss[(size_t)(b0 + i) * 5 + g];
-                if (old != steps[i].gnss_idx[g]) { same = false; old = steps[i].gnss_idx[g]; }
-            }
-        if (!same) c->strip_ok = false;
-    }
-    auto fail = [&](int code) {
-        hipStreamSynchronize(c->st);
-        if (c->st_copy) hipStreamSynchronize(c->st_copy);
-        c->staged = false; c->copy_pending = false;
-        return code;
-    };
-    if (async) {
-        // the set about to be overwritten was last read two frames ago; its "free" event is on the compute stream
-        if (c->free_valid[c->set_id ^ 1] && hipStreamWaitEvent(c->st_copy, c->ev_free[c->set_id ^ 1], 0) != hipSuccess) return fail(INGVIO_E_HIP);
-        swap_input_sets(c);
-        upl.stream = c->st_copy;
-    } else {
-        if (wait_inputs(c)) return fail(INGVIO_E_HIP);   // an earlier asynchronous stage into this set must land before it is overwritten in-stream
-    }
-    for (int i = 0; i < nb; ++i) {
-        c->st_marg[b0 + i] = steps[i].marg_idx;
-        int hi = -1;
-        for (int q = 0; q < frames[i].n_clones; ++q) if (frames[i].clone_idx[q] > hi) hi = frames[i].clone_idx[q];
-        c->st_cidx_hi[b0 + i] = hi;
-    }
+    if (int rc = stage.begin(pad64(8 * n * k * 225) + pad64(8 * n * k * 180) + pad64(8 * n * k) + pad64(8 * n * 9) + pad64(4 * n * 5) + pad64(4 * n) +
+                             frames_bytes(c, nb))) return rc;
+    if (int rc = stage.commit(steps)) return rc;
     // everything goes through ONE pinned slab: packed by a few host threads, copied asynchronously, no stream sync.  Filter i's steps
     // sit k (the call's largest count) apart in the slab and KMAX apart on the device: one strided copy each for Phi, G and dt
+    Uploader& upl = stage.upl;
     double* Phi = upl.take<double>(n * k * 225); double* G = upl.take<double>(n * k * 180); double* dt = upl.take<double>(n * k);
     double* R = upl.take<double>(n * 9); int* gi = upl.take<int>(n * 5); int* mi = upl.take<int>(n);
-    double* chi2 = upl.take<double>(CHI2_CAP); double* nz = upl.take<double>(n); double* prm = upl.take<double>(8 * (size_t)c->d.batch);
-    const double var = opts->noise * opts->noise;
     parallel_for(nb, [=](int i) {
         const size_t ki = steps[i].k;
         memcpy(Phi + (size_t)i * k * 225, steps[i].Phi, 8 * ki * 225);
@@ -3211,42 +3289,17 @@ static int frame_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_st
         memcpy(R + (size_t)i * 9, steps[i].R_i2w, 72);
         for (int g = 0; g < 5; ++g) gi[(size_t)i * 5 + g] = steps[i].gnss_idx[g];
         mi[i] = steps[i].marg_idx;
-        nz[i] = var;
     });
-    memcpy(chi2, opts->chi2_table, 8 * (size_t)opts->chi2_len);
     upl.copy_rows(c->d_Phi + (size_t)b0 * KMAX * 225, (size_t)KMAX * 225, Phi, (size_t)k * 225, (size_t)k * 225, n);
     upl.copy_rows(c->d_G + (size_t)b0 * KMAX * 180, (size_t)KMAX * 180, G, (size_t)k * 180, (size_t)k * 180, n);
     upl.copy_rows(c->d_dt + (size_t)b0 * KMAX, (size_t)KMAX, dt, (size_t)k, (size_t)k, n);
-    {
-        std::vector<int> ks((size_t)nb);
-        for (int i = 0; i < nb; ++i) ks[i] = steps[i].k;
-        int np = 0;
-        const int p0 = stage_imu_params(c, b0, nb, ks.data(), sigma, scb, srw, prm, &np);
-        upl.copy(c->d_prm + (size_t)p0 * 8, prm, (size_t)np * 8);
-    }
+    stage.upload_imu(steps);
     upl.copy(c->d_R + (size_t)b0 * 9, R, n * 9);
     upl.copy(c->d_gnss + (size_t)b0 * 5, gi, n * 5);
     upl.copy(c->d_idx + b0, mi, n);
-    upl.copy(c->d_chi2, chi2, (size_t)opts->chi2_len);
-    upl.copy(c->d_noise + b0, nz, n);
-    c->upc.chi2_ok = false; c->upc.noise_ok = false;
-    MsckfOpts& op = c->st_op;
-    memcpy(op.R_lr, opts->R_cl2cr, 72);
-    memcpy(op.t_lr, opts->t_cl2cr, 24);
-    op.var = var; op.max_accept = opts->max_accept; op.selected_variant = opts->selected_variant;
-    op.chi2 = c->d_chi2; op.chi2_len = opts->chi2_len;
+    stage.upload_gate();
     pack_frames(c, upl, b0, nb, frames, &fmx);
-    rc = upl.end();
-    if (rc) return fail(rc);
-    if (async) {
-        if (hipEventRecord(c->ev_copy, c->st_copy) != hipSuccess) return fail(INGVIO_E_HIP);
-        c->copy_pending = true;
-    }
-    c->st_stereo = opts->stereo; c->st_enable_gnss = enable_gnss;
-    if (!c->staged || fmx > c->st_fmax_used) c->st_fmax_used = fmx;
-    c->staged = true;
-    c->nom.frame = false;                          // a flattened frame: no post-frame step
-    return INGVIO_OK;
+    return stage.finish(steps, frames, fmx);
 }
 
 // ---- device-resident track store ---------------------------------------------------------------------------------------------
@@ -3282,13 +3335,9 @@ static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_f
                                    const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, int async,
                                    const int* plan)
 {
-    if (phase_busy(c)) return INGVIO_E_ARG;
-    if (c && c->nom.pending) { c->err = "a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
-    if (check_range(c, b0, nb) || !steps || !frames || !opts || !sigma) return INGVIO_E_ARG;
-    if (!c->trk.t_max) { c->err = "ingvio_frame_stage_tracks without ingvio_tracks_create"; return INGVIO_E_ARG; }
-    if (async && (b0 != 0 || nb != c->d.batch)) return INGVIO_E_ARG;
+    FrameStage stage{ c, b0, nb, opts, sigma, enable_gnss, scb, srw, async != 0 };
+    if (int rc = stage.refuse(steps && frames, true)) return rc;
     const int T = c->trk.t_max, cm = c->d.c_max, fm = c->d.f_max;
-    if (!opts->chi2_table || opts->chi2_len < 2 || opts->chi2_len > CHI2_CAP) return INGVIO_E_ARG;
     // ---- layout (counts only), then validation + packing per filter on a few host threads; nothing of the context is touched before
     //      every filter's delta has been found consistent (the pinned slab is scratch) ----
     std::vector<int> hdr((size_t)nb * TRK_HDR, 0);
@@ -3329,11 +3378,8 @@ static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_f
     }
     const size_t off_i = pad64(4 * (size_t)nb * TRK_HDR), off_m = off_i + pad64(4 * ni), off_d = off_m + pad64(8 * nm), total = off_d + pad64(8 * nd);
     if (total > c->trk.stage_cap) return INGVIO_E_CAPACITY;
-    Uploader upl{ c };
-    int rc = 0;
-    if (async) { rc = prepare_async_set(c); if (rc) return rc; }
-    rc = upl.begin(total + pad64(8 * CHI2_CAP) + pad64(8 * (size_t)nb) + pad64(64 * (size_t)c->d.batch) + 1024);
-    if (rc) return rc;
+    if (int rc = stage.begin(total)) return rc;
+    Uploader& upl = stage.upl;
     char* slab = upl.take<char>(total);
     int* hp = reinterpret_cast<int*>(slab);
     int* ipool = reinterpret_cast<int*>(slab + off_i);
@@ -3379,90 +3425,25 @@ static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_f
         }
     });
     for (int i = 0; i < nb; ++i) if (bad[i]) { c->err = "ingvio_frame_stage_tracks: a slot, track, clone index, anchor or dof is out of range"; return INGVIO_E_ARG; }
-    // ---- from here on only HIP runtime errors can occur ----
-    {
-        bool same = c->staged && enable_gnss == c->st_enable_gnss;      // as frame_stage_impl: the partial restore survives unchanged clock-state indices
-        for (int i = 0; i < nb; ++i)
-            for (int g = 0; g < 5; ++g) {
-                int& old = c->st_gnss[(size_t)(b0 + i) * 5 + g];
-                if (old != steps[i].gnss_idx[g]) { same = false; old = steps[i].gnss_idx[g]; }
-            }
-        if (!same) c->strip_ok = false;
-    }
-    auto fail = [&](int code) {
-        hipStreamSynchronize(c->st);
-        if (c->st_copy) hipStreamSynchronize(c->st_copy);
-        c->staged = false; c->copy_pending = false;
-        return code;
-    };
-    hipStream_t S = c->st;
-    char* dstage = c->trk.stage[0];
-    if (async) {
-        if (c->free_valid[c->set_id ^ 1] && hipStreamWaitEvent(c->st_copy, c->ev_free[c->set_id ^ 1], 0) != hipSuccess) return fail(INGVIO_E_HIP);
-        swap_input_sets(c);
-        upl.stream = c->st_copy; S = c->st_copy; dstage = c->trk.stage[1];
-    } else if (wait_inputs(c)) return fail(INGVIO_E_HIP);
-    double* chi2 = upl.take<double>(CHI2_CAP); double* nz = upl.take<double>(nb); double* prm = upl.take<double>(8 * (size_t)c->d.batch);
-    const double var = opts->noise * opts->noise;
-    memcpy(chi2, opts->chi2_table, 8 * (size_t)opts->chi2_len);
-    for (int i = 0; i < nb; ++i) nz[i] = var;
+    if (int rc = stage.commit(steps)) return rc;
+    const hipStream_t S = async ? c->st_copy : c->st;
+    char* dstage = c->trk.stage[async ? 1 : 0];
     upl.copy(dstage, slab, total);
-    upl.copy(c->d_chi2, chi2, (size_t)opts->chi2_len);
-    upl.copy(c->d_noise + b0, nz, (size_t)nb);
-    {
-        std::vector<int> ks((size_t)nb);
-        for (int i = 0; i < nb; ++i) ks[i] = steps[i].k;
-        int np = 0;
-        const int p0 = stage_imu_params(c, b0, nb, ks.data(), sigma, scb, srw, prm, &np);
-        upl.copy(c->d_prm + (size_t)p0 * 8, prm, (size_t)np * 8);
-    }
-    c->upc.chi2_ok = false; c->upc.noise_ok = false;
+    stage.upload_gate();
+    stage.upload_imu(steps);
     TrackStage ts{ reinterpret_cast<const int*>(dstage), reinterpret_cast<const int*>(dstage + off_i),
                    reinterpret_cast<const double*>(dstage + off_d), reinterpret_cast<const unsigned long long*>(dstage + off_m) };
     TrackStore store{ c->trk.uv, c->trk.mask, c->trk.pf, T, cm };
     FrameOut fo{ c->d_clone_idx, c->d_clone_R, c->d_clone_p, c->d_nclones, c->d_nfeat, c->d_pf, c->d_anchor, c->d_mask, c->d_uv, c->d_dof, cm, fm };
     const NomTable nt = nom_table(c);
     // from the device table on the copy stream: the uploads above overlap the running frame, the kernels wait for its post-frame step
-    if (plan && async && c->nom.ev_valid && hipStreamWaitEvent(S, c->nom.ev, 0) != hipSuccess) return fail(INGVIO_E_HIP);
+    if (plan && async && c->nom.ev_valid && hipStreamWaitEvent(S, c->nom.ev, 0) != hipSuccess) return stage.fail(INGVIO_E_HIP);
     launch_imu_steps(ts, b0, nb, KMAX, c->d_Phi, c->d_G, c->d_dt, c->d_R, S, plan ? &nt : nullptr);
-    if (hipGetLastError() != hipSuccess) return fail(INGVIO_E_HIP);       // before the store kernels change the track store
+    if (hipGetLastError() != hipSuccess) return stage.fail(INGVIO_E_HIP);       // before the store kernels change the track store
     launch_tracks_apply(ts, store, b0, nb, S);
     launch_tracks_gather(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S, plan ? &nt : nullptr);
-    if (hipGetLastError() != hipSuccess) return fail(INGVIO_E_HIP);
-    rc = upl.end();
-    if (rc) return fail(rc);
-    if (async) {
-        if (hipEventRecord(c->ev_copy, c->st_copy) != hipSuccess) return fail(INGVIO_E_HIP);
-        c->copy_pending = true;
-    }
-    for (int i = 0; i < nb; ++i) {
-        c->st_marg[b0 + i] = steps[i].marg_idx;
-        int hi = -1;
-        if (plan) hi = plan[4 * i + 1];
-        else for (int q = 0; q < frames[i].n_clones; ++q) if (frames[i].clone_idx[q] > hi) hi = frames[i].clone_idx[q];
-        c->st_cidx_hi[b0 + i] = hi;
-        c->h_nclones[b0 + i] = frames[i].n_clones;
-    }
-    if (plan) {                                   // the mirror follows what k_imu_steps<true> writes
-        for (int i = 0; i < nb; ++i) {
-            int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
-            const int slot = plan[4 * i], ncl = plan[4 * i + 2];
-            int* vc = I + NOM_IH + 4 * slot;
-            vc[0] = NOM_KIND_SE3; vc[1] = plan[4 * i + 1]; vc[2] = -1; vc[3] = 0;
-            I[NOM_CLONES + ncl - 1] = slot; I[NOM_N_CLONES] = ncl; I[NOM_N_VAR] = plan[4 * i + 3];
-        }
-        c->nom.pending = true;
-    }
-    c->nom.frame = plan != nullptr;
-    MsckfOpts& op = c->st_op;
-    memcpy(op.R_lr, opts->R_cl2cr, 72);
-    memcpy(op.t_lr, opts->t_cl2cr, 24);
-    op.var = var; op.max_accept = opts->max_accept; op.selected_variant = opts->selected_variant;
-    op.chi2 = c->d_chi2; op.chi2_len = opts->chi2_len;
-    c->st_stereo = opts->stereo; c->st_enable_gnss = enable_gnss;
-    if (!c->staged || fmx > c->st_fmax_used) c->st_fmax_used = fmx;
-    c->staged = true;
-    return INGVIO_OK;
+    if (hipGetLastError() != hipSuccess) return stage.fail(INGVIO_E_HIP);
+    return stage.finish(steps, frames, fmx, plan);
 }
 
 int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_raw* steps, const ingvio_track_frame* frames,
@@ -3895,6 +3876,59 @@ int ingvio_frame_set_imu_noise(ingvio_ctx* c, int b0, int nb, const double* nois
     return INGVIO_OK;
 }
 
+// ---- running the staged frame: the pieces ingvio_frame_run / ingvio_frame_run_phase are made of ---------------------------------
+static bool lm_in_frame(const ingvio_ctx* c) { return c->lm.staged && c->lm.in_frame; }
+static bool gnss_in_frame(const ingvio_ctx* c) { return c->gn.staged && c->gn.in_frame && c->gn.m_cap > 0; }
+// An in-frame GNSS stage rides on the MSCKF write-back when everything fits one sweep and the update's columns keep their indices
+// through the frame's marginalisation (var_order entirely below the clone that goes); else it is a pass of its own
+static bool gnss_folds(const ingvio_ctx* c)
+{
+    if (!gnss_in_frame(c) || c->d.c_max > 16 || c->gn.m_cap > 16 || c->gn.nc_max > 16) return false;
+    for (int b = 0; b < c->d.batch; ++b) if (c->st_marg[b] < 0 || c->gn.hi[b] > c->st_marg[b]) return false;
+    return true;
+}
+
+// restore_prior right after a fused frame step that itself began with a restore: half 0 still equals the snapshot outside the
+// propagation's strips.  Asked before the step's first launch (view() counts the uses of the covariance).
+static bool strips_valid(const ingvio_ctx* c, int restore_prior) { return restore_prior && c->strip_ok && c->mut_seq == c->strip_seq; }
+
+// Restore (or not), then one launch: status reset + K1 (k composed IMU steps) + K2 (clone) when a workgroup owns a whole filter.  With
+// valid strips the propagation READS the snapshot and writes half 0 where it can: no restore pass at all (round 6; before:
+// k_restore_strips, 23 us and 94 MB per 512 filters)
+static void launch_restore_propagate(ingvio_ctx* c, int restore_prior, bool strips, int b0, int nb, hipStream_t st)
+{
+    const bool from_snap = strips && propagate_can_restore(c->d.n_max) && !no_snap_propagate();
+    if (restore_prior && !from_snap) {
+        ProfScope p(c, PF_RESTORE);
+        if (strips) launch_restore_strips(view(c), b0, nb, c->d.n_max, c->Psnap, c->d_n_snap, c->st_enable_gnss ? c->d_gnss : nullptr, st);
+        else launch_restore(view(c), b0, nb, c->d.n_max, c->Psnap, c->d_n_snap, st);
+    }
+    ProfScope p(c, PF_PROPAGATE);
+    const ImuLaunch im = imu_launch(c, b0, nb);
+    launch_propagate(view(c), b0, nb, c->d.n_max, c->d_Phi + (size_t)b0 * KMAX * 225, c->d_G + (size_t)b0 * KMAX * 180, c->d_dt + (size_t)b0 * KMAX,
+                     im.k, KMAX, im.prm, c->st_enable_gnss ? c->d_gnss + (size_t)b0 * 5 : nullptr, im.sigma, c->st_enable_gnss, im.scb, im.srw, st,
+                     c->d_R + (size_t)b0 * 9, c->d_status, from_snap ? c->Psnap : nullptr, c->d_n_snap);
+}
+
+// the host mirrors of launch_restore_propagate over the whole batch and of the frame's marginalisation (true: of every filter)
+static void mirror_restore_clone(ingvio_ctx* c, int restore_prior)
+{
+    if (restore_prior) { c->h_n = c->h_n_snap; std::fill(c->h_cur.begin(), c->h_cur.end(), 0); }
+    for (int b = 0; b < c->d.batch; ++b) c->h_n[b] += 6;
+}
+static bool mirror_marg(ingvio_ctx* c)
+{
+    bool all = true;
+    for (int b = 0; b < c->d.batch; ++b) { if (c->st_marg[b] >= 0) { c->h_n[b] -= 6; c->h_cur[b] ^= 1; } else all = false; }
+    return all;
+}
+
+// An in-frame landmark or GNSS stage belongs to ONE frame: the step that applied it consumes it, so that a later frame cannot apply the
+// old rows to a state that has moved on - unless the caller replays the same prior (the bench, the parity tests)
+static void consume_in_frame(bool& staged, bool in_frame, bool replay) { if (staged && in_frame && !replay) staged = false; }
+// the strip shortcut of the NEXT restore: valid after a step from the prior that wrote every filter's posterior into the other half
+static void strips_after_step(ingvio_ctx* c, bool valid) { c->strip_ok = valid; c->strip_seq = c->mut_seq; }
+
 // The fused frame step of windows up to 16 clones with the batch dealt to P slices.  Slice p = filters [p B / P, (p + 1) B / P) rounded
 // to multiples of 8 (the kernels' XCD-aware block order works on groups of 8 filters), on stream part[p].st:
 //     restore -> propagate + clone -> [wait: gate of slice p - 1] gate [record] -> Gram -> solve -> (GNSS in-frame) -> apply + marginalise
@@ -3910,9 +3944,8 @@ static int frame_run_split(ingvio_ctx* c, int restore_prior, int P, bool gnss_fu
         for (int p = 0; p < P; ++p) HIPCHK(c, hipStreamWaitEvent(c->part[p].st, c->ev_split_fork, 0));
         c->tok_last = nullptr;
     }
-    const bool strips = restore_prior && c->strip_ok && c->mut_seq == c->strip_seq;
-    if (restore_prior) { c->h_n = c->h_n_snap; std::fill(c->h_cur.begin(), c->h_cur.end(), 0); }
-    for (int b = 0; b < B; ++b) c->h_n[b] += 6;
+    const bool strips = strips_valid(c, restore_prior);
+    mirror_restore_clone(c, restore_prior);
     int rc = 0;
     auto range = [&](int p, int& b0, int& nb) {
         b0 = (int)((long long)B * p / P) & ~7;
@@ -3927,19 +3960,7 @@ static int frame_run_split(ingvio_ctx* c, int restore_prior, int P, bool gnss_fu
         if (nb <= 0) continue;
         auto& q = c->part[p];
         c->run_st = q.st;
-        const bool from_snap = strips && propagate_can_restore(c->d.n_max) && !no_snap_propagate();
-        if (restore_prior && !from_snap) {
-            ProfScope pr(c, PF_RESTORE);
-            if (strips) launch_restore_strips(view(c), b0, nb, c->d.n_max, c->Psnap, c->d_n_snap, c->st_enable_gnss ? c->d_gnss : nullptr, q.st);
-            else launch_restore(view(c), b0, nb, c->d.n_max, c->Psnap, c->d_n_snap, q.st);
-        }
-        {
-            ProfScope pr(c, PF_PROPAGATE);
-            const ImuLaunch im = imu_launch(c, b0, nb);
-            launch_propagate(view(c), b0, nb, c->d.n_max, c->d_Phi + (size_t)b0 * KMAX * 225, c->d_G + (size_t)b0 * KMAX * 180, c->d_dt + (size_t)b0 * KMAX,
-                             im.k, KMAX, im.prm, c->st_enable_gnss ? c->d_gnss + (size_t)b0 * 5 : nullptr, im.sigma, c->st_enable_gnss, im.scb, im.srw, q.st,
-                             c->d_R + (size_t)b0 * 9, c->d_status, from_snap ? c->Psnap : nullptr, c->d_n_snap);
-        }
+        launch_restore_propagate(c, restore_prior, strips, b0, nb, q.st);
         c->tok_wait = c->tok_last; c->tok_rec = q.ev_gate;
         rc = run_msckf_factored(c, b0, nb, c->st_op, c->st_stereo, c->st_fmax_used, c->d_idx + b0, 6, 1, gnss_fuse);
         c->tok_last = rc ? nullptr : q.ev_gate;
@@ -3962,144 +3983,80 @@ static int frame_run_split(ingvio_ctx* c, int restore_prior, int P, bool gnss_fu
     c->run_st = c->st;
     c->split_pending = true;
     if (rc) { c->tok_last = nullptr; ENTER(c); return rc; }
-    bool all_marg = true;
-    for (int b = 0; b < B; ++b) { if (c->st_marg[b] >= 0) { c->h_n[b] -= 6; c->h_cur[b] ^= 1; } else all_marg = false; }
-    c->strip_ok = all_marg && restore_prior;
-    c->strip_seq = c->mut_seq;
-    if (c->gn.staged && c->gn.in_frame && !restore_prior) c->gn.staged = false;
-    return INGVIO_OK;
+    const bool all_marg = mirror_marg(c);
+    strips_after_step(c, all_marg && restore_prior);
+    consume_in_frame(c->gn.staged, c->gn.in_frame, restore_prior != 0);
+    return INGVIO_OK;                              // (the slices' input set is handed back by join_parts)
 }
 
-static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
+// front half of the split (feature-sharded) step: restore, propagate + clone, gate + Gram; the [A | b] partials stay on the device
+static int frame_run_front(ingvio_ctx* c, int restore_prior)
 {
-    if (!c || !c->staged) return INGVIO_E_ARG;
-    if (c->nom.frame) {                                                     // a frame staged from the device nominal state (DESIGN 4.11)
-        if (!c->nom.pending) { c->err = "the frame staged from the device nominal state has already run"; return INGVIO_E_ARG; }
-        if (phase) { c->err = "the split step does not take a frame staged from the device nominal state"; return INGVIO_E_UNSUPPORTED; }
-        if (restore_prior) { c->err = "restore_prior with a frame staged from the device nominal state (restore with ingvio_cov_restore before the stage)"; return INGVIO_E_ARG; }
-        // (the one in-frame stage it takes is the landmark stage from the table itself, ingvio_landmark_stage_nominal)
-        if ((c->gn.staged && c->gn.in_frame) || (c->lm.staged && c->lm.in_frame && !c->lm.nominal) || c->parts_req > 1) {
-            c->err = "the device nominal state takes no in-frame GNSS / host-fed landmark stage and frame_parts = 1 only"; return INGVIO_E_UNSUPPORTED;
-        }
-    } else if (c->lm.staged && c->lm.in_frame && c->lm.nominal) {
-        c->err = "an in-frame landmark stage from the device nominal state needs a frame staged from it"; return INGVIO_E_ARG;
-    }
-    if (phase && c->method != 1) return INGVIO_E_UNSUPPORTED;             // the split needs the information form's [A | b]
-    // protocol of the split step: 1 -> (ingvio_debug_msckf_info / ingvio_info_set) -> 2, exactly once each; the accepted-feature
-    // cap is a global order over the features and is not defined across shards
-    if (phase != 2 && phase_busy(c)) return INGVIO_E_ARG;
-    if (phase == 2 && !c->phase_pending) { c->err = "ingvio_frame_run_phase(.., 2) without a preceding phase 1"; return INGVIO_E_ARG; }
-    if (phase != 0 && c->st_op.max_accept > 0) { c->err = "max_accept is not supported by the split (feature-sharded) frame step"; return INGVIO_E_ARG; }
-    if (phase == 2) {                                                       // back half: solve + apply + marginalise from the partials
-        c->phase_pending = false;
-        const int B2 = c->d.batch;
-        const bool with_lm2 = c->lm.staged && c->lm.in_frame;
-        int rc2 = run_msckf_factored(c, 0, B2, c->st_op, c->st_stereo, c->st_fmax_used, with_lm2 ? nullptr : c->d_idx, with_lm2 ? 0 : 6, 2);
-        if (rc2) return rc2;
-        if (with_lm2) { rc2 = landmark_update_launch(c, 0, B2); if (rc2) return rc2; }
-        {
-            ProfScope p(c, PF_MARG);
-            if (!with_lm2) { if (!c->apply_flipped) launch_post_marg(view(c), 0, B2, c->d_idx, 6, c->st); }
-            else launch_marginalize(view(c), 0, B2, c->d.n_max, c->d_idx, 6, c->st);
-        }
-        for (int b = 0; b < B2; ++b) if (c->st_marg[b] >= 0) { c->h_n[b] -= 6; c->h_cur[b] ^= 1; }
-        // as in the unsplit step: a landmark stage belongs to ONE frame unless the caller replays the same prior
-        if (with_lm2 && !c->phase_restore) c->lm.staged = false;
-        c->strip_ok = false;
-        c->mut_seq++;
-        // an in-frame GNSS stage: the split step never folds it into the write-back - its own pass, as the unsplit step does for the
-        // shapes it cannot fold (it used to be dropped silently here)
-        if (c->gn.staged && c->gn.in_frame && c->gn.m_cap > 0) {
-            rc2 = gnss_run_separate(c, 0, B2, true);
-            if (rc2) return rc2;
-            if (!c->phase_restore) c->gn.staged = false;
-        }
-        if (c->alt_ready) { HIPCHK(c, hipEventRecord(c->ev_free[c->set_id], c->st)); c->free_valid[c->set_id] = true; }
-        return INGVIO_OK;
-    }
     const int B = c->d.batch;
-    // ---- every check that can refuse the step comes before the first launch and before any host-side state changes ----
-    if (restore_prior && !c->has_snap) return INGVIO_E_ARG;
-    if (c->method == 0 && c->d.c_max > 16) return INGVIO_E_UNSUPPORTED;       // the dense MSCKF method stops at 16 clones
-    {
-        const std::vector<int>& n0 = restore_prior ? c->h_n_snap : c->h_n;
-        for (int b = 0; b < B; ++b) {
-            if (n0[b] < 21) return INGVIO_E_ARG;
-            if (n0[b] + 6 > c->d.n_max) return INGVIO_E_CAPACITY;
-            if (c->st_cidx_hi[b] + 6 > n0[b] + 6) return INGVIO_E_NOT_IN_STATE;      // a staged clone lies beyond the live state
-            if (c->st_marg[b] >= 0 && c->st_marg[b] + 6 > n0[b] + 6) return INGVIO_E_NOT_IN_STATE;
-        }
-        if (c->lm.staged && c->lm.in_frame) { if (int rc = landmark_in_state(c, 0, B, n0, 6)) return rc; }
-    }
-    // ---- split step (round 6): the batch as `parts` slices on their own streams, gates chained, nothing joined at the end ----
-    {
-        const bool with_lm0 = c->lm.staged && c->lm.in_frame;
-        const bool gnss0 = c->gn.staged && c->gn.in_frame && c->gn.m_cap > 0;
-        bool gfuse0 = gnss0 && c->d.c_max <= 16 && c->gn.m_cap <= 16 && c->gn.nc_max <= 16;
-        for (int b = 0; b < B && gfuse0; ++b) if (c->st_marg[b] < 0 || c->gn.hi[b] > c->st_marg[b]) gfuse0 = false;
-        // automatic = off: measured on MI355X at 512 filters x (150 features, 11 clones, N = 249) the split LOSES - 0.535 ms unsplit, 0.58
-        // (gates chained) / 0.65 (throughput segments chained) with two slices, 0.73-0.97 with three and four
-        int P = c->parts_req > 0 ? c->parts_req : 1;
-        if (P > 4) P = 4;
-        if (phase == 0 && P > 1 && c->method == 1 && !with_lm0 && c->d.c_max <= 16 && (!gnss0 || gfuse0) && B >= 16 * P)
-            return frame_run_split(c, restore_prior, P, gfuse0);
-    }
     ENTER(c);
     if (wait_inputs(c)) return INGVIO_E_HIP;
-    // restore_prior right after a fused frame step that itself began with a restore: half 0 still equals the snapshot outside the
-    // propagation's strips - the propagation then READS the snapshot and writes half 0, no restore pass at all (round 6; before:
-    // k_restore_strips, 23 us and 94 MB per 512 filters)
-    bool from_snap = false;
-    if (restore_prior) {
-        const bool strips = c->strip_ok && c->mut_seq == c->strip_seq;
-        from_snap = strips && propagate_can_restore(c->d.n_max) && !no_snap_propagate();
-        if (!from_snap) {
-            ProfScope p(c, PF_RESTORE);
-            if (strips) launch_restore_strips(view(c), 0, B, c->d.n_max, c->Psnap, c->d_n_snap, c->st_enable_gnss ? c->d_gnss : nullptr, c->st);
-            else launch_restore(view(c), 0, B, c->d.n_max, c->Psnap, c->d_n_snap, c->st);
-        }
-        c->h_n = c->h_n_snap;
-        std::fill(c->h_cur.begin(), c->h_cur.end(), 0);
-    }
+    launch_restore_propagate(c, restore_prior, strips_valid(c, restore_prior), 0, B, c->st);
+    mirror_restore_clone(c, restore_prior);
+    strips_after_step(c, false);
+    const int rc = run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, nullptr, 0, 1);
+    // h_n is already + 6 (the clone exists on the device): only phase 2 may follow - and only after a front half that was
+    // launched; after a refused one the step has to be abandoned with ingvio_cov_restore or replayed with
+    // ingvio_frame_run(restore_prior)
+    if (rc == 0) { c->phase_pending = true; c->phase_restore = restore_prior != 0; }
+    return rc;
+}
+
+// back half: solve + apply + marginalise from the partials (a replay: the front half began with restore_prior)
+static int frame_run_back(ingvio_ctx* c)
+{
+    c->phase_pending = false;
+    const int B = c->d.batch;
+    const bool with_lm = lm_in_frame(c), replay = c->phase_restore;
+    int rc = run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, with_lm ? nullptr : c->d_idx, with_lm ? 0 : 6, 2);
+    if (rc) return rc;
+    if (with_lm) { rc = landmark_update_launch(c, 0, B); if (rc) return rc; }
     {
-        // one launch: status reset + K1 (k composed IMU steps) + K2 (clone) when a workgroup owns a whole filter
-        ProfScope p(c, PF_PROPAGATE);
-        const ImuLaunch im = imu_launch(c, 0, B);
-        launch_propagate(view(c), 0, B, c->d.n_max, c->d_Phi, c->d_G, c->d_dt, im.k, KMAX, im.prm, c->st_enable_gnss ? c->d_gnss : nullptr,
-                         im.sigma, c->st_enable_gnss, im.scb, im.srw, c->st, c->d_R, c->d_status,
-                         from_snap ? c->Psnap : nullptr, c->d_n_snap);
+        ProfScope p(c, PF_MARG);
+        if (!with_lm) { if (!c->apply_flipped) launch_post_marg(view(c), 0, B, c->d_idx, 6, c->st); }
+        else launch_marginalize(view(c), 0, B, c->d.n_max, c->d_idx, 6, c->st);
     }
-    for (int b = 0; b < B; ++b) c->h_n[b] += 6;
+    mirror_marg(c);
+    consume_in_frame(c->lm.staged, c->lm.in_frame, replay);
+    strips_after_step(c, false);
+    // an in-frame GNSS stage: the split step never folds it into the write-back - its own pass, as the unsplit step does for the
+    // shapes it cannot fold (it used to be dropped silently here)
+    if (gnss_in_frame(c)) {
+        rc = gnss_run_separate(c, 0, B, true);
+        if (rc) return rc;
+        consume_in_frame(c->gn.staged, c->gn.in_frame, replay);
+    }
+    return release_input_set(c);
+}
+
+// the whole step, unsplit, on the compute stream
+static int frame_run_whole(ingvio_ctx* c, int restore_prior)
+{
+    const int B = c->d.batch;
+    ENTER(c);
+    if (wait_inputs(c)) return INGVIO_E_HIP;
+    launch_restore_propagate(c, restore_prior, strips_valid(c, restore_prior), 0, B, c->st);
+    mirror_restore_clone(c, restore_prior);
     // factored path: the marginalisation of the oldest clone rides on the update's write-back (k_info_apply
     // stores the updated covariance compacted into the other ping-pong half); dense path: separate kernel
     // staged in-frame landmark update (IngvioFilter.cpp:296-322: MSCKF updates, landmark update, then the marginalisation):
     // the marginalisation cannot ride on the MSCKF write-back then
-    const bool with_lm = c->lm.staged && c->lm.in_frame;
+    const bool with_lm = lm_in_frame(c);
     const bool fuse = c->method == 1 && !with_lm;
-    if (phase == 1) {                                                       // front half only: [A | b] partials stay on the device
-        c->strip_ok = false;
-        c->mut_seq++;
-        const int rc1 = run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, nullptr, 0, 1);
-        // h_n is already + 6 (the clone exists on the device): only phase 2 may follow - and only after a front half that was
-        // launched; after a refused one the step has to be abandoned with ingvio_cov_restore or replayed with
-        // ingvio_frame_run(restore_prior)
-        if (rc1 == 0) { c->phase_pending = true; c->phase_restore = restore_prior != 0; }
-        return rc1;
-    }
     // with a landmark update to follow, the MSCKF update is still written OUT OF PLACE (a "marginalisation" of zero columns into the
     // other half, then the halves flip): the solve then reads P[:, clone columns] straight from the untouched prior instead of
     // copying them first (0.035 ms per 512 filters), and the landmark downdate writes back into the first half with the real
     // marginalisation fused
     const bool lm_oop = with_lm && c->method == 1;
     // in-frame GNSS stage (ingvio_gnss_opts::in_frame): on the MSCKF write-back when everything fits one sweep, else as its own pass below
-    const bool gnss_here = c->gn.staged && c->gn.in_frame && c->gn.m_cap > 0;
-    bool gnss_fuse = gnss_here && fuse && c->d.c_max <= 16 && c->gn.m_cap <= 16 && c->gn.nc_max <= 16;
-    // the update's columns must keep their indices through the frame's marginalisation: var_order entirely below the clone that goes
-    for (int b = 0; b < B && gnss_fuse; ++b) if (c->st_marg[b] < 0 || c->gn.hi[b] > c->st_marg[b]) gnss_fuse = false;
-    int rc = fuse ? run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, c->d_idx, 6, 0, gnss_fuse)
-                  : (c->method == 1 ? (lm_oop ? run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, c->d_zero_idx, 0)
-                                              : run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used))
-                                    : run_msckf(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used));
+    const bool gnss_here = gnss_in_frame(c), gnss_fuse = fuse && gnss_folds(c);
+    int rc = fuse     ? run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, c->d_idx, 6, 0, gnss_fuse)
+             : lm_oop ? run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, c->d_zero_idx, 0)
+                      : run_msckf(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used);      // (method 0: the dense path)
     if (rc) return rc;
     if (lm_oop) {
         if (!c->apply_flipped) launch_post_marg(view(c), 0, B, c->d_zero_idx, 0, c->st);
@@ -4116,11 +4073,8 @@ static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
         if (fuse || lm_fused) launch_post_marg(view(c), 0, B, c->d_idx, 6, c->st);
         else launch_marginalize(view(c), 0, B, c->d.n_max, c->d_idx, 6, c->st);
     }
-    // a landmark stage belongs to ONE frame: unless the caller replays the same prior (restore_prior, the bench and the parity tests)
-    // the staged rows are consumed here, so that a later frame cannot re-apply them to a state that has moved on
-    if (with_lm && !restore_prior) c->lm.staged = false;
-    bool all_marg = true;
-    for (int b = 0; b < B; ++b) { if (c->st_marg[b] >= 0) { c->h_n[b] -= 6; c->h_cur[b] ^= 1; } else all_marg = false; }
+    consume_in_frame(c->lm.staged, c->lm.in_frame, restore_prior != 0);
+    const bool all_marg = mirror_marg(c);
     if (c->nom.pending) {                          // device nominal state: boxPlus with the frame's dx, drop + shift, behind the marginalisation
         // (with landmarks from the table the frame's dx is on the table already: the LANDMARK update's dx, in the same index space)
         launch_nominal_update(nom_table(c), lm_nom ? c->lm.dx : c->d_dx, c->ldp, c->d_idx, 0, B, c->st);
@@ -4129,20 +4083,60 @@ static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
         c->nom.pending = false;
         if (nom_mark(c)) return INGVIO_E_HIP;
     }
-    c->strip_ok = fuse && all_marg && restore_prior;
-    c->strip_seq = c->mut_seq;
+    strips_after_step(c, fuse && all_marg && restore_prior);
     if (gnss_here && !gnss_fuse) {                 // not foldable (large window, landmarks in the frame, many rows): its own pass, now
         rc = gnss_run_separate(c, 0, B, true);
         if (rc) return rc;
     }
-    // like a landmark stage, an in-frame GNSS stage belongs to ONE frame: consumed here unless the caller replays the same prior, so
-    // that a later frame cannot apply the old rows again; ingvio_gnss_fetch still returns this frame's results
-    if (c->gn.staged && c->gn.in_frame && !restore_prior) c->gn.staged = false;
-    if (c->alt_ready) {                            // this input set may be refilled once the kernels above are done with it
-        HIPCHK(c, hipEventRecord(c->ev_free[c->set_id], c->st));
-        c->free_valid[c->set_id] = true;
+    consume_in_frame(c->gn.staged, c->gn.in_frame, restore_prior != 0);
+    return release_input_set(c);
+}
+
+// refusals -> checks against the live state -> one of {split, front half, back half, whole step}
+static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
+{
+    if (!c || !c->staged) return INGVIO_E_ARG;
+    if (c->nom.frame) {                                                     // a frame staged from the device nominal state (DESIGN 4.11)
+        if (!c->nom.pending) { c->err = "the frame staged from the device nominal state has already run"; return INGVIO_E_ARG; }
+        if (phase) { c->err = "the split step does not take a frame staged from the device nominal state"; return INGVIO_E_UNSUPPORTED; }
+        if (restore_prior) { c->err = "restore_prior with a frame staged from the device nominal state (restore with ingvio_cov_restore before the stage)"; return INGVIO_E_ARG; }
+        // (the one in-frame stage it takes is the landmark stage from the table itself, ingvio_landmark_stage_nominal)
+        if ((c->gn.staged && c->gn.in_frame) || (lm_in_frame(c) && !c->lm.nominal) || c->parts_req > 1) {
+            c->err = "the device nominal state takes no in-frame GNSS / host-fed landmark stage and frame_parts = 1 only"; return INGVIO_E_UNSUPPORTED;
+        }
+    } else if (lm_in_frame(c) && c->lm.nominal) {
+        c->err = "an in-frame landmark stage from the device nominal state needs a frame staged from it"; return INGVIO_E_ARG;
     }
-    return INGVIO_OK;
+    if (phase && c->method != 1) return INGVIO_E_UNSUPPORTED;             // the split needs the information form's [A | b]
+    // protocol of the split step: 1 -> (ingvio_debug_msckf_info / ingvio_info_set) -> 2, exactly once each; the accepted-feature
+    // cap is a global order over the features and is not defined across shards
+    if (phase != 2 && phase_busy(c)) return INGVIO_E_ARG;
+    if (phase == 2 && !c->phase_pending) { c->err = "ingvio_frame_run_phase(.., 2) without a preceding phase 1"; return INGVIO_E_ARG; }
+    if (phase != 0 && c->st_op.max_accept > 0) { c->err = "max_accept is not supported by the split (feature-sharded) frame step"; return INGVIO_E_ARG; }
+    if (phase == 2) return frame_run_back(c);
+    const int B = c->d.batch;
+    // ---- every check that can refuse the step comes before the first launch and before any host-side state changes ----
+    if (restore_prior && !c->has_snap) return INGVIO_E_ARG;
+    if (c->method == 0 && c->d.c_max > 16) return INGVIO_E_UNSUPPORTED;       // the dense MSCKF method stops at 16 clones
+    {
+        const std::vector<int>& n0 = restore_prior ? c->h_n_snap : c->h_n;
+        for (int b = 0; b < B; ++b) {
+            if (n0[b] < 21) return INGVIO_E_ARG;
+            if (n0[b] + 6 > c->d.n_max) return INGVIO_E_CAPACITY;
+            if (c->st_cidx_hi[b] + 6 > n0[b] + 6) return INGVIO_E_NOT_IN_STATE;      // a staged clone lies beyond the live state
+            if (c->st_marg[b] >= 0 && c->st_marg[b] + 6 > n0[b] + 6) return INGVIO_E_NOT_IN_STATE;
+        }
+        if (lm_in_frame(c)) { if (int rc = landmark_in_state(c, 0, B, n0, 6)) return rc; }
+    }
+    if (phase == 1) return frame_run_front(c, restore_prior);
+    // ---- split step (round 6): the batch as `parts` slices on their own streams, gates chained, nothing joined at the end ----
+    // automatic = off: measured on MI355X at 512 filters x (150 features, 11 clones, N = 249) the split LOSES - 0.535 ms unsplit, 0.58
+    // (gates chained) / 0.65 (throughput segments chained) with two slices, 0.73-0.97 with three and four
+    const int P = std::min(c->parts_req > 0 ? c->parts_req : 1, 4);
+    const bool gnss_fuse = gnss_folds(c);
+    if (P > 1 && c->method == 1 && !lm_in_frame(c) && c->d.c_max <= 16 && (!gnss_in_frame(c) || gnss_fuse) && B >= 16 * P)
+        return frame_run_split(c, restore_prior, P, gnss_fuse);
+    return frame_run_whole(c, restore_prior);
 }
 
 int ingvio_frame_run(ingvio_ctx* c, int restore_prior) { return frame_run_impl(c, restore_prior, 0); }

@@ -125,6 +125,55 @@ def test_per_filter_noise_set_and_partial_stages(orc):
     ctx.close()
 
 
+@pytest.mark.parametrize("second", ["subset", "none"])
+@pytest.mark.parametrize("tracks", [False, True], ids=["flattened", "track_store"])
+def test_restage_with_other_clock_indices_ends_the_strip_restore(orc, tracks, second):
+    """Stage with all five clock states, run twice from the prior (the second run restores only the strips the first one wrote, which
+    the staged clock-state indices name), then stage the same frame with another set of indices - a subset, or none with enable_gnss
+    = 0 - and run from the prior again: bit-identical to a fresh context that staged the second set once and ran once.  The
+    covariance is not read between the runs (that alone ends the strip restore)."""
+    nb = 3
+    cases = [_case(orc, 360 + b, (10, 7, 12)[b], C=TC, F=TF, ld=64) for b in range(nb)]
+    priors, frames = [c[0] for c in cases], [c[2] for c in cases]
+    steps_a = [c[1] for c in cases]
+    assert all(np.asarray(s["gnss_idx"]).min() >= 0 and s["marg_idx"] >= 0 for s in steps_a)
+    keep = (1, 0, 1, 0, 0) if second == "subset" else (0,) * 5
+    enable_b = 1 if second == "subset" else 0
+    steps_b = [dict(s, gnss_idx=[g if on else -1 for g, on in zip(s["gnss_idx"], keep)]) for s in steps_a]
+    sigma, scb, srw = settings(steps_a[0])
+
+    def stage(ctx, steps, enable, fill):
+        if not tracks:
+            ctx.frame_stage(0, steps, frames, sigma, enable, scb, srw)
+            return
+        for s in range(TC) if fill else (None,):        # the window's columns first; the re-stage is a delta without a new column
+            deltas = [track_delta(frames[b], b, s, feats=s in (None, TC - 1)) for b in range(nb)]
+            ctx.frame_stage_tracks_prepare(0, steps, deltas, frames[0], sigma, enable, scb, srw)()
+
+    def fresh():
+        ctx = track_ctx(nb)
+        for b, P in enumerate(priors):
+            ctx.cov_set(b, P)
+        ctx.snapshot()
+        return ctx
+
+    ctx = fresh()
+    stage(ctx, steps_a, 1, True)
+    ctx.frame_run(restore_prior=True)
+    ctx.frame_run(restore_prior=True)
+    stage(ctx, steps_b, enable_b, False)
+    got = run_fetch(ctx, nb)
+    ctx.close()
+    ref = fresh()
+    stage(ref, steps_b, enable_b, True)
+    want = run_fetch(ref, nb)
+    stage(ref, steps_a, 1, False)
+    first = run_fetch(ref, nb)
+    ref.close()
+    assert_same(got, want, (tracks, second))
+    assert not all(np.array_equal(x, y) for x, y in zip(want[3], first[3])), "the clock-state indices did not matter"
+
+
 # ---- 3. track store -------------------------------------------------------------------------------------------------------------
 def test_track_store_mixed_k(orc):
     """ingvio_frame_stage_tracks with k = 1, 17, 51, 64 in one call: k_imu_steps forms each filter's Phi / G at its own slot; the
