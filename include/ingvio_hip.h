@@ -644,6 +644,39 @@ typedef struct {
     double psr_noise_amp, dopp_noise_amp;     /* GnssUpdate::_psr_noise_amp / _dopp_noise_amp                          */
 } ingvio_gnss_epoch_nominal;
 int ingvio_gnss_front_stage_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_gnss_epoch_nominal* epochs, const ingvio_gnss_opts* opts);
+/* The raw GNSS epoch that belongs to the frame staged from the table: called AFTER ingvio_frame_stage_tracks_nominal of that frame and
+ * before its ingvio_frame_run, for the whole batch (the protocol of ingvio_landmark_stage_nominal with in_frame != 0).  The stage only
+ * uploads - ephemerides, observations, the host-owned receiver record, the gate table, on the compute stream behind the kernels of the
+ * frame enqueued last - and launches nothing: the rows are formed inside ingvio_frame_run, at the state after the MSCKF update of the
+ * same frame (IngvioFilter.cpp:277-362), from the table.  It leaves the GNSS results of the frame before alone: ingvio_gnss_fetch of
+ * frame i stays valid after the stages of frame i + 1 and is overwritten by ingvio_frame_run of frame i + 1, so
+ *   run(i); stage_tracks_nominal(i + 1, async); gnss_frame_stage_nominal(i + 1); fetch_begin(i); gnss_fetch(i); run(i + 1); fetch_end(i)
+ * is a closed loop in which the epoch of frame i does not hold back the stage of frame i + 1 (ingvio_gnss_fetch itself is optional).
+ * The run applies the epoch in one of two orders and consumes it (it runs once; ingvio_gnss_run on it is INGVIO_E_ARG):
+ *   folded      windows of at most 16 clones, at most 8 satellites (16 rows) per filter, every filter marginalises, every GNSS column
+ *               below the clone that leaves, no in-frame landmark stage: solve -> MSCKF dx -> boxPlus on the table (no drop, no shift)
+ *               -> rows from the table -> posterior columns -> row gates -> gain -> ONE write-back with the GNSS gain and the
+ *               marginalisation fused -> one retraction of the GNSS dx with drop and shift.  ingvio_gnss_fetch returns dx in the index
+ *               space AFTER the marginalisation, as for ingvio_gnss_stage with in_frame.
+ *   otherwise   the frame completes as without the epoch; then the kernels of ingvio_gnss_front_stage_nominal + ingvio_gnss_run run
+ *               behind it inside the same call, on the same inputs in the same order: results bit-identical to those two calls.
+ * A filter with n_sat = 0 or a rejected block: dx = 0, zero rows, its table moves by the frame alone.  dx, rows, keep, gamma and status
+ * of the epoch: ingvio_gnss_fetch; the frame's own dx, row counts and accept masks stay valid for ingvio_frame_fetch(_begin / _end).
+ * Refused before anything is launched or changed, on the host mirror of the table: no table, no frame staged from the table waiting to
+ * run, a range other than the whole batch, a second such stage for the same frame, no registered scalars for a filter with n_sat > 0,
+ * n_sat < 0 or > INGVIO_GNSS_MAX_SAT, a missing array (INGVIO_E_ARG); 2 n_sat rows beyond the row buffers or the update's LDS
+ * (INGVIO_E_CAPACITY); the extended pose, YOF or FS not in the table, or a GNSS column that - before or after the frame's marginalisation
+ * shift - lies outside the state the update sees or on the clone that leaves (INGVIO_E_NOT_IN_STATE).  ingvio_cov_restore abandons the
+ * stage with its frame.  Still refused: opts->in_frame on ingvio_gnss_front_stage(_nominal), a frame staged from the table while a host-fed
+ * ingvio_gnss_stage(in_frame) is pending, frame_parts > 1 and the split step with a table (INGVIO_E_UNSUPPORTED). */
+int ingvio_gnss_frame_stage_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_gnss_epoch_nominal* epochs, const ingvio_gnss_opts* opts);
+/* test hook: how the GNSS update that ran last was applied - 0: no results / ingvio_gnss_run on the frame's slots, 1: a pass of its own
+ * with its own result slots, 2: folded into the MSCKF write-back */
+int ingvio_debug_gnss_fused_last(ingvio_ctx* ctx);
+/* test hook: the retraction kernel of the folded order alone, on the TABLE of filters [b0, b0 + nb) only (the covariance is not touched) -
+ * boxPlus of dx [nb][ldp] given in the index space behind the marginalisation of marg_idx[i] (a window clone), then drop and shift.
+ * INGVIO_E_NOT_IN_STATE: marg_idx names no window clone or a variable would read beyond its row of dx. */
+int ingvio_debug_nominal_update_post(ingvio_ctx* ctx, int b0, int nb, const double* dx, const int* marg_idx);
 /* ---- in-state landmarks in the device-resident closed loop -------------------------------------------------------
  * ingvio_landmark_stage with the nominal values taken from the device table: per filter only the observations and the table slots of the
  * landmarks they belong to.  R_i2w, p_i2w (the table's extended pose), R_cl2i, p_c2i (its extrinsics), idx_epose, idx_ext and per

@@ -36,6 +36,7 @@ EXPORTS = [
     "ingvio_nominal_set_gnss", "ingvio_nominal_get_gnss", "ingvio_gnss_front_stage_nominal", "ingvio_landmark_stage_nominal",
     "ingvio_landmark_init_nominal", "ingvio_debug_landmark_init_rows", "ingvio_nominal_tail",
     "ingvio_debug_tracks_read", "ingvio_debug_staged_frame",
+    "ingvio_gnss_frame_stage_nominal", "ingvio_debug_gnss_fused_last", "ingvio_debug_nominal_update_post",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -603,6 +604,36 @@ class Context:
 
     def gnss_front_stage_nominal(self, b0, epochs, chi2_table, gate_rows=True, strong_reject=False, in_frame=False):
         self.gnss_front_stage_nominal_prepare(b0, epochs, chi2_table, gate_rows, strong_reject, in_frame)()
+
+    def gnss_frame_stage_nominal_prepare(self, b0, epochs, chi2_table, gate_rows=True, strong_reject=False):
+        """ingvio_gnss_frame_stage_nominal: the raw epochs (as for gnss_front_stage_nominal) of the frame staged from the table, issued between
+        frame_stage_tracks_nominal and frame_run, which applies them.  Returns a callable that issues the stage."""
+        nb = len(epochs)
+        arr = (GnssEpochNominal * nb)(); keep = []
+        for i, e in enumerate(epochs):
+            a = arr[i]
+            if e is None:
+                a.n_sat = 0
+                continue
+            keep.append(_epoch_host_fields(a, e))
+        o, tab = _gnss_opts(chi2_table, gate_rows, strong_reject)
+
+        def call(_keep=(keep, tab, arr, o)):
+            self._chk(self.L.ingvio_gnss_frame_stage_nominal(self.h, int(b0), nb, arr, C.byref(o)))
+            self._gnss_range = (b0, nb)
+        return call
+
+    def gnss_frame_stage_nominal(self, b0, epochs, chi2_table, gate_rows=True, strong_reject=False):
+        self.gnss_frame_stage_nominal_prepare(b0, epochs, chi2_table, gate_rows, strong_reject)()
+
+    def debug_gnss_fused_last(self):
+        """0: no GNSS results of their own slots, 1: the update that ran last was a pass of its own, 2: it rode on the MSCKF write-back"""
+        return int(self.L.ingvio_debug_gnss_fused_last(self.h))
+
+    def debug_nominal_update_post(self, b0, dx, marg_idx):
+        """the folded order's retraction kernel alone, on the table only: dx [nb, ldp] in the index space behind the marginalisation"""
+        dx = f64(dx); mg = i32(marg_idx)
+        self._chk(self.L.ingvio_debug_nominal_update_post(self.h, int(b0), len(mg), _d(dx), _i(mg)))
 
     def gnss_front_fetch(self, b0=None, nb=None):
         """-> [nb, 64, 20]: res_pos, res_vel, los (3), az, el, ion, tro, usable, then the SatState: pos (3), vel (3), dt, ddt, tgd, ttx"""

@@ -1,8 +1,8 @@
 """GNSS epochs in the closed loop of the device-resident nominal state (ingvio_nominal_set_gnss, ingvio_gnss_front_stage_nominal, DESIGN
 4.11) - harness code beside ingvio_amd/closed_loop.py, shared by tests/test_gpu_nominal_gnss.py and tools/closed_loop_bench.py --gnss:
 the loop inputs of closed_loop.make_loop with receiver clocks in the table and one raw GNSS epoch per filter and frame, the host
-reference (clock recursion of ImuPropagator.cpp:139-148, host-fed front, host boxPlus) and the loop's two forms for
-closed_loop.DeviceLoop (epochs from the table, epochs through the host).
+reference (clock recursion of ImuPropagator.cpp:139-148, host-fed front, host boxPlus) and the loop's forms for
+closed_loop.DeviceLoop (epochs from the table behind the frame, epochs from the table inside the frame, epochs through the host).
 
 The satellite data is one recorded instant (tests/golden/gnss_front.npz) while the synthetic trajectory moves, so every epoch is made
 consistent with the filter's TRUE state of its frame: the anchor maps the true position onto the fixture's evaluation point (plus a few
@@ -60,18 +60,23 @@ def move_scalars_behind_clones(c):
         g = [x - 6 if x > marg else x for x in g]
 
 
-def make_gnss_loop(z, B, n_frames, F=24, seed=5, every=3, **kw):
+def make_gnss_loop(z, B, n_frames, F=24, seed=5, every=3, scalars_in_front=False, n_sat=None, cases=None, **kw):
     """closed_loop.make_loop plus, per case: "gnss_slots", the table's clocks initialised from the fixture (xyzt[3:] plus noise, FS from
     velt[3], YOF = the epoch's yaw), and "epochs" [n_frames]: the host-owned part of a raw epoch (dict) or None; filter b has epochs
-    unless b % every == every - 1 (every = 0: all filters)."""
+    unless b % every == every - 1 (every = 0: all filters).
+    scalars_in_front: the GNSS scalars stay where make_loop puts them, in front of the clones - no marginalisation moves them, which is
+    what lets an in-frame epoch ride on the MSCKF write-back (ingvio_gnss_frame_stage_nominal).  n_sat: every epoch keeps its first n_sat
+    satellites only.  cases: the loop the epochs are added to (built with the same seed and F) instead of make_loop(B, n_frames, ...)."""
     from oracle import oracle as orc
     from ingvio_amd import synth
-    cases = make_loop(B, n_frames, F=F, seed=seed, **kw)
+    if cases is None:
+        cases = make_loop(B, n_frames, F=F, seed=seed, **kw)
     doy = float(z["doy"])
     base = orc.gnss_residuals(z["eph"], z["obs"], z["ion"], doy, np.r_[z["rcv_true"], z["cb_true"]], np.r_[z["vel_true"], z["fs_true"]])
     for b, c in enumerate(cases):
         rng = np.random.default_rng(900 + b)
-        move_scalars_behind_clones(c)
+        if not scalars_in_front:
+            move_scalars_behind_clones(c)
         sl = gnss_slots(c)
         c["gnss_slots"] = sl
         yaw = 0.3 + 0.01 * b
@@ -99,7 +104,8 @@ def make_gnss_loop(z, B, n_frames, F=24, seed=5, every=3, **kw):
             u = truth["usable"] == 1
             obs[u, 1] += truth["res_pos"][u] - base["res_pos"][u]
             obs[u, 2] -= (truth["res_vel"][u] - base["res_vel"][u]) * obs[u, 5] / C_LIGHT
-            c["epochs"].append(dict(eph=z["eph"], obs=obs, ion=z["ion"], doy=doy, R_enu2ecef=R_ENU, anchor_ecef=anchor, psr_amp=1.0, dopp_amp=1.0))
+            c["epochs"].append(dict(eph=np.array(z["eph"][:n_sat]), obs=obs[:n_sat], ion=z["ion"], doy=doy, R_enu2ecef=R_ENU, anchor_ecef=anchor,
+                                    psr_amp=1.0, dopp_amp=1.0))
     return cases
 
 
@@ -184,6 +190,29 @@ class GnssForm(Form):
         return ctx.gnss_fetch() if self.epochs else None
 
 
+def gnss_frame_stage_call(ctx, cases, f, chi2_table):
+    return ctx.gnss_frame_stage_nominal_prepare(0, [c["epochs"][f] for c in cases], chi2_table, gate_rows=True, strong_reject=True)
+
+
+class GnssInFrameForm(Form):
+    """the epoch of frame i staged right behind that frame's stage (ingvio_gnss_frame_stage_nominal); the frame's run forms its rows at
+    the state after the MSCKF update and applies them.  Not late: frame i + 1 is staged while frame i runs.  The GNSS results of frame
+    i are fetched between fetch_begin(i) and run(i + 1) (optional for the loop; it synchronises)."""
+
+    def __init__(self, chi2_table):
+        self.chi2_table = chi2_table
+
+    def prepare(self, ctx, cases, f):
+        return gnss_frame_stage_call(ctx, cases, f, self.chi2_table)
+
+    def staged(self, loop, i):
+        loop.form_call(i)()
+        loop.sync()
+
+    def collect(self, ctx):
+        return ctx.gnss_fetch()
+
+
 class GnssRoundTrip(Form):
     """the epoch through the host: ingvio_nominal_get, ingvio_gnss_front_stage with the table's values, ingvio_gnss_run,
     ingvio_gnss_fetch, ingvio_nominal_box_plus (three synchronisations per epoch)"""
@@ -201,6 +230,6 @@ class GnssRoundTrip(Form):
         ctx.nominal_box_plus(0, g[0])
 
 
-def device_loop_gnss(ctx, cases, frames, chi2_table, pipelined, sync_every_call=False):
-    """the device loop with GNSS epochs; -> [(frame results, GNSS results)] per frame"""
-    return device_loop(ctx, cases, frames, pipelined, GnssForm(chi2_table), sync_every_call)
+def device_loop_gnss(ctx, cases, frames, chi2_table, pipelined, sync_every_call=False, in_frame=False):
+    """the device loop with GNSS epochs (in_frame: staged with the frame and applied by its run); -> [(frame results, GNSS results)] per frame"""
+    return device_loop(ctx, cases, frames, pipelined, (GnssInFrameForm if in_frame else GnssForm)(chi2_table), sync_every_call)

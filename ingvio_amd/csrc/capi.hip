@@ -121,6 +121,7 @@ struct ingvio_ctx {
         // posterior (k_post_cols); Yf [B][ldp * 16]: the update's Cholesky-form gain, folded into k_info_apply; its own working rows
         // count / column count / dx (the frame's m, nc and dx slots belong to the MSCKF update)
         bool in_frame = false, fused_last = false;
+        bool folded_last = false;      // the update that ran last rode on the MSCKF write-back (ingvio_debug_gnss_fused_last)
         bool results = false;           // an update has run on the current stage: ingvio_gnss_fetch has something to return.  A non-restoring
                                         // ingvio_frame_run CONSUMES an in-frame stage (staged = false, as it does a landmark stage: the rows
                                         // belong to one frame); its results stay fetchable until the next stage
@@ -133,6 +134,9 @@ struct ingvio_ctx {
         // ingvio_gnss_run and kept after it, so that ingvio_gnss_fetch reads the right words for as long as those results are the
         // current ones; cleared by the next stage of any form (ingvio_gnss_stage, both front stages).
         bool nominal = false, nom_pending = false, own_status = false;
+        // frame_nom: the raw epoch of the frame staged from the table (ingvio_gnss_frame_stage_nominal): in_frame and nominal, its front
+        // runs inside ingvio_frame_run (the rows exist only there); hi holds the column range BEFORE the frame's marginalisation
+        bool frame_nom = false;
         int nom_b0 = 0, nom_nb = 0;
         int* stf = nullptr;
     } gn;
@@ -807,12 +811,21 @@ int make_opts(ingvio_ctx* c, const ingvio_msckf_opts* o, MsckfOpts* op)
 // In-frame GNSS update, between the MSCKF solve (stage 2) and its write-back (stage 3): the var_order columns of the posterior
 // (k_post_cols) -> per-row gates + compaction -> S, Cholesky, gain (k_ekf_core reading those columns instead of P) -> the gain
 // rides on the write-back as a rank-16 downdate (L.gY).  Working rows / counts / dx live in the stage's own buffers.
+void gnss_front_launch(ingvio_ctx* c, int b0, int nb, bool nominal, hipStream_t st);      // (defined with the GNSS front stages)
 static int gnss_in_frame_launch(ingvio_ctx* c, int b0, int nb, FactoredLaunch& L)
 {
     auto& g = c->gn;
     const size_t mld = c->mld, hs = mld * GNSS_NCW, ws = (size_t)c->ldp * 16;
     L.gcolmap = g.colmap + (size_t)b0 * GNSS_NCW; L.gnc = g.nc + b0; L.gcstride = GNSS_NCW;
     L.gW = g.W + (size_t)b0 * ws; L.gWstride = ws;
+    if (g.frame_nom) {
+        // the epoch of a frame staged from the table: its rows are formed here, at the state after the MSCKF update (IngvioFilter.cpp:277-362) -
+        // the MSCKF dx ahead of the write-back, boxPlus on the table without drop and shift (the update's index space, new clone
+        // included), then the front from the values and idx just written; the three launches are ordered by the stream
+        L.stage = 10; launch_factored(L, c->run_st);
+        launch_nominal_update(nom_table(c), c->d_dx, c->ldp, nullptr, b0, nb, c->run_st);
+        gnss_front_launch(c, b0, nb, true, c->run_st);
+    }
     { ProfScope p(c, PF_POSTCOLS); L.stage = 4; launch_factored(L, c->run_st); }
     EkfLaunch E;
     memset(&E, 0, sizeof E);
@@ -820,7 +833,7 @@ static int gnss_in_frame_launch(ingvio_ctx* c, int b0, int nb, FactoredLaunch& L
     E.colmap = c->d_colmap + (size_t)b0 * GNSS_NCW; E.m = g.mf + b0; E.nc = g.ncf + b0;
     E.noise = c->d_noiseB + (size_t)b0 * mld; E.r_kind = INGVIO_R_DIAG; E.mld = c->mld; E.hstride = (int)hs; E.cstride = GNSS_NCW;
     E.nstride = c->mld; E.Y = g.Yf + (size_t)b0 * ws; E.ystride = (int)ws; E.dx = g.dxf;
-    E.status = c->d_status; E.m_cap = g.m_cap; E.nc_cap = GNSS_NCW;
+    E.status = g.own_status ? g.stf : c->d_status; E.m_cap = g.m_cap; E.nc_cap = GNSS_NCW;
     E.W = L.gW; E.wstride = ws; E.ypad = 16; E.marg_idx = L.marg_idx; E.marg_size = L.marg_size;
     if (g.strong) { E.chi2 = g.chi2; E.chi2_len = g.chi2_len; E.gate_max_rows = 14; }      // GnssUpdate.cpp:286
     RowsGateIn in{ g.H + (size_t)b0 * hs, g.res + (size_t)b0 * mld, g.noise + (size_t)b0 * mld, g.m + b0, g.colmap + (size_t)b0 * GNSS_NCW,
@@ -831,7 +844,7 @@ static int gnss_in_frame_launch(ingvio_ctx* c, int b0, int nb, FactoredLaunch& L
     }
     { ProfScope p(c, PF_EKF_CORE); launch_ekf_core(E, c->run_st); }
     L.gY = E.Y; L.gYstride = ws; L.gm = g.mf + b0;
-    g.fused_last = true;
+    g.fused_last = true; g.folded_last = true;
     g.results = true;
     return 0;
 }
@@ -1384,6 +1397,7 @@ int ingvio_cov_restore(ingvio_ctx* c)
         if (m.pending) { c->staged = false; m.pending = false; }      // the staged frame's clone is not in the restored table
         m.frame = false;
         if (c->gn.nom_pending) { c->gn.nom_pending = false; c->gn.staged = false; }      // rows linearised at the abandoned table
+        if (c->gn.frame_nom) { c->gn.frame_nom = false; c->gn.in_frame = false; c->gn.staged = false; }      // the epoch of the abandoned frame
         if (c->lm.nominal && c->lm.staged) { c->lm.nom_pending = false; c->lm.staged = false; }      // either form: its slots name the abandoned table
         if (wait_inputs(c)) return INGVIO_E_HIP;                     // an asynchronous stage from the table must land before it is overwritten
         HIPCHK(c, hipMemcpyAsync(m.ih, m.ih_snap, sizeof(int) * (size_t)c->d.batch * m.ir, hipMemcpyDeviceToDevice, c->st));
@@ -1807,7 +1821,7 @@ int ingvio_gnss_stage(ingvio_ctx* c, int b0, int nb, const ingvio_update_block* 
     g.in_frame = o->in_frame != 0;
     g.fused_last = false;
     g.results = false;
-    g.nominal = false; g.nom_pending = false; g.own_status = false;
+    g.nominal = false; g.nom_pending = false; g.own_status = false; g.frame_nom = false;
     if (g.in_frame && !g.W) {
         const size_t B = c->d.batch, ws = (size_t)c->ldp * 16;
         if (dalloc(c, &g.W, B * ws) | dalloc(c, &g.Yf, B * ws) | dalloc(c, &g.dxf, B * (size_t)c->ldp) | dalloc(c, &g.mf, B) | dalloc(c, &g.ncf, B)) return INGVIO_E_HIP;
@@ -1821,27 +1835,10 @@ int ingvio_gnss_stage(ingvio_ctx* c, int b0, int nb, const ingvio_update_block* 
 // cannot ride on the MSCKF write-back)
 static int gnss_run_separate(ingvio_ctx* c, int b0, int nb, bool own_slots = false);
 
-// SURVEY 8(f) f-3: raw GNSS epochs -> candidate rows, on the device (kernels_gnss.hip)
-// nominal: the receiver state and the idx_* the kernel uses come from the device nominal table (the epochs' idx_* are the host mirror's, for
-// the checks below; p_w, v_w, cb, fs, yaw_offset are not read)
-static int gnss_front_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epoch* ep, const ingvio_gnss_opts* o, bool nominal)
+// the buffers, then ephemerides, observations, receiver records and the gate table of epochs [b0, b0 + nb) onto the compute stream
+// (behind whatever still reads them there); own_slots: also the result slots a stage from the device nominal state keeps apart
+static int gnss_front_upload(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epoch* ep, const ingvio_gnss_opts* o, bool own_slots)
 {
-    static_assert(GNSS_FRONT_NCW == GNSS_NCW, "column stride of the staged rows");
-    if (check_range(c, b0, nb) || !ep || !o) return INGVIO_E_ARG;
-    if ((o->gate_rows || o->strong_reject) && (!o->chi2_table || o->chi2_len < 2 || o->chi2_len > CHI2_CAP)) return INGVIO_E_ARG;
-    int smax = 1;
-    std::vector<int> his(nb, 0);
-    for (int i = 0; i < nb; ++i) {
-        const ingvio_gnss_epoch& e = ep[i];
-        if (e.n_sat < 0 || e.n_sat > INGVIO_GNSS_MAX_SAT || (e.n_sat && (!e.eph || !e.obs))) return INGVIO_E_ARG;
-        if (2 * e.n_sat > c->mld || 2 * e.n_sat > 256) return INGVIO_E_CAPACITY;
-        if (e.n_sat > smax) smax = e.n_sat;
-        int hi = 0;
-        const int idx[7] = { e.idx_se23 + 9, e.idx_yof + 1, e.idx_fs + 1, e.idx_cb[0] + 1, e.idx_cb[1] + 1, e.idx_cb[2] + 1, e.idx_cb[3] + 1 };
-        if (e.n_sat) { if (e.idx_se23 < 0 || e.idx_yof < 0 || e.idx_fs < 0) return INGVIO_E_NOT_IN_STATE; for (int v : idx) { if (v > c->d.n_max) return INGVIO_E_NOT_IN_STATE; if (v > hi) hi = v; } }
-        his[i] = hi;
-        if (!ekf_core_fits(2 * e.n_sat ? 2 * e.n_sat : 1, 15)) return INGVIO_E_CAPACITY;
-    }
     int rc = gnss_alloc(c);
     if (rc) return rc;
     auto& g = c->gn;
@@ -1851,7 +1848,7 @@ static int gnss_front_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_gns
         rc |= dalloc(c, &g.frcv, B * GR_N); rc |= dalloc(c, &g.front, B * 64 * GF_N);
         if (rc) return INGVIO_E_HIP;
     }
-    if (nominal) {                                  // the run's own result slots (shared with an in-frame stage) and status words
+    if (own_slots) {                                // the run's own result slots (shared with an in-frame stage) and status words
         if (!g.dxf) rc |= dalloc(c, &g.dxf, B * (size_t)c->ldp);
         if (!g.mf) rc |= dalloc(c, &g.mf, B);
         if (!g.ncf) rc |= dalloc(c, &g.ncf, B);
@@ -1890,6 +1887,15 @@ static int gnss_front_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_gns
     }
     rc = upl.end();
     if (rc) return rc;
+    return rc;
+}
+
+// k_gnss_front over the uploaded epochs: candidate rows, column map and counts of the stage (nominal: receiver state and idx from the table)
+namespace {      // (declared ahead of gnss_in_frame_launch)
+void gnss_front_launch(ingvio_ctx* c, int b0, int nb, bool nominal, hipStream_t st)
+{
+    auto& g = c->gn;
+    const size_t S = INGVIO_GNSS_MAX_SAT;
     const size_t mld = c->mld, hs = mld * GNSS_NCW;
     GnssFrontLaunch L;
     L.eph = g.feph + (size_t)b0 * S * GE_N; L.obs = g.fobs + (size_t)b0 * S * GO_N; L.rcv = g.frcv + (size_t)b0 * GR_N; L.smax = (int)S;
@@ -1897,7 +1903,34 @@ static int gnss_front_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_gns
     L.H = g.H + (size_t)b0 * hs; L.res = g.res + (size_t)b0 * mld; L.noise = g.noise + (size_t)b0 * mld;
     L.m = g.m + b0; L.nc = g.nc + b0; L.colmap = g.colmap + (size_t)b0 * GNSS_NCW; L.mld = c->mld; L.hstride = (int)hs;
     const NomTable nt = nom_table(c);
-    launch_gnss_front(L, nb, c->st, nominal ? &nt : nullptr, b0);
+    launch_gnss_front(L, nb, st, nominal ? &nt : nullptr, b0);
+}
+}  // namespace
+
+// SURVEY 8(f) f-3: raw GNSS epochs -> candidate rows, on the device (kernels_gnss.hip)
+// nominal: the receiver state and the idx_* the kernel uses come from the device nominal table (the epochs' idx_* are the host mirror's, for
+// the checks below; p_w, v_w, cb, fs, yaw_offset are not read)
+static int gnss_front_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epoch* ep, const ingvio_gnss_opts* o, bool nominal)
+{
+    static_assert(GNSS_FRONT_NCW == GNSS_NCW, "column stride of the staged rows");
+    if (check_range(c, b0, nb) || !ep || !o) return INGVIO_E_ARG;
+    if ((o->gate_rows || o->strong_reject) && (!o->chi2_table || o->chi2_len < 2 || o->chi2_len > CHI2_CAP)) return INGVIO_E_ARG;
+    int smax = 1;
+    std::vector<int> his(nb, 0);
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_gnss_epoch& e = ep[i];
+        if (e.n_sat < 0 || e.n_sat > INGVIO_GNSS_MAX_SAT || (e.n_sat && (!e.eph || !e.obs))) return INGVIO_E_ARG;
+        if (2 * e.n_sat > c->mld || 2 * e.n_sat > 256) return INGVIO_E_CAPACITY;
+        if (e.n_sat > smax) smax = e.n_sat;
+        int hi = 0;
+        const int idx[7] = { e.idx_se23 + 9, e.idx_yof + 1, e.idx_fs + 1, e.idx_cb[0] + 1, e.idx_cb[1] + 1, e.idx_cb[2] + 1, e.idx_cb[3] + 1 };
+        if (e.n_sat) { if (e.idx_se23 < 0 || e.idx_yof < 0 || e.idx_fs < 0) return INGVIO_E_NOT_IN_STATE; for (int v : idx) { if (v > c->d.n_max) return INGVIO_E_NOT_IN_STATE; if (v > hi) hi = v; } }
+        his[i] = hi;
+        if (!ekf_core_fits(2 * e.n_sat ? 2 * e.n_sat : 1, 15)) return INGVIO_E_CAPACITY;
+    }
+    if (int rc = gnss_front_upload(c, b0, nb, ep, o, nominal)) return rc;
+    auto& g = c->gn;
+    gnss_front_launch(c, b0, nb, nominal, c->st);
     for (int i = 0; i < nb; ++i) g.hi[b0 + i] = his[i];
     g.gate_rows = o->gate_rows ? 1 : 0; g.strong = o->strong_reject ? 1 : 0;
     g.thr1 = o->gate_rows ? o->chi2_table[1] : __builtin_inf();
@@ -1915,7 +1948,7 @@ static int gnss_front_stage_impl(ingvio_ctx* c, int b0, int nb, const ingvio_gns
     // by ingvio_gnss_run (the flags of an earlier in-frame ingvio_gnss_stage must not leak into this stage)
     if (o->in_frame) { c->err = "ingvio_gnss_front_stage: in_frame is not supported (stage the rows with ingvio_gnss_stage)"; return INGVIO_E_UNSUPPORTED; }
     g.in_frame = false; g.nc_max = 15; g.fused_last = false; g.results = false;
-    g.nominal = nominal; g.nom_pending = nominal; g.own_status = false; g.nom_b0 = b0; g.nom_nb = nb;
+    g.nominal = nominal; g.nom_pending = nominal; g.own_status = false; g.frame_nom = false; g.nom_b0 = b0; g.nom_nb = nb;
     g.staged = true;
     return last_launch(c);
 }
@@ -1967,6 +2000,84 @@ int ingvio_gnss_front_stage_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_
     }
     return gnss_front_stage_impl(c, b0, nb, full.data(), o, true);
 }
+
+// The raw epoch of the frame staged from the table: validated on the host mirror, uploaded, applied by that frame's
+// ingvio_frame_run - on the MSCKF write-back where gnss_folds() allows it, else as the two-call sequence behind the frame.  Nothing is
+// launched here (the front's inputs exist only after the MSCKF update) and the result slots of the frame before stay as they are.
+int ingvio_gnss_frame_stage_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epoch_nominal* ep, const ingvio_gnss_opts* o)
+{
+    ENTER(c);
+    if (phase_busy(c) || check_range(c, b0, nb) || !ep || !o) return INGVIO_E_ARG;
+    if ((o->gate_rows || o->strong_reject) && (!o->chi2_table || o->chi2_len < 2 || o->chi2_len > CHI2_CAP)) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    auto& g = c->gn;
+    if (!m.vmax) { c->err = "ingvio_gnss_frame_stage_nominal without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (!m.pending) { c->err = "ingvio_gnss_frame_stage_nominal: no frame staged from the device nominal state is waiting to run"; return INGVIO_E_ARG; }
+    if (b0 != 0 || nb != c->d.batch) { c->err = "ingvio_gnss_frame_stage_nominal stages the whole batch (b0 = 0, nb = batch)"; return INGVIO_E_ARG; }
+    if (g.staged && g.frame_nom) { c->err = "ingvio_gnss_frame_stage_nominal: the frame has its GNSS epoch already"; return INGVIO_E_ARG; }
+    std::vector<ingvio_gnss_epoch> full((size_t)nb);
+    std::vector<int> his(nb, 0);
+    int smax = 0;
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_gnss_epoch_nominal& e = ep[i];
+        ingvio_gnss_epoch& f = full[i];
+        memset(&f, 0, sizeof f);
+        if (e.n_sat < 0 || e.n_sat > INGVIO_GNSS_MAX_SAT || (e.n_sat && (!e.eph || !e.obs))) return INGVIO_E_ARG;
+        if (2 * e.n_sat > c->mld || 2 * e.n_sat > 256) return INGVIO_E_CAPACITY;
+        if (!ekf_core_fits(2 * e.n_sat ? 2 * e.n_sat : 1, 15)) return INGVIO_E_CAPACITY;
+        f.n_sat = e.n_sat; f.eph = e.eph; f.obs = e.obs; f.ion = e.ion; f.doy = e.doy;
+        memcpy(f.R_enu2ecef, e.R_enu2ecef, sizeof f.R_enu2ecef); memcpy(f.anchor_ecef, e.anchor_ecef, sizeof f.anchor_ecef);
+        f.psr_noise_amp = e.psr_noise_amp; f.dopp_noise_amp = e.dopp_noise_amp;
+        f.idx_se23 = f.idx_yof = f.idx_fs = -1;
+        for (int s = 0; s < 4; ++s) f.idx_cb[s] = -1;
+        if (e.n_sat == 0) continue;                 // no epoch for this filter
+        const int b = b0 + i;
+        const int* I = &m.h_ih[(size_t)b * m.ir];
+        bool reg = false;
+        for (int s = 0; s < 6; ++s) if (I[NOM_GNSS + s] >= 0) reg = true;
+        if (!reg) { c->err = "ingvio_gnss_frame_stage_nominal: no GNSS scalars registered for the filter (ingvio_nominal_set_gnss)"; return INGVIO_E_ARG; }
+        // every column the kernels will name, from the mirror (the frame's stage has put the new clone there; its 6 columns are appended
+        // by the run): [idx, idx + size) inside the state at update time, clear of the clone that leaves, and inside the state behind
+        // the marginalisation once shifted - whichever of the two orders the run takes
+        const int var_idx[7] = { nom_idx_of(c, b, I[NOM_V_POSE]), nom_idx_of(c, b, I[NOM_GNSS + NOM_G_YOF]), nom_idx_of(c, b, I[NOM_GNSS + NOM_G_FS]),
+                                 nom_idx_of(c, b, I[NOM_GNSS + 0]), nom_idx_of(c, b, I[NOM_GNSS + 1]), nom_idx_of(c, b, I[NOM_GNSS + 2]),
+                                 nom_idx_of(c, b, I[NOM_GNSS + 3]) };
+        if (var_idx[0] < 0 || var_idx[1] < 0 || var_idx[2] < 0) {
+            c->err = "ingvio_gnss_frame_stage_nominal: the extended pose, YOF or FS is not in the table"; return INGVIO_E_NOT_IN_STATE;
+        }
+        const int n_upd = std::min(c->d.n_max, c->h_n[b] + 6), mg = c->st_marg[b];
+        int hi = 0;
+        for (int q = 0; q < 7; ++q) {
+            const int lo = var_idx[q], sz = q == 0 ? 9 : 1;
+            if (lo < 0) continue;                    // (a constellation without a clock in the state)
+            bool ok = lo + sz <= n_upd;
+            if (ok && mg >= 0) ok = (lo + sz <= mg || lo >= mg + 6) && (lo > mg ? lo - 6 : lo) + sz <= n_upd - 6;
+            if (!ok) { c->err = "ingvio_gnss_frame_stage_nominal: a GNSS column lies outside the state the update will see"; return INGVIO_E_NOT_IN_STATE; }
+            hi = std::max(hi, lo + sz);
+        }
+        f.idx_se23 = var_idx[0]; f.idx_yof = var_idx[1]; f.idx_fs = var_idx[2];
+        for (int s = 0; s < 4; ++s) f.idx_cb[s] = var_idx[3 + s];
+        his[i] = hi;
+        smax = std::max(smax, e.n_sat);
+    }
+    // ---- from here on only HIP errors: buffers (first call), then the uploads on the compute stream, behind the kernels of the frame
+    //      enqueued last that may still read them ----
+    if (int rc = gnss_front_upload(c, b0, nb, full.data(), o, true)) return rc;
+    if (!g.W) {
+        const size_t B = c->d.batch, ws = (size_t)c->ldp * 16;
+        if (dalloc(c, &g.W, B * ws) | dalloc(c, &g.Yf, B * ws)) return INGVIO_E_HIP;
+    }
+    for (int i = 0; i < nb; ++i) g.hi[b0 + i] = his[i];
+    g.gate_rows = o->gate_rows ? 1 : 0; g.strong = o->strong_reject ? 1 : 0;
+    g.thr1 = o->gate_rows ? o->chi2_table[1] : __builtin_inf();
+    g.m_cap = 2 * smax; g.nc_max = 15;            // (no satellite anywhere: m_cap = 0, the frame runs alone)
+    // (results / fused_last / own_status belong to the update that ran last: ingvio_gnss_fetch of the frame before stays valid)
+    g.in_frame = true; g.nominal = true; g.nom_pending = false; g.frame_nom = true; g.nom_b0 = b0; g.nom_nb = nb;
+    g.staged = true;
+    return last_launch(c);
+}
+
+int ingvio_debug_gnss_fused_last(ingvio_ctx* c) { return c ? (c->gn.fused_last && c->gn.results ? (c->gn.folded_last ? 2 : 1) : 0) : INGVIO_E_ARG; }
 
 // gnss_comm::sat_states + psr_res + dopp_res for an arbitrary list of epochs, detached from the filters of the context and from
 // the staged update rows: what GvioAligner::batchAlign (GvioAligner.cpp:88-383) and gnss_comm::psr_pos (gnss_spp.cpp:148-254)
@@ -2068,7 +2179,7 @@ int ingvio_gnss_run(ingvio_ctx* c, int b0, int nb)
 static int gnss_run_separate(ingvio_ctx* c, int b0, int nb, bool own_slots)
 {
     auto& g = c->gn;
-    g.fused_last = own_slots;
+    g.fused_last = own_slots; g.folded_last = false;
     g.results = true;
     int n_cap = 0;
     for (int i = 0; i < nb; ++i) {
@@ -3596,6 +3707,41 @@ int ingvio_nominal_box_plus(ingvio_ctx* c, int b0, int nb, const double* dx)
     return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
 }
 
+// Test hook: k_nominal_update_post alone on the TABLE of filters [b0, b0 + nb) - boxPlus of dx [nb][ldp] given in the index space behind
+// the marginalisation of marg_idx[i] (a window clone, >= 0), then the drop and the shift.  The covariance is not touched: the caller
+// compares the table with its host model and discards the context.
+int ingvio_debug_nominal_update_post(ingvio_ctx* c, int b0, int nb, const double* dx, const int* marg_idx)
+{
+    ENTER(c);
+    if (phase_busy(c) || check_range(c, b0, nb) || !dx || !marg_idx) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    if (!m.vmax || m.pending || gnss_nom_busy(c, "ingvio_debug_nominal_update_post")) return INGVIO_E_ARG;
+    static const int size_of[5] = { 9, 6, 3, 1, 3 };
+    for (int i = 0; i < nb; ++i) {
+        const int* I = &m.h_ih[(size_t)(b0 + i) * m.ir];
+        const int* var = I + NOM_IH;
+        const int mg = marg_idx[i];
+        bool clone = false;
+        for (int q = 0; q < I[NOM_N_CLONES]; ++q) if (mg >= 0 && var[4 * I[NOM_CLONES + q] + 1] == mg) clone = true;
+        if (!clone) return INGVIO_E_NOT_IN_STATE;
+        for (int v = 0; v < I[NOM_N_VAR]; ++v) {                       // every word of dx a lane will read lies inside the row
+            const int kind = var[4 * v], idx = var[4 * v + 1];
+            if (kind == NOM_KIND_NONE || idx == mg) continue;
+            if (kind < 0 || kind > NOM_KIND_LM || idx < 0 || (idx > mg ? idx - 6 : idx) + size_of[kind] > c->ldp) return INGVIO_E_NOT_IN_STATE;
+        }
+    }
+    int* d_marg = nullptr;
+    HIPCHK(c, hipMalloc((void**)&d_marg, sizeof(int) * (size_t)c->d.batch));
+    int rc = up(c, d_marg + b0, marg_idx, sizeof(int) * (size_t)nb) | up(c, m.dx + (size_t)b0 * c->ldp, dx, 8 * (size_t)nb * c->ldp);
+    if (!rc) launch_nominal_update_post(nom_table(c), m.dx, c->ldp, d_marg, b0, nb, c->st);
+    hipStreamSynchronize(c->st);                                        // (pageable sources, the temporary)
+    hipFree(d_marg);
+    if (rc) return INGVIO_E_HIP;
+    if (int rc2 = last_launch(c)) return rc2;
+    for (int i = 0; i < nb; ++i) nom_mirror_marg(c, b0 + i, marg_idx[i]);
+    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
+}
+
 // the table slots of the GNSS scalars (State::GNSSType order: clock GPS, GLO, GAL, BDS, FS, YOF); they live in the integer record
 int ingvio_nominal_set_gnss(ingvio_ctx* c, int b0, int nb, const int* slots)
 {
@@ -4054,6 +4200,16 @@ static int frame_run_whole(ingvio_ctx* c, int restore_prior)
     const bool lm_oop = with_lm && c->method == 1;
     // in-frame GNSS stage (ingvio_gnss_opts::in_frame): on the MSCKF write-back when everything fits one sweep, else as its own pass below
     const bool gnss_here = gnss_in_frame(c), gnss_fuse = fuse && gnss_folds(c);
+    // the raw epoch of a frame staged from the table (ingvio_gnss_frame_stage_nominal): its own result slots and status words, cleared here
+    // (dx = 0 beyond the live n, for a filter without epoch and where no satellite was staged at all) - as the two-call form's run does
+    const bool gnss_nomf = c->gn.staged && c->gn.frame_nom;
+    if (gnss_nomf) {
+        auto& g = c->gn;
+        HIPCHK(c, hipMemsetAsync(g.dxf, 0, 8 * (size_t)B * c->ldp, c->st));
+        HIPCHK(c, hipMemsetAsync(g.stf, 0, sizeof(int) * (size_t)B, c->st));
+        HIPCHK(c, hipMemsetAsync(g.mf, 0, sizeof(int) * (size_t)B, c->st));
+        g.own_status = true; g.results = true; g.fused_last = true; g.folded_last = false;
+    }
     int rc = fuse     ? run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, c->d_idx, 6, 0, gnss_fuse)
              : lm_oop ? run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, c->d_zero_idx, 0)
                       : run_msckf(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used);      // (method 0: the dense path)
@@ -4077,7 +4233,10 @@ static int frame_run_whole(ingvio_ctx* c, int restore_prior)
     const bool all_marg = mirror_marg(c);
     if (c->nom.pending) {                          // device nominal state: boxPlus with the frame's dx, drop + shift, behind the marginalisation
         // (with landmarks from the table the frame's dx is on the table already: the LANDMARK update's dx, in the same index space)
-        launch_nominal_update(nom_table(c), lm_nom ? c->lm.dx : c->d_dx, c->ldp, c->d_idx, 0, B, c->st);
+        // (with the GNSS epoch folded into the write-back the MSCKF dx is on the table too, and the GNSS dx is given in the index space
+        // behind the marginalisation: retraction through the shift, drop and shift in one launch)
+        if (gnss_nomf && gnss_fuse) launch_nominal_update_post(nom_table(c), c->gn.dxf, c->ldp, c->d_idx, 0, B, c->st);
+        else launch_nominal_update(nom_table(c), lm_nom ? c->lm.dx : c->d_dx, c->ldp, c->d_idx, 0, B, c->st);
         if (int rc2 = last_launch(c)) return rc2;
         for (int b = 0; b < B; ++b) nom_mirror_marg(c, b, c->st_marg[b]);
         c->nom.pending = false;
@@ -4085,10 +4244,22 @@ static int frame_run_whole(ingvio_ctx* c, int restore_prior)
     }
     strips_after_step(c, fuse && all_marg && restore_prior);
     if (gnss_here && !gnss_fuse) {                 // not foldable (large window, landmarks in the frame, many rows): its own pass, now
+        if (gnss_nomf) {
+            // from the table: ingvio_gnss_front_stage_nominal + ingvio_gnss_run behind the frame, launch for launch - the front on the
+            // table the frame has just left (idx behind the shift), the pass with its own slots, boxPlus of its dx
+            for (int b = 0; b < B; ++b) { int& hi = c->gn.hi[b]; if (c->st_marg[b] >= 0 && hi > c->st_marg[b]) hi -= 6; }
+            gnss_front_launch(c, 0, B, true, c->st);
+        }
         rc = gnss_run_separate(c, 0, B, true);
         if (rc) return rc;
+        if (gnss_nomf) {
+            launch_nominal_update(nom_table(c), c->gn.dxf, c->ldp, nullptr, 0, B, c->st);
+            if (int rc2 = last_launch(c)) return rc2;
+            if (nom_mark(c)) return INGVIO_E_HIP;
+        }
     }
     consume_in_frame(c->gn.staged, c->gn.in_frame, restore_prior != 0);
+    if (!c->gn.staged) c->gn.frame_nom = false;
     return release_input_set(c);
 }
 
@@ -4101,11 +4272,13 @@ static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
         if (phase) { c->err = "the split step does not take a frame staged from the device nominal state"; return INGVIO_E_UNSUPPORTED; }
         if (restore_prior) { c->err = "restore_prior with a frame staged from the device nominal state (restore with ingvio_cov_restore before the stage)"; return INGVIO_E_ARG; }
         // (the one in-frame stage it takes is the landmark stage from the table itself, ingvio_landmark_stage_nominal)
-        if ((c->gn.staged && c->gn.in_frame) || (lm_in_frame(c) && !c->lm.nominal) || c->parts_req > 1) {
+        if ((c->gn.staged && c->gn.in_frame && !c->gn.frame_nom) || (lm_in_frame(c) && !c->lm.nominal) || c->parts_req > 1) {
             c->err = "the device nominal state takes no in-frame GNSS / host-fed landmark stage and frame_parts = 1 only"; return INGVIO_E_UNSUPPORTED;
         }
     } else if (lm_in_frame(c) && c->lm.nominal) {
         c->err = "an in-frame landmark stage from the device nominal state needs a frame staged from it"; return INGVIO_E_ARG;
+    } else if (c->gn.staged && c->gn.frame_nom) {
+        c->err = "a GNSS epoch staged for a frame from the device nominal state needs that frame"; return INGVIO_E_ARG;
     }
     if (phase && c->method != 1) return INGVIO_E_UNSUPPORTED;             // the split needs the information form's [A | b]
     // protocol of the split step: 1 -> (ingvio_debug_msckf_info / ingvio_info_set) -> 2, exactly once each; the accepted-feature

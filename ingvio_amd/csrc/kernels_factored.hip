@@ -1346,6 +1346,40 @@ __global__ __launch_bounds__(256) void k_post_cols(CovView cv, int b0, const dou
 }
 
 // ---------------------------------------------------------------------------------------------
+// dx = Pc t of the MSCKF update BEFORE the write-back forms it (k_info_apply writes the same words into dx again): the frame whose GNSS
+// rows are formed on the device at the state after the MSCKF update retracts the nominal table with it between the solve
+// and k_post_cols.  One thread per state row, in the prior's index space; the sums run in k_info_apply's order (four interleaved
+// partial sums added as (0 + 1) + (2 + 3); the rows of the clone about to leave: one running sum).  A filter without MSCKF rows
+// keeps the zeros the solve wrote.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_info_dx(CovView cv, int b0, int MP, const double* __restrict__ Mall, int mstride, const double* __restrict__ Pcall,
+                                                 int ystride, const int* __restrict__ m_all, const int* __restrict__ pc_base,
+                                                 const int* __restrict__ marg_idx, int msize, double* __restrict__ dx_all)
+{
+    const int bl = blockIdx.y, b = b0 + bl;
+    if (m_all[bl] == 0) return;
+    const int n = cv.n[b], ld = cv.ldp, r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    const double* P = cov_ptr(cv, b);
+    const int pcb = pc_base[bl];
+    const double* Pc = pcb >= 0 ? P + (size_t)pcb * ld : Pcall + (size_t)bl * ystride;
+    const double* tvec = Mall + (size_t)bl * mstride + (size_t)MP * MP;
+    const int midx = marg_idx ? marg_idx[bl] : -1;
+    double d;
+    if (midx >= 0 && r >= midx && r < midx + msize) {
+        d = 0.0;
+        for (int k = 0; k < MP; ++k) d += Pc[r + (size_t)k * ld] * tvec[k];
+    } else {
+        double p[4] = { 0.0, 0.0, 0.0, 0.0 };
+        for (int k4 = 0; k4 < MP / 4; ++k4)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) p[q] += Pc[r + (size_t)(4 * k4 + q) * ld] * tvec[4 * k4 + q];
+        d = (p[0] + p[1]) + (p[2] + p[3]);
+    }
+    dx_all[(size_t)b * ld + r] = d;
+}
+
+// ---------------------------------------------------------------------------------------------
 template <int CMAX, bool STEREO>
 static void launch_ft(const FactoredLaunch& L, hipStream_t st)
 {
@@ -1454,6 +1488,12 @@ int launch_factored(const FactoredLaunch& L, hipStream_t st)
     if (L.fv.cmax > 16) return launch_bigwin(L, st);          // large windows: kernels_bigwin.hip
     const int cm_sel = (L.c_used > 0 && L.c_used <= L.fv.cmax) ? L.c_used : L.fv.cmax;      // window class by the frames (launch_factored.h)
     const int ncm = 6 * cm_sel;
+    if (L.stage == 10) {                                      // dx of the MSCKF update ahead of the write-back (k_info_dx)
+        const int MP = ncm <= 36 ? 36 : (ncm <= 66 ? 68 : (ncm <= 72 ? 72 : 96));      // (NC + 3) & ~3 of the class stage 2 and 3 take
+        hipLaunchKernelGGL(k_info_dx, dim3((L.n_cap + 255) / 256, L.nb), dim3(256), 0, st, L.cv, L.b0, MP, L.T, L.mstride, L.Pc, L.ystride, L.m_out,
+                           L.pc_base, L.marg_idx, L.marg_size, L.dx);
+        return 0;
+    }
     if (L.stage == 4) {                                       // columns of the posterior for an in-frame GNSS update (between stages 2 and 3)
         const int nt = (L.n_cap + 15) / 16;
 #define POSTCOLS_DISPATCH(NC)                                                                                           \

@@ -128,6 +128,76 @@ __global__ __launch_bounds__(64) void k_nominal_update(NomTable t, const double*
     }
 }
 
+// The trailing retraction of a frame whose in-frame GNSS update rode on the MSCKF write-back: boxPlus of a dx given
+// in the index space AFTER the frame's marginalisation, then the drop and the shift of k_nominal_update<true>, in one launch.  The
+// table's idx are still those before the marginalisation, so every lane maps its idx (a landmark lane also its anchor's) through the
+// shift before it reads dx; the clone that leaves has no entry in dx and is not retracted.  A kernel of its own beside
+// k_nominal_update - the same formulas, written out again - so that the instantiations above keep their code and registers.
+__global__ __launch_bounds__(64) void k_nominal_update_post(NomTable t, const double* __restrict__ dx, int ldx, const int* __restrict__ marg, int b0)
+{
+    const int b = b0 + blockIdx.x, lane = threadIdx.x;
+    int* I = t.ih + (size_t)b * t.ir;
+    int* var = I + NOM_IH;
+    double* D = t.dv + (size_t)b * t.dr + NOM_DH;
+    const double* d = dx + (size_t)b * ldx;
+    const int nv = I[NOM_N_VAR];
+    const int m = marg[b];
+    auto post = [m](int i) { return (m >= 0 && i > m) ? i - 6 : i; };    // idx before the marginalisation -> idx behind it
+    for (int v = lane; v < nv; v += 64) {
+        const int kind = var[4 * v], idx = var[4 * v + 1];
+        if (kind == NOM_KIND_NONE || idx == m) continue;                 // (idx == m: the clone that leaves)
+        const double* dv = d + post(idx);
+        double* x = D + (size_t)v * NOM_VD;
+        if (kind == NOM_KIND_SE23 || kind == NOM_KIND_SE3) {
+            double G0[9], G1[9], R[9], t1[3], t2[3];
+            gamma01(dv, G0, G1);
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) R[3 * i + j] = G0[3 * i] * x[j] + G0[3 * i + 1] * x[3 + j] + G0[3 * i + 2] * x[6 + j];
+            mulv(G0, x + 9, t1); mulv(G1, dv + 3, t2);
+            for (int i = 0; i < 9; ++i) x[i] = R[i];
+            for (int i = 0; i < 3; ++i) x[9 + i] = t1[i] + t2[i];
+            if (kind == NOM_KIND_SE23) {
+                mulv(G0, x + 12, t1); mulv(G1, dv + 6, t2);
+                for (int i = 0; i < 3; ++i) x[12 + i] = t1[i] + t2[i];
+            }
+        } else if (kind == NOM_KIND_VEC3) {
+            for (int i = 0; i < 3; ++i) x[9 + i] = x[9 + i] + dv[i];
+        } else if (kind == NOM_KIND_SCALAR) {
+            x[9] = x[9] + dv[0];
+        } else if (kind == NOM_KIND_LM) {
+            const int as = var[4 * v + 2], a = as >= 0 ? var[4 * as + 1] : -1;
+            if (a < 0 || a == m) {                                       // no live anchor (a stage refuses a landmark on the leaving clone)
+                for (int i = 0; i < 3; ++i) x[9 + i] = x[9 + i] + dv[i];
+                continue;
+            }
+            double G0[9], G1[9], t1[3], t2[3];
+            gamma01(d + post(a), G0, G1);
+            mulv(G0, x + 9, t1); mulv(G1, dv, t2);
+            for (int i = 0; i < 3; ++i) x[9 + i] = t1[i] + t2[i];
+        }
+    }
+    if (m < 0) return;
+    __shared__ int s_drop;
+    if (lane == 0) {                                                     // the window list closes up over the clone that leaves
+        const int nc = I[NOM_N_CLONES];
+        int w = 0, drop = -1;
+        for (int q = 0; q < nc; ++q) {
+            const int s = I[NOM_CLONES + q];
+            if (drop < 0 && var[4 * s + 1] == m) { drop = s; continue; }
+            I[NOM_CLONES + w++] = s;
+        }
+        I[NOM_N_CLONES] = w;
+        s_drop = drop;
+    }
+    __syncthreads();                                                     // every lane has read the idx it needed (its own, its anchor's)
+    const int drop = s_drop;
+    for (int v = lane; v < nv; v += 64) {
+        if (var[4 * v] == NOM_KIND_NONE) continue;
+        if (v == drop) { var[4 * v] = NOM_KIND_NONE; var[4 * v + 1] = -1; var[4 * v + 2] = -1; }
+        else if (var[4 * v + 1] > m) var[4 * v + 1] -= 6;
+    }
+}
+
 void launch_nominal_update(const NomTable& t, const double* dx, int ldx, const int* marg, int b0, int nb, hipStream_t st)
 {
     if (marg) hipLaunchKernelGGL(k_nominal_update<true>, dim3(nb), dim3(64), 0, st, t, dx, ldx, marg, b0, NomGather{});
@@ -137,4 +207,9 @@ void launch_nominal_update(const NomTable& t, const double* dx, int ldx, const i
 void launch_nominal_gather(const NomTable& t, const double* dx, int ldx, const NomGather& g, int b0, int nb, hipStream_t st)
 {
     hipLaunchKernelGGL((k_nominal_update<false, true>), dim3(nb), dim3(64), 0, st, t, dx, ldx, (const int*)nullptr, b0, g);
+}
+
+void launch_nominal_update_post(const NomTable& t, const double* dx, int ldx, const int* marg, int b0, int nb, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_nominal_update_post, dim3(nb), dim3(64), 0, st, t, dx, ldx, marg, b0);
 }

@@ -49,6 +49,7 @@ struct FactoredLaunch {
                           // The kernels are instantiated per window CLASS (6 / 11 / 16 clones); the class follows the frames, not the
                           // context's capacity: a filter configured for 11 + 1 clones (the shim allocates max_sliding_window_poses + 1)
                           // otherwise ran every update on the 16-clone class - Gauss-Jordan solve, one-feature-per-wave gate
+    // stage 10 (windows up to 16 clones, between stages 2 and 3): dx of the MSCKF update before the write-back forms it (k_info_dx)
     // in-frame GNSS update (windows up to 16 clones): stage 4 = k_post_cols writes gW [nb][gWstride] (columns gcolmap of the posterior);
     // stage 3 with gY != nullptr folds the rank-16 downdate Yg Yg^T (gm[bl] rows, 0 = none) into the same sweep
     const int* gcolmap;

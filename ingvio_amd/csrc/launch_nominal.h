@@ -25,6 +25,9 @@ struct NomTable {
 // StateManager::boxPlus (StateManager.cpp:244-251) of filters [b0, b0 + nb) with dx [b][ldx] (row b of the batch); marg != nullptr: then
 // drop the variable whose idx is marg[b] (a window clone, >= 0) and shift every later idx by 6 (StateManager.cpp:155-192)
 void launch_nominal_update(const NomTable& t, const double* dx, int ldx, const int* marg, int b0, int nb, hipStream_t st);
+// the same end state from a dx given in the index space BEHIND the marginalisation (marg[b] >= 0; a frame whose in-frame GNSS update rode on
+// the write-back): each variable reads dx at its shifted idx, the clone that leaves reads nothing, then drop and shift (k_nominal_update_post)
+void launch_nominal_update_post(const NomTable& t, const double* dx, int ldx, const int* marg, int b0, int nb, hipStream_t st);
 
 // The landmark update's staged inputs (LmView, launch_lmbatch.h) filled from the table: per filter the extended pose and the extrinsics
 // into pose [B][24] and their idx into idx [B][2], and for each of the n_lm[b] staged landmarks (slot [B][lmax]: its table slot)

@@ -18,6 +18,12 @@ reported twice: *_abi_ms_per_frame, the time spent INSIDE the library's calls (w
 *_wall_ms_per_frame with this harness' Python between the calls (for the round-trip form mostly the conversion of 512 fetched tables
 into epoch structures).  device_loop_ms_per_frame is the device form free-running, without the per-frame synchronisation.  The GNSS
 modes write $RESULTS/closed_loop_bench_gnss.json.
+--gnss-in-frame: the epoch staged WITH its frame (ingvio_gnss_frame_stage_nominal) next to the two-call device form above, on the same
+build in one run; 8 satellites per filter (--sats) and the GNSS scalars in front of the clones, so that the in-frame update rides on the
+MSCKF write-back,
+  in-frame form    run(i); stage_async(i+1); gnss_frame_stage_nominal(i+1); fetch_begin(i); run(i+1); fetch_end(i)
+Each form free-running (<form>_loop_ms_per_frame) and synchronised per frame (<form>_abi / _wall_ms_per_frame), the two-call form
+first, then the in-frame form, then the two-call form again (its spread); writes $RESULTS/closed_loop_bench_gnss_in_frame.json.
 --register-only: the loop without epochs but with the GNSS scalars registered, i.e. the clock recursion of k_imu_steps<true> switched on
 (against the plain run: that kernel's time with and without registered clocks).
 --landmarks L: every filter carries L in-state landmarks that are observed in every frame (ingvio_amd/closed_loop_lm.py), two forms on
@@ -36,7 +42,7 @@ ALL landmarks change their anchor to the newest clone, two forms on the same bui
 measured and reported as the GNSS forms are; writes $RESULTS/closed_loop_bench_tail.json.
 Writes $RESULTS/closed_loop_bench.json (RESULTS defaults to results/) and prints one JSON line.
 usage: python tools/closed_loop_bench.py [--batch 512] [--features 150] [--window 11] [--k 10] [--frames 30] [--warmup 5] [--device-only]
-                                         [--gnss | --register-only | --landmarks L | --tail [--landmarks L]]"""
+                                         [--gnss | --gnss-in-frame [--sats 8] | --register-only | --landmarks L | --tail [--landmarks L]]"""
 import argparse
 import copy
 import json
@@ -175,6 +181,36 @@ def main_gnss(a):
     finish(out, "closed_loop_bench_gnss.json")
 
 
+def main_gnss_in_frame(a):
+    from ingvio_amd import synth
+    from ingvio_amd import closed_loop_gnss as cg
+    B, F, NF, W = a.batch, a.features, a.frames, a.warmup
+    z = np.load(os.path.join(ROOT, "tests", "golden", "gnss_front.npz"))
+    t0 = time.perf_counter()
+    cases = cg.make_gnss_loop(z, B, NF, F=F, every=0, ks=(a.k,), windows=(a.window,), scalars_in_front=True, n_sat=a.sats)
+    table = synth.chi2_table()
+    out = dict(batch=B, features=F, window=a.window, k=a.k, frames_timed=NF - W, sats=a.sats, setup_s=round(time.perf_counter() - t0, 1))
+    fresh = lambda: fresh_ctx(a, cases, gnss=True)
+    noms = {}
+    for name, form in (("two_call", cg.GnssForm), ("in_frame", cg.GnssInFrameForm), ("two_call_again", cg.GnssForm)):
+        o = {}
+        ctx = fresh()
+        free_run(o, ctx, cases, form(table), NF, W)
+        out[name + "_loop_ms_per_frame"] = o["device_loop_ms_per_frame"]
+        g = ctx.gnss_fetch()
+        out[name + "_last_epoch_rows_mean"] = float(g[1].mean()); out[name + "_last_epoch_ok"] = int((g[4] == 0).sum())
+        if name == "in_frame":
+            out["in_frame_folded"] = ctx.debug_gnss_fused_last() == 2
+        noms[name] = ctx.nominal_get()
+        ctx.close()
+        if not a.device_only:
+            ctx = fresh()
+            synced_run(out, name, ctx, cases, form(table), NF, W)
+            ctx.close()
+    out["max_abs_pose_in_frame_vs_two_call"] = max(float(np.max(np.abs(d["val"][0] - r["val"][0]))) for d, r in zip(noms["in_frame"], noms["two_call"]))
+    finish(out, "closed_loop_bench_gnss_in_frame.json")
+
+
 def main_landmarks(a):
     from ingvio_amd import closed_loop_lm as clm
     B, F, NF, W, L = a.batch, a.features, a.frames, a.warmup, a.landmarks
@@ -226,6 +262,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--device-only", action="store_true")
     ap.add_argument("--gnss", action="store_true")
+    ap.add_argument("--gnss-in-frame", action="store_true", help="the epoch staged with its frame next to the two-call device form")
+    ap.add_argument("--sats", type=int, default=8, help="--gnss-in-frame: satellites per epoch (at most 8 for the fold)")
     ap.add_argument("--register-only", action="store_true", help="the loop without epochs, the GNSS scalars registered (clock recursion on)")
     ap.add_argument("--landmarks", type=int, default=0, help="L in-state landmarks per filter, updated in every frame")
     ap.add_argument("--tail", action="store_true", help="the oldest clone leaves and every landmark changes its anchor behind every frame")
@@ -234,6 +272,8 @@ def main():
         return main_tail(a)
     if a.landmarks > 0:
         return main_landmarks(a)
+    if a.gnss_in_frame:
+        return main_gnss_in_frame(a)
     if a.gnss or a.register_only:
         return main_gnss(a)
     from ingvio_amd import closed_loop as cl
