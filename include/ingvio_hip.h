@@ -773,6 +773,14 @@ int ingvio_frame_run(ingvio_ctx* ctx, int restore_prior);
  * 2..4 slices.  Windows up to 16 clones, factored method, no in-frame landmark stage.  The reference has no counterpart (one filter,
  * one thread: IngvioNode.cpp:36).  Environment override at context creation: INGVIO_FRAME_PARTS. */
 int ingvio_set_frame_parts(ingvio_ctx* ctx, int parts);
+/* The Gram kernel of the unsplit ingvio_frame_run in its reduced form: windows up to 12 clones solve gauge-reduced, with
+ * the newest clone (slot n_clones - 1) as the reference whose block row and column of A the solve deletes, so the kernel does not form
+ * them.  Every entry the solve reads is the same sum in the same order: results are bit-identical to the full form
+ * (tests/test_gpu_gram_reduced.py).  on: 1 (the default) / 0 the full form everywhere, for comparison.  ingvio_msckf_update*,
+ * ingvio_frame_run_phase, the split step, the Selected-timestamp variant, the dense method and windows of more than 12 clones always
+ * take the full form.  After a step whose Gram kernel ran reduced ingvio_debug_msckf_info returns INGVIO_E_UNSUPPORTED.
+ * Environment override at context creation: INGVIO_GRAM_REDUCED (0 / 1). */
+int ingvio_set_gram_reduced(ingvio_ctx* ctx, int on);
 int ingvio_frame_fetch(ingvio_ctx* ctx, int b0, int nb, double* dx_out, int* accepted, int* rows_out);
 /* The fetch in two halves (round 6): _begin enqueues the result copies (into pinned memory) behind the frame's kernels and returns;
  * _end waits for them and fills the caller's arrays.  In between the host may stage and LAUNCH the next frame - its kernels queue up
@@ -782,7 +790,9 @@ int ingvio_frame_fetch_end(ingvio_ctx* ctx, double* dx_out, int* accepted, int* 
 
 /* parity hook (tests): the stacked measurement information of filter b's LAST MSCKF update, A_out [ncol][ncol+1] row-major =
  * [sum_j H_j^T H_j | sum_j H_j^T r_j] over the used features in window-slot column order, ncol = 6 * n_clones (caller provides
- * (6 c_max) * (6 c_max + 1) doubles).  Factored method: the gram kernel's partial sums; dense method: R^T R from the TSQR factor. */
+ * (6 c_max) * (6 c_max + 1) doubles).  Factored method: the gram kernel's partial sums; dense method: R^T R from the TSQR factor.
+ * INGVIO_E_UNSUPPORTED after an ingvio_frame_run whose Gram kernel ran in reduced form (ingvio_set_gram_reduced): the partials then
+ * lack the reference clone's block row and column. */
 int ingvio_debug_msckf_info(ingvio_ctx* ctx, int b, double* A_out, int* ncol_out);
 
 /* parity hook (tests): [M | t] of filter b's last factored update as the solve kernel left it (MP x MP row-major + MP, MP = 6 * window class

@@ -210,6 +210,8 @@ struct ingvio_ctx {
     PartStream part[4];
     int parts_alloc = 0;
     int parts_req = -1;                 // ingvio_set_frame_parts: -1 automatic, 1 off, 2..4 forced
+    int gram_reduced = 1;               // ingvio_set_gram_reduced: the fused frame step may run k_feat_gram2 in its reduced form
+    int gram_red_last = 0;              // the chunk partials in d_Rpart come from a reduced Gram launch (ingvio_debug_msckf_info refuses them)
     bool split_pending = false;         // slices of the last split step may still be running on their own streams
     hipEvent_t tok_last = nullptr;      // end of the throughput segment issued last (nullptr: none yet / chain broken)
     hipEvent_t ev_split_fork = nullptr;
@@ -849,8 +851,10 @@ static int gnss_in_frame_launch(ingvio_ctx* c, int b0, int nb, FactoredLaunch& L
     return 0;
 }
 
+// frame_step: the call is the fused frame step (ingvio_frame_run, unsplit) - nothing reads the chunk partials but the solve below, so
+// the Gram stage may take its reduced form (FactoredLaunch::gram_red); every other caller leaves the full [A | b] in d_Rpart
 int run_msckf_factored(ingvio_ctx* c, int b0, int nb, const MsckfOpts& op, int stereo, int fmax_used,
-                       const int* marg_idx = nullptr, int marg_size = 0, int phase = 0, bool gnss_fuse = false)
+                       const int* marg_idx = nullptr, int marg_size = 0, int phase = 0, bool gnss_fuse = false, bool frame_step = false)
 {
     FactoredLaunch L;
     memset(&L, 0, sizeof L);
@@ -910,7 +914,10 @@ int run_msckf_factored(ingvio_ctx* c, int b0, int nb, const MsckfOpts& op, int s
             }
             if (grc) return INGVIO_E_UNSUPPORTED;
         }
+        c->gram_red_last = 0;
+        L.gram_red = frame_step && phase == 0 && c->gram_reduced; L.gram_was_red = &c->gram_red_last;
         { ProfScope p(c, PF_GRAM); L.stage = 1; launch_factored(L, c->run_st); }
+        L.gram_was_red = nullptr;
         if (c->tok_rec) HIPCHK(c, hipEventRecord(c->tok_rec, c->run_st));
     }
     if (forked) {
@@ -943,6 +950,7 @@ int run_msckf_factored(ingvio_ctx* c, int b0, int nb, const MsckfOpts& op, int s
 int run_msckf(ingvio_ctx* c, int b0, int nb, const MsckfOpts& op, int stereo, int fmax_used)
 {
     if (c->method == 1) return run_msckf_factored(c, b0, nb, op, stereo, fmax_used);
+    c->gram_red_last = 0;
     MsckfLaunch L;
     memset(&L, 0, sizeof L);
     L.stereo = stereo; L.cv = view(c); L.fv = fview(c); L.op = op; L.b0 = b0; L.nb = nb;
@@ -1129,6 +1137,7 @@ int ingvio_ctx_create(const ingvio_ctx_desc* desc, ingvio_ctx** out)
     } else c->st = (hipStream_t)desc->stream;
     c->run_st = c->st;
     if (const char* e = getenv("INGVIO_FRAME_PARTS")) c->parts_req = atoi(e);
+    if (const char* e = getenv("INGVIO_GRAM_REDUCED")) c->gram_reduced = atoi(e) != 0;      // A/B timing of an unchanged program
     if (desc->c_max > 16) {
         // a higher priority than the compute stream's default: its short dependent launches take the slots the gate's workgroups free
         int lo = 0, hi = 0;
@@ -4210,8 +4219,8 @@ static int frame_run_whole(ingvio_ctx* c, int restore_prior)
         HIPCHK(c, hipMemsetAsync(g.mf, 0, sizeof(int) * (size_t)B, c->st));
         g.own_status = true; g.results = true; g.fused_last = true; g.folded_last = false;
     }
-    int rc = fuse     ? run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, c->d_idx, 6, 0, gnss_fuse)
-             : lm_oop ? run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, c->d_zero_idx, 0)
+    int rc = fuse     ? run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, c->d_idx, 6, 0, gnss_fuse, true)
+             : lm_oop ? run_msckf_factored(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used, c->d_zero_idx, 0, 0, false, true)
                       : run_msckf(c, 0, B, c->st_op, c->st_stereo, c->st_fmax_used);      // (method 0: the dense path)
     if (rc) return rc;
     if (lm_oop) {
@@ -4318,6 +4327,14 @@ int ingvio_set_frame_parts(ingvio_ctx* c, int parts)
     if (!c || parts < -1 || parts > 4) return INGVIO_E_ARG;
     ENTER(c);
     c->parts_req = parts == 0 ? 1 : parts;
+    return INGVIO_OK;
+}
+// the fused frame step's Gram kernel in its reduced form, on by default; off: the full form everywhere, for comparison
+int ingvio_set_gram_reduced(ingvio_ctx* c, int on)
+{
+    if (!c) return INGVIO_E_ARG;
+    ENTER(c);
+    c->gram_reduced = on ? 1 : 0;
     return INGVIO_OK;
 }
 int ingvio_frame_run_phase(ingvio_ctx* c, int restore_prior, int phase)
@@ -4451,6 +4468,10 @@ int ingvio_debug_msckf_info(ingvio_ctx* c, int b, double* A_out, int* ncol_out)
 {
     ENTER(c);
     if (check_range(c, b, 1) || !A_out || !ncol_out) return INGVIO_E_ARG;
+    if (c->method == 1 && c->gram_red_last) {      // the reference clone's block row / column of the partials was not written
+        c->err = "the last frame step formed [A | b] in reduced form; run it with ingvio_set_gram_reduced(ctx, 0) to read the full [A | b]";
+        return INGVIO_E_UNSUPPORTED;
+    }
     int C = 0;
     if (down_sync(c, &C, c->d_nclones + b, sizeof(int))) return INGVIO_E_HIP;
     const int ncol = 6 * C;

@@ -102,11 +102,19 @@ __device__ __forceinline__ double gram_rsqrt(double x)
     e = fma(-x * y, y, 1.0);
     return fma(y * e, 0.5, y);
 }
-template <int CMAX>
+// RED (the fused frame step in front of the gauge-reduced solve, k_info_solve<.., true>): that solve deletes the block row and column of
+// its reference clone - slot C - 1 of the filter, known before this kernel starts - and that clone's six entries of b.  The operand
+// panel then carries the slots below the reference only, 6 (CMAX - 1) columns, with the hs column behind them: class 11 has 4 x 4
+// tile columns and 10 upper tiles (three accumulators per wave) instead of 5 x 5 and 15 (four), class 6 has 3 tiles instead of 6,
+// class 12 keeps its 15.  Every retained element of [A | b] is the same sum over the same stacked rows in the same order, only in
+// another tile: bit-identical to the full form.  The reference clone's block row / column of the chunk partial is not written.
+template <int CMAX, bool RED = false>
 struct Gram2Cfg {
-    static constexpr int NC = 6 * CMAX;
+    static constexpr int NC = RED ? 6 * (CMAX - 1) : 6 * CMAX;      // operand-panel columns of the slots; the hs column sits at NC
     static constexpr int TI = (NC + 15) / 16;              // tiles over rows of A (columns of Y)
     static constexpr int TJ = (NC + 1 + 15) / 16;          // tiles over columns of [A | b]
+    // (measured and not taken: the reduced class-11 panel's row stride of 64 doubles puts the four stacked rows of a fragment read on
+    // the same LDS banks - SQ_LDS_BANK_CONFLICT 3.4 M -> 5.6 M per launch; padding it to 80 gave 83.35 against 83.5 us, inside sigma 0.9)
     static constexpr int LDW = 16 * TJ;
     static constexpr int NTILE = TI * TJ;
     static constexpr int NUP = TI * TJ - TI * (TI - 1) / 2;   // tiles (ti <= tj): the rank-3 Gram is symmetric
@@ -114,39 +122,46 @@ struct Gram2Cfg {
     static constexpr int KR = 3 * GRAM_NB;                 // stacked rows per batch
     static constexpr int SPW = 34;                         // per (feature, slot) sparse scratch: S1 NXs S3 (9 each) s4 s5 (3 each) key
 };
-template <int CMAX>
+template <int CMAX, bool RED = false>
 struct Gram2Batch {
-    using Cfg = Gram2Cfg<CMAX>;
+    using Cfg = Gram2Cfg<CMAX, RED>;
     double Bm[Cfg::KR][Cfg::LDW];
-    double Ym[Cfg::KR][Cfg::LDW];
+#if !GRAM2_ZFORM
+    double Ym[Cfg::KR][Cfg::LDW];            // Y = Ns^-1 B; the Z-form has one operand panel
+#endif
     double sp[CMAX * CMAX <= 128 ? 2 : 1][GRAM_NB][CMAX][Cfg::SPW];      // double-buffered when P3b runs beside the next batch's P2
 };
-template <int CMAX>
+template <int CMAX, bool RED = false>
 struct Gram2Out {
-    using Cfg = Gram2Cfg<CMAX>;
+    using Cfg = Gram2Cfg<CMAX, RED>;
     double A2[Cfg::NC][Cfg::NC + 2];         // rank-3 part (+ hs column), row stride NC+2
     double S[CMAX][CMAX][34];                // per (slot, anchor) sparse sums: S1 NXs S3 s4 s5
 };
+template <int CMAX, bool RED = false>
+constexpr size_t gram2_lds_bytes()           // the batch view and the epilogue view share the LDS; the feature lists follow
+{
+    return ((std::max(sizeof(Gram2Batch<CMAX, RED>), sizeof(Gram2Out<CMAX, RED>)) + 15) / 16) * 16;
+}
 
-template <int CMAX, bool STEREO>
+template <int CMAX, bool STEREO, bool RED = false>
 __global__ __launch_bounds__(GRAM_NT, 2) void k_feat_gram2(
     FrameView fv, MsckfOpts op, int b0, const int* __restrict__ accept_in, int* __restrict__ used_out,
     double* __restrict__ Apart, int* __restrict__ chunk_used, int G, int rstride)
 {
-    using Cfg = Gram2Cfg<CMAX>;
+    using Cfg = Gram2Cfg<CMAX, RED>;
     constexpr int NC = Cfg::NC, TJ = Cfg::TJ, LDW = Cfg::LDW, NTILE = Cfg::NTILE, TPW = Cfg::TPW, KR = Cfg::KR;
     constexpr int NUP = Cfg::NUP, TI = Cfg::TI, RPO = STEREO ? 4 : 2;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    Gram2Batch<CMAX>& sb = *reinterpret_cast<Gram2Batch<CMAX>*>(smem_raw);
-    Gram2Out<CMAX>& so = *reinterpret_cast<Gram2Out<CMAX>*>(smem_raw);             // epilogue view of the same LDS
-    constexpr size_t UNI = sizeof(Gram2Batch<CMAX>) > sizeof(Gram2Out<CMAX>) ? sizeof(Gram2Batch<CMAX>) : sizeof(Gram2Out<CMAX>);
-    int* sUse = reinterpret_cast<int*>(smem_raw + ((UNI + 15) / 16) * 16);
+    Gram2Batch<CMAX, RED>& sb = *reinterpret_cast<Gram2Batch<CMAX, RED>*>(smem_raw);
+    Gram2Out<CMAX, RED>& so = *reinterpret_cast<Gram2Out<CMAX, RED>*>(smem_raw);             // epilogue view of the same LDS
+    int* sUse = reinterpret_cast<int*>(smem_raw + gram2_lds_bytes<CMAX, RED>());
     int* sList = sUse + fv.fmax;
     __shared__ int sNu;
     __shared__ double sPose[16][12];                              // the window's clone poses: R (9, row-major), p (3)
     // wave as a scalar: the tile coordinates of a wave's accumulators are wave-uniform (see k_feat_gram_big)
     const int bl = blockIdx.y, b = b0 + bl, g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int F = fv.n_feat[b], C = fv.n_clones[b], ncol = 6 * C;
+    const int cref = RED ? C - 1 : -1;                            // the solve's reference clone: no panel columns, no block row / column
     for (int e = tid; e < 12 * C; e += GRAM_NT) {
         const int c = e / 12, q = e - 12 * c;
         sPose[c][q] = q < 9 ? fv.clone_R[((size_t)b * fv.cmax + c) * 9 + q] : fv.clone_p[((size_t)b * fv.cmax + c) * 3 + q - 9];
@@ -164,7 +179,12 @@ __global__ __launch_bounds__(GRAM_NT, 2) void k_feat_gram2(
         if (g == 0) used_out[(size_t)b * fv.fmax + j] = use;
     }
     // zero the operand panels once: padding columns (and rows of a short last batch) stay zero
-    for (int e = tid; e < KR * LDW; e += GRAM_NT) { (&sb.Bm[0][0])[e] = 0.0; (&sb.Ym[0][0])[e] = 0.0; }
+    for (int e = tid; e < KR * LDW; e += GRAM_NT) {
+        (&sb.Bm[0][0])[e] = 0.0;
+#if !GRAM2_ZFORM
+        (&sb.Ym[0][0])[e] = 0.0;
+#endif
+    }
     __syncthreads();
     if (wave == 0) {                                            // ordered list of the used features
         int cnt = 0;
@@ -183,10 +203,17 @@ __global__ __launch_bounds__(GRAM_NT, 2) void k_feat_gram2(
 
     dbg_stamp(33);
     // MFMA accumulators: wave w owns the upper tiles t = w, w+4, ... (row-major over ti <= tj)
+    // RED, class 11: 10 tiles - two waves own three, two own two.  GRAM2_RED_DEAL 1 starts the deal at wave 2 (the third tile on waves
+    // 2-3, which carry the lighter P3b), 0 deals round-robin (the third tile on waves 0-1, which carry P2).  Measured on MI355X, 512
+    // filters of config 2: 83.4 against 85.9 us (sigma 0.9; the full form 92.1) - hence 1
+#ifndef GRAM2_RED_DEAL
+#define GRAM2_RED_DEAL 1
+#endif
+    const int wdeal = (RED && GRAM2_RED_DEAL) ? (wave ^ 2) : wave;
     int tiA[TPW], tjA[TPW];
 #pragma unroll
     for (int u = 0; u < TPW; ++u) {
-        int t = wave + 4 * u, ti = 0;
+        int t = wdeal + 4 * u, ti = 0;
         while (ti < TI - 1 && t >= TJ - ti) { t -= TJ - ti; ++ti; }
         tiA[u] = ti; tjA[u] = ti + t;                          // t >= NUP gives tj >= TJ: never launched
     }
@@ -279,7 +306,12 @@ __global__ __launch_bounds__(GRAM_NT, 2) void k_feat_gram2(
         const int nbf = min(GRAM_NB, q1 - qb);
         dbg_stamp(34);
         if (rows && nbf < GRAM_NB) {                           // short last batch: clear the unused stacked rows
-            for (int e = tid; e < (KR - 3 * nbf) * LDW; e += nthr) { (&sb.Bm[3 * nbf][0])[e] = 0.0; (&sb.Ym[3 * nbf][0])[e] = 0.0; }
+            for (int e = tid; e < (KR - 3 * nbf) * LDW; e += nthr) {
+                (&sb.Bm[3 * nbf][0])[e] = 0.0;
+#if !GRAM2_ZFORM
+                (&sb.Ym[3 * nbf][0])[e] = 0.0;
+#endif
+            }
         }
         dbg_stamp(35);
         // ---- P2: operand rows B, Y = Ns^-1 B and the sparse scratch, lane = (feature, window slot) -----
@@ -356,15 +388,17 @@ __global__ __launch_bounds__(GRAM_NT, 2) void k_feat_gram2(
                 const double d1 = Ns[4] - l10 * Ns[1], s1 = d1 > 0.0 ? gram_rsqrt(d1) : 0.0, r1 = s1 * s1;
                 const double t21 = Ns[5] - l20 * Ns[1], l21 = t21 * r1;
                 const double d2 = (Ns[8] - l20 * Ns[2]) - l21 * t21, s2 = d2 > 0.0 ? gram_rsqrt(d2) : 0.0;
+                if (!RED || c != cref) {                            // RED: the reference slot's six panel columns stay at their zeros
 #pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    {
-                        const double y0 = Bt[q], y1 = Bt[3 + q] - l10 * y0, y2 = (Bt[6 + q] - l20 * y0) - l21 * y1;
-                        sb.Bm[3 * f + 0][6 * c + q] = s0 * y0; sb.Bm[3 * f + 1][6 * c + q] = s1 * y1; sb.Bm[3 * f + 2][6 * c + q] = s2 * y2;
-                    }
-                    {
-                        const double y0 = Bp[q], y1 = Bp[3 + q] - l10 * y0, y2 = (Bp[6 + q] - l20 * y0) - l21 * y1;
-                        sb.Bm[3 * f + 0][6 * c + 3 + q] = s0 * y0; sb.Bm[3 * f + 1][6 * c + 3 + q] = s1 * y1; sb.Bm[3 * f + 2][6 * c + 3 + q] = s2 * y2;
+                    for (int q = 0; q < 3; ++q) {
+                        {
+                            const double y0 = Bt[q], y1 = Bt[3 + q] - l10 * y0, y2 = (Bt[6 + q] - l20 * y0) - l21 * y1;
+                            sb.Bm[3 * f + 0][6 * c + q] = s0 * y0; sb.Bm[3 * f + 1][6 * c + q] = s1 * y1; sb.Bm[3 * f + 2][6 * c + q] = s2 * y2;
+                        }
+                        {
+                            const double y0 = Bp[q], y1 = Bp[3 + q] - l10 * y0, y2 = (Bp[6 + q] - l20 * y0) - l21 * y1;
+                            sb.Bm[3 * f + 0][6 * c + 3 + q] = s0 * y0; sb.Bm[3 * f + 1][6 * c + 3 + q] = s1 * y1; sb.Bm[3 * f + 2][6 * c + 3 + q] = s2 * y2;
+                        }
                     }
                 }
                 if (c == 0) {
@@ -377,15 +411,17 @@ __global__ __launch_bounds__(GRAM_NT, 2) void k_feat_gram2(
                 double Yt[9], Yp[9];
                 mul33(Nsi, Bt, Yt);
                 mul33(Nsi, Bp, Yp);
+                if (!RED || c != cref) {
 #pragma unroll
-                for (int k = 0; k < 3; ++k)
+                    for (int k = 0; k < 3; ++k)
 #pragma unroll
-                    for (int q = 0; q < 3; ++q) {
-                        sb.Bm[3 * f + k][6 * c + q] = Bt[3 * k + q];
-                        sb.Bm[3 * f + k][6 * c + 3 + q] = Bp[3 * k + q];
-                        sb.Ym[3 * f + k][6 * c + q] = Yt[3 * k + q];
-                        sb.Ym[3 * f + k][6 * c + 3 + q] = Yp[3 * k + q];
-                    }
+                        for (int q = 0; q < 3; ++q) {
+                            sb.Bm[3 * f + k][6 * c + q] = Bt[3 * k + q];
+                            sb.Bm[3 * f + k][6 * c + 3 + q] = Bp[3 * k + q];
+                            sb.Ym[3 * f + k][6 * c + q] = Yt[3 * k + q];
+                            sb.Ym[3 * f + k][6 * c + 3 + q] = Yp[3 * k + q];
+                        }
+                }
                 if (c == 0) {
 #pragma unroll
                     for (int k = 0; k < 3; ++k) sb.Bm[3 * f + k][NC] = hs[k];      // extra column: hs
@@ -420,9 +456,13 @@ __global__ __launch_bounds__(GRAM_NT, 2) void k_feat_gram2(
             if (st < nst) {                                  // issued while the earlier MFMAs run
 #pragma unroll
                 for (int u = 0; u < TPW; ++u) {
-                    if (wave + 4 * u < NUP) {
+                    if (wdeal + 4 * u < NUP) {
                         const int ti = tiA[u], tj = tjA[u];
-                        const double af = (GRAM2_ZFORM ? sb.Bm : sb.Ym)[4 * st + kq][16 * ti + l15];      // A[i][k] = Y[k][i]  (Z-form: Z[k][i])
+#if GRAM2_ZFORM
+                        const double af = sb.Bm[4 * st + kq][16 * ti + l15];      // A[i][k] = Z[k][i]
+#else
+                        const double af = sb.Ym[4 * st + kq][16 * ti + l15];      // A[i][k] = Y[k][i]
+#endif
                         const double bf = sb.Bm[4 * st + kq][16 * tj + l15];      // B[k][j]
                         acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[u], 0, 0, 0);
                     }
@@ -499,7 +539,7 @@ __global__ __launch_bounds__(GRAM_NT, 2) void k_feat_gram2(
     // ---- epilogue: assemble [A | b] of the chunk ---------------------------------------------------
 #pragma unroll
     for (int u = 0; u < TPW; ++u) {
-        if (wave + 4 * u < NUP) {
+        if (wdeal + 4 * u < NUP) {
             const int ti = tiA[u], tj = tjA[u];
             const int jc = 16 * tj + l15;
 #pragma unroll
@@ -528,7 +568,9 @@ __global__ __launch_bounds__(GRAM_NT, 2) void k_feat_gram2(
     }
     __syncthreads();
     double* out = Apart + ((size_t)bl * G + g) * rstride;      // [ncol][ncol+1] row-major, b in the last column
-    if (pairlane && pc < C && pa < C) {
+    // RED: blocks of the reference clone's row and column are neither assembled nor written (the diagonal blocks of the others still
+    // sum over every anchor, the reference slot included); what is written goes to the same address as in the full form
+    if (pairlane && pc < C && pa < C && pc != cref && pa != cref) {
         const int c = pc, c2 = pa;
         double blk[36];
 #pragma unroll
@@ -1380,8 +1422,23 @@ __global__ __launch_bounds__(256) void k_info_dx(CovView cv, int b0, int MP, con
 }
 
 // ---------------------------------------------------------------------------------------------
+template <int CMAX, bool STEREO, bool RED>
+static void launch_gram2(const FactoredLaunch& L, hipStream_t st)
+{
+    const size_t sm = gram2_lds_bytes<CMAX, RED>() + 2 * sizeof(int) * (size_t)L.fv.fmax;
+    static size_t attr_sm = 0;
+    if (sm > attr_sm) {
+        hipFuncSetAttribute((const void*)k_feat_gram2<CMAX, STEREO, RED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+        attr_sm = sm;
+    }
+    hipLaunchKernelGGL((k_feat_gram2<CMAX, STEREO, RED>), dim3(L.G, L.nb), dim3(GRAM_NT), sm, st,
+                       L.fv, L.op, L.b0, L.accept, L.used, L.Apart, L.chunk_used, L.G, L.rstride);
+    if (L.gram_was_red) *L.gram_was_red = RED ? 1 : 0;
+}
+
+// gram_red: the Gram stage takes the reduced form of k_feat_gram2 (decided in launch_factored)
 template <int CMAX, bool STEREO>
-static void launch_ft(const FactoredLaunch& L, hipStream_t st)
+static void launch_ft(const FactoredLaunch& L, hipStream_t st, bool gram_red)
 {
     if (L.stage == 0) {
         const int nb8 = (L.nb + 7) / 8 * 8;
@@ -1440,15 +1497,10 @@ static void launch_ft(const FactoredLaunch& L, hipStream_t st)
             }
         }
 #endif
-        constexpr size_t uni = sizeof(Gram2Batch<CMAX>) > sizeof(Gram2Out<CMAX>) ? sizeof(Gram2Batch<CMAX>) : sizeof(Gram2Out<CMAX>);
-        const size_t sm = ((uni + 15) / 16) * 16 + 2 * sizeof(int) * (size_t)L.fv.fmax;
-        static size_t attr_sm = 0;
-        if (sm > attr_sm) {
-            hipFuncSetAttribute((const void*)k_feat_gram2<CMAX, STEREO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-            attr_sm = sm;
+        if constexpr (CMAX <= 12) {                                  // the classes whose solve has a gauge-reduced form
+            if (gram_red) { launch_gram2<CMAX, STEREO, true>(L, st); return; }
         }
-        hipLaunchKernelGGL((k_feat_gram2<CMAX, STEREO>), dim3(L.G, L.nb), dim3(GRAM_NT), sm, st,
-                           L.fv, L.op, L.b0, L.accept, L.used, L.Apart, L.chunk_used, L.G, L.rstride);
+        launch_gram2<CMAX, STEREO, false>(L, st);
     }
 }
 
@@ -1573,8 +1625,21 @@ int launch_factored(const FactoredLaunch& L, hipStream_t st)
     // Gram kernel spills (132 B of scratch per lane) and both kernels loop over four slots that do not exist
     const int cls = cm <= 6 ? 6 : (cm <= 11 ? 11 : (cm <= 12 ? 12 : (cm <= 16 ? 16 : -1)));
     if (cls < 0) return -1;
+    // The reduced form of the Gram kernel (Gram2Cfg): only where the caller asks for it (the fused frame step with the context's switch
+    // on, FactoredLaunch::gram_red - nothing there reads the chunk partials but the solve) and the solve that follows is the gauge-reduced
+    // one with its reference at slot C - 1, i.e. launch_info_solve's rule: RemoveLost Jacobians, a window class up to 12 clones (the
+    // 13..16-clone class solves by Gauss-Jordan on all of A), the reduction not switched off
+#ifdef INGVIO_ALT_KERNELS
+    static const bool full_solve = [] {
+        const char* e = getenv("INGVIO_INFO_GAUGE"); const char* s = getenv("INGVIO_INFO_SOLVE");
+        return (e && !strcmp(e, "off")) || (s && !strcmp(s, "gj"));
+    }();
+#else
+    constexpr bool full_solve = false;
+#endif
+    const bool gram_red = L.stage == 1 && L.gram_red && !L.op.selected_variant && cls <= 12 && !full_solve;
 #define DISPATCH(CM)                                                         \
-    if (cls == CM) { if (L.stereo) launch_ft<CM, true>(L, st); else launch_ft<CM, false>(L, st); return 0; }
+    if (cls == CM) { if (L.stereo) launch_ft<CM, true>(L, st, gram_red); else launch_ft<CM, false>(L, st, gram_red); return 0; }
     DISPATCH(6)
     DISPATCH(11)
     DISPATCH(12)

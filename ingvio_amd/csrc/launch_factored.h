@@ -42,6 +42,10 @@ struct FactoredLaunch {
     int* flip_cnt;        // stage 3 with a fused marginalisation: [nb] arrival counters (zero between launches) - the LAST workgroup of a
                           // filter to START flips the ping-pong halves and shrinks n (what k_post_marg did in a launch of its own), or nullptr
     int* did_flip;        // host flag, set by launch_factored when the stage-3 kernel it chose does that flip
+    int gram_red;         // stage 1, windows up to 12 clones: the caller reads the chunk partials through the gauge-reduced solve only (the
+                          // fused frame step) and allows the reduced form of k_feat_gram2, which leaves the block row / column of the solve's
+                          // reference clone (slot n_clones - 1) unwritten; launch_factored takes it where that solve follows
+    int* gram_was_red;    // host flag, set to 1 / 0 by the k_feat_gram2 launch: the partials it wrote are reduced / full (or nullptr)
     double* big_sg;       // large-window path: [nb][G][36][36][34] sparse sums (kernels_bigwin.hip)
     double* big_wk;       // large-window path: per-filter solve workspace (bigwin_wk_doubles)
     int ncol_cap;         // 6 * (context c_max): size class of the large-window solve
