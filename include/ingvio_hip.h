@@ -574,6 +574,32 @@ typedef struct {
 int ingvio_frame_stage_tracks_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,
                                       const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double sigma_cb, double sigma_rw,
                                       int async);
+/* The SECOND MSCKF update of a camera frame (SwMargUpdate / KeyframeUpdate::updateState*, IngvioFilter.cpp:271-324: behind RemoveLostUpdate,
+ * linearised at the state that update left) as an update-only frame from the table and the track store: no IMU steps, no new clone, the
+ * window is the table's as it stands (frames[].n_clones / clone_* are ignored).  frames[i].append_slot must be -1 and n_obs 0; n_drop,
+ * n_free and n_pf are applied to the store as usual; feat_sel selects the stamps the update uses.  marg_idx [nb]: the idx of the window
+ * clone the frame marginalises, -1: none (key-frame mode: ingvio_nominal_tail drops its two clones afterwards).
+ * tri != NULL: ingvio_frame_run first triangulates every listed feature on the device from EVERY observation the store holds over the
+ * window (SwMargUpdate.cpp:236-257, KeyframeUpdate.cpp:607-628, MapServerManager.cpp:309-341), with the settings of ingvio_msckf_update_tri
+ * and without a host synchronisation; a feature whose triangulation fails or whose point lies behind its anchor drops out of the update,
+ * a point that succeeded is also written to the store's point of its track (setValuePosXyz, MapServerManager.cpp:335), so a later frame
+ * that lists the track without triangulating uses it.  tri == NULL: the store's points.
+ * The context is left exactly as by ingvio_frame_stage_tracks_nominal: ingvio_frame_run / ingvio_frame_fetch(_begin / _end) follow, the run
+ * ends with boxPlus of its dx, the drop and the shift on the table; async, snapshot / restore and ingvio_nominal_tail behind it as there.
+ * ingvio_landmark_stage_nominal(in_frame) is accepted while it is pending (the reference runs the landmark update behind the second
+ * MSCKF update, IngvioFilter.cpp:281-289).
+ * Refused before anything changes: no table or no track store, a range other than the whole batch, another frame staged from the table
+ * that has not run, append_slot >= 0 or n_obs > 0 (INGVIO_E_ARG); marg_idx not a window clone (INGVIO_E_NOT_IN_STATE); a landmark
+ * anchored to the clone that leaves (INGVIO_E_ARG); frame_parts > 1 or an in-frame GNSS / host-fed landmark stage (INGVIO_E_UNSUPPORTED).
+ * While it is pending: ingvio_gnss_frame_stage_nominal returns INGVIO_E_UNSUPPORTED (ingvio_gnss_front_stage_nominal + ingvio_gnss_run
+ * behind the frame is the reference's order), ingvio_frame_run_phase INGVIO_E_UNSUPPORTED, ingvio_frame_run(restore_prior != 0)
+ * INGVIO_E_ARG. */
+int ingvio_update_stage_tracks_nominal(ingvio_ctx* ctx, int b0, int nb, const int* marg_idx /* [nb], -1: none */,
+                                       const ingvio_track_frame* frames, const ingvio_msckf_opts* opts,
+                                       const ingvio_tri_opts* tri /* NULL: the store's points */, int async);
+/* flags and points of the update-only frame's triangulation, after its run (and, pipelined, after the ingvio_frame_fetch_begin that
+ * follows it): pf_out [nb][f_max][3], tri_ok [nb][f_max] as ingvio_msckf_update_tri; INGVIO_E_ARG without a run that triangulated */
+int ingvio_frame_fetch_tri(ingvio_ctx* ctx, int b0, int nb, double* pf_out, int* tri_ok);
 /* ---- GNSS epochs in the device-resident closed loop ------------------------------------------------------------
  * Names the GNSS scalars of filters [b0, b0 + nb)'s tables: slots [nb][6] = the table slots of the clock biases GPS, GLO, GAL, BDS, then
  * FS, then YOF (State::GNSSType order, State.h:75); -1: not in the state.  From then on

@@ -37,6 +37,7 @@ EXPORTS = [
     "ingvio_landmark_init_nominal", "ingvio_debug_landmark_init_rows", "ingvio_nominal_tail",
     "ingvio_debug_tracks_read", "ingvio_debug_staged_frame",
     "ingvio_gnss_frame_stage_nominal", "ingvio_debug_gnss_fused_last", "ingvio_debug_nominal_update_post",
+    "ingvio_update_stage_tracks_nominal", "ingvio_frame_fetch_tri",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -1061,6 +1062,36 @@ class Context:
                                                                       C.c_double(sigma_cb), C.c_double(sigma_rw), 1 if use_async else 0))
         return call
 
+    def update_stage_tracks_nominal_prepare(self, b0, marg_idx, track_frames, opts_frame, tri=None, max_accept=0, compress_rule=1,
+                                            selected_variant=0, use_async=False):
+        """the update-only frame from the table and the track store (ingvio_update_stage_tracks_nominal): marg_idx [nb] (-1: none);
+        track_frames as frame_stage_tracks_nominal_prepare takes them (no append, no observations); tri: None (the store's points) or
+        a dict of ingvio_tri_opts fields that differ from tri_opts()'s defaults ({}: the defaults) - the run then triangulates"""
+        nb = len(track_frames)
+        fa = (TrackFrame * nb)()
+        keeps = []
+        for i in range(nb):
+            d = dict(track_frames[i])
+            d.setdefault("clone_idx", []); d.setdefault("clone_R", np.zeros((0, 9))); d.setdefault("clone_p", np.zeros((0, 3)))
+            f, k2 = make_track_frame(d)
+            fa[i] = f; keeps.append(k2)
+        mg = i32(np.asarray(marg_idx, dtype=np.int32).reshape(-1))
+        o, chi2 = make_opts(opts_frame, max_accept, compress_rule, selected_variant)
+        t = None if tri is None else tri_opts(opts_frame, **tri)
+
+        def call():
+            _keep = (keeps, chi2, mg, t)
+            return self._chk(self.L.ingvio_update_stage_tracks_nominal(self.h, int(b0), nb, _i(mg), fa, C.byref(o), None if t is None else C.byref(t),
+                                                                       1 if use_async else 0))
+        return call
+
+    def frame_fetch_tri(self, b0=0, nb=None):
+        """(pf [nb, f_max, 3], tri_ok [nb, f_max]) of the update-only frame's triangulation (ingvio_frame_fetch_tri)"""
+        nb = self.batch if nb is None else nb
+        pf = np.zeros((nb, self.f_max, 3)); ok = np.zeros((nb, self.f_max), dtype=np.int32)
+        self._chk(self.L.ingvio_frame_fetch_tri(self.h, int(b0), nb, _d(pf), _i(ok)))
+        return pf, ok
+
     def frame_stage_prepare(self, b0, steps, frames, sigma, enable_gnss=0, sigma_cb=0.0, sigma_rw=0.0, max_accept=0,
                             compress_rule=1, selected_variant=0, use_async=False):
         """Builds the C argument arrays once and returns a callable that re-issues ingvio_frame_stage on them (for timing
@@ -1174,6 +1205,21 @@ class TriOpts(C.Structure):
                 ("trans_thres", C.c_double), ("huber_epsilon", C.c_double), ("conv_precision", C.c_double),
                 ("init_damping", C.c_double), ("outer_loop_max_iter", C.c_int), ("inner_loop_max_iter", C.c_int),
                 ("max_depth", C.c_double), ("min_depth", C.c_double), ("mask_failed", C.c_int)]
+
+
+def tri_opts(opts_frame, stereo=None, **params):
+    """ingvio_tri_opts with the reference's defaults (Triangulator.h:67-75), the outer calibration and (stereo=None) the camera
+    model of opts_frame; params: the fields that differ"""
+    pr = dict(trans_thres=0.1, huber_epsilon=0.01, conv_precision=5e-7, init_damping=1e-3, outer_loop_max_iter=10,
+              inner_loop_max_iter=10, max_depth=60.0, min_depth=0.2)
+    pr.update(params)
+    t = TriOpts()
+    t.stereo = int(opts_frame.get("stereo", 1)) if stereo is None else (1 if stereo else 0)
+    t.R_cl2cr = (C.c_double * 9)(*np.asarray(opts_frame["R_cl2cr"], dtype=np.float64).reshape(9))
+    t.t_cl2cr = (C.c_double * 3)(*np.asarray(opts_frame["t_cl2cr"], dtype=np.float64).reshape(3))
+    for k, v in pr.items():
+        setattr(t, k, v)
+    return t
 
 
 class DeviceCov:

@@ -2,7 +2,8 @@
 tests/test_gpu_nominal_*.py and tools/closed_loop_bench.py: inputs of a loop of frames (raw IMU samples, track deltas, the
 marginalised clone), the pieces of the host reference that keeps the nominal values with the C oracle's functions and the Var semantics
 of oracle/stream_filter.py, and DeviceLoop, the one driver of the device loop.  closed_loop_gnss.py and closed_loop_lm.py add their
-inputs, their host reference step and their Form of the driver."""
+inputs, their host reference step and their Form of the driver; closed_loop_update.py the camera frame's second MSCKF update as a frame
+entry of its own (UpdateEntry)."""
 import numpy as np
 
 
@@ -217,6 +218,17 @@ def host_step(ctx, cases, tabs, f):
 
 
 # ---- the device loop -----------------------------------------------------------------------------------------------------------------
+class UpdateEntry:
+    """a frame entry of DeviceLoop that is an update-only frame from the table: the second MSCKF update of camera frame f; tri: its run
+    triangulates"""
+
+    def __init__(self, f, tri=True):
+        self.f, self.tri = f, tri
+
+    def __repr__(self):
+        return "UpdateEntry(%d)" % self.f
+
+
 class Form:
     """What a form of the loop adds to the frame stage / run / fetch of DeviceLoop; this one, the plain loop, adds nothing.
     late: the form's work on frame i follows that frame's run (after), and the table must see it before frame i + 1 is staged."""
@@ -246,27 +258,37 @@ class DeviceLoop:
       pipelined, late   fetch_begin(i) after(i) stage(i+1) staged(i+1) run(i+1) fetch_end(i) collect(i)
     fetch_end(i) is issued after run(i + 1) and still returns frame i's results.  prepare() builds every stage callable ahead of
     the loop (otherwise each is built when it is due), collect=False leaves the form's results unfetched: what the bench tool times.
-    sync_every_call (serial): a context synchronisation after every call that only enqueues."""
+    sync_every_call (serial): a context synchronisation after every call that only enqueues.
+    A frame entry may be an update-only frame from the table (closed_loop_update.py): an UpdateEntry(f) instead of the number f.  It is
+    staged with update_stage(ctx, cases, f, use_async) and takes its place in the same sequences; where its run triangulated, its
+    results are (dx, accept, rows, pf, tri_ok).  The form's prepare / staged belong to the numbered entries."""
 
-    def __init__(self, ctx, cases, frames, form=None, pipelined=True, sync_every_call=False, collect=True):
+    def __init__(self, ctx, cases, frames, form=None, pipelined=True, sync_every_call=False, collect=True, update_stage=None):
         self.ctx, self.cases, self.frames, self.form, self.pipelined = ctx, cases, list(frames), form or Form(), pipelined
         self.sync = ctx.sync if sync_every_call and not pipelined else (lambda: None)
         self.collect = self.form.collect if collect else (lambda ctx: None)
         self.stages, self.form_calls = {}, {}
+        self.update_stage = update_stage
+
+    def stage_of(self, f):
+        if isinstance(f, UpdateEntry):
+            return self.update_stage(self.ctx, self.cases, f.f, self.pipelined)
+        return nominal_stage(self.ctx, self.cases, f, use_async=self.pipelined)
 
     def prepare(self):
         for i, f in enumerate(self.frames):
-            self.stages[i] = nominal_stage(self.ctx, self.cases, f, use_async=self.pipelined)
-            self.form_calls[i] = self.form.prepare(self.ctx, self.cases, f)
+            self.stages[i] = self.stage_of(f)
+            self.form_calls[i] = None if isinstance(f, UpdateEntry) else self.form.prepare(self.ctx, self.cases, f)
         return self
 
     def form_call(self, i):
         return self.form_calls[i] if i in self.form_calls else self.form.prepare(self.ctx, self.cases, self.frames[i])
 
     def stage(self, i):
-        (self.stages.get(i) or nominal_stage(self.ctx, self.cases, self.frames[i], use_async=self.pipelined))()
+        (self.stages.get(i) or self.stage_of(self.frames[i]))()
         self.sync()
-        self.form.staged(self, i)
+        if not isinstance(self.frames[i], UpdateEntry):
+            self.form.staged(self, i)
 
     def start(self):
         if self.pipelined:
@@ -275,6 +297,14 @@ class DeviceLoop:
 
     def frame(self, i):
         """-> frame i's (dx, accept, rows), with a form that collects: (that, the form's results)"""
+        out = self.plain_frame(i)
+        e = self.frames[i]
+        if isinstance(e, UpdateEntry) and e.tri:                         # (the last fetch_begin was entry i's: its flags and points came along)
+            tri = self.ctx.frame_fetch_tri()
+            out = (out[0] + tri, out[1]) if len(out) == 2 else out + tri
+        return out
+
+    def plain_frame(self, i):
         ctx, form, last = self.ctx, self.form, i + 1 == len(self.frames)
         if self.pipelined and not form.late and not last:
             self.stage(i + 1)

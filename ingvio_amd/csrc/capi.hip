@@ -231,6 +231,13 @@ struct ingvio_ctx {
         bool pending = false;                                 // a frame staged from the table has not run yet
         bool frame = false;                                   // the staged frame came from the table (it runs once)
         hipEvent_t ev = nullptr; bool ev_valid = false;       // behind the post-frame kernel of the frame enqueued last
+        // update-only frame from the table (ingvio_update_stage_tracks_nominal): no propagation, no new clone; tri_on: its run
+        // triangulates the listed features first (tri: the settings); tri_ran: the result slab holds that run's flags and points
+        bool noprop = false, tri_on = false, tri_ran = false;
+        int tri_fmx = 0;                                      // the largest feature count of the stage that set tri_on
+        bool tri_fetched = false; int tri_b0 = 0, tri_nb = 0; // the pinned result mirror holds a triangulating run's flags and points of this range
+        ingvio_tri_opts tri;
+        int* d_tri_track = nullptr;                           // [B][f_max] track of each listed feature (k_tracks_gather_upd)
     } nom;
     // ingvio_nominal_tail (kernels_tail.hip), grown on demand: the uploaded lists, the panel kernel's workspace (transient: nothing in it
     // outlives the call, so a snapshot has nothing to copy) and the pinned mirror of the verdicts and the new dimensions
@@ -1080,9 +1087,9 @@ struct FrameStage {
         c->upc.chi2_ok = false; c->upc.noise_ok = false;
     }
     // Frame: ingvio_msckf_frame or ingvio_track_frame (n_clones, clone_idx); fmx: the call's largest feature count; plan: as
-    // frame_stage_tracks_impl takes it
+    // frame_stage_tracks_impl takes it; upd: the update-only frame from the table (no clone joins the mirror)
     template <class Step, class Frame>
-    int finish(const Step* steps, const Frame* frames, int fmx, const int* plan = nullptr)
+    int finish(const Step* steps, const Frame* frames, int fmx, const int* plan = nullptr, bool upd = false)
     {
         if (int rc = upl.end()) return fail(rc);
         if (async) {
@@ -1098,7 +1105,7 @@ struct FrameStage {
             c->h_nclones[b0 + i] = frames[i].n_clones;
         }
         if (plan) {                                   // the mirror follows what k_imu_steps<true> writes
-            for (int i = 0; i < nb; ++i) {
+            for (int i = 0; i < nb && !upd; ++i) {
                 int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
                 const int slot = plan[4 * i], ncl = plan[4 * i + 2];
                 int* vc = I + NOM_IH + 4 * slot;
@@ -1108,6 +1115,7 @@ struct FrameStage {
             c->nom.pending = true;
         }
         c->nom.frame = plan != nullptr;                // a frame from the table is followed by the post-frame step
+        c->nom.noprop = upd; c->nom.tri_on = false;
         c->st_stereo = opts->stereo; c->st_enable_gnss = enable_gnss;
         if (!c->staged || fmx > c->st_fmax_used) c->st_fmax_used = fmx;
         c->staged = true;
@@ -1278,7 +1286,7 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
         for (auto e : c->ev_free) if (e) hipEventDestroy(e);
     }
     for (void* p : { (void*)c->trk.uv, (void*)c->trk.pf, (void*)c->trk.mask, (void*)c->trk.stage[0], (void*)c->trk.stage[1] }) if (p) hipFree(p);
-    for (void* p : { (void*)c->nom.ih, (void*)c->nom.dv, (void*)c->nom.ih_snap, (void*)c->nom.dv_snap, (void*)c->nom.dx }) if (p) hipFree(p);
+    for (void* p : { (void*)c->nom.ih, (void*)c->nom.dv, (void*)c->nom.ih_snap, (void*)c->nom.dv_snap, (void*)c->nom.dx, (void*)c->nom.d_tri_track }) if (p) hipFree(p);
     if (c->nom.ev) hipEventDestroy(c->nom.ev);
     for (auto& r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (int p = 0; p < c->parts_alloc; ++p) { hipStreamDestroy(c->part[p].st); hipEventDestroy(c->part[p].ev_gate); hipEventDestroy(c->part[p].ev_apply); hipEventDestroy(c->part[p].ev_done); }
@@ -2022,6 +2030,10 @@ int ingvio_gnss_frame_stage_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_
     auto& g = c->gn;
     if (!m.vmax) { c->err = "ingvio_gnss_frame_stage_nominal without ingvio_nominal_create"; return INGVIO_E_ARG; }
     if (!m.pending) { c->err = "ingvio_gnss_frame_stage_nominal: no frame staged from the device nominal state is waiting to run"; return INGVIO_E_ARG; }
+    if (m.noprop) {
+        c->err = "ingvio_gnss_frame_stage_nominal: an update-only frame takes no GNSS epoch (ingvio_gnss_front_stage_nominal + ingvio_gnss_run behind it)";
+        return INGVIO_E_UNSUPPORTED;
+    }
     if (b0 != 0 || nb != c->d.batch) { c->err = "ingvio_gnss_frame_stage_nominal stages the whole batch (b0 = 0, nb = batch)"; return INGVIO_E_ARG; }
     if (g.staged && g.frame_nom) { c->err = "ingvio_gnss_frame_stage_nominal: the frame has its GNSS epoch already"; return INGVIO_E_ARG; }
     std::vector<ingvio_gnss_epoch> full((size_t)nb);
@@ -2350,6 +2362,7 @@ static int msckf_update_impl(ingvio_ctx* c, int b0, int nb, const ingvio_msckf_f
     if (tri && (tri->outer_loop_max_iter < 0 || tri->inner_loop_max_iter < 0)) return INGVIO_E_ARG;
     MsckfOpts op;
     c->fork_recorded = false;
+    c->nom.tri_ran = false; c->nom.tri_fetched = false;      // (the result slab and its mirror are this call's from here on)
     HIPCHK(c, hipMemsetAsync(c->d_status + b0, 0, sizeof(int) * (size_t)nb, c->st));      // first: it runs while the host packs the frame
     int rc = make_opts(c, opts, &op);
     if (rc) return rc;
@@ -3202,8 +3215,9 @@ int ingvio_landmark_stage_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_la
         const int* I = &m.h_ih[(size_t)b * m.ir];
         const int* var = I + NOM_IH;
         if (I[NOM_V_POSE] < 0 || I[NOM_V_EXT] < 0) { c->err = "ingvio_landmark_stage_nominal: the table names no extended pose or extrinsics"; return INGVIO_E_ARG; }
-        // (in_frame: the stage of the frame has already put the new clone into the mirror, its 6 columns are appended by the run)
-        const int n_lim = std::min(c->d.n_max, c->h_n[b] + (o->in_frame ? 6 : 0));
+        // (in_frame: the stage of the frame has already put the new clone into the mirror, its 6 columns are appended by the run -
+        // unless the frame is an update-only one, which appends none)
+        const int n_lim = std::min(c->d.n_max, c->h_n[b] + (o->in_frame && !m.noprop ? 6 : 0));
         const int ie = var[4 * I[NOM_V_POSE] + 1], ix = var[4 * I[NOM_V_EXT] + 1];
         if (ie < 0 || ie + 9 > n_lim || ix < 0 || ix + 6 > n_lim) return INGVIO_E_NOT_IN_STATE;
         int hi = f.n_lm ? std::max(ie + 9, ix + 6) : 0;
@@ -3451,9 +3465,13 @@ int ingvio_tracks_create(ingvio_ctx* c, int t_max)
 
 // plan [nb][4] (device nominal stage, else nullptr): the new clone's variable slot, its idx, the window's clone count with it and the
 // table's slots in use after it; frames[i].n_clones is that count, the frames' clone arrays are not read
+// upd (with a plan; the update-only frame from the table, ingvio_update_stage_tracks_nominal): steps[i].k = 0 and no IMU samples, nothing is
+// propagated and no clone is appended - plan [nb][4] = -1, the window's highest clone idx, its clone count, the table's slots in use;
+// tri_mask / tri_track: where the gather leaves the triangulation's masks and the features' tracks (nullptr: no triangulation)
+struct UpdStage { unsigned long long* tri_mask; int* tri_track; };
 static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_raw* steps, const ingvio_track_frame* frames,
                                    const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, int async,
-                                   const int* plan)
+                                   const int* plan, const UpdStage* upd = nullptr)
 {
     FrameStage stage{ c, b0, nb, opts, sigma, enable_gnss, scb, srw, async != 0 };
     if (int rc = stage.refuse(steps && frames, true)) return rc;
@@ -3466,7 +3484,7 @@ static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_f
     for (int i = 0; i < nb; ++i) {
         const ingvio_track_frame& f = frames[i];
         const ingvio_frame_step_raw& s = steps[i];
-        if (s.k < 1 || s.k > KMAX || !s.imu) return INGVIO_E_ARG;
+        if (upd ? s.k != 0 : (s.k < 1 || s.k > KMAX || !s.imu)) return INGVIO_E_ARG;
         if (f.n_drop < 0 || f.n_drop > cm || f.n_free < 0 || f.n_free > T || f.n_obs < 0 || f.n_obs > T || f.n_pf < 0 || f.n_pf > T) return INGVIO_E_CAPACITY;
         if (f.n_clones < 0 || f.n_clones > cm || f.n_feat < 0 || f.n_feat > fm) return INGVIO_E_CAPACITY;
         if ((f.n_drop && !f.drop_slots) || (f.n_free && !f.free_tracks) || (f.n_obs && (!f.obs_track || !f.obs_uv)) || (f.n_pf && (!f.pf_track || !f.pf)) ||
@@ -3538,7 +3556,7 @@ static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_f
         }
         for (int g = 0; g < 5; ++g) ip[h[TRK_I_GNSS] + g] = s.gnss_idx[g];
         if (f.feat_sel) memcpy(mpool + h[TRK_OFF_M], f.feat_sel, 8 * (size_t)f.n_feat);
-        memcpy(dp + h[TRK_D_IMU], s.imu, 56 * (size_t)s.k);
+        if (s.k) memcpy(dp + h[TRK_D_IMU], s.imu, 56 * (size_t)s.k);
         if (!plan) {
             double* st0 = dp + h[TRK_D_STATE];
             memcpy(st0, s.R, 72); memcpy(st0 + 9, s.p, 24); memcpy(st0 + 12, s.v, 24); memcpy(st0 + 15, s.bg, 24); memcpy(st0 + 18, s.ba, 24); memcpy(st0 + 21, s.gravity, 24);
@@ -3550,7 +3568,7 @@ static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_f
     char* dstage = c->trk.stage[async ? 1 : 0];
     upl.copy(dstage, slab, total);
     stage.upload_gate();
-    stage.upload_imu(steps);
+    if (!upd) stage.upload_imu(steps);
     TrackStage ts{ reinterpret_cast<const int*>(dstage), reinterpret_cast<const int*>(dstage + off_i),
                    reinterpret_cast<const double*>(dstage + off_d), reinterpret_cast<const unsigned long long*>(dstage + off_m) };
     TrackStore store{ c->trk.uv, c->trk.mask, c->trk.pf, T, cm };
@@ -3558,12 +3576,13 @@ static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_f
     const NomTable nt = nom_table(c);
     // from the device table on the copy stream: the uploads above overlap the running frame, the kernels wait for its post-frame step
     if (plan && async && c->nom.ev_valid && hipStreamWaitEvent(S, c->nom.ev, 0) != hipSuccess) return stage.fail(INGVIO_E_HIP);
-    launch_imu_steps(ts, b0, nb, KMAX, c->d_Phi, c->d_G, c->d_dt, c->d_R, S, plan ? &nt : nullptr);
+    if (!upd) launch_imu_steps(ts, b0, nb, KMAX, c->d_Phi, c->d_G, c->d_dt, c->d_R, S, plan ? &nt : nullptr);
     if (hipGetLastError() != hipSuccess) return stage.fail(INGVIO_E_HIP);       // before the store kernels change the track store
     launch_tracks_apply(ts, store, b0, nb, S);
-    launch_tracks_gather(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S, plan ? &nt : nullptr);
+    if (upd) launch_tracks_gather_update(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S, nt, upd->tri_mask, upd->tri_track);
+    else launch_tracks_gather(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S, plan ? &nt : nullptr);
     if (hipGetLastError() != hipSuccess) return stage.fail(INGVIO_E_HIP);
-    return stage.finish(steps, frames, fmx, plan);
+    return stage.finish(steps, frames, fmx, plan, upd != nullptr);
 }
 
 int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_raw* steps, const ingvio_track_frame* frames,
@@ -3990,6 +4009,71 @@ int ingvio_frame_stage_tracks_nominal(ingvio_ctx* c, int b0, int nb, const ingvi
     return frame_stage_tracks_impl(c, b0, nb, raw.data(), fr.data(), opts, sigma, enable_gnss, scb, srw, async, plan.data());
 }
 
+// The second MSCKF update of a camera frame (SwMargUpdate / KeyframeUpdate::updateState*, IngvioFilter.cpp:271-324) as a frame from the
+// table of its own: no IMU steps, no new clone, the window as the table holds it
+int ingvio_update_stage_tracks_nominal(ingvio_ctx* c, int b0, int nb, const int* marg_idx, const ingvio_track_frame* frames, const ingvio_msckf_opts* opts,
+                                       const ingvio_tri_opts* tri, int async)
+{
+    ENTER(c);
+    if (phase_busy(c) || check_range(c, b0, nb) || !marg_idx || !frames || !opts) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    const char* who = "ingvio_update_stage_tracks_nominal";
+    if (!m.vmax) { c->err = std::string(who) + " without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (!c->trk.t_max) { c->err = std::string(who) + " without ingvio_tracks_create"; return INGVIO_E_ARG; }
+    if (b0 != 0 || nb != c->d.batch) { c->err = std::string(who) + " stages the whole batch (b0 = 0, nb = batch)"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = "a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, who)) return INGVIO_E_ARG;
+    if ((c->gn.staged && c->gn.in_frame) || (c->lm.staged && c->lm.in_frame)) {
+        c->err = "the device nominal state does not take an in-frame GNSS or landmark stage";
+        return INGVIO_E_UNSUPPORTED;
+    }
+    if (c->parts_req > 1) { c->err = "the device nominal state runs with frame_parts = 1 only"; return INGVIO_E_UNSUPPORTED; }
+    if (tri && (tri->outer_loop_max_iter < 0 || tri->inner_loop_max_iter < 0)) return INGVIO_E_ARG;
+    std::vector<int> plan((size_t)nb * 4);
+    std::vector<ingvio_frame_step_raw> raw((size_t)nb);
+    std::vector<ingvio_track_frame> fr(frames, frames + nb);
+    for (int i = 0; i < nb; ++i) {
+        const int b = b0 + i;
+        const int* I = &m.h_ih[(size_t)b * m.ir];
+        const int* var = I + NOM_IH;
+        if (frames[i].append_slot >= 0 || frames[i].n_obs > 0) { c->err = std::string(who) + ": an update-only frame appends no observations"; return INGVIO_E_ARG; }
+        const int ncl = I[NOM_N_CLONES], mg = marg_idx[i];
+        int hi = -1, ms = -1;
+        for (int q = 0; q < ncl; ++q) {
+            const int idx = var[4 * I[NOM_CLONES + q] + 1];
+            if (idx > hi) hi = idx;
+            if (mg >= 0 && ms < 0 && idx == mg) ms = I[NOM_CLONES + q];
+        }
+        if (mg >= 0) {
+            if (ms < 0) { c->err = std::string(who) + ": marg_idx names no clone of the window"; return INGVIO_E_NOT_IN_STATE; }
+            for (int v = 0; v < I[NOM_N_VAR]; ++v)
+                if (var[4 * v] == NOM_KIND_LM && var[4 * v + 2] == ms) {
+                    c->err = std::string(who) + ": a landmark is anchored to the clone that leaves the window"; return INGVIO_E_ARG;
+                }
+        }
+        plan[4 * i] = -1; plan[4 * i + 1] = hi; plan[4 * i + 2] = ncl; plan[4 * i + 3] = I[NOM_N_VAR];
+        ingvio_frame_step_raw& r = raw[i];
+        memset(&r, 0, sizeof r);
+        r.marg_idx = mg < 0 ? -1 : mg;
+        for (int g = 0; g < 5; ++g) r.gnss_idx[g] = c->st_gnss[(size_t)b * 5 + g];      // no propagation: the clock indices stay what they are
+        fr[i].n_clones = ncl; fr[i].clone_idx = nullptr; fr[i].clone_R = nullptr; fr[i].clone_p = nullptr;
+    }
+    UpdStage upd{ nullptr, nullptr };
+    if (tri) {
+        const size_t cnt = (size_t)c->d.batch * c->d.f_max;
+        if (!c->d_tri_mask && dalloc(c, &c->d_tri_mask, cnt)) return INGVIO_E_HIP;
+        if (!m.d_tri_track && dalloc(c, &m.d_tri_track, cnt)) return INGVIO_E_HIP;
+        upd.tri_mask = c->d_tri_mask; upd.tri_track = m.d_tri_track;
+    }
+    static const double no_sigma[4] = { 0.0, 0.0, 0.0, 0.0 };
+    const int rc = frame_stage_tracks_impl(c, b0, nb, raw.data(), fr.data(), opts, no_sigma, c->staged ? c->st_enable_gnss : 0, 0.0, 0.0, async, plan.data(), &upd);
+    if (rc == INGVIO_OK && tri) {
+        m.tri_on = true; m.tri = *tri; m.tri_fmx = 0;
+        for (int i = 0; i < nb; ++i) m.tri_fmx = std::max(m.tri_fmx, frames[i].n_feat);
+    }
+    return rc;
+}
+
 int ingvio_frame_stage(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step* steps, const ingvio_msckf_frame* frames,
                        const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw)
 {
@@ -4194,8 +4278,34 @@ static int frame_run_whole(ingvio_ctx* c, int restore_prior)
     const int B = c->d.batch;
     ENTER(c);
     if (wait_inputs(c)) return INGVIO_E_HIP;
-    launch_restore_propagate(c, restore_prior, strips_valid(c, restore_prior), 0, B, c->st);
-    mirror_restore_clone(c, restore_prior);
+    c->nom.tri_ran = false;
+    if (c->nom.frame && c->nom.noprop) {
+        // the update-only frame from the table: nothing is propagated and no clone joins, so the status reset that rides on the
+        // propagation launch is issued here; then (tri_on) the listed features' points from every stored observation, with the settings
+        // of ingvio_msckf_update_tri - a feature that fails loses its mask and drops out of the gate - and the points that succeeded
+        // into the track store (setValuePosXyz, MapServerManager.cpp:335).  No host synchronisation.
+        HIPCHK(c, hipMemsetAsync(c->d_status, 0, sizeof(int) * (size_t)B, c->st));
+        if (c->nom.tri_on) {
+            const ingvio_tri_opts& o = c->nom.tri;
+            TriLaunch T;
+            memset(&T, 0, sizeof T);
+            T.fv = fview(c); T.b0 = 0;
+            memcpy(T.R_lr, o.R_cl2cr, 72); memcpy(T.t_lr, o.t_cl2cr, 24);
+            T.trans_thres = o.trans_thres; T.huber_epsilon = o.huber_epsilon; T.conv_precision = o.conv_precision;
+            T.init_damping = o.init_damping; T.max_depth = o.max_depth; T.min_depth = o.min_depth;
+            T.outer_loop_max_iter = o.outer_loop_max_iter; T.inner_loop_max_iter = o.inner_loop_max_iter;
+            T.pf = c->d_pf; T.ok = c->d_tri_ok; T.mask_failed = 1; T.mask_rw = c->d_mask; T.check_anchor = 1;
+            T.ok2 = (int*)(c->d_result_slab + c->ro_tok); T.pf2 = (double*)(c->d_result_slab + c->ro_tpf);
+            T.tri_mask = c->d_tri_mask;
+            if (launch_triangulate(T, B, c->nom.tri_fmx > 0 ? c->nom.tri_fmx : 1, o.stereo, c->st)) return INGVIO_E_UNSUPPORTED;
+            const TrackStore store{ c->trk.uv, c->trk.mask, c->trk.pf, c->trk.t_max, c->d.c_max };
+            launch_tracks_store_points(store, 0, B, c->d_nfeat, c->d.f_max, c->nom.d_tri_track, T.ok2, T.pf2, c->st);
+            c->nom.tri_ran = true;
+        }
+    } else {
+        launch_restore_propagate(c, restore_prior, strips_valid(c, restore_prior), 0, B, c->st);
+        mirror_restore_clone(c, restore_prior);
+    }
     // factored path: the marginalisation of the oldest clone rides on the update's write-back (k_info_apply
     // stores the updated covariance compacted into the other ping-pong half); dense path: separate kernel
     // staged in-frame landmark update (IngvioFilter.cpp:296-322: MSCKF updates, landmark update, then the marginalisation):
@@ -4302,13 +4412,14 @@ static int frame_run_impl(ingvio_ctx* c, int restore_prior, int phase)
     if (c->method == 0 && c->d.c_max > 16) return INGVIO_E_UNSUPPORTED;       // the dense MSCKF method stops at 16 clones
     {
         const std::vector<int>& n0 = restore_prior ? c->h_n_snap : c->h_n;
+        const int grow = c->nom.frame && c->nom.noprop ? 0 : 6;             // (an update-only frame from the table takes no new clone)
         for (int b = 0; b < B; ++b) {
             if (n0[b] < 21) return INGVIO_E_ARG;
-            if (n0[b] + 6 > c->d.n_max) return INGVIO_E_CAPACITY;
-            if (c->st_cidx_hi[b] + 6 > n0[b] + 6) return INGVIO_E_NOT_IN_STATE;      // a staged clone lies beyond the live state
-            if (c->st_marg[b] >= 0 && c->st_marg[b] + 6 > n0[b] + 6) return INGVIO_E_NOT_IN_STATE;
+            if (n0[b] + grow > c->d.n_max) return INGVIO_E_CAPACITY;
+            if (c->st_cidx_hi[b] + 6 > n0[b] + grow) return INGVIO_E_NOT_IN_STATE;      // a staged clone lies beyond the live state
+            if (c->st_marg[b] >= 0 && c->st_marg[b] + 6 > n0[b] + grow) return INGVIO_E_NOT_IN_STATE;
         }
-        if (lm_in_frame(c)) { if (int rc = landmark_in_state(c, 0, B, n0, 6)) return rc; }
+        if (lm_in_frame(c)) { if (int rc = landmark_in_state(c, 0, B, n0, grow)) return rc; }
     }
     if (phase == 1) return frame_run_front(c, restore_prior);
     // ---- split step (round 6): the batch as `parts` slices on their own streams, gates chained, nothing joined at the end ----
@@ -4428,9 +4539,37 @@ int ingvio_frame_fetch_begin(ingvio_ctx* c, int b0, int nb)
     HIPCHK(c, hipMemcpyAsync(c->h_result + 8 * (size_t)b0 * c->ldp, c->d_dx + (size_t)b0 * c->ldp, 8 * (size_t)nb * c->ldp, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(c->h_result + c->ro_used + sizeof(int) * (size_t)b0 * fm, c->d_used + (size_t)b0 * fm, sizeof(int) * (size_t)nb * fm, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(c->h_result + c->ro_m + sizeof(int) * (size_t)b0, c->d_m + b0, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, c->st));
+    // a run that triangulated (the update-only frame from the table): its flags and points travel with the frame's results
+    c->nom.tri_fetched = false;
+    if (c->nom.tri_ran) {
+        HIPCHK(c, hipMemcpyAsync(c->h_result + c->ro_tok + sizeof(int) * (size_t)b0 * fm, c->d_result_slab + c->ro_tok + sizeof(int) * (size_t)b0 * fm,
+                                 sizeof(int) * (size_t)nb * fm, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipMemcpyAsync(c->h_result + c->ro_tpf + 8 * (size_t)b0 * fm * 3, c->d_result_slab + c->ro_tpf + 8 * (size_t)b0 * fm * 3,
+                                 8 * (size_t)nb * fm * 3, hipMemcpyDeviceToHost, c->st));
+        c->nom.tri_fetched = true; c->nom.tri_b0 = b0; c->nom.tri_nb = nb;
+    }
     HIPCHK(c, hipEventRecord(c->ev_fetch, c->st));
     c->fetch_b0 = b0; c->fetch_nb = nb;
     return last_launch(c);
+}
+
+// the flags and points of the run that triangulated: those the last ingvio_frame_fetch(_begin) of that run brought along (they stay
+// valid until the next fetch, whatever ran in between), else straight from the device
+int ingvio_frame_fetch_tri(ingvio_ctx* c, int b0, int nb, double* pf_out, int* tri_ok)
+{
+    if (!c || check_range(c, b0, nb)) return INGVIO_E_ARG;
+    const int fm = c->d.f_max;
+    if (c->nom.tri_fetched && b0 >= c->nom.tri_b0 && b0 + nb <= c->nom.tri_b0 + c->nom.tri_nb) {
+        HIPCHK(c, hipEventSynchronize(c->ev_fetch));
+        if (tri_ok) memcpy(tri_ok, c->h_result + c->ro_tok + sizeof(int) * (size_t)b0 * fm, sizeof(int) * (size_t)nb * fm);
+        if (pf_out) memcpy(pf_out, c->h_result + c->ro_tpf + 8 * (size_t)b0 * fm * 3, 8 * (size_t)nb * fm * 3);
+        return INGVIO_OK;
+    }
+    if (!c->nom.tri_ran) { c->err = "ingvio_frame_fetch_tri: the frame that ran last did not triangulate"; return INGVIO_E_ARG; }
+    ENTER(c);
+    if (tri_ok && down_sync(c, tri_ok, c->d_result_slab + c->ro_tok + sizeof(int) * (size_t)b0 * fm, sizeof(int) * (size_t)nb * fm)) return INGVIO_E_HIP;
+    if (pf_out && down_sync(c, pf_out, c->d_result_slab + c->ro_tpf + 8 * (size_t)b0 * fm * 3, 8 * (size_t)nb * fm * 3)) return INGVIO_E_HIP;
+    return INGVIO_OK;
 }
 
 int ingvio_frame_fetch_end(ingvio_ctx* c, double* dx_out, int* accepted, int* rows_out)

@@ -342,8 +342,12 @@ __global__ __launch_bounds__(256) void k_tracks_apply(TrackStage ts, TrackStore 
 // feat word = track | anchor slot << 16 | dof << 24; sel [n_feat] optional u64 masks ANDed onto the stored ones (the
 // Selected-timestamp updates, SwMargUpdate.cpp:236-257).
 // NOM: the window's clone table comes from the device-resident nominal state (after k_imu_steps<true> appended the new clone).
-template <bool NOM>
-__global__ __launch_bounds__(256) void k_tracks_gather(TrackStage ts, TrackStore st, FrameOut fv, NomTable nt, int b0, int* __restrict__ idx_marg, int* __restrict__ gnss_idx)
+// UPD (k_tracks_gather_upd, the update-only frame from the table: no IMU steps ran, the window is the table's as it stands): with
+// tri_mask != nullptr also the feature's FULL stored mask over the window (the triangulation of the selected-stamp updates reads every
+// stored observation, SwMargUpdate.cpp:236-257) and its track number, for the points' way back into the store.
+template <bool NOM, bool UPD>
+__device__ __forceinline__ void tracks_gather(const TrackStage& ts, const TrackStore& st, const FrameOut& fv, const NomTable& nt, int b0, int* __restrict__ idx_marg,
+                                              int* __restrict__ gnss_idx, unsigned long long* __restrict__ tri_mask, int* __restrict__ tri_track)
 {
     const int bl = blockIdx.x, b = b0 + bl, tid = threadIdx.x;
     const int* h = ts.hdr + (size_t)bl * TRK_HDR;
@@ -384,14 +388,48 @@ __global__ __launch_bounds__(256) void k_tracks_gather(TrackStage ts, TrackStore
         fv.dof[o] = (int)(w >> 24);
         fv.obs_mask[o] = m;
         fv.pf[3 * o] = pfB[3 * t]; fv.pf[3 * o + 1] = pfB[3 * t + 1]; fv.pf[3 * o + 2] = pfB[3 * t + 2];
+        if constexpr (UPD) {
+            if (tri_mask) { tri_mask[o] = mkB[t] & (Cn >= 64 ? ~0ULL : ((1ULL << Cn) - 1ULL)); tri_track[o] = t; }
+        }
     }
     for (int j = F + tid; j < fv.fmax; j += 256) fv.obs_mask[(size_t)b * fv.fmax + j] = 0ULL;      // as pack_frames leaves the rows behind the frame's features
+    if constexpr (UPD) {
+        if (tri_mask) for (int j = F + tid; j < fv.fmax; j += 256) tri_mask[(size_t)b * fv.fmax + j] = 0ULL;
+    }
     // measurements: F rows of C x 4 doubles, coalesced by (feature, element) pairs
     const int per = fv.cmax * 4;
     for (int e = tid; e < F * per; e += 256) {
         const int j = e / per, r = e - j * per;
         const int t = (int)((unsigned)feat[j] & 0xffffu);
         fv.uv[((size_t)b * fv.fmax + j) * per + r] = r < C * 4 ? uvB[(size_t)t * C * 4 + r] : 0.0;
+    }
+}
+
+template <bool NOM>
+__global__ __launch_bounds__(256) void k_tracks_gather(TrackStage ts, TrackStore st, FrameOut fv, NomTable nt, int b0, int* __restrict__ idx_marg, int* __restrict__ gnss_idx)
+{
+    tracks_gather<NOM, false>(ts, st, fv, nt, b0, idx_marg, gnss_idx, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void k_tracks_gather_upd(TrackStage ts, TrackStore st, FrameOut fv, NomTable nt, int b0, int* __restrict__ idx_marg, int* __restrict__ gnss_idx,
+                                                           unsigned long long* __restrict__ tri_mask, int* __restrict__ tri_track)
+{
+    tracks_gather<true, true>(ts, st, fv, nt, b0, idx_marg, gnss_idx, tri_mask, tri_track);
+}
+
+// The points an in-run triangulation found go back into the store (FeatureInfo's setValuePosXyz, MapServerManager.cpp:335): one
+// workgroup per filter, one thread per listed feature; ok [B][fmax] (1: triangulated in front of its anchor), pf [B][fmax][3] and
+// track [B][fmax] as k_triangulate and k_tracks_gather_upd left them.  A track listed twice is written twice with the same values.
+__global__ __launch_bounds__(256) void k_tracks_store_points(TrackStore st, int b0, const int* __restrict__ n_feat, int fmax, const int* __restrict__ track,
+                                                             const int* __restrict__ ok, const double* __restrict__ pf)
+{
+    const int b = b0 + blockIdx.x;
+    const int F = min(n_feat[b], fmax);
+    double* pfB = st.pf + (size_t)b * st.tmax * 3;
+    for (int j = threadIdx.x; j < F; j += 256) {
+        const size_t o = (size_t)b * fmax + j;
+        const int t = track[o];
+        if (ok[o] != 1 || t < 0 || t >= st.tmax) continue;
+        pfB[3 * t] = pf[3 * o]; pfB[3 * t + 1] = pf[3 * o + 1]; pfB[3 * t + 2] = pf[3 * o + 2];
     }
 }
 
@@ -409,4 +447,13 @@ void launch_tracks_gather(const TrackStage& ts, const TrackStore& store, const F
 {
     if (nom) hipLaunchKernelGGL(k_tracks_gather<true>, dim3(nb), dim3(256), 0, st, ts, store, fv, *nom, b0, idx_marg, gnss_idx);
     else hipLaunchKernelGGL(k_tracks_gather<false>, dim3(nb), dim3(256), 0, st, ts, store, fv, NomTable{}, b0, idx_marg, gnss_idx);
+}
+void launch_tracks_gather_update(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st,
+                                 const NomTable& nom, unsigned long long* tri_mask, int* tri_track)
+{
+    hipLaunchKernelGGL(k_tracks_gather_upd, dim3(nb), dim3(256), 0, st, ts, store, fv, nom, b0, idx_marg, gnss_idx, tri_mask, tri_track);
+}
+void launch_tracks_store_points(const TrackStore& store, int b0, int nb, const int* n_feat, int fmax, const int* track, const int* ok, const double* pf, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_tracks_store_points, dim3(nb), dim3(256), 0, st, store, b0, n_feat, fmax, track, ok, pf);
 }

@@ -40,6 +40,15 @@ ALL landmarks change their anchor to the newest clone, two forms on the same bui
   round-trip form  the tail through the host: ingvio_nominal_get, one ingvio_replace_var_linear per landmark and one ingvio_marginalize
                    per variable and filter, ingvio_nominal_set
 measured and reported as the GNSS forms are; writes $RESULTS/closed_loop_bench_tail.json.
+--two-updates [--second 40]: both MSCKF updates of the camera callback per camera frame (ingvio_amd/closed_loop_update.py): the first
+with --features - --second tracks, the second with --second tracks over three or four selected stamps, triangulated first, marginalising
+the frame's clone; two forms on the same build,
+  device form      run(i); ustage(i, async); fetch_begin(i); run_u(i); fetch_end(i); stage(i+1, async); ... - the second update an
+                   update-only frame from the table and the track store (ingvio_update_stage_tracks_nominal)
+  round-trip form  the plain frame, then ingvio_nominal_get, ingvio_msckf_update_tri with tri_masks, ingvio_marginalize, boxPlus / drop /
+                   shift on the host, ingvio_nominal_set
+the device form free-running (device_loop_ms_per_frame) and both synchronised per camera frame; writes
+$RESULTS/closed_loop_bench_two_updates.json.
 Writes $RESULTS/closed_loop_bench.json (RESULTS defaults to results/) and prints one JSON line.
 usage: python tools/closed_loop_bench.py [--batch 512] [--features 150] [--window 11] [--k 10] [--frames 30] [--warmup 5] [--device-only]
                                          [--gnss | --gnss-in-frame [--sats 8] | --register-only | --landmarks L | --tail [--landmarks L]]"""
@@ -252,6 +261,59 @@ def main_tail(a):
     finish(out, "closed_loop_bench_tail.json")
 
 
+def main_two_updates(a):
+    """both MSCKF updates of the camera callback per camera frame (ingvio_amd/closed_loop_update.py): the first lists
+    --features - --second tracks, the second --second tracks over selected stamps with their points triangulated in the run"""
+    from ingvio_amd import closed_loop as cl
+    from ingvio_amd import closed_loop_update as cu
+    B, F, NF, W = a.batch, a.features, a.frames, a.warmup
+    t0 = time.perf_counter()
+    cases = cu.make_update_loop(B, NF, F=F, n_lost=F - a.second, carry_point=False, ks=(a.k,), windows=(a.window,))
+    out = dict(batch=B, features=F, second=a.second, window=a.window, k=a.k, frames_timed=NF - W, two_updates=True, setup_s=round(time.perf_counter() - t0, 1))
+    fresh = lambda: fresh_ctx(a, cases)
+    entries = cu.two_update_entries(range(NF))
+
+    def device_run(name, synced):
+        ctx = fresh()
+        loop = cl.DeviceLoop(ctx, cases, entries, None, collect=False, update_stage=cu.update_stage).prepare()
+        loop.start()
+        if synced:
+            ctx.L = TimedLib(ctx.L)
+        wall = 0.0
+        for f in range(NF):
+            if synced or f == W:
+                ctx.sync()
+            if f == W:
+                t0 = time.perf_counter()
+                if synced:
+                    ctx.L.t = 0.0
+            t1 = time.perf_counter()
+            r1, r2 = loop.frame(2 * f), loop.frame(2 * f + 1)
+            if synced:
+                ctx.sync()
+                wall += time.perf_counter() - t1 if f >= W else 0.0
+        ctx.sync()
+        if synced:
+            out[name + "_abi_ms_per_frame"] = round(1e3 * ctx.L.t / (NF - W), 4)
+            out[name + "_wall_ms_per_frame"] = round(1e3 * wall / (NF - W), 4)
+            ctx.L = ctx.L._lib
+        else:
+            out[name + "_loop_ms_per_frame"] = round(1e3 * (time.perf_counter() - t0) / (NF - W), 4)
+            out["last_second_update_rows_mean"] = float(r2[2].mean()); out["last_second_update_tri_ok_mean"] = float((r2[4][:, :a.second] == 1).sum(axis=1).mean())
+        nom = ctx.nominal_get()
+        ctx.close()
+        return nom
+    dev_nom = device_run("device", False)
+    if not a.device_only:
+        device_run("device", True)
+        ctx = fresh()
+        synced_run(out, "roundtrip", ctx, cases, cu.UpdateRoundTrip(cases, range(NF), a.window + 1), NF, W)
+        rt_nom = ctx.nominal_get()
+        ctx.close()
+        out["max_abs_pose_device_vs_roundtrip"] = max(float(np.max(np.abs(d["val"][0] - r["val"][0]))) for d, r in zip(dev_nom, rt_nom))
+    finish(out, "closed_loop_bench_two_updates.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=512)
@@ -267,7 +329,11 @@ def main():
     ap.add_argument("--register-only", action="store_true", help="the loop without epochs, the GNSS scalars registered (clock recursion on)")
     ap.add_argument("--landmarks", type=int, default=0, help="L in-state landmarks per filter, updated in every frame")
     ap.add_argument("--tail", action="store_true", help="the oldest clone leaves and every landmark changes its anchor behind every frame")
+    ap.add_argument("--two-updates", action="store_true", help="both MSCKF updates of the camera callback: the second as an update-only frame from the table")
+    ap.add_argument("--second", type=int, default=40, help="--two-updates: features of the second update")
     a = ap.parse_args()
+    if a.two_updates:
+        return main_two_updates(a)
     if a.tail:
         return main_tail(a)
     if a.landmarks > 0:
