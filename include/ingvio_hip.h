@@ -299,7 +299,10 @@ int ingvio_add_variable_delayed_invertible(ingvio_ctx* ctx, int b, const int* vi
  * modified; the Givens rotations run on the device copy).  chi2_check = quantile(chi_squared(m), 0.95)
  * (boost in the reference, :610-612; the caller supplies it).  *added = 0 when m <= s (:571-575) or when the
  * chi2 test fails (:614-618; state untouched).  On success the variable is appended (new_idx), the EKF update
- * with the remaining m-s rows is applied to the covariance and dx_out [N+s] = K res; the host applies boxPlus. */
+ * with the remaining m-s rows is applied to the covariance and dx_out [N+s] = K res; the host applies boxPlus.
+ * INGVIO_E_CAPACITY: n + s > n_max, m > ingvio_mld, the trailing update's S beyond LDS, or the gate's bound
+ * 8 (nc (m-s) + (m-s+1)^2) <= 150 KB (stereo: 22 clones).  Under ingvio_set_delayed_form(ctx, 1) a candidate beyond the gate's
+ * bound is not refused: it runs as a one-filter call of ingvio_add_variable_delayed_batch, with the same outputs. */
 int ingvio_add_variable_delayed(ingvio_ctx* ctx, int b, const int* vidx, const int* vsize, int k,
                                 const double* H_old, int ldh, const double* H_new, int ldn, int m, int s,
                                 const double* res, double noise, double chi2_mult, int do_chi2, double chi2_check,
@@ -328,7 +331,9 @@ int ingvio_add_variable_delayed(ingvio_ctx* ctx, int b, const int* vidx, const i
  * INGVIO_E_CAPACITY (n + sum of the filter's s > n_max, m > ingvio_mld, more columns than the context holds, the
  * trailing update's S beyond LDS, the single-filter gate's bound 8 (nc (m-s) + (m-s+1)^2) <= 150 KB, or the front's own:
  * it keeps the rows AND T = Pcc H^T in LDS, 8 ((2 nc + 1)(m | 1) + 3 s m + (m-s+1)^2) + 4 nc + 1.3 KB <= 160 KB - tighter
- * than the single-filter call for wide windows, e.g. m = 64 rows on 16 clones fit, m = 84 on 21 clones do not). */
+ * than the single-filter call for wide windows, e.g. m = 64 rows on 16 clones fit, m = 84 on 21 clones do not).  The last two hold
+ * under ingvio_set_delayed_form(ctx, 0) only: under mode 1 or 2 such a candidate takes the large form of the front (a round whose
+ * filters mix the forms is two launches, one per form) and only the other bounds refuse. */
 typedef struct {
     const int* vidx; const int* vsize; int k;   /* var_old_order as (idx, size)[k]                       */
     const double* H_old; int ldh;               /* m x sum(vsize), column-major                          */
@@ -764,7 +769,8 @@ int ingvio_landmark_stage_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_
  * epoch / landmark stage from the table that has not run); INGVIO_E_NOT_IN_STATE (a window clone beyond the filter's n);
  * INGVIO_E_CAPACITY (fewer free table slots than candidates, n + 3 n_cand > n_max, the worst-case m - every window clone observing -
  * beyond ingvio_mld, more columns than the context holds, and the three LDS bounds of ingvio_add_variable_delayed_batch taken at that
- * worst-case m: the trailing update's S, the single-filter gate's 150 KB, the front's 160 KB - e.g. a stereo candidate on 20 clones).
+ * worst-case m: the trailing update's S, the single-filter gate's 150 KB, the front's 160 KB - e.g. a stereo candidate on 20 clones;
+ * under ingvio_set_delayed_form(ctx, 1) the last two do not refuse: the call's fronts then take the large form, up to 36 clones).
  * Not reproduced: the reference's hasNaN skip of an observation (:479, :866) - a point on a camera's z = 0 plane gives a non-finite
  * chi2 and is refused (with do_chi2 != 0).  The call runs where ingvio_add_variable_delayed_batch runs: between frames, on the window the
  * table holds then; it is not part of ingvio_frame_run.  Which tracks to try, triangulation, the max_landmarks cap and the MapServer's
@@ -807,6 +813,20 @@ int ingvio_set_frame_parts(ingvio_ctx* ctx, int parts);
  * take the full form.  After a step whose Gram kernel ran reduced ingvio_debug_msckf_info returns INGVIO_E_UNSUPPORTED.
  * Environment override at context creation: INGVIO_GRAM_REDUCED (0 / 1). */
 int ingvio_set_gram_reduced(ingvio_ctx* ctx, int on);
+/* Which form of the delayed-initialisation front ingvio_add_variable_delayed, ingvio_add_variable_delayed_batch and
+ * ingvio_landmark_init_nominal take.  The LDS form keeps [H_old | res], T = Pcc H_old^T and S in LDS at once, which bounds
+ * the window (stereo: 17 clones, mono: 21 - 26).  The large form keeps [H_old | res | T^T] in a per-filter workspace in device memory
+ * (grown on demand, 8 (2 nc + 1) m bytes per filter, no part of ingvio_cov_snapshot), sweeps it through LDS in panels of 64 columns and
+ * holds S as a packed triangle: every window the context accepts (36 clones, m <= 144, nc <= 216) runs.  Same outputs and side effects.
+ *   0 (the default): the LDS form only, with its refusals.
+ *   1: a candidate that fits the LDS form takes it (bit-identical to mode 0), any other takes the large form.  The front's 160 KB bound
+ *      and the single-filter gate's 150 KB bound no longer refuse; m > ingvio_mld, more columns than the context holds, the trailing
+ *      update's S beyond LDS (m - s > 141) and n + sum s > n_max still do.  ingvio_landmark_init_nominal chooses once per call, at the
+ *      worst-case m of its widest window; ingvio_add_variable_delayed runs a candidate beyond its gate bound as a one-filter call of
+ *      the batch path; ingvio_debug_landmark_init_rows forms rows that do not fit LDS in device memory.
+ *   2: a test setting - every candidate takes the large form, so that the two forms can be compared on the same inputs.
+ * INGVIO_E_ARG: any other value, a split frame step pending, or a frame staged from the nominal table that has not run. */
+int ingvio_set_delayed_form(ingvio_ctx* ctx, int mode);
 int ingvio_frame_fetch(ingvio_ctx* ctx, int b0, int nb, double* dx_out, int* accepted, int* rows_out);
 /* The fetch in two halves (round 6): _begin enqueues the result copies (into pinned memory) behind the frame's kernels and returns;
  * _end waits for them and fills the caller's arrays.  In between the host may stage and LAUNCH the next frame - its kernels queue up

@@ -37,7 +37,7 @@ EXPORTS = [
     "ingvio_landmark_init_nominal", "ingvio_debug_landmark_init_rows", "ingvio_nominal_tail",
     "ingvio_debug_tracks_read", "ingvio_debug_staged_frame",
     "ingvio_gnss_frame_stage_nominal", "ingvio_debug_gnss_fused_last", "ingvio_debug_nominal_update_post",
-    "ingvio_update_stage_tracks_nominal", "ingvio_frame_fetch_tri",
+    "ingvio_update_stage_tracks_nominal", "ingvio_frame_fetch_tri", "ingvio_set_delayed_form",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -1128,6 +1128,11 @@ class Context:
         """True (default): the unsplit frame_run forms [A | b] without the block row / column of the solve's reference clone; False: the
         full form everywhere (ingvio_set_gram_reduced).  Bit-identical results."""
         self._chk(self.L.ingvio_set_gram_reduced(self.h, 1 if on else 0))
+
+    def set_delayed_form(self, mode):
+        """0 (default): delayed initialisation in its LDS form only; 1: the large form for candidates the LDS form cannot take (windows
+        up to 36 clones); 2, a test setting: the large form for every candidate (ingvio_set_delayed_form)."""
+        self._chk(self.L.ingvio_set_delayed_form(self.h, int(mode)))
 
     def frame_fetch(self, b0=0, nb=None):
         nb = self.batch if nb is None else nb

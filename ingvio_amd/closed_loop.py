@@ -82,7 +82,7 @@ def make_loop(B, n_frames, F=24, seed=5, ks=KS, windows=None, n_landmarks=2, lm_
     cases = []
     for b in range(B):
         C = 5 + b % 7 if windows is None else windows[b % len(windows)]
-        flt, step, frame, info = synth.build_case(lambda P: orc.Cov(P, ld=160), orc.imu_transition, seed=seed + b, F=8, C=C, n_gnss=6, n_landmarks=n_landmarks,
+        flt, step, frame, info = synth.build_case(lambda P, C=C: orc.Cov(P, ld=max(160, 48 + 6 * C)), orc.imu_transition, seed=seed + b, F=8, C=C, n_gnss=6, n_landmarks=n_landmarks,
                                                   lm_sigma=lm_sigma)
         P = flt.cov.P() if callable(flt.cov.P) else flt.cov.P
         raw = step["raw"]

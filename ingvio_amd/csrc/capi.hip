@@ -165,7 +165,10 @@ struct ingvio_ctx {
     char* d_multi = nullptr;            // ingvio_chi2_gamma_multi: packed blocks (grown on demand)
     // ingvio_add_variable_delayed_batch (kernels_delayed.hip), grown on demand: the packed candidates of a call, the rows / row
     // counts its fronts hand to the update kernels, and the results of every round with their pinned mirror
-    struct DelayedWs { char *in = nullptr, *wk = nullptr, *out = nullptr, *h_out = nullptr; size_t in_cap = 0, wk_cap = 0, out_cap = 0; } dl;
+    struct DelayedWs {
+        char *in = nullptr, *wk = nullptr, *out = nullptr, *h_out = nullptr; size_t in_cap = 0, wk_cap = 0, out_cap = 0;
+        char* ws = nullptr; size_t ws_cap = 0;      // the large form's [H_old | res | T^T] per filter (ingvio_set_delayed_form); no part of a snapshot
+    } dl;
     size_t multi_cap = 0;
     // staged frame state
     int st_stereo, st_enable_gnss, st_fmax_used;
@@ -211,6 +214,7 @@ struct ingvio_ctx {
     int parts_alloc = 0;
     int parts_req = -1;                 // ingvio_set_frame_parts: -1 automatic, 1 off, 2..4 forced
     int gram_reduced = 1;               // ingvio_set_gram_reduced: the fused frame step may run k_feat_gram2 in its reduced form
+    int delayed_form = 0;               // ingvio_set_delayed_form: 0 LDS form only, 1 the large form where the LDS form does not fit, 2 the large form everywhere
     int gram_red_last = 0;              // the chunk partials in d_Rpart come from a reduced Gram launch (ingvio_debug_msckf_info refuses them)
     bool split_pending = false;         // slices of the last split step may still be running on their own streams
     hipEvent_t tok_last = nullptr;      // end of the throughput segment issued last (nullptr: none yet / chain broken)
@@ -1268,7 +1272,7 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
                      c->lm.lm_idx, c->lm.anchor_idx, c->lm.tracked, c->lm.accept, c->lm.slot, c->lm.dx, c->d_xchg, c->dw.U, c->dw.rowmap, c->d_zero_idx,
                      c->d_Asum, c->d_used_sum, c->d_Tflat, c->d_imu, c->d_tri_mask, c->d_prm };
     for (void* p : ptrs) if (p) hipFree(p);
-    for (void* p : { (void*)c->dl.in, (void*)c->dl.wk, (void*)c->dl.out }) if (p) hipFree(p);
+    for (void* p : { (void*)c->dl.in, (void*)c->dl.wk, (void*)c->dl.out, (void*)c->dl.ws }) if (p) hipFree(p);
     if (c->dl.h_out) hipHostFree(c->dl.h_out);
     for (void* p : { (void*)c->tl.in, (void*)c->tl.ws }) if (p) hipFree(p);
     if (c->tl.h_out) hipHostFree(c->tl.h_out);
@@ -2498,6 +2502,26 @@ int ingvio_add_variable_delayed(ingvio_ctx* c, int b, const int* vidx, const int
     *added = 0;
     if (m <= s) return INGVIO_OK;                                                  // StateManager.cpp:571-575
     if (c->h_n[b] + s > c->d.n_max) return INGVIO_E_CAPACITY;
+    if (c->delayed_form && vidx && vsize && k >= 1) {
+        // ingvio_set_delayed_form: a candidate beyond the gate's bound (mode 2: every candidate) runs as a one-filter call of the batch path
+        size_t ncq = 0;
+        for (int t = 0; t < k; ++t) ncq += vsize[t] > 0 ? vsize[t] : 0;
+        const size_t muq = (size_t)(m - s);
+        if (c->delayed_form == 2 || 8 * (ncq * muq + (muq + 1) * (muq + 1)) > 150 * 1024) {
+            const ingvio_delayed_cand q{ vidx, vsize, k, H_old, ldh, H_new, ldn, res, m, s, chi2_check };
+            const ingvio_delayed_block blk{ 1, &q };
+            std::vector<double> dxb(dx_out ? (size_t)c->ldp : 0);
+            int idx = -1, st = INGVIO_OK;
+            double chi2 = 0.0;
+            const int rc = ingvio_add_variable_delayed_batch(c, b, 1, &blk, noise, chi2_mult, do_chi2, 1, added, &idx, &chi2, dx_out ? dxb.data() : nullptr, &st);
+            if (chi2_out && (rc == INGVIO_OK || rc == INGVIO_NEG_DIAG || rc == INGVIO_E_NOT_PD)) *chi2_out = chi2;
+            if (*added) {
+                if (new_idx) *new_idx = idx;
+                if (dx_out) memcpy(dx_out, dxb.data(), 8 * (size_t)c->h_n[b]);
+            }
+            return rc;
+        }
+    }
     int nc = 0;
     const double var = noise * noise;
     int rc = stage_generic(c, b, vidx, vsize, k, H_old, ldh, m, res, &var, 0, &nc);
@@ -2564,12 +2588,15 @@ int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvi
     if (c->nom.pending) { c->err = "ingvio_add_variable_delayed_batch: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
     if (gnss_nom_busy(c, "ingvio_add_variable_delayed_batch")) return INGVIO_E_ARG;
     // ---- everything that can be wrong, before anything changes ----
-    int R = 0, mu_cap = 0, nc_cap = 0, n_cap = 0;
-    size_t lds = 0, dtot = 0;
+    int R = 0, mu_cap = 0, nc_cap = 0, n_cap = 0, ldw = 0, ncw = 0;
+    size_t lds = 0, lds_large = 0, dtot = 0;
+    const int form = c->delayed_form;             // ingvio_set_delayed_form
     for (int i = 0; i < nb; ++i) if (blocks[i].n_cand > R) R = blocks[i].n_cand;      // rounds (a wrong n_cand is refused below)
     if (R > cand_cap) return INGVIO_E_ARG;
     const size_t RN = (size_t)R * nb;
     std::vector<int> ncs(RN, 0);                  // [round][filter]: columns of the candidate, 0 = none / skipped
+    std::vector<char> large(RN, 0);               // [round][filter]: the candidate takes the large form of the front
+    std::vector<int> n_lds(R > 0 ? R : 1, 0), n_large(R > 0 ? R : 1, 0);      // per round: candidates of either form
     std::vector<size_t> offs(RN, 0);
     for (int i = 0; i < nb; ++i) {
         const ingvio_delayed_block& blk = blocks[i];
@@ -2589,10 +2616,20 @@ int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvi
             if (nc < 1) return INGVIO_E_ARG;
             const int mu = q.m - q.s;
             if (q.m > c->mld || nc > c->nc_cap || !ekf_core_fits(mu, nc)) return INGVIO_E_CAPACITY;
-            if ((size_t)8 * ((size_t)nc * mu + (size_t)(mu + 1) * (mu + 1)) > 150 * 1024) return INGVIO_E_CAPACITY;      // the single-filter gate's bound
+            if (!form && (size_t)8 * ((size_t)nc * mu + (size_t)(mu + 1) * (mu + 1)) > 150 * 1024) return INGVIO_E_CAPACITY;      // the single-filter gate's bound
             const size_t l = delayed_front_lds(q.m, q.s, nc);
-            if (l > 160 * 1024) return INGVIO_E_CAPACITY;                               // the front's own: rows and T stay in LDS
-            if (l > lds) lds = l;
+            if (form == 2 || (form == 1 && l > 160 * 1024)) {                           // the large form: rows and T in the workspace
+                const size_t ll = delayed_front_large_lds(q.m, q.s, nc);
+                if (ll > 160 * 1024) return INGVIO_E_CAPACITY;
+                if (ll > lds_large) lds_large = ll;
+                if (q.m > ldw) ldw = q.m;
+                if (nc > ncw) ncw = nc;
+                large[(size_t)j * nb + i] = 1; ++n_large[j];
+            } else {
+                if (l > 160 * 1024) return INGVIO_E_CAPACITY;                           // the front's own: rows and T stay in LDS
+                if (l > lds) lds = l;
+                ++n_lds[j];
+            }
             if (mu > mu_cap) mu_cap = mu;
             if (nc > nc_cap) nc_cap = nc;
             grow += q.s;
@@ -2610,8 +2647,12 @@ int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvi
     if (R == 0 || nc_cap == 0) return INGVIO_OK;                                        // nothing to try anywhere
     // ---- one slab up: [m | s | nc | colmap | offsets | thresholds | var | rows] ----
     const size_t cs = nc_cap;
+    // (rounds that mix the two forms: the LDS launch's row counts with the large form's candidates struck, the large launch's selection)
     const size_t o_m = 0, o_s = o_m + pad64(4 * RN), o_nc = o_s + pad64(4 * RN), o_cm = o_nc + pad64(4 * RN), o_off = o_cm + pad64(4 * RN * cs),
-                 o_thr = o_off + pad64(8 * RN), o_var = o_thr + pad64(8 * RN), o_d = o_var + 64, in_bytes = o_d + pad64(8 * dtot);
+                 o_thr = o_off + pad64(8 * RN), o_var = o_thr + pad64(8 * RN), o_ml = o_var + 64, o_sel = o_ml + (ldw ? pad64(4 * RN) : 0),
+                 o_d = o_sel + (ldw ? pad64(4 * RN) : 0), in_bytes = o_d + pad64(8 * dtot);
+    ldw = (ldw + 1) & ~1;
+    const size_t ws_stride = (size_t)(2 * ncw + 1) * ldw;
     const int mldu = (mu_cap + 15) & ~15;
     const size_t hsu = (size_t)mldu * nc_cap;
     const size_t w_res = pad64(8 * (size_t)nb * hsu), w_mu = w_res + pad64(8 * (size_t)nb * mldu), wk_bytes = w_mu + pad64(4 * (size_t)nb);
@@ -2621,6 +2662,7 @@ int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvi
     auto& w = c->dl;
     if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
     if (int rc = dl_grow(c, &w.wk, &w.wk_cap, wk_bytes)) return rc;
+    if (ldw) if (int rc = dl_grow(c, &w.ws, &w.ws_cap, 8 * (size_t)nb * ws_stride)) return rc;
     if (w.out_cap < out_bytes && w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; }      // the pinned mirror grows with the device slab
     if (int rc = dl_grow(c, &w.out, &w.out_cap, out_bytes)) return rc;
     if (!w.h_out) HIPCHK(c, hipHostMalloc((void**)&w.h_out, w.out_cap, hipHostMallocDefault));
@@ -2632,7 +2674,8 @@ int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvi
     size_t* hoff = (size_t*)(h + o_off);
     double *hthr = (double*)(h + o_thr), *hd = (double*)(h + o_d);
     *(double*)(h + o_var) = noise * noise;
-    parallel_for(nb, [=, &ncs, &offs](int i) {
+    int *hml = (int*)(h + o_ml), *hsel = (int*)(h + o_sel);
+    parallel_for(nb, [=, &ncs, &offs, &large](int i) {
         const ingvio_delayed_block& blk = blocks[i];
         for (int j = 0; j < blk.n_cand; ++j) {
             const size_t e = (size_t)j * nb + i;
@@ -2640,6 +2683,7 @@ int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvi
             if (!nc) continue;
             const ingvio_delayed_cand& q = blk.cand[j];
             hm[e] = q.m; hs[e] = q.s; hnc[e] = nc; hoff[e] = offs[e]; hthr[e] = chi2_mult * q.chi2_check;
+            if (ldw) { hml[e] = large[e] ? 0 : q.m; hsel[e] = large[e]; }
             int* cm = hcm + e * cs;
             int wr = 0;
             for (int t = 0; t < q.k; ++t) for (int u = 0; u < q.vsize[t]; ++u) cm[wr++] = q.vidx[t] + u;
@@ -2667,7 +2711,15 @@ int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvi
         F.Hu = (double*)w.wk; F.resu = (double*)(w.wk + w_res); F.mldu = mldu; F.hsu = hsu; F.mu = (int*)(w.wk + w_mu);
         F.Y = c->d_Y + (size_t)b0 * c->ystride; F.ystride = (size_t)c->ystride; F.status = d_st;
         F.added = (int*)w.out + r0; F.new_idx = (int*)(w.out + r_idx) + r0; F.chi2 = (double*)(w.out + r_chi) + r0;
-        if (launch_delayed_front(F, lds, c->st)) return INGVIO_E_CAPACITY;
+        // one launch per form: the LDS form first (it writes "nothing tried" for the filters it does not take), then the large
+        // form, which skips every filter that is not its own
+        if (!n_large[j]) { if (launch_delayed_front(F, lds, c->st)) return INGVIO_E_CAPACITY; }
+        else {
+            const int* m_all = F.m;
+            if (n_lds[j]) { F.m = (const int*)(w.in + o_ml) + r0; if (launch_delayed_front(F, lds, c->st)) return INGVIO_E_CAPACITY; F.m = m_all; }
+            DelayedLarge G{ (double*)w.ws, ws_stride, ldw, n_lds[j] ? (const int*)(w.in + o_sel) + r0 : nullptr };
+            if (launch_delayed_front_large(F, G, lds_large, c->st)) return INGVIO_E_CAPACITY;
+        }
         EkfLaunch E;                                                                    // :623-624 ekfUpdate with the lower rows on the extended state
         memset(&E, 0, sizeof E);
         E.cv = cv; E.b0 = b0; E.nb = nb; E.H = F.Hu; E.res = F.resu; E.colmap = F.colmap; E.m = F.mu; E.nc = F.nc;
@@ -2706,6 +2758,9 @@ int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvi
 struct LmInitPlan {
     int R = 0, mu_cap = 0, nc_cap = 0, n_cap = 0, per = 2;
     size_t lds = 0;
+    bool large = false;                 // ingvio_set_delayed_form: the call's fronts take the large form (chosen at the worst-case m of the widest window)
+    size_t lds_large = 0;
+    int ldw = 0;
     std::vector<int> slots;             // [round][filter] reserved table slot (-1: no candidate)
     std::vector<unsigned long long> dropm;
 };
@@ -2762,9 +2817,17 @@ static int lm_init_validate(ingvio_ctx* c, const char* who, int b0, int nb, cons
         if (mw > c->mld || nc > c->nc_cap) { cap_err = 1; continue; }
         if (mu > 0) {
             const size_t l = delayed_front_lds(mw, 3, nc);
-            if (l > 160 * 1024 || !ekf_core_fits(mu, nc)) { cap_err = 1; continue; }
-            if ((size_t)8 * ((size_t)nc * mu + (size_t)(mu + 1) * (mu + 1)) > 150 * 1024) { cap_err = 1; continue; }      // as ingvio_add_variable_delayed_batch
-            if (l > pl.lds) pl.lds = l;
+            const int form = c->delayed_form;
+            if ((!form && l > 160 * 1024) || !ekf_core_fits(mu, nc)) { cap_err = 1; continue; }
+            if (!form && (size_t)8 * ((size_t)nc * mu + (size_t)(mu + 1) * (mu + 1)) > 150 * 1024) { cap_err = 1; continue; }      // as ingvio_add_variable_delayed_batch
+            if (form) {
+                const size_t ll = delayed_front_large_lds(mw, 3, nc);
+                if (ll > 160 * 1024) { cap_err = 1; continue; }
+                if (ll > pl.lds_large) pl.lds_large = ll;
+                if (mw > pl.ldw) pl.ldw = mw;
+                if (form == 2 || l > 160 * 1024) pl.large = true;
+            }
+            if (l <= 160 * 1024 && l > pl.lds) pl.lds = l;
             if (mu > pl.mu_cap) pl.mu_cap = mu;
         }
         if (nc > pl.nc_cap) pl.nc_cap = nc;
@@ -2809,6 +2872,9 @@ int ingvio_landmark_init_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_lm_
     auto& w = c->dl;
     if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
     if (int rc = dl_grow(c, &w.wk, &w.wk_cap, wk_bytes)) return rc;
+    const int ldw = (pl.ldw + 1) & ~1;
+    const size_t ws_stride = (size_t)(2 * pl.nc_cap + 1) * ldw;
+    if (pl.large) if (int rc = dl_grow(c, &w.ws, &w.ws_cap, 8 * (size_t)nb * ws_stride)) return rc;
     if (w.out_cap < out_bytes && w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; }
     if (int rc = dl_grow(c, &w.out, &w.out_cap, out_bytes)) return rc;
     if (!w.h_out) HIPCHK(c, hipHostMalloc((void**)&w.h_out, w.out_cap, hipHostMallocDefault));
@@ -2852,7 +2918,10 @@ int ingvio_landmark_init_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_lm_
         F.added = (int*)w.out + r0; F.new_idx = (int*)(w.out + r_idx) + r0; F.chi2 = (double*)(w.out + r_chi) + r0;
         Rw.track = (const int*)(w.in + o_tr) + r0; Rw.anchor = (const int*)(w.in + o_an) + r0; Rw.slot = (const int*)(w.in + o_sl) + r0;
         Rw.pf = (const double*)(w.in + o_pf) + 3 * r0; Rw.slot_out = (int*)(w.out + r_sl) + r0;
-        if (launch_delayed_front_rows(F, Rw, pl.lds, c->st)) return INGVIO_E_CAPACITY;
+        if (pl.large) {
+            const DelayedLarge G{ (double*)w.ws, ws_stride, ldw, nullptr };
+            if (launch_delayed_front_rows_large(F, Rw, G, pl.lds_large, c->st)) return INGVIO_E_CAPACITY;
+        } else if (launch_delayed_front_rows(F, Rw, pl.lds, c->st)) return INGVIO_E_CAPACITY;
         EkfLaunch E;                                                                    // :623-624 ekfUpdate with the lower rows on the extended state
         memset(&E, 0, sizeof E);
         E.cv = cv; E.b0 = b0; E.nb = nb; E.H = F.Hu; E.res = F.resu; E.colmap = Rw.colmap_out; E.m = F.mu; E.nc = Rw.nc_out;
@@ -2917,7 +2986,9 @@ int ingvio_debug_landmark_init_rows(ingvio_ctx* c, int b, const ingvio_lm_init_c
     Rw.track = (const int*)w.in; Rw.anchor = (const int*)w.in + 1; Rw.pf = (const double*)(w.in + o_pf); Rw.dropm = (const unsigned long long*)(w.in + o_dm);
     int* d_m = (int*)(w.wk + pad64(8 * rows));
     const size_t lds = delayed_front_lds(mw > 0 ? mw : 1, 3, nc);
-    if (launch_delayed_rows_debug(Rw, b, (double*)w.wk, d_m, lds, c->st)) return INGVIO_E_CAPACITY;
+    const bool big = c->delayed_form && lds > 160 * 1024;      // rows formed in global memory: [H_old | res | H_new]
+    if (big) launch_delayed_rows_debug_large(Rw, b, (double*)w.wk, d_m, c->st);
+    else if (launch_delayed_rows_debug(Rw, b, (double*)w.wk, d_m, lds, c->st)) return INGVIO_E_CAPACITY;
     std::vector<double> out(rows);
     int m = 0;
     HIPCHK(c, hipMemcpyAsync(out.data(), w.wk, 8 * rows, hipMemcpyDeviceToHost, c->st));
@@ -2925,8 +2996,8 @@ int ingvio_debug_landmark_init_rows(ingvio_ctx* c, int b, const ingvio_lm_init_c
     if (int rc = last_launch(c)) return rc;
     *m_out = m;
     memcpy(H_old, out.data(), 8 * (size_t)m * nc);
-    memcpy(H_new, out.data() + (size_t)m * nc, 8 * (size_t)m * 3);
-    memcpy(res, out.data() + (size_t)m * (nc + 3), 8 * (size_t)m);
+    memcpy(H_new, out.data() + (size_t)m * (big ? nc + 1 : nc), 8 * (size_t)m * 3);
+    memcpy(res, out.data() + (size_t)m * (big ? nc : nc + 3), 8 * (size_t)m);
     return INGVIO_OK;
 }
 
@@ -4446,6 +4517,17 @@ int ingvio_set_gram_reduced(ingvio_ctx* c, int on)
     if (!c) return INGVIO_E_ARG;
     ENTER(c);
     c->gram_reduced = on ? 1 : 0;
+    return INGVIO_OK;
+}
+// which form of the delayed-initialisation front the three entry points take (kernels_delayed.hip)
+int ingvio_set_delayed_form(ingvio_ctx* c, int mode)
+{
+    if (!c) return INGVIO_E_ARG;
+    ENTER(c);
+    if (mode < 0 || mode > 2) { c->err = "ingvio_set_delayed_form: mode is 0, 1 or 2"; return INGVIO_E_ARG; }
+    if (phase_busy(c)) return INGVIO_E_ARG;
+    if (c->nom.pending) { c->err = "ingvio_set_delayed_form: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    c->delayed_form = mode;
     return INGVIO_OK;
 }
 int ingvio_frame_run_phase(ingvio_ctx* c, int restore_prior, int phase)

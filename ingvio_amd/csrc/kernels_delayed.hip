@@ -355,6 +355,329 @@ __global__ __launch_bounds__(WAVE) void k_delayed_rows_debug(DelayedRows r, int 
     for (int e = tid; e < m; e += WAVE) out[(size_t)m * (nc + s) + e] = sA[e + (size_t)nc * L.ldA];
 }
 
+
+// ---- the large form (ingvio_set_delayed_form): [H_old | res | T^T] in a per-filter HBM workspace, through LDS in column panels ----
+// Same inputs, outputs and side effects as k_delayed_front.  What differs is where the (2 nc + 1) columns of m doubles live: in
+// ws (column stride ldw) instead of LDS.  T is formed straight into the workspace beside the serial derivation of the rotations;
+// the sweep takes DLL_W columns at a time through LDS (a column needs only itself and the rotation list); S is accumulated as a
+// packed lower triangle in LDS from DLL_K-column chunks of the rotated lower rows, in ascending column order as the LDS form sums it.
+#define DLL_W 64
+#define DLL_K 8
+
+struct DelayedLargeLds { size_t Hn, CS, sm, R, Sc, col, q, bytes; int ldA; };      // offsets in doubles (every one even)
+
+__host__ __device__ inline DelayedLargeLds delayed_large_carve(int m, int s, int nc)
+{
+    auto even = [](size_t x) { return (x + 1) & ~(size_t)1; };
+    DelayedLargeLds L;
+    const size_t mu = m - s;
+    L.ldA = m | 1;
+    L.Hn = 0;                                                // [s][m]
+    L.CS = even((size_t)s * m);                              // [s][m][2]
+    L.sm = even(L.CS + 2 * (size_t)s * m);                   // 4 x [6][6]
+    L.R = even(L.sm + 4 * DL_SMAX * DL_SMAX);                // one region, three tenants in turn:
+    const size_t tri = even((mu + 1) * (mu + 2) / 2);        //   the sweep's panel [DLL_W][ldA];
+    L.Sc = L.R + tri;                                        //   S packed [(mu + 1)(mu + 2) / 2] + the chunk [2][DLL_K][mu];
+    size_t r = (size_t)DLL_W * L.ldA;                        //   the upper s rows of H and T [2][nc][DL_SMAX]
+    if (tri + 2 * DLL_K * mu > r) r = tri + 2 * DLL_K * mu;
+    if (2 * (size_t)nc * DL_SMAX > r) r = 2 * (size_t)nc * DL_SMAX;
+    L.col = even(L.R + r);                                   // nc ints
+    L.q = L.col + ((((size_t)nc + 3) & ~(size_t)3) >> 1);    // 64 ints: window position of the observer of every row group
+    L.bytes = 8 * L.q + 4 * 64;
+    return L;
+}
+
+template <bool ROWS>
+__global__ __launch_bounds__(DL_NT) void k_delayed_front_large(DelayedFront a, std::conditional_t<ROWS, DelayedRows, NoRows> r, DelayedLarge g)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int bl = blockIdx.x, b = a.b0 + bl, tid = threadIdx.x;
+    if (g.sel && !g.sel[bl]) return;                         // a filter of the other form (or none): that launch writes its outputs
+    int m_ = 0, s_ = 3, nc_ = 0;
+    unsigned long long um = 0ULL, dm = 0ULL;
+    if constexpr (ROWS) {
+        const int track = r.track[bl];
+        if (track >= 0 && !(a.status[b] & 4)) {
+            const int cw = r.nt.ih[(size_t)b * r.nt.ir + NOM_N_CLONES];
+            dm = r.dropm[bl];
+            um = rows_used(r.ts.mask[(size_t)b * r.ts.tmax + track], dm, cw, r.ts.cmax);
+            m_ = (r.stereo ? 4 : 2) * __popcll(um);
+            nc_ = 6 * cw;
+        }
+        if (m_ <= s_) {
+            if (tid == 0) { a.added[bl] = 0; a.new_idx[bl] = -1; a.chi2[bl] = 0.0; a.mu[bl] = 0; r.slot_out[bl] = -1; }
+            return;
+        }
+    } else {
+        m_ = a.m[bl];
+        if (m_ == 0 || (a.status[b] & 4)) {
+            if (tid == 0) { a.added[bl] = 0; a.new_idx[bl] = -1; a.chi2[bl] = 0.0; a.mu[bl] = 0; }
+            return;
+        }
+        s_ = a.s[bl]; nc_ = a.nc[bl];
+    }
+    const int m = m_, s = s_, nc = nc_, mu = m - s;
+    const DelayedLargeLds L = delayed_large_carve(m, s, nc);
+    double* base = reinterpret_cast<double*>(smem_raw);
+    double *sHn = base + L.Hn, *sCS = base + L.CS, *sR = base + L.R, *sS = sR, *sC = base + L.Sc;
+    double *sHf = base + L.sm, *sHi = sHf + DL_SMAX * DL_SMAX, *sS3 = sHi + DL_SMAX * DL_SMAX, *sT3 = sS3 + DL_SMAX * DL_SMAX;
+    int *sCol = reinterpret_cast<int*>(base + L.col), *sQ = reinterpret_cast<int*>(base + L.q);
+    const int ldA = L.ldA, n = a.cv.n[b], ld = a.cv.ldp, ldw = g.ldw;
+    double* P = cov_ptr(a.cv, b);
+    double* W = g.ws + (size_t)bl * g.ws_stride;             // [2 nc + 1][ldw]: H_old columns, res, the rows of T
+    double* WT = W + (size_t)(nc + 1) * ldw;
+    // where the unrotated H_old and res are read: the workspace (formed rows) or the call's packed rows (host-fed)
+    const double *Hsrc = W, *rsrc = W + (size_t)nc * ldw;
+    int ldh = ldw;
+
+    // ---- 1. stage H_new, the column map; formed rows go to the workspace -------------------------------------------------
+    if constexpr (ROWS) {
+        for (size_t e = tid; e < (size_t)(nc + 1) * ldw; e += DL_NT) W[e] = 0.0;
+        for (int e = tid; e < s * m; e += DL_NT) sHn[e] = 0.0;
+        const int* I = r.nt.ih + (size_t)b * r.nt.ir;
+        for (int c = tid; c < nc; c += DL_NT) {
+            const int col = I[NOM_IH + 4 * I[NOM_CLONES + c / 6] + 1] + c % 6;
+            sCol[c] = col; r.colmap_out[(size_t)bl * a.cs + c] = col;
+        }
+        if (tid < WAVE && ((um >> tid) & 1ULL)) {            // row group -> window position of its observer
+            const unsigned long long below = (1ULL << tid) - 1ULL;
+            sQ[__popcll(um & below)] = tid - __popcll(dm & below);
+        }
+        if (tid == 0) r.nc_out[bl] = nc;
+        __syncthreads();
+        if (tid < WAVE) rows_form(r, b, bl, um, dm, tid, m, nc, W, ldw, sHn);
+    } else {
+        const double* in = a.dbuf + a.doff[bl];
+        Hsrc = in; ldh = m; rsrc = in + (size_t)m * (nc + s);
+        const double* Hnin = in + (size_t)m * nc;
+        for (int e = tid; e < s * m; e += DL_NT) sHn[e] = Hnin[e];
+        for (int c = tid; c < nc; c += DL_NT) sCol[c] = a.colmap[(size_t)bl * a.cs + c];
+    }
+    __syncthreads();
+    // ---- 2. the rotation list (one lane) beside T = Pcc H_old^T (the other waves), T into the workspace ------------------
+    if (tid < WAVE) {
+        if (tid == 0)
+            for (int col = 0; col < s; ++col)
+                for (int rr = m - 1; rr > col; --rr) {
+                    double c, sn;
+                    make_givens(sHn[(rr - 1) + col * m], sHn[rr + col * m], c, sn);
+                    sCS[2 * (col * m + rr)] = c; sCS[2 * (col * m + rr) + 1] = sn;
+                    for (int j = col; j < s; ++j) {
+                        const double x = sHn[(rr - 1) + j * m], y = sHn[rr + j * m];
+                        sHn[(rr - 1) + j * m] = c * x - sn * y;
+                        sHn[rr + j * m] = sn * x + c * y;
+                    }
+                }
+    } else if constexpr (ROWS) {
+        // a formed row has nine non-zero entries: the anchor's theta block and the observer's six columns.  Taken in ascending
+        // column order, the sum is the dense one with its zero terms left out.
+        const int per = r.stereo ? 4 : 2, anc = r.anchor[bl];
+        const int items = nc * m;
+        for (int it = tid - WAVE; it < items; it += DL_NT - WAVE) {
+            const int c = it % nc, i = it / nc, q = sQ[i / per];
+            const double* prow = P + sCol[c];
+            const double* h = W + i;
+            double acc = 0.0;
+            if (anc < q)
+                for (int k = 0; k < 3; ++k) acc += prow[(size_t)sCol[6 * anc + k] * ld] * h[(size_t)(6 * anc + k) * ldw];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) acc += prow[(size_t)sCol[6 * q + k] * ld] * h[(size_t)(6 * q + k) * ldw];
+            if (anc > q)
+                for (int k = 0; k < 3; ++k) acc += prow[(size_t)sCol[6 * anc + k] * ld] * h[(size_t)(6 * anc + k) * ldw];
+            WT[i + (size_t)c * ldw] = acc;
+        }
+    } else {
+        const int items = nc * ((m + DL_IB - 1) / DL_IB);
+        for (int it = tid - WAVE; it < items; it += DL_NT - WAVE) {
+            const int c = it % nc, ib = (it / nc) * DL_IB;
+            const int nr = m - ib < DL_IB ? m - ib : DL_IB;
+            const double* prow = P + sCol[c];
+            double acc[DL_IB];
+#pragma unroll
+            for (int ii = 0; ii < DL_IB; ++ii) acc[ii] = 0.0;
+#pragma unroll 4
+            for (int c2 = 0; c2 < nc; ++c2) {
+                const double p = prow[(size_t)sCol[c2] * ld];
+                const double* h = Hsrc + ib + (size_t)c2 * ldh;
+#pragma unroll
+                for (int ii = 0; ii < DL_IB; ++ii) acc[ii] += p * (ii < nr ? h[ii] : 0.0);      // no read past the column
+            }
+#pragma unroll
+            for (int ii = 0; ii < DL_IB; ++ii) if (ii < nr) WT[(ib + ii) + (size_t)c * ldw] = acc[ii];
+        }
+    }
+    __syncthreads();
+    // ---- 3. the sweep, DLL_W columns at a time through LDS: every column by its own lane, running carry -------------------
+    const int ncols = 2 * nc + 1;
+    for (int p0 = 0; p0 < ncols; p0 += DLL_W) {
+        const int pw = ncols - p0 < DLL_W ? ncols - p0 : DLL_W;
+        for (int e = tid; e < pw * m; e += DL_NT) {
+            const int jj = e / m, rr = e - jj * m, j = p0 + jj;
+            const double* src = j < nc ? Hsrc + (size_t)j * ldh : (j == nc ? rsrc : W + (size_t)j * ldw);
+            sR[rr + (size_t)jj * ldA] = src[rr];
+        }
+        __syncthreads();
+        if (tid < pw) {
+            double* A = sR + (size_t)tid * ldA;
+            for (int col = 0; col < s; ++col) {
+                double carry = A[m - 1];
+                for (int rr = m - 1; rr > col; --rr) {
+                    const double c = sCS[2 * (col * m + rr)], sn = sCS[2 * (col * m + rr) + 1];
+                    const double x = A[rr - 1];
+                    A[rr] = sn * x + c * carry;
+                    carry = c * x - sn * carry;
+                }
+                A[col] = carry;
+            }
+        }
+        __syncthreads();
+        for (int e = tid; e < pw * m; e += DL_NT) {
+            const int jj = e / m, rr = e - jj * m;
+            W[rr + (size_t)(p0 + jj) * ldw] = sR[rr + (size_t)jj * ldA];
+        }
+        __syncthreads();
+    }
+    // ---- 4. S of the lower rows, packed lower triangle S(i, k) = sS[i (i + 1) / 2 + k], from chunks of DLL_K columns ------
+    double *sHc = sC, *sTc = sC + (size_t)DLL_K * mu;
+    for (int c0 = 0; c0 < nc; c0 += DLL_K) {
+        const int kc = nc - c0 < DLL_K ? nc - c0 : DLL_K;
+        for (int e = tid; e < kc * mu; e += DL_NT) {
+            const int k = e / mu, i = e - k * mu;
+            sHc[e] = W[(s + i) + (size_t)(c0 + k) * ldw];
+            sTc[e] = WT[(s + i) + (size_t)(c0 + k) * ldw];
+        }
+        __syncthreads();
+        for (int e = tid; e < mu * mu; e += DL_NT) {
+            const int i = e % mu, i2 = e / mu;
+            if (i < i2) continue;
+            const int idx = i * (i + 1) / 2 + i2;
+            double acc = c0 ? sS[idx] : 0.0;
+            for (int k = 0; k < kc; ++k) acc += sHc[i + k * mu] * sTc[i2 + k * mu];
+            if (i == i2 && c0 + kc == nc) acc += a.var;
+            sS[idx] = acc;
+        }
+        __syncthreads();
+    }
+    const int bord = mu * (mu + 1) / 2;
+    for (int e = tid; e <= mu; e += DL_NT) sS[bord + e] = (e < mu) ? W[(s + e) + (size_t)nc * ldw] : 0.0;
+    __syncthreads();
+    for (int j = 0; j < mu; ++j) {
+        const int jj = j * (j + 1) / 2 + j;
+        const double inv = 1.0 / sS[jj];
+        const int w = mu - j;
+        for (int e = tid; e < w * w; e += DL_NT) {
+            const int i = j + 1 + e % w, k = j + 1 + e / w;
+            if (k > i) continue;
+            const int ri = i * (i + 1) / 2, rk = k * (k + 1) / 2;
+            sS[ri + k] -= sS[ri + j] * sS[rk + j] * inv;
+        }
+        __syncthreads();
+    }
+    // ---- 5. the verdict ------------------------------------------------------------------------------------------------
+    const double chi2 = -sS[bord + mu];
+    bool refuse;
+    if constexpr (ROWS) refuse = !(chi2 <= r.chi2_mult * r.chi2[m]);
+    else refuse = chi2 > a.thr[bl];
+    if (refuse && a.do_chi2) {
+        if (tid == 0) {
+            a.added[bl] = 0; a.new_idx[bl] = -1; a.chi2[bl] = chi2; a.mu[bl] = 0;
+            if constexpr (ROWS) r.slot_out[bl] = -1;
+        }
+        return;
+    }
+    __syncthreads();                                         // every thread has read chi2: the region changes tenant
+    // the upper s rows of the rotated H and T into LDS; the trailing update's rows, from row 0
+    double *sHup = sR, *sTup = sR + (size_t)nc * DL_SMAX;
+    for (int e = tid; e < s * nc; e += DL_NT) {
+        const int j = e % s, c = e / s;
+        sHup[j + c * DL_SMAX] = W[j + (size_t)c * ldw];
+        sTup[j + c * DL_SMAX] = WT[j + (size_t)c * ldw];
+    }
+    double* Hu = a.Hu + (size_t)bl * a.hsu;
+    for (int e = tid; e < mu * nc; e += DL_NT) { const int i = e % mu, c = e / mu; Hu[i + (size_t)c * a.mldu] = W[(s + i) + (size_t)c * ldw]; }
+    for (int e = tid; e < mu; e += DL_NT) a.resu[(size_t)bl * a.mldu + e] = W[(s + e) + (size_t)nc * ldw];
+    __syncthreads();
+    // addVariableDelayedInvertible with the upper s rows, as k_delayed_front
+    double* Y = a.Y + (size_t)bl * a.ystride;
+    for (int rr = tid; rr < n; rr += DL_NT) {
+        double acc[DL_SMAX];
+#pragma unroll
+        for (int j = 0; j < DL_SMAX; ++j) acc[j] = 0.0;
+#pragma unroll 4
+        for (int c = 0; c < nc; ++c) {
+            const double p = P[rr + (size_t)sCol[c] * ld];
+#pragma unroll
+            for (int j = 0; j < DL_SMAX; ++j) if (j < s) acc[j] += p * sHup[j + c * DL_SMAX];
+        }
+#pragma unroll
+        for (int j = 0; j < DL_SMAX; ++j) if (j < s) Y[rr + (size_t)j * ld] = acc[j];
+    }
+    if (tid < s * s) {
+        const int i = tid % s, j = tid / s;
+        double acc = 0.0;
+        for (int c = 0; c < nc; ++c) acc += sHup[i + c * DL_SMAX] * sTup[j + c * DL_SMAX];
+        sS3[i + j * s] = acc + (i == j ? a.var : 0.0);
+        sHf[i + j * s] = sHn[i + j * m];
+    }
+    __syncthreads();
+    if (tid == 0) inv_small(sHf, sHi, s);
+    __syncthreads();
+    if (tid < s * s) {
+        const int i = tid % s, j = tid / s;
+        double acc = 0.0;
+        for (int l = 0; l < s; ++l) acc += sHi[i + l * s] * sS3[l + j * s];
+        sT3[i + j * s] = acc;
+    }
+    __syncthreads();
+    if (tid < s * s) {
+        const int i = tid % s, j = tid / s;
+        double x = 0.0, y = 0.0;
+        for (int l = 0; l < s; ++l) { x += sT3[i + l * s] * sHi[j + l * s]; y += sT3[j + l * s] * sHi[i + l * s]; }
+        P[(n + i) + (size_t)(n + j) * ld] = 0.5 * (x + y);
+    }
+    for (int rr = tid; rr < n; rr += DL_NT) {
+        double y[DL_SMAX];
+#pragma unroll
+        for (int l = 0; l < DL_SMAX; ++l) y[l] = l < s ? Y[rr + (size_t)l * ld] : 0.0;
+        for (int j = 0; j < s; ++j) {
+            double acc = 0.0;
+#pragma unroll
+            for (int l = 0; l < DL_SMAX; ++l) if (l < s) acc += y[l] * sHi[j + l * s];
+            P[rr + (size_t)(n + j) * ld] = -acc;
+            P[(n + j) + (size_t)rr * ld] = -acc;
+        }
+    }
+    if (tid == 0) { a.cv.n[b] = n + s; a.added[bl] = 1; a.new_idx[bl] = n; a.chi2[bl] = chi2; a.mu[bl] = mu; }
+    if constexpr (ROWS) {
+        if (tid == 0) {                                      // the landmark's table record, as k_delayed_front<true> enters it
+            int* I = r.nt.ih + (size_t)b * r.nt.ir;
+            const int slot = r.slot[bl];
+            int* v = I + NOM_IH + 4 * slot;
+            v[0] = NOM_KIND_LM; v[1] = n; v[2] = I[NOM_CLONES + r.anchor[bl]]; v[3] = 0;
+            double* x = r.nt.dv + (size_t)b * r.nt.dr + NOM_DH + (size_t)slot * NOM_VD;
+            for (int i = 0; i < NOM_VD; ++i) x[i] = (i == 0 || i == 4 || i == 8) ? 1.0 : 0.0;
+            for (int i = 0; i < 3; ++i) x[9 + i] = r.pf[3 * (size_t)bl + i];
+            if (slot >= I[NOM_N_VAR]) I[NOM_N_VAR] = slot + 1;
+            r.slot_out[bl] = slot;
+        }
+    }
+}
+
+// test hook: the row stage alone for a window whose rows do not fit LDS, formed straight into global memory
+__global__ __launch_bounds__(WAVE) void k_delayed_rows_debug_large(DelayedRows r, int b, double* __restrict__ out, int* __restrict__ m_out)
+{
+    const int tid = threadIdx.x;
+    const int cw = r.nt.ih[(size_t)b * r.nt.ir + NOM_N_CLONES], nc = 6 * cw, s = 3;
+    const unsigned long long dm = r.dropm[0];
+    const unsigned long long um = rows_used(r.ts.mask[(size_t)b * r.ts.tmax + r.track[0]], dm, cw, r.ts.cmax);
+    const int m = (r.stereo ? 4 : 2) * __popcll(um);
+    if (tid == 0) *m_out = m;
+    if (m == 0) return;
+    for (size_t e = tid; e < (size_t)m * (nc + s + 1); e += WAVE) out[e] = 0.0;
+    __syncthreads();
+    rows_form(r, b, 0, um, dm, tid, m, nc, out, m, out + (size_t)m * (nc + 1));      // [H_old | res | H_new], column stride m
+}
+
 }  // namespace
 
 size_t delayed_front_lds(int m, int s, int nc) { return delayed_carve(m, s, nc).bytes; }
@@ -380,5 +703,29 @@ int launch_delayed_rows_debug(const DelayedRows& R, int b, double* out, int* m_o
     if (lds_bytes > 160 * 1024) return -1;
     hipFuncSetAttribute((const void*)k_delayed_rows_debug, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     hipLaunchKernelGGL(k_delayed_rows_debug, dim3(1), dim3(WAVE), lds_bytes, st, R, b, out, m_out);
+    return 0;
+}
+
+size_t delayed_front_large_lds(int m, int s, int nc) { return delayed_large_carve(m, s, nc).bytes; }
+
+int launch_delayed_front_large(const DelayedFront& L, const DelayedLarge& G, size_t lds_bytes, hipStream_t st)
+{
+    if (lds_bytes > 160 * 1024 || !G.ws) return -1;
+    hipFuncSetAttribute((const void*)k_delayed_front_large<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(k_delayed_front_large<false>, dim3(L.nb), dim3(DL_NT), lds_bytes, st, L, NoRows{}, G);
+    return 0;
+}
+
+int launch_delayed_front_rows_large(const DelayedFront& L, const DelayedRows& R, const DelayedLarge& G, size_t lds_bytes, hipStream_t st)
+{
+    if (lds_bytes > 160 * 1024 || !G.ws) return -1;
+    hipFuncSetAttribute((const void*)k_delayed_front_large<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(k_delayed_front_large<true>, dim3(L.nb), dim3(DL_NT), lds_bytes, st, L, R, G);
+    return 0;
+}
+
+int launch_delayed_rows_debug_large(const DelayedRows& R, int b, double* out, int* m_out, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_delayed_rows_debug_large, dim3(1), dim3(WAVE), 0, st, R, b, out, m_out);
     return 0;
 }

@@ -52,6 +52,15 @@ struct DelayedRows {
     int* slot_out;                      // [nb] out: the slot the landmark was entered at, -1 when not added
 };
 
+// The large form of the front (k_delayed_front_large, ingvio_set_delayed_form): [H_old | res | T^T] lives in a per-filter workspace
+// in device memory and passes through LDS in column panels, so m and nc are bounded by the context, not by LDS.
+struct DelayedLarge {
+    double* ws;                 // [nb][ws_stride]: (2 nc + 1) columns of ldw doubles per filter
+    size_t ws_stride;           // >= (2 nc + 1) * ldw for every candidate of the launch
+    int ldw;                    // >= m of every candidate of the launch
+    const int* sel;             // [nb] or null: 0 = the filter is not this launch's (left untouched), null = every filter is
+};
+
 // dynamic LDS of one workgroup of k_delayed_front for a candidate (m, s, nc)
 size_t delayed_front_lds(int m, int s, int nc);
 // lds_bytes: the largest delayed_front_lds of the round's candidates.  -1: beyond the LDS of a CU
@@ -61,3 +70,12 @@ int launch_delayed_front(const DelayedFront& L, size_t lds_bytes, hipStream_t st
 int launch_delayed_front_rows(const DelayedFront& L, const DelayedRows& R, size_t lds_bytes, hipStream_t st);
 // test hook: the row formation alone for filter b (entry 0 of R's arrays) -> out = [H_old m x nc (ld m) | H_new m x 3 | res m], *m_out
 int launch_delayed_rows_debug(const DelayedRows& R, int b, double* out, int* m_out, size_t lds_bytes, hipStream_t st);
+
+// dynamic LDS of one workgroup of k_delayed_front_large for a candidate (m, s, nc)
+size_t delayed_front_large_lds(int m, int s, int nc);
+// the large form of launch_delayed_front / launch_delayed_front_rows: same inputs, outputs and side effects.  lds_bytes: the largest
+// delayed_front_large_lds of the launch's candidates.  -1: beyond the LDS of a CU, or no workspace
+int launch_delayed_front_large(const DelayedFront& L, const DelayedLarge& G, size_t lds_bytes, hipStream_t st);
+int launch_delayed_front_rows_large(const DelayedFront& L, const DelayedRows& R, const DelayedLarge& G, size_t lds_bytes, hipStream_t st);
+// test hook for windows whose rows do not fit LDS: out = [H_old m x nc | res m | H_new m x 3], column stride m, (nc + 4) m doubles
+int launch_delayed_rows_debug_large(const DelayedRows& R, int b, double* out, int* m_out, hipStream_t st);

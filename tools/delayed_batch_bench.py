@@ -7,6 +7,11 @@ repetition; a repetition is timed from its first call to the return of its last 
 --reps repetitions after --warmup.  Prints one JSON line.  Both forms are called through ctypes with arguments built ahead of
 the timed region.  Only figures of one run are compared with each other.
 usage: python tools/delayed_batch_bench.py [--batch 512] [--cands 1,4] [--reps 20] [--warmup 3] [--mode delayed|init]
+                                          [--clones C] [--mono] [--form 0|1|2[,..]] [--no-single]
+--clones C (--mode delayed): every clone of a window of C observing, m = 4 C (--mono: 2 C) rows on 6 C columns, N = 21 + 6 C + 3 x 54
+  beyond 11 clones (the default shape keeps N = 249).  --form: ingvio_set_delayed_form for the batch form; several values (0,2) time the
+  batch form once per value on the same context, "batch_form<k>" each.  The loop of single-filter calls runs under mode 0 and is left
+  out where the single-filter call cannot take the shape (beyond 22 clones stereo) or with --no-single.
 --mode init: landmark initialisation from the track store and the nominal table, two forms on the same build and inputs:
   call        one ingvio_landmark_init_nominal call for B filters x K candidates (rows formed on the device, 40 bytes per candidate)
   round_trip  per candidate: nominal_get -> host rows (numpy, vectorised over the batch) -> ingvio_add_variable_delayed_batch ->
@@ -148,17 +153,27 @@ def run_init(a, ks):
 
 
 def main():
+    global CLONES, M, N
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--cands", default="1,4")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mode", default="delayed", choices=["delayed", "init"])
+    ap.add_argument("--clones", type=int, default=CLONES)
+    ap.add_argument("--mono", action="store_true")
+    ap.add_argument("--form", default="0")
+    ap.add_argument("--no-single", action="store_true")
     a = ap.parse_args()
     ks = [int(x) for x in a.cands.split(",")]
     if a.mode == "init":
         return run_init(a, ks)
     B, kmax = a.batch, max(ks)
+    forms = [int(x) for x in a.form.split(",")]
+    CLONES, M = a.clones, (2 if a.mono else 4) * a.clones
+    N = 249 if CLONES <= 11 else 21 + 6 * CLONES + 162
+    mu = M - S
+    single_fits = 8 * (6 * CLONES * mu + (mu + 1) ** 2) <= 150 * 1024 and not a.no_single
     rng = np.random.default_rng(1)
     A = rng.standard_normal((N, N))
     P0 = 1e-2 * (A @ A.T / N + 0.1 * np.eye(N))
@@ -172,7 +187,7 @@ def main():
     cands = [(vidx, vsize, rng.standard_normal((M, 6 * CLONES)), rng.standard_normal((M, S)), 0.05 * rng.standard_normal(M), chk)
              for _ in range(kmax)]
     L, h = ctx.L, ctx.h
-    out = {"tool": "delayed_batch_bench", "batch": B, "m": M, "s": S, "n": N, "reps": a.reps, "forms": {}}
+    out = {"tool": "delayed_batch_bench", "batch": B, "clones": CLONES, "m": M, "s": S, "n": N, "reps": a.reps, "forms": {}}
     for K in ks:
         arr, cap, keep = capi.make_delayed_blocks([cands[:K]] * B)
         added = np.zeros((B, cap), dtype=np.int32); idx = np.zeros((B, cap), dtype=np.int32); g = np.zeros((B, cap))
@@ -197,7 +212,9 @@ def main():
                     assert rc == 0 and a1.value == 1, (rc, a1.value)
 
         res = {}
-        for name, fn in (("batch", batch), ("single", single)):
+        runs = [("batch" if forms == [0] else "batch_form%d" % f, batch, f) for f in forms] + ([("single", single, 0)] if single_fits else [])
+        for name, fn, form in runs:
+            ctx.set_delayed_form(form)
             ts = []
             for r in range(a.warmup + a.reps):
                 ctx.restore(); ctx.sync()
@@ -206,9 +223,10 @@ def main():
                 ts.append((time.perf_counter() - t0) * 1e3)
             ts = np.array(ts[a.warmup:])
             res[name] = {"median_ms": float(np.median(ts)), "min_ms": float(ts.min()), "max_ms": float(ts.max())}
-            if name == "batch":
+            if name != "single":
                 assert added.all() and (idx[:, K - 1] == N + S * (K - 1)).all()
-        res["ratio_single_over_batch"] = res["single"]["median_ms"] / res["batch"]["median_ms"]
+        if single_fits:
+            res["ratio_single_over_batch"] = res["single"]["median_ms"] / res[runs[0][0]]["median_ms"]
         out["forms"]["%dx%d" % (B, K)] = res
     ctx.close()
     print(json.dumps(out))
