@@ -813,6 +813,15 @@ int ingvio_set_frame_parts(ingvio_ctx* ctx, int parts);
  * take the full form.  After a step whose Gram kernel ran reduced ingvio_debug_msckf_info returns INGVIO_E_UNSUPPORTED.
  * Environment override at context creation: INGVIO_GRAM_REDUCED (0 / 1). */
 int ingvio_set_gram_reduced(ingvio_ctx* ctx, int on);
+/* The reduced form of the Gram kernel as k_feat_gram3 (window classes of up to 6 and up to 11 clones): operand panel and
+ * sparse scratch double-buffered, the wave pairs of a workgroup decoupled, one barrier per batch.  The same sums in the same order:
+ * results are bit-identical to the reduced k_feat_gram2 (tests/test_gpu_gram_decoupled.py).  on: 1 (the default) / 0 the reduced
+ * k_feat_gram2, for comparison.  Has no effect where ingvio_set_gram_reduced has none, nor on 12-clone windows.
+ * Environment override at context creation: INGVIO_GRAM_DECOUPLED (0 / 1). */
+int ingvio_set_gram_decoupled(ingvio_ctx* ctx, int on);
+/* The form the Gram stage of the context's last MSCKF update took: 0 the full form, 1 the reduced k_feat_gram2, 2 the reduced
+ * k_feat_gram3.  A negative error code for a null context. */
+int ingvio_last_gram_form(ingvio_ctx* ctx);
 /* Which form of the delayed-initialisation front ingvio_add_variable_delayed, ingvio_add_variable_delayed_batch and
  * ingvio_landmark_init_nominal take.  The LDS form keeps [H_old | res], T = Pcc H_old^T and S in LDS at once, which bounds
  * the window (stereo: 17 clones, mono: 21 - 26).  The large form keeps [H_old | res | T^T] in a per-filter workspace in device memory

@@ -215,6 +215,8 @@ struct ingvio_ctx {
     int parts_req = -1;                 // ingvio_set_frame_parts: -1 automatic, 1 off, 2..4 forced
     int gram_reduced = 1;               // ingvio_set_gram_reduced: the fused frame step may run k_feat_gram2 in its reduced form
     int delayed_form = 0;               // ingvio_set_delayed_form: 0 LDS form only, 1 the large form where the LDS form does not fit, 2 the large form everywhere
+    int gram_decoupled = 1;             // ingvio_set_gram_decoupled: the reduced form runs as k_feat_gram3 in the window classes 6 and 11
+    int gram_form_last = 0;             // ingvio_last_gram_form: 0 full, 1 reduced k_feat_gram2, 2 reduced k_feat_gram3
     int gram_red_last = 0;              // the chunk partials in d_Rpart come from a reduced Gram launch (ingvio_debug_msckf_info refuses them)
     bool split_pending = false;         // slices of the last split step may still be running on their own streams
     hipEvent_t tok_last = nullptr;      // end of the throughput segment issued last (nullptr: none yet / chain broken)
@@ -925,10 +927,11 @@ int run_msckf_factored(ingvio_ctx* c, int b0, int nb, const MsckfOpts& op, int s
             }
             if (grc) return INGVIO_E_UNSUPPORTED;
         }
-        c->gram_red_last = 0;
+        c->gram_red_last = 0; c->gram_form_last = 0;
         L.gram_red = frame_step && phase == 0 && c->gram_reduced; L.gram_was_red = &c->gram_red_last;
+        L.gram_dec = c->gram_decoupled; L.gram_form = &c->gram_form_last;
         { ProfScope p(c, PF_GRAM); L.stage = 1; launch_factored(L, c->run_st); }
-        L.gram_was_red = nullptr;
+        L.gram_was_red = nullptr; L.gram_form = nullptr;
         if (c->tok_rec) HIPCHK(c, hipEventRecord(c->tok_rec, c->run_st));
     }
     if (forked) {
@@ -961,7 +964,7 @@ int run_msckf_factored(ingvio_ctx* c, int b0, int nb, const MsckfOpts& op, int s
 int run_msckf(ingvio_ctx* c, int b0, int nb, const MsckfOpts& op, int stereo, int fmax_used)
 {
     if (c->method == 1) return run_msckf_factored(c, b0, nb, op, stereo, fmax_used);
-    c->gram_red_last = 0;
+    c->gram_red_last = 0; c->gram_form_last = 0;
     MsckfLaunch L;
     memset(&L, 0, sizeof L);
     L.stereo = stereo; L.cv = view(c); L.fv = fview(c); L.op = op; L.b0 = b0; L.nb = nb;
@@ -1150,6 +1153,7 @@ int ingvio_ctx_create(const ingvio_ctx_desc* desc, ingvio_ctx** out)
     c->run_st = c->st;
     if (const char* e = getenv("INGVIO_FRAME_PARTS")) c->parts_req = atoi(e);
     if (const char* e = getenv("INGVIO_GRAM_REDUCED")) c->gram_reduced = atoi(e) != 0;      // A/B timing of an unchanged program
+    if (const char* e = getenv("INGVIO_GRAM_DECOUPLED")) c->gram_decoupled = atoi(e) != 0;
     if (desc->c_max > 16) {
         // a higher priority than the compute stream's default: its short dependent launches take the slots the gate's workgroups free
         int lo = 0, hi = 0;
@@ -4518,6 +4522,20 @@ int ingvio_set_gram_reduced(ingvio_ctx* c, int on)
     ENTER(c);
     c->gram_reduced = on ? 1 : 0;
     return INGVIO_OK;
+}
+// the reduced form as k_feat_gram3 (wave pairs decoupled, one barrier per batch; window classes 6 and 11), on by default; off: k_feat_gram2
+int ingvio_set_gram_decoupled(ingvio_ctx* c, int on)
+{
+    if (!c) return INGVIO_E_ARG;
+    ENTER(c);
+    c->gram_decoupled = on ? 1 : 0;
+    return INGVIO_OK;
+}
+// the form the last MSCKF update's Gram stage took: 0 full, 1 reduced k_feat_gram2, 2 reduced k_feat_gram3
+int ingvio_last_gram_form(ingvio_ctx* c)
+{
+    if (!c) return INGVIO_E_ARG;
+    return c->gram_form_last;
 }
 // which form of the delayed-initialisation front the three entry points take (kernels_delayed.hip)
 int ingvio_set_delayed_form(ingvio_ctx* c, int mode)

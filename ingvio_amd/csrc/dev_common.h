@@ -139,6 +139,15 @@ __device__ __forceinline__ void dbg_stamp(int slot)
     (void)slot;
 #endif
 }
+// the same probe stamped by thread `t` of the block (a wave other than wave 0: the consumer role of k_feat_gram3)
+__device__ __forceinline__ void dbg_stamp_at(int slot, int t)
+{
+#ifdef INGVIO_DBG_STAMPS
+    if (blockIdx.x == INGVIO_DBG_BLOCK && blockIdx.y == INGVIO_DBG_BLOCK_Y && (int)threadIdx.x == t) g_dbg[slot] = clock64();
+#else
+    (void)slot; (void)t;
+#endif
+}
 static inline int dbg_read_local(long long* out, int n)
 {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dbg), sizeof(long long) * n);

@@ -621,9 +621,9 @@ __global__ __launch_bounds__(GRAM_NT, 2) void k_feat_gram2(
     dbg_stamp(40);
 }
 
-#ifdef INGVIO_ALT_KERNELS      // k_feat_gram3 (round 6, measured and rejected: 115 against 107 us per 512 filters): one operand panel (Z^T Z),
-#include "gram3_kernel.h"      // double-buffered, one barrier per batch - variant build only, INGVIO_GRAM=3
-#endif
+// k_feat_gram3: the wave pairs decoupled, operand panel and sparse scratch double-buffered, one barrier per batch.  Its reduced form is
+// the fused frame step's Gram kernel for the window classes 6 and 11; the full form is the variant build's INGVIO_GRAM=3
+#include "gram3_kernel.h"
 
 // ---------------------------------------------------------------------------------------------
 // K8/K9/K11 in information form, one workgroup per filter:
@@ -1434,6 +1434,23 @@ static void launch_gram2(const FactoredLaunch& L, hipStream_t st)
     hipLaunchKernelGGL((k_feat_gram2<CMAX, STEREO, RED>), dim3(L.G, L.nb), dim3(GRAM_NT), sm, st,
                        L.fv, L.op, L.b0, L.accept, L.used, L.Apart, L.chunk_used, L.G, L.rstride);
     if (L.gram_was_red) *L.gram_was_red = RED ? 1 : 0;
+    if (L.gram_form) *L.gram_form = RED ? 1 : 0;
+}
+
+// k_feat_gram3 (gram3_kernel.h), window classes 6 and 11: RED from the fused frame step, the full form from the variant build's INGVIO_GRAM=3
+template <int CMAX, bool STEREO, bool RED>
+static void launch_gram3(const FactoredLaunch& L, hipStream_t st)
+{
+    const size_t sm = gram3_lds_bytes<CMAX, RED>() + 2 * sizeof(int) * (size_t)L.fv.fmax;
+    static size_t attr_sm = 0;
+    if (sm > attr_sm) {
+        hipFuncSetAttribute((const void*)k_feat_gram3<CMAX, STEREO, RED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+        attr_sm = sm;
+    }
+    hipLaunchKernelGGL((k_feat_gram3<CMAX, STEREO, RED>), dim3(L.G, L.nb), dim3(GRAM_NT), sm, st,
+                       L.fv, L.op, L.b0, L.accept, L.used, L.Apart, L.chunk_used, L.G, L.rstride);
+    if (L.gram_was_red) *L.gram_was_red = RED ? 1 : 0;
+    if (L.gram_form) *L.gram_form = RED ? 2 : 0;
 }
 
 // gram_red: the Gram stage takes the reduced form of k_feat_gram2 (decided in launch_factored)
@@ -1480,23 +1497,13 @@ static void launch_ft(const FactoredLaunch& L, hipStream_t st, bool gram_red)
         LAUNCH_GATE(L, (k_feat_gate3<CMAX, STEREO>), dim3(nb8 * ((L.fmax_used + GATE_FPW - 1) / GATE_FPW)), dim3(GATE_FPW * WAVE), 0, st,
                            L.cv, L.fv, L.op, L.b0, L.nb, L.fmax_used, L.gamma, L.accept, L.rec);
     } else {
+        if constexpr (CMAX <= 11) {                                  // window classes 6 and 11: the decoupled kernel (gram3_kernel.h)
 #ifdef INGVIO_ALT_KERNELS
-        if constexpr (CMAX * CMAX <= 128) {                          // window classes 6 and 11, INGVIO_GRAM=3: the third generation (gram3_kernel.h)
-            static const bool gram3 = [] { const char* e = getenv("INGVIO_GRAM"); return e && e[0] == '3'; }();
-            if (gram3) {
-                constexpr size_t uni3 = sizeof(Gram3Batch<CMAX>) > sizeof(Gram2Out<CMAX>) ? sizeof(Gram3Batch<CMAX>) : sizeof(Gram2Out<CMAX>);
-                const size_t sm3 = ((uni3 + 15) / 16) * 16 + 2 * sizeof(int) * (size_t)L.fv.fmax;
-                static size_t attr_sm3 = 0;
-                if (sm3 > attr_sm3) {
-                    hipFuncSetAttribute((const void*)k_feat_gram3<CMAX, STEREO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm3);
-                    attr_sm3 = sm3;
-                }
-                hipLaunchKernelGGL((k_feat_gram3<CMAX, STEREO>), dim3(L.G, L.nb), dim3(GRAM_NT), sm3, st,
-                                   L.fv, L.op, L.b0, L.accept, L.used, L.Apart, L.chunk_used, L.G, L.rstride);
-                return;
-            }
-        }
+            static const bool gram3 = [] { const char* e = getenv("INGVIO_GRAM"); return e && e[0] == '3'; }();      // its full form, everywhere
+            if (gram3) { launch_gram3<CMAX, STEREO, false>(L, st); return; }
 #endif
+            if (gram_red && L.gram_dec) { launch_gram3<CMAX, STEREO, true>(L, st); return; }
+        }
         if constexpr (CMAX <= 12) {                                  // the classes whose solve has a gauge-reduced form
             if (gram_red) { launch_gram2<CMAX, STEREO, true>(L, st); return; }
         }

@@ -46,6 +46,8 @@ struct FactoredLaunch {
                           // fused frame step) and allows the reduced form of k_feat_gram2, which leaves the block row / column of the solve's
                           // reference clone (slot n_clones - 1) unwritten; launch_factored takes it where that solve follows
     int* gram_was_red;    // host flag, set to 1 / 0 by the k_feat_gram2 launch: the partials it wrote are reduced / full (or nullptr)
+    int gram_dec;         // with gram_red, window classes 6 and 11: the reduced form runs as k_feat_gram3 (wave pairs decoupled, gram3_kernel.h)
+    int* gram_form;       // host value, set by the Gram launch: 0 full, 1 reduced k_feat_gram2, 2 reduced k_feat_gram3 (or nullptr)
     double* big_sg;       // large-window path: [nb][G][36][36][34] sparse sums (kernels_bigwin.hip)
     double* big_wk;       // large-window path: per-filter solve workspace (bigwin_wk_doubles)
     int ncol_cap;         // 6 * (context c_max): size class of the large-window solve
