@@ -84,6 +84,16 @@ int ingvio_cov_get(ingvio_ctx* ctx, int b, double* P, int ld);
 int ingvio_get_n(ingvio_ctx* ctx, int b, int* n);
 /* getMarginalCov (StateManager.cpp:128-153): out is ns x ns column-major, ns = sum(vsize). */
 int ingvio_cov_get_marginal(ingvio_ctx* ctx, int b, const int* vidx, const int* vsize, int k, double* out);
+/* getMarginalCov for filters [b0, b0 + nb) in one call: filter b0 + i takes the list vidx / vsize [i][k] (entries with vsize 0 pad a
+ * shorter list) and gets its block - column-major ns x ns, ns = the sum of its vsize, exactly as ingvio_cov_get_marginal lays it out -
+ * at out + i * ns_max * ns_max; the doubles of a filter's slot behind its ns * ns are not written.  The blocks are gathered on the
+ * device from the live covariances (the entries are copies, bit for bit); one copy of the blocks alone and one synchronisation serve
+ * the whole range, no full P travels.  Works with or without a nominal table.  1 <= ns_max <= INGVIO_MARGINAL_NS_MAX (the columns
+ * one workgroup of the gather kernel lists).  INGVIO_E_ARG: range, NULL, k < 1, ns_max out of bounds, a filter's ns > ns_max, a
+ * negative vsize; INGVIO_E_NOT_IN_STATE: an entry with vidx < 0 or vidx + vsize > the filter's n - nothing is written for any filter. */
+#define INGVIO_MARGINAL_NS_MAX 64
+int ingvio_cov_get_marginal_batch(ingvio_ctx* ctx, int b0, int nb, const int* vidx /* [nb][k] */, const int* vsize /* [nb][k] */,
+                                  int k, int ns_max, double* out /* [nb][ns_max * ns_max] */);
 /* device-to-device snapshot / restore of all filters' covariances and dims (benchmark hygiene). */
 int ingvio_cov_snapshot(ingvio_ctx* ctx);
 int ingvio_cov_restore(ingvio_ctx* ctx);
@@ -649,6 +659,51 @@ typedef struct {
 } ingvio_nominal_tail_block;
 int ingvio_nominal_tail(ingvio_ctx* ctx, int b0, int nb, const ingvio_nominal_tail_block* blocks, int lm_cap,
                         int* verdict /* [nb][lm_cap] */, int* status /* [nb], may be NULL */);
+/* ---- odometry output of the device-resident loop ----------------------------------------------------------------
+ * What the reference publishes at the end of every callback (IngvioFilter.cpp:409-454: _extended_pose rotation, position, velocity and
+ * their covariance) and prints after ekfUpdate (a negative diagonal of P, StateManager.cpp:413-421), taken from the table and the live
+ * covariance WITHOUT a host synchronisation.  ingvio_odom_begin only enqueues on the context's stream, behind everything already there:
+ * one kernel over filters [b0, b0 + nb), one device-to-host copy of the records into a pinned buffer of their own, an event; the table
+ * event is recorded behind the kernel, so a later asynchronous stage from the table cannot advance the pose before the record is taken.
+ * ingvio_odom_end waits for that event and copies the nb records out: they are those of the state at the moment of _begin, whatever has
+ * been staged or launched since.  One slot is pending at a time; the call changes no state, so a partial range is allowed.
+ *   run(i); odom_begin(i); stage_tracks_nominal(i + 1, async); fetch_begin(i); run(i + 1); fetch_end(i); odom_end(i)
+ * (with a late GNSS epoch or tail: odom_begin(i) behind its run) is a closed loop without a host synchronisation.  (The first call of a
+ * context allocates the record buffers.)
+ * what: INGVIO_ODOM_COV requests cov_err, INGVIO_ODOM_EUCL cov_pose and cov_vel (it implies COV), INGVIO_ODOM_DIAG the diagonal scan; the
+ * values are always written, fields that were not requested are zero.
+ * status: INGVIO_ODOM_NONFINITE a non-finite number among the values or cov_err; INGVIO_ODOM_NEG_DIAG diag_min < 0 (with DIAG);
+ * INGVIO_ODOM_ABSENT one of the extended pose, bg, ba, extrinsics has no slot (-1) or idx + size > n: its values and its rows and columns
+ * of the covariances are zero, the rest of the record is valid.
+ * Refused with INGVIO_E_ARG before anything is enqueued, the context unchanged: no nominal table, a bad range, an unknown bit in what, a
+ * split frame step pending, any stage from the table that has not run (a frame, an update-only frame, a GNSS epoch, a landmark stage:
+ * the table has then already advanced or is about to be read by that run's own order), an ingvio_odom_begin that has not been ended.
+ * ingvio_odom_end without a pending _begin: INGVIO_E_ARG.  ingvio_cov_snapshot / _restore are not involved: the record is of the live state. */
+#define INGVIO_ODOM_COV 1
+#define INGVIO_ODOM_EUCL 2
+#define INGVIO_ODOM_DIAG 4
+#define INGVIO_ODOM_NONFINITE 1
+#define INGVIO_ODOM_NEG_DIAG 2
+#define INGVIO_ODOM_ABSENT 4
+typedef struct {
+    int n;                        /* the filter's state dimension, read on the device                                              */
+    int status;                   /* INGVIO_ODOM_NONFINITE | _NEG_DIAG | _ABSENT                                                    */
+    int gnss_mask;                /* bit s: gnss[s] is registered (ingvio_nominal_set_gnss)                                        */
+    int reserved;
+    double R_i2w[9], p[3], v[3];  /* State::_extended_pose, R row-major                                                            */
+    double bg[3], ba[3];
+    double R_c2i[9], p_c2i[3];    /* _camleft_imu_extrinsics                                                                       */
+    double gnss[6];               /* clock bias GPS, GLO, GAL, BDS, then FS, then YOF (State::GNSSType order)                      */
+    double diag_min, diag_max;    /* over P[i][i], i < n                                                                           */
+    double cov_err[15 * 15];      /* P over (extended pose 9: d_theta, d_p, d_v; bg 3; ba 3) gathered through each variable's idx, in
+                                     the filter's own error coordinates; column-major as ingvio_cov_get_marginal, copies bit for bit */
+    double cov_pose[6 * 6];       /* (position, orientation) in the world frame and Euclidean error: J_p S J_p^T on the 9 x 9 pose
+                                     block S with J_p = [-[p]x I 0; I 0 0] (the retraction p' = Gamma0(dth) p + Gamma1(dth) dp gives
+                                     delta p = dp - [p]x dth to first order; dth is a world-axis rotation already); exactly symmetric */
+    double cov_vel[3 * 3];        /* J_v S J_v^T, J_v = [-[v]x 0 I]; exactly symmetric                                              */
+} ingvio_odom;
+int ingvio_odom_begin(ingvio_ctx* ctx, int b0, int nb, int what);
+int ingvio_odom_end(ingvio_ctx* ctx, ingvio_odom* out /* [nb] */);
 /* ingvio_gnss_front_stage with the receiver taken from the device table: the epoch carries only what the host owns.  p_w, v_w
  * (State::_extended_pose), the clock biases, FS and YOF (GnssUpdate.cpp:98-122 reads them from the state) and every Type::idx() come
  * from the filter's table as the frame that has just run left it - IngvioFilter.cpp:329-362 runs after :276-327 and after margSwPose,

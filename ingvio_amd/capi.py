@@ -38,11 +38,17 @@ EXPORTS = [
     "ingvio_debug_tracks_read", "ingvio_debug_staged_frame",
     "ingvio_gnss_frame_stage_nominal", "ingvio_debug_gnss_fused_last", "ingvio_debug_nominal_update_post",
     "ingvio_update_stage_tracks_nominal", "ingvio_frame_fetch_tri", "ingvio_set_delayed_form",
+    "ingvio_odom_begin", "ingvio_odom_end", "ingvio_cov_get_marginal_batch",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
 NOM_NONE, NOM_SE23, NOM_SE3, NOM_VEC3, NOM_SCALAR, NOM_LANDMARK = -1, 0, 1, 2, 3, 4
 NOM_VAL = 15
+# odometry record (ingvio_odom_begin / _end): the bits of `what` and of a record's status; the batch getter's column capacity
+ODOM_COV, ODOM_EUCL, ODOM_DIAG = 1, 2, 4
+ODOM_ALL = ODOM_COV | ODOM_EUCL | ODOM_DIAG
+ODOM_NONFINITE, ODOM_NEG_DIAG, ODOM_ABSENT = 1, 2, 4
+MARGINAL_NS_MAX = 64
 
 
 class GateBlock(C.Structure):
@@ -203,6 +209,34 @@ class FrameStepRaw(C.Structure):
 class Nominal(C.Structure):
     _fields_ = [("n_var", C.c_int), ("kind", c_ip), ("idx", c_ip), ("anchor", c_ip), ("val", c_dp), ("n_clones", C.c_int), ("clone_var", c_ip),
                 ("v_ext", C.c_int), ("v_pose", C.c_int), ("v_bg", C.c_int), ("v_ba", C.c_int), ("gravity", C.c_double * 3)]
+
+
+class Odom(C.Structure):
+    _fields_ = [("n", C.c_int), ("status", C.c_int), ("gnss_mask", C.c_int), ("reserved", C.c_int),
+                ("R_i2w", C.c_double * 9), ("p", C.c_double * 3), ("v", C.c_double * 3), ("bg", C.c_double * 3), ("ba", C.c_double * 3),
+                ("R_c2i", C.c_double * 9), ("p_c2i", C.c_double * 3), ("gnss", C.c_double * 6), ("diag_min", C.c_double), ("diag_max", C.c_double),
+                ("cov_err", C.c_double * 225), ("cov_pose", C.c_double * 36), ("cov_vel", C.c_double * 9)]
+
+
+ODOM_DTYPE = np.dtype(Odom)
+
+
+def odom_dicts(rec):
+    """records (a numpy array of ODOM_DTYPE) as the dicts odom_end() and odom.odom_model() share: matrices as [row, column]"""
+    def colmajor(x, m):
+        return x.reshape(-1, m, m).transpose(0, 2, 1)
+    mats = dict(R_i2w=rec["R_i2w"].reshape(-1, 3, 3), R_c2i=rec["R_c2i"].reshape(-1, 3, 3), cov_err=colmajor(rec["cov_err"], 15),
+                cov_pose=colmajor(rec["cov_pose"], 6), cov_vel=colmajor(rec["cov_vel"], 3))
+    out = []
+    for i in range(len(rec)):
+        d = dict(n=int(rec["n"][i]), status=int(rec["status"][i]), gnss_mask=int(rec["gnss_mask"][i]), diag_min=float(rec["diag_min"][i]),
+                 diag_max=float(rec["diag_max"][i]))
+        for k in ("p", "v", "bg", "ba", "p_c2i", "gnss"):
+            d[k] = rec[k][i].copy()
+        for k, m in mats.items():
+            d[k] = m[i].copy()
+        out.append(d)
+    return out
 
 
 class FrameStepNominal(C.Structure):
@@ -1008,6 +1042,36 @@ class Context:
         sl = np.zeros((nb, 6), dtype=np.int32)
         self._chk(self.L.ingvio_nominal_get_gnss(self.h, int(b0), nb, _i(sl)))
         return sl
+
+    # ---- odometry output -----------------------------------------------------------------------------------------
+    def odom_begin(self, b0=0, nb=None, what=ODOM_ALL):
+        """enqueues the odometry records of filters [b0, b0 + nb) behind everything on the stream; no synchronisation (ingvio_odom_begin)"""
+        nb = self.batch - int(b0) if nb is None else nb
+        self._chk(self.L.ingvio_odom_begin(self.h, int(b0), int(nb), int(what)))
+        self._odom_nb = int(nb)
+
+    def odom_end(self, raw=None, dicts=True):
+        """waits for the pending records; -> a list of dicts (odom_dicts), or with dicts=False the records as one numpy array of
+        ODOM_DTYPE (fields as in ingvio_odom: rec["p"] is [nb][3]).  raw: an (Odom * m) array to fill instead of a fresh one"""
+        nb = getattr(self, "_odom_nb", 0)
+        arr = (Odom * max(nb, 1))() if raw is None else raw
+        self._chk(self.L.ingvio_odom_end(self.h, arr))
+        rec = np.frombuffer(arr, dtype=ODOM_DTYPE, count=nb)
+        return odom_dicts(rec) if dicts else rec
+
+    def cov_get_marginal_batch(self, b0, lists, ns_max=None):
+        """lists: per filter of [b0, b0 + len(lists)) a (vidx, vsize) pair; -> a list of ns x ns blocks (ingvio_cov_get_marginal_batch).
+        ns_max: the stride's side (default: the largest ns of the call)"""
+        nb = len(lists)
+        k = max(1, max(len(v) for v, _ in lists))
+        vidx, vsize = np.zeros((nb, k), dtype=np.int32), np.zeros((nb, k), dtype=np.int32)
+        for i, (v, s) in enumerate(lists):
+            vidx[i, :len(v)] = v; vsize[i, :len(s)] = s
+        ns = [int(np.sum(s)) for _, s in lists]
+        ns_max = max(1, max(ns)) if ns_max is None else int(ns_max)
+        out = np.zeros((nb, ns_max * ns_max))
+        self._chk(self.L.ingvio_cov_get_marginal_batch(self.h, int(b0), nb, _i(vidx), _i(vsize), k, ns_max, _d(out)))
+        return [out[i, :m * m].reshape(m, m, order="F").copy() for i, m in enumerate(ns)]
 
     def nominal_box_plus(self, b0, dx):
         """StateManager::boxPlus on the device: dx [nb][ldp] in the live index space (ingvio_nominal_box_plus)"""

@@ -241,6 +241,9 @@ class Form:
     def staged(self, loop, i):
         """right after the frame stage of frames[i]"""
 
+    def ran(self, loop, i):
+        """right behind the frame_run of frames[i], in front of whatever is enqueued next"""
+
     def after(self, loop, i):
         """behind the run of frames[i]: serial after its fetch, pipelined right after its fetch_begin"""
 
@@ -256,6 +259,7 @@ class DeviceLoop:
       pipelined         start: stage(0) staged(0) run(0), then per frame
                         stage(i+1) staged(i+1) fetch_begin(i) collect(i) run(i+1) fetch_end(i)      (the last frame: fetch(i) collect(i))
       pipelined, late   fetch_begin(i) after(i) stage(i+1) staged(i+1) run(i+1) fetch_end(i) collect(i)
+    Right behind every run(i) the form's ran(i) is called (closed_loop_odom.py takes the odometry record there).
     fetch_end(i) is issued after run(i + 1) and still returns frame i's results.  prepare() builds every stage callable ahead of
     the loop (otherwise each is built when it is due), collect=False leaves the form's results unfetched: what the bench tool times.
     sync_every_call (serial): a context synchronisation after every call that only enqueues.
@@ -290,10 +294,14 @@ class DeviceLoop:
         if not isinstance(self.frames[i], UpdateEntry):
             self.form.staged(self, i)
 
+    def run_entry(self, i):
+        self.ctx.frame_run()
+        self.form.ran(self, i)
+
     def start(self):
         if self.pipelined:
             self.stage(0)
-            self.ctx.frame_run()
+            self.run_entry(0)
 
     def frame(self, i):
         """-> frame i's (dx, accept, rows), with a form that collects: (that, the form's results)"""
@@ -310,12 +318,12 @@ class DeviceLoop:
             self.stage(i + 1)
             ctx.frame_fetch_begin()
             res = self.collect(ctx)                                      # after stage i + 1: its upload leaves frame i's results alone
-            ctx.frame_run()
+            self.run_entry(i + 1)
             fr = ctx.frame_fetch_end()
             return fr if res is None else (fr, res)
         if not self.pipelined:
             self.stage(i)
-            ctx.frame_run()
+            self.run_entry(i)
             self.sync()
             fr = ctx.frame_fetch()
             form.after(self, i)
@@ -324,7 +332,7 @@ class DeviceLoop:
             form.after(self, i)
             if not last:
                 self.stage(i + 1)
-                ctx.frame_run()
+                self.run_entry(i + 1)
             fr = ctx.frame_fetch_end()                                   # issued after run(i + 1): still frame i's results
         else:
             fr = ctx.frame_fetch()

@@ -16,6 +16,7 @@
 #include "launch_lmbatch.h"
 #include "launch_nominal.h"
 #include "launch_tail.h"
+#include "launch_odom.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -248,6 +249,13 @@ struct ingvio_ctx {
     // ingvio_nominal_tail (kernels_tail.hip), grown on demand: the uploaded lists, the panel kernel's workspace (transient: nothing in it
     // outlives the call, so a snapshot has nothing to copy) and the pinned mirror of the verdicts and the new dimensions
     struct TailWs { char *in = nullptr, *ws = nullptr, *h_out = nullptr; size_t in_cap = 0, ws_cap = 0, out_cap = 0; } tl;
+    // odometry output (ingvio_odom_begin / _end, kernels_odom.hip), allocated by the first _begin: the records [B][ODOM_REC] on the device
+    // and their pinned mirror - its own, h_result is shared between the fetches - with the event behind the copy; one slot pending.
+    // cols / ns / blk: ingvio_cov_get_marginal_batch's column lists and blocks, grown on demand
+    struct OdomOut {
+        double *d = nullptr, *h = nullptr; hipEvent_t ev = nullptr; bool pending = false; int b0 = 0, nb = 0;
+        int *cols = nullptr, *ns = nullptr; double* blk = nullptr; size_t cols_cap = 0, blk_cap = 0;
+    } od;
     // profiling
     bool prof;
     std::vector<ProfRec> recs;
@@ -1296,6 +1304,9 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
     for (void* p : { (void*)c->trk.uv, (void*)c->trk.pf, (void*)c->trk.mask, (void*)c->trk.stage[0], (void*)c->trk.stage[1] }) if (p) hipFree(p);
     for (void* p : { (void*)c->nom.ih, (void*)c->nom.dv, (void*)c->nom.ih_snap, (void*)c->nom.dv_snap, (void*)c->nom.dx, (void*)c->nom.d_tri_track }) if (p) hipFree(p);
     if (c->nom.ev) hipEventDestroy(c->nom.ev);
+    for (void* p : { (void*)c->od.d, (void*)c->od.cols, (void*)c->od.ns, (void*)c->od.blk }) if (p) hipFree(p);
+    if (c->od.h) hipHostFree(c->od.h);
+    if (c->od.ev) hipEventDestroy(c->od.ev);
     for (auto& r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (int p = 0; p < c->parts_alloc; ++p) { hipStreamDestroy(c->part[p].st); hipEventDestroy(c->part[p].ev_gate); hipEventDestroy(c->part[p].ev_apply); hipEventDestroy(c->part[p].ev_done); }
     if (c->ev_split_fork) hipEventDestroy(c->ev_split_fork);
@@ -1381,6 +1392,60 @@ int ingvio_cov_get_marginal(ingvio_ctx* c, int b, const int* vidx, const int* vs
         }
         r0 += vsize[a];
     }
+    return INGVIO_OK;
+}
+
+// The read-only view of the covariances: view() counts a use that may change P (it ends the validity of the propagation strips).
+static CovView view_ro(ingvio_ctx* c)
+{
+    CovView v;
+    v.Pbase = c->Pbase; v.cur = c->d_cur; v.n = c->d_n; v.ldp = c->ldp; v.B = c->d.batch; v.pstride = c->pp;
+    return v;
+}
+
+int ingvio_cov_get_marginal_batch(ingvio_ctx* c, int b0, int nb, const int* vidx, const int* vsize, int k, int ns_max, double* out)
+{
+    if (check_range(c, b0, nb) || !vidx || !vsize || !out || k < 1 || ns_max < 1 || ns_max > INGVIO_MARGINAL_NS_MAX) return INGVIO_E_ARG;
+    std::vector<int> cols((size_t)nb * ns_max, -1), ns((size_t)nb, 0);
+    for (int i = 0; i < nb; ++i) {                                     // every filter is checked before anything is enqueued or written
+        const int n = c->h_n[b0 + i];
+        int w = 0;
+        for (int a = 0; a < k; ++a) {
+            const int v0 = vidx[(size_t)i * k + a], sz = vsize[(size_t)i * k + a];
+            if (sz < 0) return INGVIO_E_ARG;
+            if (sz == 0) continue;
+            if (v0 < 0 || v0 + sz > n) return INGVIO_E_NOT_IN_STATE;
+            if (w + sz > ns_max) return INGVIO_E_ARG;
+            for (int j = 0; j < sz; ++j) cols[(size_t)i * ns_max + w++] = v0 + j;
+        }
+        ns[i] = w;
+    }
+    ENTER(c);
+    auto& o = c->od;
+    const size_t nblk = (size_t)nb * ns_max * ns_max;
+    if (o.cols_cap < cols.size()) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (o.cols) hipFree(o.cols);
+        if (o.ns) hipFree(o.ns);
+        o.cols = nullptr; o.ns = nullptr; o.cols_cap = 0;
+        HIPCHK(c, hipMalloc((void**)&o.cols, sizeof(int) * cols.size()));
+        HIPCHK(c, hipMalloc((void**)&o.ns, sizeof(int) * cols.size()));
+        o.cols_cap = cols.size();
+    }
+    if (o.blk_cap < nblk) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        if (o.blk) hipFree(o.blk);
+        o.blk = nullptr; o.blk_cap = 0;
+        HIPCHK(c, hipMalloc((void**)&o.blk, 8 * nblk));
+        o.blk_cap = nblk;
+    }
+    if (up(c, o.cols, cols.data(), sizeof(int) * cols.size()) || up(c, o.ns, ns.data(), sizeof(int) * ns.size())) return INGVIO_E_HIP;
+    launch_cov_marginal(view_ro(c), o.cols, o.ns, ns_max, o.blk, b0, nb, c->st);
+    if (int rc = last_launch(c)) return rc;
+    std::vector<double> blk(nblk);
+    if (down_sync(c, blk.data(), o.blk, 8 * nblk)) return INGVIO_E_HIP;      // the blocks alone, one synchronisation
+    for (int i = 0; i < nb; ++i)
+        memcpy(out + (size_t)i * ns_max * ns_max, blk.data() + (size_t)i * ns_max * ns_max, 8 * (size_t)ns[i] * ns[i]);
     return INGVIO_OK;
 }
 
@@ -3884,6 +3949,63 @@ int ingvio_nominal_get_gnss(ingvio_ctx* c, int b0, int nb, int* slots)
     auto& m = c->nom;
     if (!m.vmax) { c->err = "ingvio_nominal_get_gnss without ingvio_nominal_create"; return INGVIO_E_ARG; }
     for (int i = 0; i < nb; ++i) memcpy(slots + 6 * (size_t)i, &m.h_ih[(size_t)(b0 + i) * m.ir + NOM_GNSS], sizeof(int) * 6);      // the mirror is the record
+    return INGVIO_OK;
+}
+
+// ---- odometry output (kernels_odom.hip) -----------------------------------------------------------------------------
+static_assert(sizeof(ingvio_odom) == 8 * ODOM_REC, "ingvio_odom and the kernel's record differ");
+static_assert(offsetof(ingvio_odom, R_i2w) == 8 * (ODOM_HDR + ODOM_O_VAL) && offsetof(ingvio_odom, diag_min) == 8 * (ODOM_HDR + ODOM_O_DIAG) &&
+              offsetof(ingvio_odom, cov_err) == 8 * (ODOM_HDR + ODOM_O_ERR) && offsetof(ingvio_odom, cov_pose) == 8 * (ODOM_HDR + ODOM_O_POSE) &&
+              offsetof(ingvio_odom, cov_vel) == 8 * (ODOM_HDR + ODOM_O_VEL) && offsetof(ingvio_odom, gnss) == 8 * (ODOM_HDR + ODOM_O_VAL + 33),
+              "ingvio_odom and the kernel's record differ");
+static_assert(INGVIO_ODOM_COV == ODOM_W_COV && INGVIO_ODOM_EUCL == ODOM_W_EUCL && INGVIO_ODOM_DIAG == ODOM_W_DIAG &&
+              INGVIO_ODOM_NONFINITE == ODOM_S_NONFINITE && INGVIO_ODOM_NEG_DIAG == ODOM_S_NEG_DIAG && INGVIO_ODOM_ABSENT == ODOM_S_ABSENT &&
+              INGVIO_MARGINAL_NS_MAX == MARG_NS_MAX, "ingvio_hip.h and launch_odom.h differ");
+
+// Only enqueues: the kernel, the table event behind it (an asynchronous stage from the table waits for that one before its IMU steps
+// advance the pose), the copy of the records into their pinned mirror, the event ingvio_odom_end waits for.  Every refusal comes first.
+int ingvio_odom_begin(ingvio_ctx* c, int b0, int nb, int what)
+{
+    if (!c || check_range(c, b0, nb)) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    auto& o = c->od;
+    if (what & ~(INGVIO_ODOM_COV | INGVIO_ODOM_EUCL | INGVIO_ODOM_DIAG)) { c->err = "ingvio_odom_begin: an unknown bit in what"; return INGVIO_E_ARG; }
+    if (phase_busy(c)) return INGVIO_E_ARG;
+    if (!m.vmax) { c->err = "ingvio_odom_begin without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = "ingvio_odom_begin: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, "ingvio_odom_begin")) return INGVIO_E_ARG;
+    if ((c->gn.frame_nom && c->gn.staged) || (c->lm.nominal && c->lm.staged)) {
+        c->err = "ingvio_odom_begin: an in-frame GNSS epoch or landmark update staged from the device nominal state has not run yet";
+        return INGVIO_E_ARG;
+    }
+    if (o.pending) { c->err = "ingvio_odom_begin: the previous ingvio_odom_begin has not been ended"; return INGVIO_E_ARG; }
+    ENTER(c);
+    if (!o.d) {                                                        // the first call of the context
+        HIPCHK(c, hipMalloc((void**)&o.d, 8 * (size_t)c->d.batch * ODOM_REC));
+        if (hipHostMalloc((void**)&o.h, 8 * (size_t)c->d.batch * ODOM_REC, hipHostMallocDefault) != hipSuccess) {
+            hipFree(o.d); o.d = nullptr; o.h = nullptr;
+            c->err = "ingvio_odom_begin: hipHostMalloc"; return INGVIO_E_HIP;
+        }
+    }
+    if (!o.ev) HIPCHK(c, hipEventCreateWithFlags(&o.ev, hipEventDisableTiming));
+    if (what & INGVIO_ODOM_EUCL) what |= INGVIO_ODOM_COV;
+    launch_odom_out(nom_table(c), view_ro(c), o.d, b0, nb, what, c->st);
+    if (int rc = last_launch(c)) return rc;
+    if (nom_mark(c)) return INGVIO_E_HIP;
+    HIPCHK(c, hipMemcpyAsync(o.h + (size_t)b0 * ODOM_REC, o.d + (size_t)b0 * ODOM_REC, 8 * (size_t)nb * ODOM_REC, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipEventRecord(o.ev, c->st));
+    o.pending = true; o.b0 = b0; o.nb = nb;
+    return INGVIO_OK;
+}
+
+int ingvio_odom_end(ingvio_ctx* c, ingvio_odom* out)
+{
+    if (!c || !out) return INGVIO_E_ARG;                                // (no ENTER: the records are already on their way)
+    auto& o = c->od;
+    if (!o.pending) { c->err = "ingvio_odom_end without a pending ingvio_odom_begin"; return INGVIO_E_ARG; }
+    HIPCHK(c, hipEventSynchronize(o.ev));
+    o.pending = false;
+    memcpy(out, o.h + (size_t)o.b0 * ODOM_REC, 8 * (size_t)o.nb * ODOM_REC);
     return INGVIO_OK;
 }
 

@@ -49,9 +49,18 @@ the frame's clone; two forms on the same build,
                    shift on the host, ingvio_nominal_set
 the device form free-running (device_loop_ms_per_frame) and both synchronised per camera frame; writes
 $RESULTS/closed_loop_bench_two_updates.json.
+--odom: what the odometry record costs (ingvio_odom_begin / _end, ingvio_amd/closed_loop_odom.py), on one build in one run; the forms
+free-running and alternated A B C A B C,
+  A  the plain pipelined loop
+  B  the loop with the record of every frame, values only:   run(i); odom_begin(i); stage_async(i+1); fetch_begin(i); run(i+1);
+  C  the loop with the full record                            odom_end(i); odom_begin(i+1); fetch_end(i)
+then C with the record collected in front of run(i+1) (the order of a loop that hands every record out before it launches the next
+frame), then the stalling form the record replaces: ingvio_nominal_get plus one ingvio_cov_get_marginal of the pose block per filter
+behind every run, timed over --stall-frames frames.  Writes $RESULTS/closed_loop_bench_odom.json.
 Writes $RESULTS/closed_loop_bench.json (RESULTS defaults to results/) and prints one JSON line.
 usage: python tools/closed_loop_bench.py [--batch 512] [--features 150] [--window 11] [--k 10] [--frames 30] [--warmup 5] [--device-only]
-                                         [--gnss | --gnss-in-frame [--sats 8] | --register-only | --landmarks L | --tail [--landmarks L]]"""
+                                         [--gnss | --gnss-in-frame [--sats 8] | --register-only | --landmarks L | --tail [--landmarks L] |
+                                          --odom [--repeats 2] [--stall-frames 3]]"""
 import argparse
 import copy
 import json
@@ -314,6 +323,73 @@ def main_two_updates(a):
     finish(out, "closed_loop_bench_two_updates.json")
 
 
+def main_odom(a):
+    import ctypes
+    from ingvio_amd import capi
+    from ingvio_amd import closed_loop as cl
+    from ingvio_amd.closed_loop_odom import OdomForm
+    B, F, NF, W = a.batch, a.features, a.frames, a.warmup
+    t0 = time.perf_counter()
+    cases = cl.make_loop(B, NF, F=F, ks=(a.k,), windows=(a.window,))
+    out = dict(batch=B, features=F, window=a.window, k=a.k, frames_timed=NF - W, odom=True, setup_s=round(time.perf_counter() - t0, 1))
+    forms = dict(A=lambda: None, B=lambda: OdomForm(what=0, dicts=False), C=lambda: OdomForm(what=capi.ODOM_ALL, dicts=False))
+    if a.device_only:                                                    # the kernel-trace run: form C alone
+        ctx = fresh_ctx(a, cases)
+        free_run(out, ctx, cases, forms["C"](), NF, W)
+        ctx.close()
+        return finish(out)
+    times = {k: [] for k in forms}
+    last = {}
+    for rep in range(a.repeats):
+        for name, make in forms.items():
+            o, form = {}, make()
+            ctx = fresh_ctx(a, cases)
+            free_run(o, ctx, cases, form, NF, W)
+            times[name].append(o["device_loop_ms_per_frame"])
+            if form is not None:
+                last[name] = form.finish(ctx)
+            ctx.close()
+    for name, t in times.items():
+        out[name + "_ms_per_frame"] = t
+        out[name + "_ms_per_frame_min"] = min(t)
+    out["A_spread_ms"] = round(max(times["A"]) - min(times["A"]), 4)
+    out["record_bytes"] = ctypes.sizeof(capi.Odom)
+    out["last_record_status_or"] = int(np.bitwise_or.reduce(last["C"]["status"]))
+    out["values_equal_B_C"] = bool(np.array_equal(last["B"]["p"], last["C"]["p"]) and np.array_equal(last["B"]["R_i2w"], last["C"]["R_i2w"]))
+
+    # C with every record handed out in front of the next run
+    ctx = fresh_ctx(a, cases)
+    loop = cl.DeviceLoop(ctx, cases, range(NF), OdomForm(what=capi.ODOM_ALL, dicts=False)).prepare()
+    loop.start()
+    for f in range(NF):
+        if f == W:
+            ctx.sync()
+            t0 = time.perf_counter()
+        loop.frame(f)
+    ctx.sync()
+    out["C_collected_ms_per_frame"] = round(1e3 * (time.perf_counter() - t0) / (NF - W), 4)
+    ctx.close()
+
+    # the stalling form
+    class Stall(cl.Form):
+        def ran(self, loop, i):
+            nom = loop.ctx.nominal_get()
+            self.out = [loop.ctx.marginal(b, [int(q["idx"][q["v_pose"]])], [9]) for b, q in enumerate(nom)]
+    NS, WS = a.stall_frames + 1, 1
+    ctx = fresh_ctx(a, cases)
+    loop = cl.DeviceLoop(ctx, cases, range(NS), Stall()).prepare()
+    loop.start()
+    for f in range(NS):
+        if f == WS:
+            ctx.sync()
+            t0 = time.perf_counter()
+        loop.frame(f)
+    ctx.sync()
+    out["stalling_ms_per_frame"] = round(1e3 * (time.perf_counter() - t0) / (NS - WS), 3)
+    ctx.close()
+    finish(out, "closed_loop_bench_odom.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=512)
@@ -331,7 +407,12 @@ def main():
     ap.add_argument("--tail", action="store_true", help="the oldest clone leaves and every landmark changes its anchor behind every frame")
     ap.add_argument("--two-updates", action="store_true", help="both MSCKF updates of the camera callback: the second as an update-only frame from the table")
     ap.add_argument("--second", type=int, default=40, help="--two-updates: features of the second update")
+    ap.add_argument("--odom", action="store_true", help="the plain loop against the loop with the odometry record, and the stalling form")
+    ap.add_argument("--repeats", type=int, default=2, help="--odom: rounds of A B C")
+    ap.add_argument("--stall-frames", type=int, default=3, help="--odom: timed frames of the stalling form")
     a = ap.parse_args()
+    if a.odom:
+        return main_odom(a)
     if a.two_updates:
         return main_two_updates(a)
     if a.tail:
