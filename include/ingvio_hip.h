@@ -589,6 +589,28 @@ typedef struct {
 int ingvio_frame_stage_tracks_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,
                                       const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double sigma_cb, double sigma_rw,
                                       int async);
+/* The FIRST MSCKF update of a camera frame (RemoveLostUpdate::updateStateStereo / Mono) with its features' points found on the device.
+ * tri == NULL: ingvio_frame_stage_tracks_nominal exactly (that export is this call with NULL).
+ * tri != NULL: the following ingvio_frame_run triangulates every listed feature of every filter from the window's clone poses as they
+ * stand behind the IMU integration and the new clone (FeatureInfoManager::triangulateFeatureInfo*, MapServerManager.cpp:275-341) and in
+ * front of the gate: from EVERY observation the store holds over the window, the new clone's column included (the full stored mask, not
+ * stored & feat_sel), with the settings of ingvio_msckf_update_tri (check_anchor and mask_failed on).  A feature whose triangulation
+ * fails or whose point lies behind its anchor camera loses its mask and drops out of the gate (accepted = 0); a point that succeeded
+ * goes into the staged frame and into the store's point of its track (setValuePosXyz).  No host synchronisation; ingvio_frame_fetch_tri
+ * returns flags and points.  Everything else is ingvio_frame_stage_tracks_nominal's: ingvio_landmark_stage_nominal(in_frame) and
+ * ingvio_gnss_frame_stage_nominal on it, snapshot / restore, ingvio_nominal_tail behind it, the post-frame boxPlus / drop / shift.
+ * Refused before anything is enqueued or changed: everything ingvio_frame_stage_tracks_nominal refuses, with its codes; tri without a
+ * track store (INGVIO_E_ARG); tri->outer_loop_max_iter < 0 or tri->inner_loop_max_iter < 0 (INGVIO_E_ARG).  One thing precedes the
+ * checks of the delta itself (capacity, slots, tracks out of range): a context's first stage with tri allocates its mask / track (and,
+ * at placement 1, result) buffers and synchronises the compute stream once; a stage refused after that leaves table, store, covariance
+ * and n as they were.  A HIP runtime error while enqueueing (INGVIO_E_HIP) invalidates the staged frame as for every stage. */
+int ingvio_frame_stage_tracks_nominal_tri(ingvio_ctx* ctx, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,
+                                          const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double sigma_cb, double sigma_rw,
+                                          const ingvio_tri_opts* tri /* NULL: the store's points */, int async);
+/* Where the triangulation of ingvio_frame_stage_tracks_nominal_tri is issued: 0 (default) on the compute stream in front of the gate, as
+ * the update-only frame's; 1 at the stage, behind the gather (the copy stream of an asynchronous stage: off the step's chain).  Results
+ * are bit-identical.  INGVIO_E_ARG for another mode or while a frame staged from the table has not run. */
+int ingvio_set_first_tri_placement(ingvio_ctx* ctx, int mode);
 /* The SECOND MSCKF update of a camera frame (SwMargUpdate / KeyframeUpdate::updateState*, IngvioFilter.cpp:271-324: behind RemoveLostUpdate,
  * linearised at the state that update left) as an update-only frame from the table and the track store: no IMU steps, no new clone, the
  * window is the table's as it stands (frames[].n_clones / clone_* are ignored).  frames[i].append_slot must be -1 and n_obs 0; n_drop,
@@ -612,8 +634,9 @@ int ingvio_frame_stage_tracks_nominal(ingvio_ctx* ctx, int b0, int nb, const ing
 int ingvio_update_stage_tracks_nominal(ingvio_ctx* ctx, int b0, int nb, const int* marg_idx /* [nb], -1: none */,
                                        const ingvio_track_frame* frames, const ingvio_msckf_opts* opts,
                                        const ingvio_tri_opts* tri /* NULL: the store's points */, int async);
-/* flags and points of the update-only frame's triangulation, after its run (and, pipelined, after the ingvio_frame_fetch_begin that
- * follows it): pf_out [nb][f_max][3], tri_ok [nb][f_max] as ingvio_msckf_update_tri; INGVIO_E_ARG without a run that triangulated */
+/* flags and points of the triangulation of a frame from the table staged with tri (ingvio_frame_stage_tracks_nominal_tri or
+ * ingvio_update_stage_tracks_nominal), after its run (and, pipelined, after the ingvio_frame_fetch_begin that follows it, for both kinds
+ * of frame): pf_out [nb][f_max][3], tri_ok [nb][f_max] as ingvio_msckf_update_tri; INGVIO_E_ARG without a run that triangulated */
 int ingvio_frame_fetch_tri(ingvio_ctx* ctx, int b0, int nb, double* pf_out, int* tri_ok);
 /* ---- GNSS epochs in the device-resident closed loop ------------------------------------------------------------
  * Names the GNSS scalars of filters [b0, b0 + nb)'s tables: slots [nb][6] = the table slots of the clock biases GPS, GLO, GAL, BDS, then

@@ -39,6 +39,7 @@ EXPORTS = [
     "ingvio_gnss_frame_stage_nominal", "ingvio_debug_gnss_fused_last", "ingvio_debug_nominal_update_post",
     "ingvio_update_stage_tracks_nominal", "ingvio_frame_fetch_tri", "ingvio_set_delayed_form",
     "ingvio_odom_begin", "ingvio_odom_end", "ingvio_cov_get_marginal_batch",
+    "ingvio_frame_stage_tracks_nominal_tri", "ingvio_set_first_tri_placement",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -1104,6 +1105,18 @@ class Context:
                                            compress_rule=1, selected_variant=0, use_async=False):
         """as frame_stage_tracks_prepare, the nominal values from the device table (ingvio_frame_stage_tracks_nominal): steps are dicts
         imu [k][7], gnss_idx (optional), marg_idx; track_frames need no clone arrays"""
+        return self._nominal_stage_prepare(False, None, b0, steps, track_frames, opts_frame, sigma, enable_gnss, sigma_cb, sigma_rw, max_accept,
+                                           compress_rule, selected_variant, use_async)
+
+    def frame_stage_tracks_nominal_tri_prepare(self, b0, steps, track_frames, opts_frame, sigma, enable_gnss=0, sigma_cb=0.0, sigma_rw=0.0, tri=None,
+                                               max_accept=0, compress_rule=1, selected_variant=0, use_async=False):
+        """ingvio_frame_stage_tracks_nominal_tri: as frame_stage_tracks_nominal_prepare; tri as update_stage_tracks_nominal_prepare takes it
+        (None: NULL, the store's points; a dict: the run triangulates the listed features)"""
+        return self._nominal_stage_prepare(True, tri, b0, steps, track_frames, opts_frame, sigma, enable_gnss, sigma_cb, sigma_rw, max_accept,
+                                           compress_rule, selected_variant, use_async)
+
+    def _nominal_stage_prepare(self, tri_export, tri, b0, steps, track_frames, opts_frame, sigma, enable_gnss, sigma_cb, sigma_rw, max_accept,
+                               compress_rule, selected_variant, use_async):
         nb = len(steps)
         sa = (FrameStepNominal * nb)(); fa = (TrackFrame * nb)()
         keeps = []
@@ -1119,12 +1132,21 @@ class Context:
             sa[i] = s; fa[i] = f; keeps.append((imu, k2))
         o, chi2 = make_opts(opts_frame, max_accept, compress_rule, selected_variant)
         sg = f64(sigma)
+        t = None if tri is None else tri_opts(opts_frame, **tri)
 
         def call():
-            _keep = (keeps, chi2, sg)
+            _keep = (keeps, chi2, sg, t)
+            if tri_export:
+                return self._chk(self.L.ingvio_frame_stage_tracks_nominal_tri(self.h, b0, nb, sa, fa, C.byref(o), _d(sg), int(enable_gnss), C.c_double(sigma_cb),
+                                                                              C.c_double(sigma_rw), None if t is None else C.byref(t), 1 if use_async else 0))
             return self._chk(self.L.ingvio_frame_stage_tracks_nominal(self.h, b0, nb, sa, fa, C.byref(o), _d(sg), int(enable_gnss),
                                                                       C.c_double(sigma_cb), C.c_double(sigma_rw), 1 if use_async else 0))
         return call
+
+    def set_first_tri_placement(self, mode):
+        """0 (default): the triangulation of a first update staged with tri runs on the compute stream in front of the gate; 1: at the
+        stage, behind the gather (ingvio_set_first_tri_placement).  Bit-identical results."""
+        self._chk(self.L.ingvio_set_first_tri_placement(self.h, int(mode)))
 
     def update_stage_tracks_nominal_prepare(self, b0, marg_idx, track_frames, opts_frame, tri=None, max_accept=0, compress_rule=1,
                                             selected_variant=0, use_async=False):

@@ -145,7 +145,7 @@ def make_loop(B, n_frames, F=24, seed=5, ks=KS, windows=None, n_landmarks=2, lm_
                      feat_dof=[nobs - 1] * F if nobs >= 3 else [])
             if f == 0:
                 d.update(pf_track=list(range(F)), pf=pf_true)
-            frames.append(dict(delta=d, imu=imus[f], marg=marg, new_idx=n, gnss_idx=step["gnss_idx"]))
+            frames.append(dict(delta=d, imu=imus[f], marg=marg, new_idx=n, gnss_idx=step["gnss_idx"], t=times[f]))
             cidx = [c - 6 if c > marg else c for c in cidx if c != marg]
         cases.append(dict(P=P, table=table, frames=frames, step=step, frame=frame, C=C))
     return cases
@@ -168,9 +168,17 @@ def stage_args(cases):
     return c0["frame"], st["sigma"], st["enable_gnss"], st["sigma_cb"], st["sigma_rw"]
 
 
+def first_tri(cases):
+    """the cases' first updates triangulate on the device (closed_loop_update.make_update_loop(first_tri=True))"""
+    return bool(cases[0].get("first_tri"))
+
+
 def nominal_stage(ctx, cases, f, use_async=False, enable_gnss=None):
     opts_frame, sigma, eg, scb, srw = stage_args(cases)
     steps = [dict(imu=c["frames"][f]["imu"], gnss_idx=c["frames"][f]["gnss_idx"], marg_idx=c["frames"][f]["marg"]) for c in cases]
+    if first_tri(cases):
+        return ctx.frame_stage_tracks_nominal_tri_prepare(0, steps, [c["frames"][f]["delta"] for c in cases], opts_frame, sigma,
+                                                          eg if enable_gnss is None else enable_gnss, scb, srw, tri={}, use_async=use_async)
     return ctx.frame_stage_tracks_nominal_prepare(0, steps, [c["frames"][f]["delta"] for c in cases], opts_frame, sigma,
                                                   eg if enable_gnss is None else enable_gnss, scb, srw, use_async=use_async)
 
@@ -265,7 +273,8 @@ class DeviceLoop:
     sync_every_call (serial): a context synchronisation after every call that only enqueues.
     A frame entry may be an update-only frame from the table (closed_loop_update.py): an UpdateEntry(f) instead of the number f.  It is
     staged with update_stage(ctx, cases, f, use_async) and takes its place in the same sequences; where its run triangulated, its
-    results are (dx, accept, rows, pf, tri_ok).  The form's prepare / staged belong to the numbered entries."""
+    results are (dx, accept, rows, pf, tri_ok).  The form's prepare / staged belong to the numbered entries.  Cases whose first updates
+    triangulate (first_tri) stage their numbered entries with ingvio_frame_stage_tracks_nominal_tri; those results carry (pf, tri_ok) too."""
 
     def __init__(self, ctx, cases, frames, form=None, pipelined=True, sync_every_call=False, collect=True, update_stage=None):
         self.ctx, self.cases, self.frames, self.form, self.pipelined = ctx, cases, list(frames), form or Form(), pipelined
@@ -273,6 +282,7 @@ class DeviceLoop:
         self.collect = self.form.collect if collect else (lambda ctx: None)
         self.stages, self.form_calls = {}, {}
         self.update_stage = update_stage
+        self.staged_hook = None                                          # staged_hook(loop, i): right behind the stage of ANY entry i (tests read the staged frame there)
 
     def stage_of(self, f):
         if isinstance(f, UpdateEntry):
@@ -291,6 +301,8 @@ class DeviceLoop:
     def stage(self, i):
         (self.stages.get(i) or self.stage_of(self.frames[i]))()
         self.sync()
+        if self.staged_hook:
+            self.staged_hook(self, i)
         if not isinstance(self.frames[i], UpdateEntry):
             self.form.staged(self, i)
 
@@ -307,7 +319,8 @@ class DeviceLoop:
         """-> frame i's (dx, accept, rows), with a form that collects: (that, the form's results)"""
         out = self.plain_frame(i)
         e = self.frames[i]
-        if isinstance(e, UpdateEntry) and e.tri:                         # (the last fetch_begin was entry i's: its flags and points came along)
+        # (an ordinary entry of a loop whose first updates triangulate carries flags and points as the update-only entry does)
+        if e.tri if isinstance(e, UpdateEntry) else first_tri(self.cases):      # (the last fetch_begin was entry i's: its flags and points came along)
             tri = self.ctx.frame_fetch_tri()
             out = (out[0] + tri, out[1]) if len(out) == 2 else out + tri
         return out

@@ -20,33 +20,72 @@ from ingvio_amd.closed_loop import DeviceLoop, Form, HostTable, UpdateEntry, hos
 N_LOST = 7
 
 
-def make_update_loop(B, n_frames, F=24, seed=5, stereo=True, n_lost=N_LOST, carry_point=True, **kw):
+FAR_DEPTH = 2000.0
+
+
+def far_track(F):
+    """first_tri: the track whose true point lies FAR_DEPTH m out, far beyond ingvio_tri_opts' max_depth (60 m): its inverse depth is not
+    observable over the window (1e-3 of noise against 5e-4 of parallax per metre of baseline), so whatever the iteration finds, a depth
+    beyond max_depth, a negative one or no convergence, the triangulation refuses it - for geometry, with every observation stored"""
+    return F - 3
+
+
+def make_update_loop(B, n_frames, F=24, seed=5, stereo=True, n_lost=N_LOST, carry_point=True, first_tri=False, **kw):
     """closed_loop.make_loop in the two-update form (see the module's text); mono: the right eye's measurements are zero and the
     options name a mono camera; n_lost: the first update's tracks, the second lists the other F - n_lost; carry_point=False: the first
-    update never lists a track whose point only the triangulation knows"""
-    return split_updates(make_loop(B, n_frames, F=F, seed=seed, **kw), F, stereo, n_lost, carry_point)
+    update never lists a track whose point only the triangulation knows.
+    first_tri: no point is ever handed over (no pf_track / pf in any delta) - the first update's stage carries tri
+    (ingvio_frame_stage_tracks_nominal_tri) and finds its points itself.  Its list then also names the restarted track F - 1 in the frames
+    where that one holds one or two observations (refused for want of observations) and far_track(F) (refused for its geometry)."""
+    return split_updates(make_loop(B, n_frames, F=F, seed=seed, **kw), F, stereo, n_lost, carry_point, first_tri)
 
 
-def split_updates(cases, F=24, stereo=True, n_lost=N_LOST, carry_point=True):
+def far_observations(c, b, F):
+    """[n_frames][4]: the far track's measurements from the true camera poses of case c's frames, with the features' pixel noise"""
+    from ingvio_amd import synth
+    times = [fr["t"] for fr in c["frames"]]
+    Rm, pm = synth.true_cam_pose(times[len(times) // 2])
+    pw = Rm @ np.array([0.05 * FAR_DEPTH, -0.03 * FAR_DEPTH, FAR_DEPTH]) + pm
+    Rlr, tlr = synth.t_cl2cr()
+    rng = np.random.default_rng(900 + b)
+    out = np.zeros((len(times), 4))
+    for f, t in enumerate(times):
+        Rc, pc = synth.true_cam_pose(t)
+        q = Rc.T @ (pw - pc)
+        qr = Rlr @ q + tlr
+        out[f] = [q[0] / q[2], q[1] / q[2], qr[0] / qr[2], qr[1] / qr[2]]
+    return out + rng.normal(0.0, 1e-3, out.shape)
+
+
+def split_updates(cases, F=24, stereo=True, n_lost=N_LOST, carry_point=True, first_tri=False):
     """the cases of closed_loop.make_loop (or of a loop built on it: closed_loop_lm.make_lm_loop) in the two-update form, in place"""
-    for c in cases:
+    for b, c in enumerate(cases):
         W = len(c["table"].clones) + 1                                   # the window with the frame's new clone
         if not stereo:
             c["frame"] = dict(c["frame"], stereo=0)
+        if first_tri:
+            c["first_tri"] = True
+            far = far_observations(c, b, F)
         for f, fr in enumerate(c["frames"]):
             d = fr["delta"]
             nobs = min(f + 1, W - 1)                                     # the trailing window slots that hold observations
             uv = np.array(d["obs_uv"], dtype=np.float64, copy=True)
             if f >= 1:
                 uv[F - 2, 0] += 0.3 * (-1.0) ** f
+            if first_tri:
+                uv[far_track(F)] = far[f]
             if not stereo:
                 uv[:, 2:] = 0.0
             d["obs_uv"] = uv
             if f % 3 == 2:
                 d["free"] = [F - 1]
+            if first_tri:
+                d.pop("pf_track", None); d.pop("pf", None)
             if "pf_track" in d:                                          # only the lost tracks' points travel
                 d["pf_track"], d["pf"] = list(range(n_lost)), np.asarray(d["pf"])[:n_lost].copy()
             lost = (list(range(n_lost)) + ([n_lost] if f >= 3 and carry_point else [])) if nobs >= 3 else []
+            if first_tri and lost:
+                lost += ([F - 1] if f % 3 != 1 else []) + [far_track(F)]
             d["feat_track"], d["feat_anchor"], d["feat_dof"] = lost, [d["append"]] * len(lost), [nobs - 1] * len(lost)
             obs = list(range(W - nobs, W))
             sel = selected_slots(obs)
@@ -64,17 +103,21 @@ def selected_slots(obs):
     return sorted(set([obs[0], obs[n // 2], obs[-1]] + ([obs[1]] if n >= 5 else []))) if n >= 3 else []
 
 
-def make_keyframe_loop(B, n_frames, F=24, seed=5, **kw):
+def make_keyframe_loop(B, n_frames, F=24, seed=5, first_tri=False, **kw):
     """the two-update form with a key-frame cadence (KeyframeUpdate: two clones leave every other frame): neither update marginalises
     (fr["marg"] = fr["marg_upd"] = -1); behind every second camera frame the window's second and third clone leave through
     ingvio_nominal_tail (fr["tail_pos"] = [1, 2], else []), so the window grows by one clone and shrinks by one in turn.  No landmarks in
     the state.  The window bookkeeping of make_loop (one clone per frame) is redone here: the store's drop list, the append slot, the new
-    clone's idx."""
+    clone's idx.  first_tri: as make_update_loop's, without the two tracks meant to fail."""
     cases = make_loop(B, n_frames, F=F, seed=seed, n_landmarks=0, **kw)
     for c in cases:
         win, n, leaving = [False] * len(c["table"].clones), c["P"].shape[0], []
+        if first_tri:
+            c["first_tri"] = True
         for f, fr in enumerate(c["frames"]):
             d = fr["delta"]
+            if first_tri:
+                d.pop("pf_track", None); d.pop("pf", None)
             d["drop"] = list(leaving)
             win = [w for i, w in enumerate(win) if i not in leaving]
             d["append"] = len(win)
@@ -144,24 +187,92 @@ def host_second_update(ctx, cases, clones, f, marg=True, sel=True):
     return res
 
 
-def host_step_update(ctx, cases, tabs, f, points, lm_opts=None):
+class HostStore:
+    """what a host that keeps its own map holds of one filter's tracks: masks [F], uv [F][c_max][4] and the points its own triangulations
+    found; apply() replays a frame's delta (drop, free, append; as k_tracks_apply)"""
+
+    def __init__(self, F, c_max):
+        self.mask, self.uv, self.points, self.c_max = np.zeros(F, dtype=np.uint64), np.zeros((F, c_max, 4)), {}, c_max
+
+    def apply(self, d):
+        keep = [s for s in range(self.c_max) if s not in d.get("drop", [])]
+        if len(keep) < self.c_max:
+            self.uv[:, :len(keep)] = self.uv[:, keep]
+            bits = np.stack([(self.mask >> np.uint64(s)) & np.uint64(1) for s in keep], axis=1)
+            self.mask[:] = (bits << np.arange(len(keep), dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
+        self.mask[np.asarray(d.get("free", []), dtype=np.int64)] = 0
+        tr = np.asarray(d["obs_track"], dtype=np.int64)
+        self.uv[tr, d["append"]] = np.asarray(d["obs_uv"]).reshape(-1, 4)
+        self.mask[tr] |= np.uint64(1 << d["append"])
+
+
+def host_first_tri(ctx, cases, tfs, stores, tri=None, poses=None):
+    """the first update's points on the host, in front of its stage: the host-fed ingvio_triangulate at the host tables' clones (tfs: the
+    track frames of host_propagate) from every observation the host's own stores hold, the anchor's depth test of
+    MapServerManager.cpp:290,325 in numpy; the points that succeeded go into the host's store model and travel with the frame's delta
+    (pf_track / pf), a feature that failed is listed with an empty selection.  poses [B] of (clone_R, clone_p): the triangulation's clone
+    poses where they are not the track frames' (a comparison on the very bits another form staged).
+    -> (pf [B][f_max][3], tri_ok [B][f_max])"""
+    frames = []
+    poses = poses or [(tf["clone_R"], tf["clone_p"]) for tf in tfs]
+    for c, tf, st, (cR, cp) in zip(cases, tfs, stores, poses):
+        st.apply(tf)
+        tr, n = np.asarray(tf["feat_track"], dtype=np.int64), len(tf["clone_idx"])
+        full = st.mask[tr] & np.uint64((1 << n) - 1)
+        frames.append(dict(c["frame"], clone_idx=tf["clone_idx"], clone_R=cR, clone_p=cp, pf=np.zeros((len(tr), 3)),
+                           anchor=tf["feat_anchor"], dof=tf["feat_dof"], uv=st.uv[tr][:, :n, :], obs_mask=full))
+    B = len(cases)
+    pf, ok = np.zeros((B, ctx.f_max, 3)), np.zeros((B, ctx.f_max), dtype=np.int32)
+    if any(len(tf["feat_track"]) for tf in tfs):
+        pf, ok = ctx.triangulate(0, frames, stereo=bool(cases[0]["frame"].get("stereo", 1)), **(tri or {}))
+        pf, ok = np.array(pf), np.array(ok)
+    for b, (tf, st) in enumerate(zip(tfs, stores)):
+        nf = len(tf["feat_track"])
+        for j in range(nf):
+            if ok[b, j] == 1:
+                a = tf["feat_anchor"][j]
+                if (np.asarray(poses[b][0][a]).reshape(3, 3).T @ (pf[b, j] - np.asarray(poses[b][1][a])))[2] <= 0.0:
+                    ok[b, j], pf[b, j] = 2, 0.0
+            if ok[b, j] == 1:
+                st.points[int(tf["feat_track"][j])] = pf[b, j].copy()
+        won = sorted({int(t) for j, t in enumerate(tf["feat_track"]) if ok[b, j] == 1})
+        tf["pf_track"], tf["pf"] = won, np.array([st.points[t] for t in won]).reshape(-1, 3)
+        sel = np.asarray(tf["feat_sel"], dtype=np.uint64) if tf.get("feat_sel") is not None else np.full(nf, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        tf["feat_sel"] = np.where(ok[b, :nf] == 1, sel, np.uint64(0)).astype(np.uint64)
+    return pf, ok
+
+
+def host_step_update(ctx, cases, tabs, f, points, lm_opts=None, stores=None, staged=None):
     """the reference loop of one camera frame, in the reference's order: host_propagate(marg=False) -> ingvio_frame_stage_tracks -> run ->
     fetch -> host boxPlus; ingvio_msckf_update_tri with tri_masks at the table's values; ingvio_marginalize; host boxPlus / drop / shift.
     points [B]: {track: point} the earlier frames' triangulations found, handed to the store with the first update's delta (what the
     device loop's run writes itself).  lm_opts (cases of closed_loop_lm.make_lm_loop): the landmark update behind the second MSCKF update
     and in front of the marginalisation (IngvioFilter.cpp:281-289), host-fed with the values both updates left.
-    -> ((dx, accept, rows), (dx, accept, gamma, rows, pf, tri_ok)[, the landmark update's (dx, rows, accept, gamma, status)])"""
+    stores [B] of HostStore (cases with first_tri): the first update's points come from host_first_tri; its results then carry (pf, tri_ok).
+    staged = (first, second), each [B] of (clone_R, clone_p): the clone tables another form staged for the two updates (staged_clones).
+    Both triangulations then run on those very bits, and the second update, which ingvio_msckf_update_tri linearises at the clones it
+    triangulates from, is formed at them: points compare exactly, and what is left between the forms is the arithmetic of the updates.
+    ->((dx, accept, rows), (dx, accept, gamma, rows, pf, tri_ok)[, the landmark update's (dx, rows, accept, gamma, status)])"""
     steps, tfs = host_propagate(cases, tabs, f, marg=False)
+    tri1 = host_first_tri(ctx, cases, tfs, stores, poses=staged[0] if staged else None) if stores is not None else None
     for tf, pts in zip(tfs, points):
+        if tri1 is not None:                                             # (a track both updates triangulated: the later point, the first update's)
+            pts = {**pts, **{int(t): p for t, p in zip(tf["pf_track"], tf["pf"])}}
+            tf["pf_track"], tf["pf"] = [], np.zeros((0, 3))
         tr = list(tf.get("pf_track", [])) + sorted(pts)
         tf["pf"] = np.concatenate([np.asarray(tf.get("pf", np.zeros((0, 3)))).reshape(-1, 3), np.array([pts[t] for t in sorted(pts)]).reshape(-1, 3)])
         tf["pf_track"] = tr
     host_stage(ctx, cases, steps, tfs)
     ctx.frame_run()
     first = ctx.frame_fetch()
+    if tri1 is not None:
+        first = tuple(first) + tri1
     for b, t in enumerate(tabs):
         t.box_plus(first[0][b])
-    second = host_second_update(ctx, cases, [[t.slots[s] for s in t.clones] for t in tabs], f, marg=lm_opts is None)
+    clones = [[t.slots[s] for s in t.clones] for t in tabs]
+    if staged:
+        clones = [[dict(idx=s["idx"], R=R, p=p) for s, R, p in zip(cl, cR, cp)] for cl, (cR, cp) in zip(clones, staged[1])]
+    second = host_second_update(ctx, cases, clones, f, marg=lm_opts is None)
     lm = None
     for b, t in enumerate(tabs):
         t.box_plus(second[0][b])
@@ -178,6 +289,16 @@ def host_step_update(ctx, cases, tabs, f, points, lm_opts=None):
             t.marginalize(c["frames"][f]["marg_upd"])
         points[b] = {int(tr): second[4][b, j].copy() for j, tr in enumerate(c["frames"][f]["upd"]["feat_track"]) if second[5][b, j] == 1}
     return (first, second) if lm is None else (first, second, lm)
+
+
+def staged_clones(ctx):
+    """[B] of (clone_R [n][3][3], clone_p [n][3]): the clone table of the frame ctx has staged (ingvio_debug_staged_frame)"""
+    out = []
+    for b in range(ctx.batch):
+        sf = ctx.debug_staged_frame(b)
+        n = sf["n_clones"]
+        out.append((sf["clone_R"][:n].reshape(n, 3, 3).copy(), sf["clone_p"][:n].copy()))
+    return out
 
 
 def host_table_of(nom):

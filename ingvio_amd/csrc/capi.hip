@@ -245,6 +245,13 @@ struct ingvio_ctx {
         bool tri_fetched = false; int tri_b0 = 0, tri_nb = 0; // the pinned result mirror holds a triangulating run's flags and points of this range
         ingvio_tri_opts tri;
         int* d_tri_track = nullptr;                           // [B][f_max] track of each listed feature (k_tracks_gather_upd)
+        // the triangulating ORDINARY frame from the table (ingvio_frame_stage_tracks_nominal_tri): tri_place 0 - k_triangulate on the compute
+        // stream in front of the gate, 1 - at the stage behind the gather (the copy stream of an asynchronous stage), flags and points into
+        // d_tri_ok_st / d_tri_pf_st [B][f_max] of its own (the result slab may still wait for the previous frame's fetch); tri_staged: the
+        // staged frame's triangulation was issued that way, its run only copies the two into the result slab
+        int tri_place = 0;
+        bool tri_staged = false;
+        int* d_tri_ok_st = nullptr; double* d_tri_pf_st = nullptr;
     } nom;
     // ingvio_nominal_tail (kernels_tail.hip), grown on demand: the uploaded lists, the panel kernel's workspace (transient: nothing in it
     // outlives the call, so a snapshot has nothing to copy) and the pinned mirror of the verdicts and the new dimensions
@@ -1130,7 +1137,7 @@ struct FrameStage {
             c->nom.pending = true;
         }
         c->nom.frame = plan != nullptr;                // a frame from the table is followed by the post-frame step
-        c->nom.noprop = upd; c->nom.tri_on = false;
+        c->nom.noprop = upd; c->nom.tri_on = false; c->nom.tri_staged = false;
         c->st_stereo = opts->stereo; c->st_enable_gnss = enable_gnss;
         if (!c->staged || fmx > c->st_fmax_used) c->st_fmax_used = fmx;
         c->staged = true;
@@ -1302,7 +1309,8 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
         for (auto e : c->ev_free) if (e) hipEventDestroy(e);
     }
     for (void* p : { (void*)c->trk.uv, (void*)c->trk.pf, (void*)c->trk.mask, (void*)c->trk.stage[0], (void*)c->trk.stage[1] }) if (p) hipFree(p);
-    for (void* p : { (void*)c->nom.ih, (void*)c->nom.dv, (void*)c->nom.ih_snap, (void*)c->nom.dv_snap, (void*)c->nom.dx, (void*)c->nom.d_tri_track }) if (p) hipFree(p);
+    for (void* p : { (void*)c->nom.ih, (void*)c->nom.dv, (void*)c->nom.ih_snap, (void*)c->nom.dv_snap, (void*)c->nom.dx, (void*)c->nom.d_tri_track,
+                     (void*)c->nom.d_tri_ok_st, (void*)c->nom.d_tri_pf_st }) if (p) hipFree(p);
     if (c->nom.ev) hipEventDestroy(c->nom.ev);
     for (void* p : { (void*)c->od.d, (void*)c->od.cols, (void*)c->od.ns, (void*)c->od.blk }) if (p) hipFree(p);
     if (c->od.h) hipHostFree(c->od.h);
@@ -3605,14 +3613,60 @@ int ingvio_tracks_create(ingvio_ctx* c, int t_max)
 
 // plan [nb][4] (device nominal stage, else nullptr): the new clone's variable slot, its idx, the window's clone count with it and the
 // table's slots in use after it; frames[i].n_clones is that count, the frames' clone arrays are not read
-// upd (with a plan; the update-only frame from the table, ingvio_update_stage_tracks_nominal): steps[i].k = 0 and no IMU samples, nothing is
+// tg with noprop = true (upd; with a plan; the update-only frame from the table, ingvio_update_stage_tracks_nominal): steps[i].k = 0 and no IMU samples, nothing is
 // propagated and no clone is appended - plan [nb][4] = -1, the window's highest clone idx, its clone count, the table's slots in use;
 // tri_mask / tri_track: where the gather leaves the triangulation's masks and the features' tracks (nullptr: no triangulation)
-struct UpdStage { unsigned long long* tri_mask; int* tri_track; };
+// tg with noprop = false (with a plan, the ordinary frame from the table that triangulates, ingvio_frame_stage_tracks_nominal_tri): the
+// gather leaves the same two arrays; tg->at_stage != nullptr: k_triangulate with these settings and k_tracks_store_points follow the
+// gather on the stage's stream
+// (both are one TableStage: noprop tells the update-only frame from the ordinary one that triangulates)
+struct TableStage { bool noprop; unsigned long long* tri_mask; int* tri_track; const ingvio_tri_opts* at_stage; };
+
+// The buffers a triangulating frame from the table leaves its masks, tracks and (at_stage) flags and points in, allocated by the first
+// stage that needs them.  dalloc clears on the compute stream while the stage's kernels may write them on the copy stream, and no event
+// orders the two at a context's first stage: a fresh allocation synchronises the compute stream, once.  Nothing else of the context changes.
+static int tri_buffers(ingvio_ctx* c, bool at_stage)
+{
+    auto& m = c->nom;
+    const size_t cnt = (size_t)c->d.batch * c->d.f_max;
+    bool fresh = false;
+    if (!c->d_tri_mask) { if (dalloc(c, &c->d_tri_mask, cnt)) return INGVIO_E_HIP; fresh = true; }
+    if (!m.d_tri_track) { if (dalloc(c, &m.d_tri_track, cnt)) return INGVIO_E_HIP; fresh = true; }
+    if (at_stage && !m.d_tri_ok_st) { if (dalloc(c, &m.d_tri_ok_st, cnt)) return INGVIO_E_HIP; fresh = true; }
+    if (at_stage && !m.d_tri_pf_st) { if (dalloc(c, &m.d_tri_pf_st, cnt * 3)) return INGVIO_E_HIP; fresh = true; }
+    if (fresh) HIPCHK(c, hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// The triangulation of a frame from the table on stream st: the listed features' points from every stored observation (the masks
+// k_tracks_gather_upd left in d_tri_mask), with the settings of ingvio_msckf_update_tri - a feature that fails loses its mask and drops out
+// of the gate - flags and points also into ok2 / pf2 [B][f_max], and the points that succeeded into the track store (setValuePosXyz,
+// MapServerManager.cpp:335).  No host synchronisation.
+static int nom_triangulate(ingvio_ctx* c, hipStream_t st, int* ok2, double* pf2)
+{
+    const int B = c->d.batch;
+    const ingvio_tri_opts& o = c->nom.tri;
+    TriLaunch T;
+    memset(&T, 0, sizeof T);
+    T.fv = fview(c); T.b0 = 0;
+    memcpy(T.R_lr, o.R_cl2cr, 72); memcpy(T.t_lr, o.t_cl2cr, 24);
+    T.trans_thres = o.trans_thres; T.huber_epsilon = o.huber_epsilon; T.conv_precision = o.conv_precision;
+    T.init_damping = o.init_damping; T.max_depth = o.max_depth; T.min_depth = o.min_depth;
+    T.outer_loop_max_iter = o.outer_loop_max_iter; T.inner_loop_max_iter = o.inner_loop_max_iter;
+    T.pf = c->d_pf; T.ok = c->d_tri_ok; T.mask_failed = 1; T.mask_rw = c->d_mask; T.check_anchor = 1;
+    T.ok2 = ok2; T.pf2 = pf2;
+    T.tri_mask = c->d_tri_mask;
+    if (launch_triangulate(T, B, c->nom.tri_fmx > 0 ? c->nom.tri_fmx : 1, o.stereo, st)) return INGVIO_E_UNSUPPORTED;
+    const TrackStore store{ c->trk.uv, c->trk.mask, c->trk.pf, c->trk.t_max, c->d.c_max };
+    launch_tracks_store_points(store, 0, B, c->d_nfeat, c->d.f_max, c->nom.d_tri_track, ok2, pf2, st);
+    return 0;
+}
+
 static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_raw* steps, const ingvio_track_frame* frames,
                                    const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, int async,
-                                   const int* plan, const UpdStage* upd = nullptr)
+                                   const int* plan, const TableStage* tg = nullptr)
 {
+    const bool upd = tg && tg->noprop;
     FrameStage stage{ c, b0, nb, opts, sigma, enable_gnss, scb, srw, async != 0 };
     if (int rc = stage.refuse(steps && frames, true)) return rc;
     const int T = c->trk.t_max, cm = c->d.c_max, fm = c->d.f_max;
@@ -3719,10 +3773,14 @@ static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_f
     if (!upd) launch_imu_steps(ts, b0, nb, KMAX, c->d_Phi, c->d_G, c->d_dt, c->d_R, S, plan ? &nt : nullptr);
     if (hipGetLastError() != hipSuccess) return stage.fail(INGVIO_E_HIP);       // before the store kernels change the track store
     launch_tracks_apply(ts, store, b0, nb, S);
-    if (upd) launch_tracks_gather_update(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S, nt, upd->tri_mask, upd->tri_track);
+    if (tg) launch_tracks_gather_tri(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S, nt, tg->tri_mask, tg->tri_track);
     else launch_tracks_gather(ts, store, fo, b0, nb, c->d_idx, c->d_gnss, S, plan ? &nt : nullptr);
     if (hipGetLastError() != hipSuccess) return stage.fail(INGVIO_E_HIP);
-    return stage.finish(steps, frames, fmx, plan, upd != nullptr);
+    if (tg && tg->at_stage) {                    // in front of finish(): the run's wait for the inputs covers it
+        c->nom.tri = *tg->at_stage; c->nom.tri_fmx = fmx;
+        if (nom_triangulate(c, S, c->nom.d_tri_ok_st, c->nom.d_tri_pf_st) || hipGetLastError() != hipSuccess) return stage.fail(INGVIO_E_HIP);
+    }
+    return stage.finish(steps, frames, fmx, plan, upd);
 }
 
 int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_raw* steps, const ingvio_track_frame* frames,
@@ -4157,10 +4215,32 @@ int ingvio_nominal_tail(ingvio_ctx* c, int b0, int nb, const ingvio_nominal_tail
 int ingvio_frame_stage_tracks_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,
                                       const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw, int async)
 {
+    return ingvio_frame_stage_tracks_nominal_tri(c, b0, nb, steps, frames, opts, sigma, enable_gnss, scb, srw, nullptr, async);
+}
+
+// where the triangulation of ingvio_frame_stage_tracks_nominal_tri is issued (Nominal::tri_place); results are bit-identical
+int ingvio_set_first_tri_placement(ingvio_ctx* c, int mode)
+{
+    if (!c) return INGVIO_E_ARG;
+    ENTER(c);
+    if (mode < 0 || mode > 1) { c->err = "ingvio_set_first_tri_placement: mode is 0 or 1"; return INGVIO_E_ARG; }
+    if (c->nom.pending) { c->err = "ingvio_set_first_tri_placement: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    c->nom.tri_place = mode;
+    return INGVIO_OK;
+}
+
+// The first MSCKF update of a camera frame (RemoveLostUpdate::updateStateStereo / Mono) from the table: tri != NULL, its features' points
+// come from the window's clones as they stand behind the IMU integration and the new clone (MapServerManager.cpp:275-341)
+int ingvio_frame_stage_tracks_nominal_tri(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,
+                                          const ingvio_msckf_opts* opts, const double sigma[4], int enable_gnss, double scb, double srw,
+                                          const ingvio_tri_opts* tri, int async)
+{
     ENTER(c);
     if (phase_busy(c) || check_range(c, b0, nb) || !steps || !frames) return INGVIO_E_ARG;
     auto& m = c->nom;
     if (!m.vmax) { c->err = "ingvio_frame_stage_tracks_nominal without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (tri && !c->trk.t_max) { c->err = "ingvio_frame_stage_tracks_nominal_tri without ingvio_tracks_create"; return INGVIO_E_ARG; }
+    if (tri && (tri->outer_loop_max_iter < 0 || tri->inner_loop_max_iter < 0)) return INGVIO_E_ARG;
     // the post-frame step retracts, drops and shifts EVERY filter of the batch, and a second stage before the run is refused: the frame
     // staged from the table is the whole batch's
     if (b0 != 0 || nb != c->d.batch) { c->err = "ingvio_frame_stage_tracks_nominal stages the whole batch (b0 = 0, nb = batch)"; return INGVIO_E_ARG; }
@@ -4203,7 +4283,16 @@ int ingvio_frame_stage_tracks_nominal(ingvio_ctx* c, int b0, int nb, const ingvi
         memcpy(r.gnss_idx, steps[i].gnss_idx, sizeof r.gnss_idx);
         fr[i].n_clones = ncl; fr[i].clone_idx = nullptr; fr[i].clone_R = nullptr; fr[i].clone_p = nullptr;
     }
-    return frame_stage_tracks_impl(c, b0, nb, raw.data(), fr.data(), opts, sigma, enable_gnss, scb, srw, async, plan.data());
+    if (!tri) return frame_stage_tracks_impl(c, b0, nb, raw.data(), fr.data(), opts, sigma, enable_gnss, scb, srw, async, plan.data());
+    const bool at_stage = m.tri_place == 1;
+    if (int rc = tri_buffers(c, at_stage)) return rc;
+    const TableStage ft{ false, c->d_tri_mask, m.d_tri_track, at_stage ? tri : nullptr };
+    const int rc = frame_stage_tracks_impl(c, b0, nb, raw.data(), fr.data(), opts, sigma, enable_gnss, scb, srw, async, plan.data(), &ft);
+    if (rc == INGVIO_OK) {
+        m.tri_on = true; m.tri_staged = at_stage; m.tri = *tri; m.tri_fmx = 0;
+        for (int i = 0; i < nb; ++i) m.tri_fmx = std::max(m.tri_fmx, frames[i].n_feat);
+    }
+    return rc;
 }
 
 // The second MSCKF update of a camera frame (SwMargUpdate / KeyframeUpdate::updateState*, IngvioFilter.cpp:271-324) as a frame from the
@@ -4255,11 +4344,9 @@ int ingvio_update_stage_tracks_nominal(ingvio_ctx* c, int b0, int nb, const int*
         for (int g = 0; g < 5; ++g) r.gnss_idx[g] = c->st_gnss[(size_t)b * 5 + g];      // no propagation: the clock indices stay what they are
         fr[i].n_clones = ncl; fr[i].clone_idx = nullptr; fr[i].clone_R = nullptr; fr[i].clone_p = nullptr;
     }
-    UpdStage upd{ nullptr, nullptr };
+    TableStage upd{ true, nullptr, nullptr, nullptr };
     if (tri) {
-        const size_t cnt = (size_t)c->d.batch * c->d.f_max;
-        if (!c->d_tri_mask && dalloc(c, &c->d_tri_mask, cnt)) return INGVIO_E_HIP;
-        if (!m.d_tri_track && dalloc(c, &m.d_tri_track, cnt)) return INGVIO_E_HIP;
+        if (int rc = tri_buffers(c, false)) return rc;
         upd.tri_mask = c->d_tri_mask; upd.tri_track = m.d_tri_track;
     }
     static const double no_sigma[4] = { 0.0, 0.0, 0.0, 0.0 };
@@ -4483,25 +4570,22 @@ static int frame_run_whole(ingvio_ctx* c, int restore_prior)
         // into the track store (setValuePosXyz, MapServerManager.cpp:335).  No host synchronisation.
         HIPCHK(c, hipMemsetAsync(c->d_status, 0, sizeof(int) * (size_t)B, c->st));
         if (c->nom.tri_on) {
-            const ingvio_tri_opts& o = c->nom.tri;
-            TriLaunch T;
-            memset(&T, 0, sizeof T);
-            T.fv = fview(c); T.b0 = 0;
-            memcpy(T.R_lr, o.R_cl2cr, 72); memcpy(T.t_lr, o.t_cl2cr, 24);
-            T.trans_thres = o.trans_thres; T.huber_epsilon = o.huber_epsilon; T.conv_precision = o.conv_precision;
-            T.init_damping = o.init_damping; T.max_depth = o.max_depth; T.min_depth = o.min_depth;
-            T.outer_loop_max_iter = o.outer_loop_max_iter; T.inner_loop_max_iter = o.inner_loop_max_iter;
-            T.pf = c->d_pf; T.ok = c->d_tri_ok; T.mask_failed = 1; T.mask_rw = c->d_mask; T.check_anchor = 1;
-            T.ok2 = (int*)(c->d_result_slab + c->ro_tok); T.pf2 = (double*)(c->d_result_slab + c->ro_tpf);
-            T.tri_mask = c->d_tri_mask;
-            if (launch_triangulate(T, B, c->nom.tri_fmx > 0 ? c->nom.tri_fmx : 1, o.stereo, c->st)) return INGVIO_E_UNSUPPORTED;
-            const TrackStore store{ c->trk.uv, c->trk.mask, c->trk.pf, c->trk.t_max, c->d.c_max };
-            launch_tracks_store_points(store, 0, B, c->d_nfeat, c->d.f_max, c->nom.d_tri_track, T.ok2, T.pf2, c->st);
+            if (int rc = nom_triangulate(c, c->st, (int*)(c->d_result_slab + c->ro_tok), (double*)(c->d_result_slab + c->ro_tpf))) return rc;
             c->nom.tri_ran = true;
         }
     } else {
         launch_restore_propagate(c, restore_prior, strips_valid(c, restore_prior), 0, B, c->st);
         mirror_restore_clone(c, restore_prior);
+        // the ordinary frame from the table that triangulates (ingvio_frame_stage_tracks_nominal_tri): the same two launches in front of the
+        // gate, or - issued at the stage already (Nominal::tri_place) - only the flags and points on their way into the result slab
+        if (c->nom.frame && c->nom.tri_on) {
+            if (c->nom.tri_staged) {
+                const size_t cnt = (size_t)B * c->d.f_max;
+                HIPCHK(c, hipMemcpyAsync(c->d_result_slab + c->ro_tok, c->nom.d_tri_ok_st, sizeof(int) * cnt, hipMemcpyDeviceToDevice, c->st));
+                HIPCHK(c, hipMemcpyAsync(c->d_result_slab + c->ro_tpf, c->nom.d_tri_pf_st, 8 * cnt * 3, hipMemcpyDeviceToDevice, c->st));
+            } else if (int rc = nom_triangulate(c, c->st, (int*)(c->d_result_slab + c->ro_tok), (double*)(c->d_result_slab + c->ro_tpf))) return rc;
+            c->nom.tri_ran = true;
+        }
     }
     // factored path: the marginalisation of the oldest clone rides on the update's write-back (k_info_apply
     // stores the updated covariance compacted into the other ping-pong half); dense path: separate kernel
@@ -4761,7 +4845,8 @@ int ingvio_frame_fetch_begin(ingvio_ctx* c, int b0, int nb)
     HIPCHK(c, hipMemcpyAsync(c->h_result + 8 * (size_t)b0 * c->ldp, c->d_dx + (size_t)b0 * c->ldp, 8 * (size_t)nb * c->ldp, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(c->h_result + c->ro_used + sizeof(int) * (size_t)b0 * fm, c->d_used + (size_t)b0 * fm, sizeof(int) * (size_t)nb * fm, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(c->h_result + c->ro_m + sizeof(int) * (size_t)b0, c->d_m + b0, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, c->st));
-    // a run that triangulated (the update-only frame from the table): its flags and points travel with the frame's results
+    // a run that triangulated (a frame from the table staged with tri, ordinary or update-only): its flags and points travel with the
+    // frame's results
     c->nom.tri_fetched = false;
     if (c->nom.tri_ran) {
         HIPCHK(c, hipMemcpyAsync(c->h_result + c->ro_tok + sizeof(int) * (size_t)b0 * fm, c->d_result_slab + c->ro_tok + sizeof(int) * (size_t)b0 * fm,
@@ -4787,7 +4872,7 @@ int ingvio_frame_fetch_tri(ingvio_ctx* c, int b0, int nb, double* pf_out, int* t
         if (pf_out) memcpy(pf_out, c->h_result + c->ro_tpf + 8 * (size_t)b0 * fm * 3, 8 * (size_t)nb * fm * 3);
         return INGVIO_OK;
     }
-    if (!c->nom.tri_ran) { c->err = "ingvio_frame_fetch_tri: the frame that ran last did not triangulate"; return INGVIO_E_ARG; }
+    if (!c->nom.tri_ran) { c->err = "ingvio_frame_fetch_tri: the frame that ran last did not triangulate (neither stage from the table was given tri)"; return INGVIO_E_ARG; }
     ENTER(c);
     if (tri_ok && down_sync(c, tri_ok, c->d_result_slab + c->ro_tok + sizeof(int) * (size_t)b0 * fm, sizeof(int) * (size_t)nb * fm)) return INGVIO_E_HIP;
     if (pf_out && down_sync(c, pf_out, c->d_result_slab + c->ro_tpf + 8 * (size_t)b0 * fm * 3, 8 * (size_t)nb * fm * 3)) return INGVIO_E_HIP;

@@ -344,7 +344,10 @@ __global__ __launch_bounds__(256) void k_tracks_apply(TrackStage ts, TrackStore 
 // NOM: the window's clone table comes from the device-resident nominal state (after k_imu_steps<true> appended the new clone).
 // UPD (k_tracks_gather_upd, the update-only frame from the table: no IMU steps ran, the window is the table's as it stands): with
 // tri_mask != nullptr also the feature's FULL stored mask over the window (the triangulation of the selected-stamp updates reads every
-// stored observation, SwMargUpdate.cpp:236-257) and its track number, for the points' way back into the store.
+// stored observation, SwMargUpdate.cpp:236-257) and its track number, for the points' way back into the store.  UPD changes nothing
+// else in the body - the update-only frame differs from the ordinary one in its header words alone - so the ordinary frame from the table
+// that triangulates (ingvio_frame_stage_tracks_nominal_tri, behind k_imu_steps<true>: the new clone's column is in the window) launches
+// this same kernel; the plain k_tracks_gather<true> / <false> of frames that do not triangulate stay what they were.
 template <bool NOM, bool UPD>
 __device__ __forceinline__ void tracks_gather(const TrackStage& ts, const TrackStore& st, const FrameOut& fv, const NomTable& nt, int b0, int* __restrict__ idx_marg,
                                               int* __restrict__ gnss_idx, unsigned long long* __restrict__ tri_mask, int* __restrict__ tri_track)
@@ -448,8 +451,8 @@ void launch_tracks_gather(const TrackStage& ts, const TrackStore& store, const F
     if (nom) hipLaunchKernelGGL(k_tracks_gather<true>, dim3(nb), dim3(256), 0, st, ts, store, fv, *nom, b0, idx_marg, gnss_idx);
     else hipLaunchKernelGGL(k_tracks_gather<false>, dim3(nb), dim3(256), 0, st, ts, store, fv, NomTable{}, b0, idx_marg, gnss_idx);
 }
-void launch_tracks_gather_update(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st,
-                                 const NomTable& nom, unsigned long long* tri_mask, int* tri_track)
+void launch_tracks_gather_tri(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st,
+                              const NomTable& nom, unsigned long long* tri_mask, int* tri_track)
 {
     hipLaunchKernelGGL(k_tracks_gather_upd, dim3(nb), dim3(256), 0, st, ts, store, fv, nom, b0, idx_marg, gnss_idx, tri_mask, tri_track);
 }

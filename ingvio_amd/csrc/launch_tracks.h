@@ -40,8 +40,10 @@ void launch_imu_steps(const TrackStage& ts, int b0, int nb, int kst, double* Phi
 void launch_tracks_apply(const TrackStage& ts, const TrackStore& store, int b0, int nb, hipStream_t st);
 void launch_tracks_gather(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st,
                           const NomTable* nom = nullptr);
-// the update-only frame from the table (ingvio_update_stage_tracks_nominal): k_tracks_gather_upd; tri_mask / tri_track [B][fmax] or nullptr
-void launch_tracks_gather_update(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st,
-                                 const NomTable& nom, unsigned long long* tri_mask, int* tri_track);
+// the gather of a frame from the table that may triangulate - the update-only frame (ingvio_update_stage_tracks_nominal) and the ordinary
+// one staged with tri (ingvio_frame_stage_tracks_nominal_tri): k_tracks_gather_upd (the kernel keeps the name it was introduced and
+// profiled under); tri_mask / tri_track [B][fmax] or nullptr
+void launch_tracks_gather_tri(const TrackStage& ts, const TrackStore& store, const FrameOut& fv, int b0, int nb, int* idx_marg, int* gnss_idx, hipStream_t st,
+                              const NomTable& nom, unsigned long long* tri_mask, int* tri_track);
 // triangulated points (ok == 1) of the listed features into the store's pf
 void launch_tracks_store_points(const TrackStore& store, int b0, int nb, const int* n_feat, int fmax, const int* track, const int* ok, const double* pf, hipStream_t st);

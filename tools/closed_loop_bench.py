@@ -49,6 +49,8 @@ the frame's clone; two forms on the same build,
                    shift on the host, ingvio_nominal_set
 the device form free-running (device_loop_ms_per_frame) and both synchronised per camera frame; writes
 $RESULTS/closed_loop_bench_two_updates.json.
+--two-updates --tri-first: the first update's points found on the device (ingvio_frame_stage_tracks_nominal_tri), both placements of its
+triangulation, against the form with host-sent points and the stalling form (main_tri_first); $RESULTS/closed_loop_bench_tri_first.json.
 --odom: what the odometry record costs (ingvio_odom_begin / _end, ingvio_amd/closed_loop_odom.py), on one build in one run; the forms
 free-running and alternated A B C A B C,
   A  the plain pipelined loop
@@ -323,6 +325,66 @@ def main_two_updates(a):
     finish(out, "closed_loop_bench_two_updates.json")
 
 
+def main_tri_first(a):
+    """--two-updates --tri-first: what it costs to find the first update's points on the device (ingvio_frame_stage_tracks_nominal_tri), on
+    one build in one process, the forms free-running and alternated T0 T1 P T0 T1 P,
+      T0 / T1  no point ever handed over, both updates triangulate in their runs; the first update's k_triangulate in front of the gate
+               (ingvio_set_first_tri_placement 0) / at the stage behind the gather (1)
+      P        the two-update loop with the first update's points sent by the host once (--two-updates as it was)
+    then the stalling form a caller without the export is left with: the first update staged without tri, ingvio_nominal_get (both
+    streams drained) and ingvio_triangulate on the staged frames (drained again) in front of every first update's run, over
+    --stall-frames camera frames - a lower bound for a host-fed triangulation from the values of ingvio_nominal_get, which would also
+    upload its frames.  Writes $RESULTS/closed_loop_bench_tri_first.json."""
+    from ingvio_amd import closed_loop as cl
+    from ingvio_amd import closed_loop_update as cu
+    B, F, NF, W = a.batch, a.features, a.frames, a.warmup
+    t0 = time.perf_counter()
+    base = cl.make_loop(B, NF, F=F, ks=(a.k,), windows=(a.window,))                      # (one set of inputs, split both ways)
+    sent = cu.split_updates(copy.deepcopy(base), F, True, F - a.second, False)
+    tri = cu.split_updates(base, F, True, F - a.second, False, first_tri=True)
+    out = dict(batch=B, features=F, second=a.second, window=a.window, k=a.k, frames_timed=NF - W, tri_first=True, setup_s=round(time.perf_counter() - t0, 1))
+    entries = cu.two_update_entries(range(NF))
+
+    def run(cases, placement, nf=NF, w=W, stall=False):
+        ctx = fresh_ctx(a, cases)
+        ctx.set_first_tri_placement(placement)
+
+        class Stall(cl.Form):
+            def staged(self, loop, i):
+                loop.ctx.nominal_get()
+                loop.ctx.triangulate(0, None, stereo=True, mask_failed=True)
+        loop = cl.DeviceLoop(ctx, cases, entries[:2 * nf], Stall() if stall else None, collect=False, update_stage=cu.update_stage).prepare()
+        loop.start()
+        for f in range(nf):
+            if f == w:
+                ctx.sync()
+                t1 = time.perf_counter()
+            r1, r2 = loop.frame(2 * f), loop.frame(2 * f + 1)
+        ctx.sync()
+        ms = round(1e3 * (time.perf_counter() - t1) / (nf - w), 4)
+        ctx.close()
+        return ms, r1
+    forms = dict(T0=(tri, 0), T1=(tri, 1), P=(sent, 0))
+    if a.device_only:                                                    # the kernel-trace run: the default form alone
+        out["T0_ms_per_frame"] = run(tri, 0)[0]
+        return finish(out)
+    times = {k: [] for k in forms}
+    for rep in range(a.repeats):
+        for name, (cases, placement) in forms.items():
+            ms, r1 = run(cases, placement)
+            times[name].append(ms)
+            if name == "T0":
+                n1 = len(tri[0]["frames"][NF - 1]["delta"]["feat_track"])
+                out["last_first_update_listed"] = n1
+                out["last_first_update_tri_ok_mean"] = float((r1[4][:, :n1] == 1).sum(axis=1).mean())
+                out["last_first_update_rows_mean"] = float(r1[2].mean())
+    for name, t in times.items():
+        out[name + "_ms_per_frame"] = t
+        out[name + "_ms_per_frame_min"] = min(t)
+    out["stalling_ms_per_frame"] = run(sent, 0, a.stall_frames + 1, 1, stall=True)[0]
+    finish(out, "closed_loop_bench_tri_first.json")
+
+
 def main_odom(a):
     import ctypes
     from ingvio_amd import capi
@@ -407,6 +469,7 @@ def main():
     ap.add_argument("--tail", action="store_true", help="the oldest clone leaves and every landmark changes its anchor behind every frame")
     ap.add_argument("--two-updates", action="store_true", help="both MSCKF updates of the camera callback: the second as an update-only frame from the table")
     ap.add_argument("--second", type=int, default=40, help="--two-updates: features of the second update")
+    ap.add_argument("--tri-first", action="store_true", help="--two-updates: the first update's points triangulated on the device, against host-sent points and the stalling form")
     ap.add_argument("--odom", action="store_true", help="the plain loop against the loop with the odometry record, and the stalling form")
     ap.add_argument("--repeats", type=int, default=2, help="--odom: rounds of A B C")
     ap.add_argument("--stall-frames", type=int, default=3, help="--odom: timed frames of the stalling form")
@@ -414,7 +477,7 @@ def main():
     if a.odom:
         return main_odom(a)
     if a.two_updates:
-        return main_two_updates(a)
+        return main_tri_first(a) if a.tri_first else main_two_updates(a)
     if a.tail:
         return main_tail(a)
     if a.landmarks > 0:
