@@ -900,6 +900,16 @@ int ingvio_set_gram_decoupled(ingvio_ctx* ctx, int on);
 /* The form the Gram stage of the context's last MSCKF update took: 0 the full form, 1 the reduced k_feat_gram2, 2 the reduced
  * k_feat_gram3.  A negative error code for a null context. */
 int ingvio_last_gram_form(ingvio_ctx* ctx);
+/* The write-back of ingvio_frame_run's fused step as k_info_apply_res: one workgroup per filter keeps the filter's whole
+ * P[:, window columns] in the 160 KB LDS of a CU and sweeps the tiles without workgroup barriers.  Taken for more than 64 filters of the
+ * window classes of up to 6 and up to 11 clones, ldp <= 256, with the marginalisation riding on the write-back and no in-frame GNSS
+ * fold; everything else keeps k_info_apply whatever the switch says.  The same products in the same order: results are bit-identical
+ * (tests/test_gpu_apply_resident.py).  on: 1 (the default) / 0 k_info_apply, for comparison.
+ * Environment override at context creation: INGVIO_APPLY_RESIDENT (0 / 1). */
+int ingvio_set_apply_resident(ingvio_ctx* ctx, int on);
+/* The form the write-back of the context's last MSCKF update took: 1 k_info_apply_res, 0 any other kernel.  A negative error code for
+ * a null context. */
+int ingvio_last_apply_form(ingvio_ctx* ctx);
 /* Which form of the delayed-initialisation front ingvio_add_variable_delayed, ingvio_add_variable_delayed_batch and
  * ingvio_landmark_init_nominal take.  The LDS form keeps [H_old | res], T = Pcc H_old^T and S in LDS at once, which bounds
  * the window (stereo: 17 clones, mono: 21 - 26).  The large form keeps [H_old | res | T^T] in a per-filter workspace in device memory

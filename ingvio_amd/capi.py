@@ -25,7 +25,7 @@ EXPORTS = [
     "ingvio_cov_set", "ingvio_cov_get", "ingvio_get_n", "ingvio_cov_get_marginal", "ingvio_cov_snapshot",
     "ingvio_cov_restore", "ingvio_propagate", "ingvio_propagate_fused", "ingvio_augment_clone", "ingvio_marginalize",
     "ingvio_append_independent", "ingvio_ekf_update", "ingvio_chi2_gamma", "ingvio_msckf_update", "ingvio_msckf_update_tri", "ingvio_qr_compress",
-    "ingvio_frame_stage", "ingvio_frame_stage_async", "ingvio_frame_set_imu_noise", "ingvio_frame_fetch_begin", "ingvio_frame_fetch_end", "ingvio_tracks_create", "ingvio_frame_stage_tracks", "ingvio_frame_run", "ingvio_set_frame_parts", "ingvio_set_gram_reduced", "ingvio_set_gram_decoupled", "ingvio_last_gram_form", "ingvio_frame_fetch", "ingvio_profile_enable", "ingvio_profile_select",
+    "ingvio_frame_stage", "ingvio_frame_stage_async", "ingvio_frame_set_imu_noise", "ingvio_frame_fetch_begin", "ingvio_frame_fetch_end", "ingvio_tracks_create", "ingvio_frame_stage_tracks", "ingvio_frame_run", "ingvio_set_frame_parts", "ingvio_set_gram_reduced", "ingvio_set_gram_decoupled", "ingvio_last_gram_form", "ingvio_set_apply_resident", "ingvio_last_apply_form", "ingvio_frame_fetch", "ingvio_profile_enable", "ingvio_profile_select",
     "ingvio_profile_reset",
     "ingvio_profile_get", "ingvio_set_msckf_method", "ingvio_set_qr_method", "ingvio_landmark_stage", "ingvio_landmark_run",
     "ingvio_landmark_fetch", "ingvio_frame_run_phase", "ingvio_info_set", "ingvio_debug_read", "ingvio_triangulate",
@@ -1223,6 +1223,16 @@ class Context:
     def last_gram_form(self):
         """the form the last MSCKF update's Gram stage took: 0 full, 1 reduced k_feat_gram2, 2 reduced k_feat_gram3 (ingvio_last_gram_form)"""
         return int(self.L.ingvio_last_gram_form(self.h))
+
+    def set_apply_resident(self, on):
+        """True (default): the fused frame step's write-back runs as k_info_apply_res (P[:, window] resident in LDS, one workgroup per filter) for
+        more than 64 filters of the window classes 6 and 11 at ldp <= 256; False: k_info_apply (ingvio_set_apply_resident).
+        Bit-identical results."""
+        self._chk(self.L.ingvio_set_apply_resident(self.h, 1 if on else 0))
+
+    def last_apply_form(self):
+        """the form the last MSCKF update's write-back took: 1 k_info_apply_res, 0 any other kernel (ingvio_last_apply_form)"""
+        return int(self.L.ingvio_last_apply_form(self.h))
 
     def set_delayed_form(self, mode):
         """0 (default): delayed initialisation in its LDS form only; 1: the large form for candidates the LDS form cannot take (windows

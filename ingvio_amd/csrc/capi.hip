@@ -218,6 +218,8 @@ struct ingvio_ctx {
     int delayed_form = 0;               // ingvio_set_delayed_form: 0 LDS form only, 1 the large form where the LDS form does not fit, 2 the large form everywhere
     int gram_decoupled = 1;             // ingvio_set_gram_decoupled: the reduced form runs as k_feat_gram3 in the window classes 6 and 11
     int gram_form_last = 0;             // ingvio_last_gram_form: 0 full, 1 reduced k_feat_gram2, 2 reduced k_feat_gram3
+    int apply_resident = 1;             // ingvio_set_apply_resident: the fused frame step's write-back runs as k_info_apply_res where launch_factored can take it
+    int apply_form_last = 0;            // ingvio_last_apply_form: 0 k_info_apply (or a few-filter / large-window kernel), 1 k_info_apply_res
     int gram_red_last = 0;              // the chunk partials in d_Rpart come from a reduced Gram launch (ingvio_debug_msckf_info refuses them)
     bool split_pending = false;         // slices of the last split step may still be running on their own streams
     hipEvent_t tok_last = nullptr;      // end of the throughput segment issued last (nullptr: none yet / chain broken)
@@ -971,6 +973,8 @@ int run_msckf_factored(ingvio_ctx* c, int b0, int nb, const MsckfOpts& op, int s
     }
     if (gnss_fuse) { if (int rc = gnss_in_frame_launch(c, b0, nb, L)) return rc; }
     if (phase == 2 && c->tok_wait) HIPCHK(c, hipStreamWaitEvent(c->run_st, c->tok_wait, 0));
+    c->apply_form_last = 0;
+    L.apply_res = frame_step && phase == 0 && c->apply_resident; L.apply_form = &c->apply_form_last;
     { ProfScope p(c, PF_APPLY); L.stage = 3; launch_factored(L, c->run_st); }
     if (phase == 2 && c->tok_rec) HIPCHK(c, hipEventRecord(c->tok_rec, c->run_st));
     return last_launch(c);
@@ -1169,6 +1173,7 @@ int ingvio_ctx_create(const ingvio_ctx_desc* desc, ingvio_ctx** out)
     if (const char* e = getenv("INGVIO_FRAME_PARTS")) c->parts_req = atoi(e);
     if (const char* e = getenv("INGVIO_GRAM_REDUCED")) c->gram_reduced = atoi(e) != 0;      // A/B timing of an unchanged program
     if (const char* e = getenv("INGVIO_GRAM_DECOUPLED")) c->gram_decoupled = atoi(e) != 0;
+    if (const char* e = getenv("INGVIO_APPLY_RESIDENT")) c->apply_resident = atoi(e) != 0;
     if (desc->c_max > 16) {
         // a higher priority than the compute stream's default: its short dependent launches take the slots the gate's workgroups free
         int lo = 0, hi = 0;
@@ -4742,6 +4747,21 @@ int ingvio_last_gram_form(ingvio_ctx* c)
 {
     if (!c) return INGVIO_E_ARG;
     return c->gram_form_last;
+}
+// the fused frame step's write-back with Pc resident in LDS (k_info_apply_res; full batches of the window classes 6 and 11,
+// ldp <= 256, no in-frame GNSS fold); off: k_info_apply
+int ingvio_set_apply_resident(ingvio_ctx* c, int on)
+{
+    if (!c) return INGVIO_E_ARG;
+    ENTER(c);
+    c->apply_resident = on ? 1 : 0;
+    return INGVIO_OK;
+}
+// the form the last MSCKF update's write-back took: 0 k_info_apply (or a few-filter / large-window kernel), 1 k_info_apply_res
+int ingvio_last_apply_form(ingvio_ctx* c)
+{
+    if (!c) return INGVIO_E_ARG;
+    return c->apply_form_last;
 }
 // which form of the delayed-initialisation front the three entry points take (kernels_delayed.hip)
 int ingvio_set_delayed_form(ingvio_ctx* c, int mode)

@@ -1191,6 +1191,247 @@ __global__ __launch_bounds__(256, 2) void k_info_apply(CovView cv, int b0, int n
 }
 
 // ---------------------------------------------------------------------------------------------
+// K8 + K10 + K11 (+ fused K12) with the filter's whole Pc RESIDENT in LDS: one workgroup of eight waves per filter, one per CU.
+// 256 rows x MP columns of Pc are 136 KB at MP = 68 - they fit the 160 KB LDS of a gfx950 CU - so every B fragment of the sweep is an
+// LDS read, nothing is staged per step, and after the ONE workgroup barrier behind the T phase no wave waits for another.
+//   fill   : wave w owns the tile rows { nt - 1 - w, w } (nt + 1 tiles, the balanced deal of k_info_apply).  Its Pc fragments
+//            Pc[src(16 ti + l15)][4 k4 + kq] (rows in the OUTPUT index space, clamped) are loaded as in k_info_apply and written to
+//            sPc[row][k], row stride MP + 2 doubles: (MP + 2) / 2 is odd, so the 32 lanes of a half-wave (l15, kq in {0, 1} or {2, 3})
+//            fall on 32 different 8-byte bank pairs (stride MP itself, = 4 mod 32, puts rows l15 and l15 + 8 on the same banks).
+//   T      : formed TRANSPOSED (operands swapped as in k_apply_T_flat: M fragments as A, Pc fragments as B - same products, same k
+//            order): register r of lane (kq, l15) holds T[16 ti + l15][16 jt + 4 r + kq], which IS the sweep's A fragment k4 = 4 jt + r.
+//            No layout change through LDS.  M (37 KB) does not fit beside sPc: its fragments come from L2, once per jt for both rows,
+//            the next jt's requested before the current one's MFMAs.
+//   sweep  : per owned row and tj <= ti: K4 LDS reads (shared by both rows while tj <= the short row), K4 MFMAs, store_tile as in
+//            k_info_apply; the prior's tiles run APPLY_RES_PF tiles ahead in a register ring.  No barrier, no staging.
+// The flip of the fused marginalisation (cur ^= 1, n -= msize) is done by thread 0 behind the barrier: every wave has formed its pointers
+// by then, and no other workgroup works on the filter - no arrival counter.
+// Same MFMAs over the same operand pairs in the same k order as k_info_apply<NC, 1, 0>, pv - acc unchanged: bit-identical posterior,
+// dx and status (tests/test_gpu_apply_resident.py).  Needs nt <= 16 (ldp <= 256) and MP <= 68: launch_factored selects it.
+// ---------------------------------------------------------------------------------------------
+#ifndef APPLY_RES_PF
+#define APPLY_RES_PF 2      // steps (a tile per row) the prior runs ahead of the MFMAs that consume it; measured 1 / 2 / 3: DESIGN 4.4
+#endif
+constexpr int APPLY_RES_ROWS = 256, APPLY_RES_NW = 8;
+#ifndef APPLY_RES_ABL
+#define APPLY_RES_ABL 0     // timing probes, results invalid: 1 no stores, 2 the prior not read, 4 the sweep's MFMAs as one VALU FMA each
+#endif
+#if APPLY_RES_ABL & 4
+#define APPLY_RES_MFMA(a, b, c) double4_f{ fma((a), (b), (c)[0]), (c)[1], (c)[2], (c)[3] }
+#else
+#define APPLY_RES_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
+#endif
+template <int NC>
+constexpr size_t apply_res_lds_bytes() { return sizeof(double) * ((size_t)APPLY_RES_ROWS * (((NC + 3) & ~3) + 2) + APPLY_RES_NW * 16 * 17); }
+
+template <int NC>
+__global__ __launch_bounds__(64 * APPLY_RES_NW) void k_info_apply_res(CovView cv, int b0, const double* __restrict__ Mall, int mstride,
+                                                                      const double* __restrict__ Pcall, int ystride, const int* __restrict__ m_all,
+                                                                      double* __restrict__ dx_all, int* __restrict__ status,
+                                                                      const int* __restrict__ marg_idx, int msize, const int* __restrict__ pc_base)
+{
+    constexpr int MP = (NC + 3) & ~3, K4 = MP / 4, JT = (MP + 15) / 16, LS = MP + 2, PF = APPLY_RES_PF;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    double* sPc = reinterpret_cast<double*>(smem_raw);                                         // [APPLY_RES_ROWS][LS]
+    double (*sV)[16][17] = reinterpret_cast<double (*)[16][17]>(sPc + (size_t)APPLY_RES_ROWS * LS);      // the stores' transposition buffers, one per wave
+    const int bl = blockIdx.x, b = b0 + bl;
+    const bool upd = m_all[bl] != 0;
+    const int midx = marg_idx[bl];                            // fused StateManager::marginalize of [midx, midx + msize)
+    const bool fused = midx >= 0;
+    if (!upd && !fused) return;
+    const int n = cv.n[b], ld = cv.ldp;
+    const int no = fused ? n - msize : n, nt = (no + 15) >> 4;      // tiles in the index space of the OUTPUT (see k_info_apply)
+    if (nt > APPLY_RES_ROWS / 16) return;                     // (never: the launch site requires ldp <= 256)
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int rowL = nt - 1 - wave, rowS = wave;              // this wave's long and short tile row
+    const bool onL = 2 * wave < nt, onS = wave < rowL;        // (odd nt: the middle row is its wave's only one)
+    const double* P = cov_ptr(cv, b);
+    double* dst = fused ? cov_alt_ptr(cv, b) : cov_ptr(cv, b);
+    const int pcb = upd ? pc_base[bl] : -1;
+    const double* Pc = pcb >= 0 ? P + (size_t)pcb * ld : Pcall + (size_t)bl * ystride;
+    const double* M = Mall + (size_t)bl * mstride;
+    const double* tvec = M + (size_t)MP * MP;
+    const int l15 = lane & 15, kq = lane >> 4;
+    auto src_of = [&](int o) __attribute__((always_inline)) { return (fused && o >= midx) ? o + msize : o; };      // output index -> index in the prior
+
+    bool neg_diag = false;                                     // StateManager.cpp:413-421, reported once at the end
+    // store_tile / load_p: k_info_apply's, with a third path for the off-diagonal tiles of a partial last tile row (same values stored)
+    auto store_tile = [&](int ti, int tj, const double4_f& acc, const double (&pv)[4]) __attribute__((always_inline)) {
+        const int col = tj * 16 + l15, row0 = ti * 16 + kq, row2 = ti * 16 + l15, col20 = tj * 16 + kq;
+        double v[4], t[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { v[r] = pv[r] - acc[r]; sV[wave][kq + 4 * r][l15] = v[r]; }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) t[r] = sV[wave][l15][kq + 4 * r];
+        __builtin_amdgcn_wave_barrier();
+        double* d1 = dst + col + (size_t)row0 * ld;
+        double* d2 = dst + row2 + (size_t)col20 * ld;
+#if APPLY_RES_ABL & 1      // ablation probe: no stores (one that never happens keeps the values alive)
+        if (v[0] + v[1] + v[2] + v[3] + t[0] + t[1] + t[2] + t[3] == 1.2345e-300) dst[0] = v[0];
+        else if (ti < 0)
+#endif
+        if (ti > tj && ti * 16 + 15 < no) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) APPLY_STORE(d1 + (size_t)(4 * r) * ld, v[r]);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) APPLY_STORE(d2 + (size_t)(4 * r) * ld, t[r]);
+        } else if (ti > tj) {
+            // a partial last tile row (every tile of the wave that owns it): off the diagonal only the ROW can be out of range, and the
+            // values are all formed above - the predicates guard nothing but the stores themselves
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (row0 + 4 * r < no) APPLY_STORE(d1 + (size_t)(4 * r) * ld, v[r]);
+            if (row2 < no) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) APPLY_STORE(d2 + (size_t)(4 * r) * ld, t[r]);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + 4 * r;
+                if (row < no && col < no && row >= col) APPLY_STORE(d1 + (size_t)(4 * r) * ld, v[r]);
+                neg_diag |= row == col && row < no && v[r] < 0.0;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int col2 = col20 + 4 * r;
+                if (row2 < no && col2 < no && row2 > col2) APPLY_STORE(d2 + (size_t)(4 * r) * ld, t[r]);
+            }
+        }
+    };
+    auto load_p = [&](int ti, int tj, double (&pv)[4]) __attribute__((always_inline)) {
+        const int col = tj * 16 + l15, row0 = ti * 16 + kq;
+#if APPLY_RES_ABL & 2      // ablation probe: the prior is not read
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pv[r] = 1.0 + r;
+        if (ti < 0)
+#endif
+        if (ti > tj && ti * 16 + 15 < no) {                   // mirrored (coalesced) address; rows and columns in the prior's index space
+            const double* p0 = P + src_of(col);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) pv[r] = APPLY_LOADP(p0 + (size_t)src_of(row0 + 4 * r) * ld);
+        } else if (ti > tj) {                                 // partial last tile row: the row clamped, the loads unconditional (rows past the end are never stored)
+            const double* p0 = P + src_of(col);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) pv[r] = APPLY_LOADP(p0 + (size_t)src_of(min(row0 + 4 * r, no - 1)) * ld);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + 4 * r;
+                pv[r] = (row < no && col < no && row >= col) ? APPLY_LOADP(&P[src_of(col) + (size_t)src_of(row) * ld]) : 0.0;
+            }
+        }
+    };
+    double pq[PF + 1][2][4];                                   // [.][0]: the long row's tile, [.][1]: the short row's
+    auto load_step = [&](int tj, double (&d)[2][4]) __attribute__((always_inline)) {
+        if (onL && tj <= rowL) load_p(rowL, tj, d[0]);
+        if (onS && tj <= rowS) load_p(rowS, tj, d[1]);
+    };
+
+    // ---- fill: this wave's Pc fragments, kept for the T phase and written to sPc for everybody's sweep -------------------------
+    double pcf[2][K4], tf[2][K4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int k4 = 0; k4 < K4; ++k4) { pcf[h][k4] = 0.0; tf[h][k4] = 0.0; }
+    if (upd) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            if (h == 0 ? onL : onS) {
+                const int ti = h == 0 ? rowL : rowS;
+                const int ra = src_of(min(ti * 16 + l15, no - 1));           // clamped: rows past the end are computed but never stored
+#pragma unroll
+                for (int k4 = 0; k4 < K4; ++k4) pcf[h][k4] = (Pc + (size_t)(4 * k4) * ld)[ra + kq * ld];      // uniform base + one lane offset
+            }
+    }
+    if (upd && fused && wave == 0) {      // the correction of the states about to be marginalised: no tile covers them
+        for (int q = lane; q < msize; q += WAVE) {
+            double d = 0.0;
+            for (int k = 0; k < MP; ++k) d += Pc[midx + q + (size_t)k * ld] * tvec[k];
+            dx_all[(size_t)b * ld + midx + q] = d;
+        }
+    }
+    if (upd && onL) {
+        double mf[2][K4];
+        auto load_m = [&](int jt, double (&m)[K4]) __attribute__((always_inline)) {
+            const int jc = min(jt * 16 + l15, MP - 1);
+#pragma unroll
+            for (int k4 = 0; k4 < K4; ++k4) m[k4] = (M + (size_t)(4 * k4) * MP)[kq * MP + jc];      // A[i][k] = M[k][16 jt + i]
+        };
+        load_m(0, mf[0]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            if (h == 0 || onS) {
+                const int ti = h == 0 ? rowL : rowS;
+                const int ra = src_of(min(ti * 16 + l15, no - 1));
+#pragma unroll
+                for (int k4 = 0; k4 < K4; ++k4) sPc[(size_t)(ti * 16 + l15) * LS + 4 * k4 + kq] = pcf[h][k4];
+                double d = 0.0;
+#pragma unroll
+                for (int k4 = 0; k4 < K4; ++k4) d += pcf[h][k4] * tvec[4 * k4 + kq];
+                d += __shfl_xor(d, 16, WAVE);
+                d += __shfl_xor(d, 32, WAVE);
+                if (kq == 0 && ti * 16 + l15 < no) dx_all[(size_t)b * ld + ra] = d;      // dx stays in the prior's index space
+            }
+        // ---- T rows of the wave's tile rows, straight into the sweep's A-operand layout ----------------------------------------
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt) {
+            if (jt + 1 < JT) load_m(jt + 1, mf[(jt + 1) & 1]);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (h == 0 || onS) {
+                    double4_f acc = { 0.0, 0.0, 0.0, 0.0 };
+#pragma unroll
+                    for (int k4 = 0; k4 < K4; ++k4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(mf[jt & 1][k4], pcf[h][k4], acc, 0, 0, 0);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) if (4 * jt + r < K4) tf[h][4 * jt + r] = acc[r];      // T[16 ti + l15][16 jt + 4 r + kq]
+                }
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < PF; ++d) load_step(d, pq[d]);
+    __syncthreads();                                          // all of sPc is written; every wave holds its pointers
+    if (fused && tid == 0) { cv.cur[b] ^= 1; cv.n[b] = n - msize; }
+
+    // ---- sweep: free-running, B fragments from sPc ------------------------------------------------------------------------------
+    if (onL) {
+#pragma unroll 1
+        for (int tj = 0; tj <= rowL; ++tj) {
+            load_step(tj + PF, pq[PF]);
+            const bool doS = onS && tj <= rowS;
+            double bfrag[K4];
+            if (upd) {
+#pragma unroll
+                for (int k4 = 0; k4 < K4; ++k4) bfrag[k4] = sPc[(size_t)(16 * tj + l15) * LS + 4 * k4 + kq];      // B[k][j] = Pc[16 tj + j][k]
+            }
+            if (doS) {
+                double4_f acc = { 0.0, 0.0, 0.0, 0.0 };
+                if (upd) {
+#pragma unroll
+                    for (int k4 = 0; k4 < K4; ++k4) acc = APPLY_RES_MFMA(tf[1][k4], bfrag[k4], acc);
+                }
+                store_tile(rowS, tj, acc, pq[0][1]);
+            }
+            {
+                double4_f acc = { 0.0, 0.0, 0.0, 0.0 };
+                if (upd) {
+#pragma unroll
+                    for (int k4 = 0; k4 < K4; ++k4) acc = APPLY_RES_MFMA(tf[0][k4], bfrag[k4], acc);
+                }
+                store_tile(rowL, tj, acc, pq[0][0]);
+            }
+#pragma unroll
+            for (int d = 0; d < PF; ++d)
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pq[d][h][r] = pq[d + 1][h][r];
+        }
+    }
+    if (upd && __any(neg_diag) && lane == 0) atomicOr(&status[b], 2);
+}
+
+// ---------------------------------------------------------------------------------------------
 // K10 (+ fused K12) for FEW filters (round 5, VERDICT r04 #5: the reference is ONE real-time filter, IngvioNode.cpp:36).  k_info_apply
 // gives a filter two workgroups whose waves walk 17 tiles each, one dependent step after the other: 42 us for one filter at N = 249 on
 // an otherwise idle chip.  Here every 16 x 16 tile is one wave's whole job - T = Pc M in one launch (80 waves per filter), P - T Pc^T
@@ -1564,6 +1805,7 @@ int launch_factored(const FactoredLaunch& L, hipStream_t st)
     }
     if (L.stage == 3) {
         const int nt = (L.n_cap + 15) / 16, wgpf = ((nt + 1) / 2 + 3) / 4, nb8 = (L.nb + 7) / 8 * 8;
+        if (L.apply_form) *L.apply_form = 0;
         // two tile columns per step (half the steps): measured 0.194 against 0.151 ms (256 VGPRs + 76 B scratch) - selectable only
 #ifdef INGVIO_ALT_KERNELS
         static const bool tw1 = [] { const char* e = getenv("INGVIO_APPLY_TW"); return !(e && e[0] == '2'); }();
@@ -1591,6 +1833,25 @@ int launch_factored(const FactoredLaunch& L, hipStream_t st)
         else { hipLaunchKernelGGL((k_info_apply<NC, 1>), dim3(nb8 * wgpf), dim3(256), 0, st, L.cv, L.b0, L.nb, wgpf, L.T, L.mstride, L.Pc, \
                            L.ystride, L.m_out, L.dx, L.status, L.marg_idx, L.marg_size, L.pc_base, (const double*)nullptr, (size_t)0, (const int*)nullptr, flip); if (flip) *L.did_flip = 1; }
         int* const flip = (L.marg_idx && L.did_flip) ? L.flip_cnt : nullptr;
+        // the fused frame step of a full batch, window classes 6 and 11: Pc resident in LDS, one workgroup per filter (k_info_apply_res);
+        // it flips the halves itself and needs no arrival counter
+        if (L.apply_res && flip && !L.gY && L.nb > APPLY_FLAT_NB && L.cv.ldp <= APPLY_RES_ROWS && L.n_cap <= APPLY_RES_ROWS && ncm <= 66) {
+#define APPLY_RES_DISPATCH(NC)                                                                                        \
+            {                                                                                                         \
+                static bool attr_set = false;                                                                         \
+                if (!attr_set) {                                                                                      \
+                    hipFuncSetAttribute((const void*)k_info_apply_res<NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)apply_res_lds_bytes<NC>()); \
+                    attr_set = true;                                                                                  \
+                }                                                                                                     \
+                hipLaunchKernelGGL((k_info_apply_res<NC>), dim3(L.nb), dim3(64 * APPLY_RES_NW), apply_res_lds_bytes<NC>(), st, L.cv, L.b0, L.T,  \
+                                   L.mstride, L.Pc, L.ystride, L.m_out, L.dx, L.status, L.marg_idx, L.marg_size, L.pc_base);  \
+            }
+            if (ncm <= 36) APPLY_RES_DISPATCH(36) else APPLY_RES_DISPATCH(66)
+#undef APPLY_RES_DISPATCH
+            *L.did_flip = 1;
+            if (L.apply_form) *L.apply_form = 1;
+            return 0;
+        }
         // class 72 = a 12-clone window: an 11-pose window in sliding-window mode holds 12 clones at update time (SwMargUpdate.cpp:412-419)
         if (ncm <= 36) { APPLY_DISPATCH(36) } else if (ncm <= 66) { APPLY_DISPATCH(66) } else if (ncm <= 72) { APPLY_DISPATCH(72) } else { APPLY_DISPATCH(96) }
 #undef APPLY_DISPATCH

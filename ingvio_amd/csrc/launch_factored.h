@@ -48,6 +48,10 @@ struct FactoredLaunch {
     int* gram_was_red;    // host flag, set to 1 / 0 by the k_feat_gram2 launch: the partials it wrote are reduced / full (or nullptr)
     int gram_dec;         // with gram_red, window classes 6 and 11: the reduced form runs as k_feat_gram3 (wave pairs decoupled, gram3_kernel.h)
     int* gram_form;       // host value, set by the Gram launch: 0 full, 1 reduced k_feat_gram2, 2 reduced k_feat_gram3 (or nullptr)
+    int apply_res;        // stage 3: the caller is the fused frame step and allows k_info_apply_res (Pc resident in LDS, one workgroup per
+                          // filter); launch_factored takes it for more than APPLY_FLAT_NB filters of the window classes 6 and 11 with the
+                          // flip done in the kernel, no in-frame GNSS fold and ldp <= 256
+    int* apply_form;      // host value, set by the stage-3 launch: 1 k_info_apply_res, 0 anything else (or nullptr)
     double* big_sg;       // large-window path: [nb][G][36][36][34] sparse sums (kernels_bigwin.hip)
     double* big_wk;       // large-window path: per-filter solve workspace (bigwin_wk_doubles)
     int ncol_cap;         // 6 * (context c_max): size class of the large-window solve
