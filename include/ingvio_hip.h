@@ -872,6 +872,60 @@ int ingvio_landmark_init_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_l
  * m = rows per observation x window size. */
 int ingvio_debug_landmark_init_rows(ingvio_ctx* ctx, int b, const ingvio_lm_init_cand* cand, const ingvio_msckf_opts* opts,
                                     int n_drop, const int* drop_cols, double* H_old, double* H_new, double* res, int* m_out);
+/* ---- GNSS clock states initialised in the device-resident closed loop ----------------------------------------------
+ * GnssUpdate::addNewTrackedSys (GnssUpdate.cpp:295-470, oracle/stream_filter.py::add_new_tracked_sys) for filters [b0, b0 + nb): the
+ * frequency shift and the clock bias of every constellation the SPP fix reports and the table lacks are initialised by
+ * addVariableDelayed, on the device, from the table.  The sibling of ingvio_landmark_init_nominal on the same front kernel.
+ *   Which scalars to try is decided on the host, from its mirror of the table and the SPP fix: candidate 0 (FS) when |vel_spp[3]| > 1e-3
+ *     and no FS is registered, candidate 1 + s (clock bias of GPS, GLO, GAL, BDS) when |pos_spp[3 + s]| > 1e-3 and clock s is not
+ *     registered.  A filter with n_sat = 0 or without a registered YOF has no candidates (the reference returns silently there, :300;
+ *     it is not an error).  Nothing else about the candidates is decided on the host.
+ *   Residuals, once per call: the satellite front at the table's receiver state, with the clock biases to add taken from pos_spp[3 + s],
+ *     FS from vel_spp[3] when it is to be added (0 when it is neither in the state nor to be added, :362-370), everything else from the
+ *     table.  R_w2ecef = R_enu2ecef Rz(YOF) is formed once, from YOF at the call's start (:332), and kept for all rounds.
+ *   One round per candidate, in the order above, each against the state the previous round left:
+ *     - rows (getResJacobianOfSys, :472-521), one per usable satellite (FS) or per usable satellite of the constellation (a clock), in
+ *       ascending satellite order: Hx [m x 10] over [SE23 (9), YOF (1)] with u^T R_w2ecef [x]x in columns 0-2 and -u^T R_w2ecef in columns
+ *       6-8 (FS, x = v_w) or 3-5 (a clock, x = p_w); x is read from the table in this round (:397 / :458).  Column 9 is zero:
+ *       is_adjust_yof = 0 only, as in every golden stream.  H_new is all ones, s = 1; res = -res_vel (FS) or -res_pos (a clock).
+ *     - noise = amp * sqrt(mean(ura * std / sin^2 el)) over the rows, computed on the device: std = psr_std, amp = psr_noise_amp for a
+ *       clock; std = dopp_std * c / freq, amp = dopp_noise_amp for FS; |sin el| floored at 1e-6.  It is the R of the Givens rounds, of
+ *       the gate and of the trailing update, and is returned per candidate.
+ *     - the gate: chi2 > chi2_mult * chi2_table[m] refuses (do_chi2 != 0), with the device's m.  m <= 1 is skipped: added = 0, chi2 = 0,
+ *       noise = 0, state untouched.
+ *     - on acceptance the scalar enters the table ON THE DEVICE: kind INGVIO_NOM_SCALAR, idx = the live n, value vel_spp[3] /
+ *       pos_spp[3 + s], in the slot the host reserved - the k-th candidate of a filter gets the k-th lowest free slot at the call's start,
+ *       a refused candidate leaves its slot free - and is registered as that GNSS scalar (what ingvio_nominal_set_gnss would do): the IMU
+ *       steps of the next frame advance it and later epochs read it.  Then the trailing update on the m - 1 lower rows and
+ *       StateManager::boxPlus of its dx on the table, the new scalar included.
+ * The host synchronises once, at the end; then the live sizes, its mirror of the table and the GNSS slots follow the verdicts.
+ *   added / new_idx / slot / chi2 / noise [nb][INGVIO_GNSS_INIT_CAND], dx [nb][INGVIO_GNSS_INIT_CAND][ldp] (may be NULL), status [nb] (may
+ *   be NULL) and the soft INGVIO_NEG_DIAG / INGVIO_E_NOT_PD return with the stop of that filter's sequence: as
+ *   ingvio_add_variable_delayed_batch.  A refused or skipped candidate leaves P, n and the table untouched.
+ * Refused before anything changes, from the host mirror only: INGVIO_E_ARG (no table, range, NULL where data is needed, n_sat outside
+ * 0..64, a missing array, chi2_len <= n_sat, a split frame step pending, a frame / GNSS epoch / landmark stage from the table that has
+ * not run); INGVIO_E_NOT_IN_STATE (extended pose or YOF beyond the live state, for a filter with candidates); INGVIO_E_CAPACITY (fewer
+ * free table slots than candidates, n + candidates > n_max, n_sat > ingvio_mld).
+ * The call runs where ingvio_landmark_init_nominal runs: between frames, after the epoch's ingvio_gnss_run or after an ingvio_frame_run
+ * that carried the epoch in-frame.  It is not part of ingvio_frame_run.  The clock indices the next frame's propagation takes
+ * (ingvio_frame_step_nominal::gnss_idx) are the host's to extend with new_idx.  checkYofStatus' addGNSSVariable and batchAlign stay
+ * host policy. */
+#define INGVIO_GNSS_INIT_CAND 5          /* candidate j: 0 = FS, 1..4 = clock bias GPS, GLO, GAL, BDS: the order of
+                                            stream_filter.py:908-911 and host/GnssUpdate.cpp:206-207 */
+typedef struct {
+    ingvio_gnss_epoch_nominal epoch;     /* n_sat = 0: nothing for this filter */
+    double pos_spp[7], vel_spp[4];       /* SppMeas::posSpp / velSpp */
+} ingvio_gnss_init_block;
+int ingvio_gnss_init_nominal(ingvio_ctx* ctx, int b0, int nb, const ingvio_gnss_init_block* blocks,
+                             const double* chi2_table, int chi2_len, double chi2_mult, int do_chi2,
+                             int* added, int* new_idx, int* slot, double* chi2, double* noise,   /* [nb][5] */
+                             double* dx /* [nb][5][ldp] or NULL */, int* status /* [nb] or NULL */);
+/* parity hook (tests): the row formation of ingvio_gnss_init_nominal alone for filter b, its block and candidate g (any of 0..4, tried
+ * by the call or not; the receiver is the call's: every scalar the call would add is overridden); nothing changes, so neither a free
+ * table slot nor room in the state is asked for.  H_old [m x 10] column-major with leading dimension *m_out, res [m], *noise; the caller
+ * provides room for 64 rows.  *m_out = 0: no usable satellite (or no YOF / n_sat = 0). */
+int ingvio_debug_gnss_init_rows(ingvio_ctx* ctx, int b, const ingvio_gnss_init_block* block, int g,
+                                double* H_old, double* res, double* noise, int* m_out);
 int ingvio_frame_run(ingvio_ctx* ctx, int restore_prior);
 /* Throughput batches (round 6, an experiment kept selectable): ingvio_frame_run deals the batch to `parts` slices of filters, each
  * on its own HIP stream; the slices' throughput-bound segments (gate + Gram, apply) are chained by events so that only ONE runs at a

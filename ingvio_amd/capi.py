@@ -40,6 +40,7 @@ EXPORTS = [
     "ingvio_update_stage_tracks_nominal", "ingvio_frame_fetch_tri", "ingvio_set_delayed_form",
     "ingvio_odom_begin", "ingvio_odom_end", "ingvio_cov_get_marginal_batch",
     "ingvio_frame_stage_tracks_nominal_tri", "ingvio_set_first_tri_placement",
+    "ingvio_gnss_init_nominal", "ingvio_debug_gnss_init_rows",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -153,6 +154,28 @@ class GnssEpochNominal(C.Structure):
     _fields_ = [("n_sat", C.c_int), ("eph", C.POINTER(C.c_double)), ("obs", C.POINTER(C.c_double)), ("ion", C.POINTER(C.c_double)),
                 ("doy", C.c_double), ("R_enu2ecef", C.c_double * 9), ("anchor_ecef", C.c_double * 3), ("psr_noise_amp", C.c_double),
                 ("dopp_noise_amp", C.c_double)]
+
+
+GNSS_INIT_CAND = 5       # ingvio_gnss_init_nominal: candidate 0 = FS, 1..4 = clock bias GPS, GLO, GAL, BDS
+
+
+class GnssInitBlock(C.Structure):
+    _fields_ = [("epoch", GnssEpochNominal), ("pos_spp", C.c_double * 7), ("vel_spp", C.c_double * 4)]
+
+
+def make_gnss_init_blocks(blocks):
+    """blocks: per filter None (nothing for this filter) or a dict(epoch=dict as for gnss_front_stage_nominal or None, pos_spp [7],
+    vel_spp [4]).  Returns (ingvio_gnss_init_block array, objects that own the memory the array points to)."""
+    arr = (GnssInitBlock * max(len(blocks), 1))(); keep = []
+    for i, bk in enumerate(blocks):
+        a = arr[i]
+        a.epoch.n_sat = 0
+        if bk is None:
+            continue
+        if bk.get("epoch") is not None:
+            keep.append(_epoch_host_fields(a.epoch, bk["epoch"]))
+        a.pos_spp = (C.c_double * 7)(*f64(bk["pos_spp"]).reshape(7)); a.vel_spp = (C.c_double * 4)(*f64(bk["vel_spp"]).reshape(4))
+    return arr, keep
 
 
 class LandmarkFrame(C.Structure):
@@ -885,6 +908,39 @@ class Context:
                                                          _d(H_old), _d(H_new), _d(res), C.byref(m)))
         m, nc = m.value, 6 * int(n_clones)
         return (H_old[:m * nc].reshape(nc, m).T.copy(), H_new[:3 * m].reshape(3, m).T.copy(), res[:m].copy())
+
+    def gnss_init_nominal_prepare(self, b0, blocks, chi2_table, chi2_mult=0.95, do_chi2=True, want_dx=True):
+        """builds the C arguments of ingvio_gnss_init_nominal once (blocks as make_gnss_init_blocks takes them) and returns a callable
+        that issues the call and returns dict(added, new_idx, slot [nb, 5] int, chi2, noise [nb, 5], dx [nb, 5, ldp] or None, status [nb]);
+        self.delayed_status as add_variable_delayed_batch leaves it."""
+        nb = len(blocks)
+        arr, keep = make_gnss_init_blocks(blocks)
+        tab = f64(chi2_table)
+
+        def call(_keep=(keep, arr, tab)):
+            K = GNSS_INIT_CAND
+            added = np.zeros((nb, K), dtype=np.int32); idx = np.full((nb, K), -1, dtype=np.int32); slot = np.full((nb, K), -1, dtype=np.int32)
+            chi2 = np.zeros((nb, K)); noise = np.zeros((nb, K)); dx = np.zeros((nb, K, self.ldp)) if want_dx else None
+            st = np.zeros(nb, dtype=np.int32)
+            rc = self.L.ingvio_gnss_init_nominal(self.h, int(b0), nb, arr, _d(tab), len(tab), C.c_double(chi2_mult), 1 if do_chi2 else 0,
+                                                 _i(added), _i(idx), _i(slot), _d(chi2), _d(noise), _d(dx) if want_dx else None, _i(st))
+            if rc != E_NOT_PD:
+                self._chk(rc)
+            self.delayed_status = st
+            return dict(added=added, new_idx=idx, slot=slot, chi2=chi2, noise=noise, dx=dx, status=st)
+        return call
+
+    def gnss_init_nominal(self, b0, blocks, chi2_table, chi2_mult=0.95, do_chi2=True, want_dx=True):
+        """ingvio_gnss_init_nominal for filters b0, b0+1, ...: GnssUpdate::addNewTrackedSys from the device nominal table"""
+        return self.gnss_init_nominal_prepare(b0, blocks, chi2_table, chi2_mult, do_chi2, want_dx)()
+
+    def debug_gnss_init_rows(self, b, block, g):
+        """the rows ingvio_gnss_init_nominal forms for filter b, its block and candidate g: (H_old [m, 10], res [m], noise)"""
+        arr, keep = make_gnss_init_blocks([block])
+        H = np.zeros(64 * 10); res = np.zeros(64); noise = C.c_double(0.0); m = C.c_int(0)
+        self._chk(self.L.ingvio_debug_gnss_init_rows(self.h, int(b), arr, int(g), _d(H), _d(res), C.byref(noise), C.byref(m)))
+        m = m.value
+        return H[:10 * m].reshape(10, m).T.copy(), res[:m].copy(), noise.value
 
     def replace_var_linear(self, b, tidx, tsize, vidx, vsize, H):
         H = np.asfortranarray(np.atleast_2d(H), dtype=np.float64)

@@ -3083,6 +3083,258 @@ int ingvio_debug_landmark_init_rows(ingvio_ctx* c, int b, const ingvio_lm_init_c
     return INGVIO_OK;
 }
 
+// ---- GnssUpdate::addNewTrackedSys (GnssUpdate.cpp:295-470) from the nominal table: the twin of ingvio_landmark_init_nominal ----
+// k_gnss_front<true> once at the receiver the SPP fix overrides, R_w2ecef once, then one round per candidate scalar (FS, clock GPS, GLO,
+// GAL, BDS): k_delayed_front<DL_GNSS> (rows, noise, rotations, gate, verdict, append, table record), the trailing update, boxPlus on the
+// table.  Validation on the host mirror only, no decision between the rounds, one synchronisation.
+struct GnssInitPlan {
+    int smax = 1, n_cap = 0;
+    bool any = false;
+    std::vector<int> cand, slots;       // [round][filter]: tried / reserved table slot
+    bool round[INGVIO_GNSS_INIT_CAND] = { false, false, false, false, false };
+};
+
+// rows_only: the parity hook - it appends nothing, so neither a free table slot nor room in the state is asked for, and the candidate
+// it names need not be one the call would try
+static int gnss_init_validate(ingvio_ctx* c, const char* who, int b0, int nb, const ingvio_gnss_init_block* blocks, const double* chi2_table, int chi2_len,
+                              GnssInitPlan& pl, bool rows_only = false)
+{
+    auto& m = c->nom;
+    if (phase_busy(c)) return INGVIO_E_ARG;
+    if (check_range(c, b0, nb) || !blocks) return INGVIO_E_ARG;
+    if (!m.vmax) { c->err = std::string(who) + " without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = std::string(who) + ": a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, who)) return INGVIO_E_ARG;
+    if ((c->gn.frame_nom && c->gn.staged) || (c->lm.nominal && c->lm.staged)) {
+        c->err = std::string(who) + ": an in-frame GNSS epoch or landmark update staged from the device nominal state has not run yet"; return INGVIO_E_ARG;
+    }
+    const int NC = INGVIO_GNSS_INIT_CAND;
+    pl.cand.assign((size_t)NC * nb, 0);
+    pl.slots.assign((size_t)NC * nb, -1);
+    int cap_err = 0;
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_gnss_epoch_nominal& e = blocks[i].epoch;
+        if (e.n_sat < 0 || e.n_sat > INGVIO_GNSS_MAX_SAT || (e.n_sat && (!e.eph || !e.obs))) { c->err = std::string(who) + ": n_sat outside 0..64 or a missing array"; return INGVIO_E_ARG; }
+        if (!rows_only && (!chi2_table || chi2_len <= e.n_sat)) { c->err = std::string(who) + ": chi2_table is shorter than n_sat + 1"; return INGVIO_E_ARG; }
+        if (e.n_sat == 0) continue;
+        if (e.n_sat > pl.smax) pl.smax = e.n_sat;
+        const int b = b0 + i;
+        const int* I = &m.h_ih[(size_t)b * m.ir];
+        const int* var = I + NOM_IH;
+        if (I[NOM_GNSS + NOM_G_YOF] < 0) continue;                    // GnssUpdate.cpp:300-301 returns silently: no candidates, not an error
+        int nc = 0;
+        if (rows_only) nc = 1;
+        else {
+            if (fabs(blocks[i].vel_spp[3]) > 1e-3 && I[NOM_GNSS + NOM_G_FS] < 0) { pl.cand[(size_t)0 * nb + i] = 1; ++nc; }
+            for (int s4 = 0; s4 < 4; ++s4)
+                if (fabs(blocks[i].pos_spp[3 + s4]) > 1e-3 && I[NOM_GNSS + s4] < 0) { pl.cand[(size_t)(1 + s4) * nb + i] = 1; ++nc; }
+        }
+        if (!nc) continue;
+        const int ix_pose = nom_idx_of(c, b, I[NOM_V_POSE]), ix_yof = nom_idx_of(c, b, I[NOM_GNSS + NOM_G_YOF]);
+        if (ix_pose < 0 || ix_pose + 9 > c->h_n[b] || ix_yof < 0 || ix_yof + 1 > c->h_n[b]) {
+            c->err = std::string(who) + ": the extended pose or YOF lies beyond the live state"; return INGVIO_E_NOT_IN_STATE;
+        }
+        pl.any = true;
+        if (rows_only) continue;
+        // capacity (reported after every argument of the call has been looked at)
+        int got = 0, v = 0;
+        for (int g = 0; g < NC; ++g) {
+            if (!pl.cand[(size_t)g * nb + i]) continue;
+            while (v < m.vmax && var[4 * v] != NOM_KIND_NONE) ++v;
+            if (v < m.vmax) { pl.slots[(size_t)g * nb + i] = v++; ++got; }
+            pl.round[g] = true;
+        }
+        if (got < nc || c->h_n[b] + nc > c->d.n_max || e.n_sat > c->mld) { cap_err = 1; continue; }
+        if (c->h_n[b] + nc > pl.n_cap) pl.n_cap = c->h_n[b] + nc;
+    }
+    if (!cap_err && pl.any && !rows_only && !ekf_core_fits(63, 10)) cap_err = 1;
+    return cap_err ? INGVIO_E_CAPACITY : INGVIO_OK;
+}
+
+// the call's epochs, ephemerides and receiver records (the SPP fix in the scalars the table lacks) into the host slab h
+static void gnss_init_fill(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_init_block* blocks, const GnssInitPlan& pl, double* he, double* ho, double* hr,
+                           int only_g = -1)
+{
+    const size_t S = pl.smax;
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_gnss_epoch_nominal& e = blocks[i].epoch;
+        if (e.n_sat) {
+            memcpy(he + (size_t)i * S * GE_N, e.eph, 8 * (size_t)e.n_sat * GE_N);
+            memcpy(ho + (size_t)i * S * GO_N, e.obs, 8 * (size_t)e.n_sat * GO_N);
+        }
+        double* r = hr + (size_t)i * GR_N;
+        r[GR_NSAT] = e.n_sat; r[GR_DOY] = e.doy; r[GR_HAVE_ION] = e.ion ? 1.0 : 0.0;
+        if (e.ion) memcpy(r + GR_ION, e.ion, 64);
+        memcpy(r + GR_RENU, e.R_enu2ecef, 72); memcpy(r + GR_ANCHOR, e.anchor_ecef, 24);
+        r[GR_PSR_AMP] = e.psr_noise_amp; r[GR_DOPP_AMP] = e.dopp_noise_amp;
+        // the scalars to add take the SPP fix (:343-372); k_gnss_front reads these fields only where the table has no such scalar
+        const int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
+        const bool fs_add = only_g >= 0 ? (fabs(blocks[i].vel_spp[3]) > 1e-3 && I[NOM_GNSS + NOM_G_FS] < 0) : pl.cand[(size_t)0 * nb + i] != 0;
+        r[GR_FS] = fs_add ? blocks[i].vel_spp[3] : 0.0;
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const bool add = only_g >= 0 ? (fabs(blocks[i].pos_spp[3 + s4]) > 1e-3 && I[NOM_GNSS + s4] < 0) : pl.cand[(size_t)(1 + s4) * nb + i] != 0;
+            r[GR_CB + s4] = add ? blocks[i].pos_spp[3 + s4] : 0.0;
+        }
+    }
+}
+
+int ingvio_gnss_init_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_init_block* blocks, const double* chi2_table, int chi2_len, double chi2_mult,
+                             int do_chi2, int* added, int* new_idx, int* slot, double* chi2, double* noise, double* dx, int* status)
+{
+    ENTER(c);
+    if (!c) return INGVIO_E_ARG;
+    if (!added || !new_idx || !slot || !chi2 || !noise) return INGVIO_E_ARG;
+    GnssInitPlan pl;
+    if (int rc = gnss_init_validate(c, "ingvio_gnss_init_nominal", b0, nb, blocks, chi2_table, chi2_len, pl)) return rc;
+    const int NC = INGVIO_GNSS_INIT_CAND;
+    const size_t RN = (size_t)NC * nb, S = pl.smax;
+    for (size_t e = 0; e < RN; ++e) { added[e] = 0; new_idx[e] = -1; slot[e] = -1; chi2[e] = 0.0; noise[e] = 0.0; }
+    if (dx) memset(dx, 0, 8 * RN * c->ldp);
+    if (status) for (int i = 0; i < nb; ++i) status[i] = INGVIO_OK;
+    if (!pl.any) return INGVIO_OK;                                                      // nothing to try anywhere: nothing is launched
+    // ---- one slab up: candidates, slots, values, the chi2 table, ephemerides, observations, receiver records ----
+    const size_t ntab = 65;
+    const size_t o_cd = 0, o_sl = o_cd + pad64(4 * RN), o_val = o_sl + pad64(4 * RN), o_tab = o_val + pad64(8 * RN), o_eph = o_tab + pad64(8 * ntab),
+                 o_obs = o_eph + pad64(8 * (size_t)nb * S * GE_N), o_rcv = o_obs + pad64(8 * (size_t)nb * S * GO_N), in_bytes = o_rcv + pad64(8 * (size_t)nb * GR_N);
+    const int mu_cap = 63, nc_cap = 10, mldu = 64;
+    const size_t cs = nc_cap, hsu = (size_t)mldu * nc_cap;
+    const size_t w_res = pad64(8 * (size_t)nb * hsu), w_mu = w_res + pad64(8 * (size_t)nb * mldu), w_nc = w_mu + pad64(4 * (size_t)nb),
+                 w_cm = w_nc + pad64(4 * (size_t)nb), w_var = w_cm + pad64(4 * (size_t)nb * cs), w_rw = w_var + pad64(8 * (size_t)nb),
+                 w_fr = w_rw + pad64(72 * (size_t)nb), wk_bytes = w_fr + pad64(8 * (size_t)nb * 64 * GF_N);
+    const size_t B = c->d.batch;
+    const size_t r_idx = pad64(4 * RN), r_st = r_idx + pad64(4 * RN), r_chi = r_st + pad64(4 * B), r_sl = r_chi + pad64(8 * RN), r_nz = r_sl + pad64(4 * RN),
+                 r_dx = r_nz + pad64(8 * RN), out_bytes = r_dx + (dx ? 8 * RN * c->ldp : 0);
+    auto& w = c->dl;
+    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
+    if (int rc = dl_grow(c, &w.wk, &w.wk_cap, wk_bytes)) return rc;
+    if (w.out_cap < out_bytes && w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; }
+    if (int rc = dl_grow(c, &w.out, &w.out_cap, out_bytes)) return rc;
+    if (!w.h_out) HIPCHK(c, hipHostMalloc((void**)&w.h_out, w.out_cap, hipHostMallocDefault));
+    Uploader upl{ c };
+    if (int rc = upl.begin(in_bytes + 64)) return rc;
+    char* h = upl.take<char>(in_bytes);
+    memset(h, 0, in_bytes);
+    memcpy(h + o_cd, pl.cand.data(), 4 * RN); memcpy(h + o_sl, pl.slots.data(), 4 * RN);
+    double* hval = (double*)(h + o_val);
+    for (int i = 0; i < nb; ++i) {
+        hval[i] = blocks[i].vel_spp[3];
+        for (int s4 = 0; s4 < 4; ++s4) hval[(size_t)(1 + s4) * nb + i] = blocks[i].pos_spp[3 + s4];
+    }
+    memcpy(h + o_tab, chi2_table, 8 * std::min((size_t)chi2_len, ntab));
+    gnss_init_fill(c, b0, nb, blocks, pl, (double*)(h + o_eph), (double*)(h + o_obs), (double*)(h + o_rcv));
+    upl.copy(w.in, h, in_bytes);
+    if (int rc = upl.end()) return rc;
+    int* d_st = (int*)(w.out + r_st);
+    HIPCHK(c, hipMemsetAsync(w.out, 0, r_dx, c->st));                                    // rounds nobody tries are never launched: their slots read "nothing"
+    HIPCHK(c, hipMemsetAsync(c->d_dx + (size_t)b0 * c->ldp, 0, 8 * (size_t)nb * c->ldp, c->st));
+    const NomTable nt = nom_table(c);
+    // ---- the residuals, once (:343-372), and R_w2ecef from YOF as it stands now (:332) ----
+    GnssFrontLaunch G;
+    memset(&G, 0, sizeof G);
+    G.eph = (const double*)(w.in + o_eph); G.obs = (const double*)(w.in + o_obs); G.rcv = (const double*)(w.in + o_rcv); G.smax = (int)S;
+    G.front = (double*)(w.wk + w_fr);                                                   // G.H == nullptr: no staged rows
+    launch_gnss_front(G, nb, c->st, &nt, b0);
+    launch_delayed_gnss_rw(nt, G.rcv, b0, nb, (double*)(w.wk + w_rw), c->st);
+    const CovView cv = view(c);
+    const size_t lds = delayed_front_lds(64, 1, 10);
+    DelayedGnssRows Rw;
+    memset(&Rw, 0, sizeof Rw);
+    Rw.nt = nt; Rw.front = G.front; Rw.eph = G.eph; Rw.obs = G.obs; Rw.rcv = G.rcv; Rw.smax = (int)S; Rw.Rw = (const double*)(w.wk + w_rw);
+    Rw.chi2 = (const double*)(w.in + o_tab); Rw.chi2_mult = chi2_mult;
+    Rw.var_out = (double*)(w.wk + w_var); Rw.nc_out = (int*)(w.wk + w_nc); Rw.colmap_out = (int*)(w.wk + w_cm);
+    for (int g = 0; g < NC; ++g) {
+        if (!pl.round[g]) continue;
+        const size_t r0 = (size_t)g * nb;
+        DelayedFront F;
+        memset(&F, 0, sizeof F);
+        F.cv = cv; F.b0 = b0; F.nb = nb; F.cs = (int)cs; F.do_chi2 = do_chi2 ? 1 : 0;
+        F.Hu = (double*)w.wk; F.resu = (double*)(w.wk + w_res); F.mldu = mldu; F.hsu = hsu; F.mu = (int*)(w.wk + w_mu);
+        F.Y = c->d_Y + (size_t)b0 * c->ystride; F.ystride = (size_t)c->ystride; F.status = d_st;
+        F.added = (int*)w.out + r0; F.new_idx = (int*)(w.out + r_idx) + r0; F.chi2 = (double*)(w.out + r_chi) + r0;
+        Rw.g = g; Rw.cand = (const int*)(w.in + o_cd) + r0; Rw.slot = (const int*)(w.in + o_sl) + r0; Rw.value = (const double*)(w.in + o_val) + r0;
+        Rw.slot_out = (int*)(w.out + r_sl) + r0; Rw.noise_out = (double*)(w.out + r_nz) + r0;
+        if (launch_delayed_front_gnss(F, Rw, lds, c->st)) return INGVIO_E_CAPACITY;
+        EkfLaunch E;                                                                    // StateManager.cpp:623-624: ekfUpdate with the lower rows, R = the round's noise^2
+        memset(&E, 0, sizeof E);
+        E.cv = cv; E.b0 = b0; E.nb = nb; E.H = F.Hu; E.res = F.resu; E.colmap = Rw.colmap_out; E.m = F.mu; E.nc = Rw.nc_out;
+        E.noise = Rw.var_out; E.r_kind = 0; E.mld = mldu; E.hstride = (int)hsu; E.cstride = (int)cs; E.nstride = 1;
+        E.Y = c->d_Y + (size_t)b0 * c->ystride; E.ystride = c->ystride; E.dx = c->d_dx; E.status = d_st; E.m_cap = mu_cap; E.nc_cap = nc_cap;
+        { ProfScope p(c, PF_EKF_CORE); launch_ekf_core(E, c->st); }
+        { ProfScope p(c, PF_DOWNDATE); launch_downdate(E, pl.n_cap, c->st); }
+        launch_nominal_update(nt, c->d_dx, c->ldp, nullptr, b0, nb, c->st);             // boxPlus of the round's dx, the new scalar included (:631-632)
+        if (dx) HIPCHK(c, hipMemcpyAsync(w.out + r_dx + 8 * r0 * c->ldp, c->d_dx + (size_t)b0 * c->ldp, 8 * (size_t)nb * c->ldp, hipMemcpyDeviceToDevice, c->st));
+    }
+    HIPCHK(c, hipMemcpyAsync(w.h_out, w.out, out_bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (int rc = last_launch(c)) return rc;
+    const int *ra = (const int*)w.h_out, *ri = (const int*)(w.h_out + r_idx), *rs = (const int*)(w.h_out + r_st) + b0, *rl = (const int*)(w.h_out + r_sl);
+    const double *rc2 = (const double*)(w.h_out + r_chi), *rnz = (const double*)(w.h_out + r_nz), *rdx = (const double*)(w.h_out + r_dx);
+    int soft = INGVIO_OK;
+    for (int i = 0; i < nb; ++i) {
+        int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
+        for (int g = 0; g < NC; ++g) {
+            const size_t e = (size_t)g * nb + i, oo = (size_t)i * NC + g;
+            if (!pl.cand[e]) continue;
+            added[oo] = ra[e]; new_idx[oo] = ri[e]; slot[oo] = ra[e] ? rl[e] : -1; chi2[oo] = rc2[e]; noise[oo] = rnz[e];
+            if (!ra[e]) continue;
+            if (dx) memcpy(dx + oo * c->ldp, rdx + e * c->ldp, 8 * (size_t)c->ldp);
+            c->h_n[b0 + i] += 1;                                                        // the mirror follows the front's record
+            int* v = I + NOM_IH + 4 * rl[e];
+            v[0] = NOM_KIND_SCALAR; v[1] = ri[e]; v[2] = -1; v[3] = 0;
+            I[NOM_GNSS + (g == 0 ? NOM_G_FS : g - 1)] = rl[e];
+            if (rl[e] >= I[NOM_N_VAR]) I[NOM_N_VAR] = rl[e] + 1;
+        }
+        const int st = (rs[i] & 4) ? INGVIO_E_NOT_PD : ((rs[i] & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
+        if (status) status[i] = st;
+        if (st != INGVIO_OK) soft = st;
+    }
+    if (nom_mark(c)) return INGVIO_E_HIP;
+    return soft;
+}
+
+// parity hook (tests): the row stage of ingvio_gnss_init_nominal alone, for one filter and candidate g; changes nothing
+int ingvio_debug_gnss_init_rows(ingvio_ctx* c, int b, const ingvio_gnss_init_block* block, int g, double* H_old, double* res, double* noise, int* m_out)
+{
+    ENTER(c);
+    if (!c || !block || g < 0 || g >= INGVIO_GNSS_INIT_CAND || !H_old || !res || !noise || !m_out) return INGVIO_E_ARG;
+    GnssInitPlan pl;
+    if (int rc = gnss_init_validate(c, "ingvio_debug_gnss_init_rows", b, 1, block, nullptr, 0, pl, true)) return rc;
+    *m_out = 0; *noise = 0.0;
+    if (!pl.any) return INGVIO_OK;
+    const size_t S = pl.smax, nrow = 64 * 11 + 1;
+    const size_t o_eph = 0, o_obs = o_eph + pad64(8 * S * GE_N), o_rcv = o_obs + pad64(8 * S * GO_N), in_bytes = o_rcv + pad64(8 * GR_N);
+    const size_t w_rw = pad64(8 * nrow), w_fr = w_rw + 128, w_m = w_fr + pad64(8 * 64 * GF_N), wk_bytes = w_m + 64;
+    auto& w = c->dl;
+    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
+    if (int rc = dl_grow(c, &w.wk, &w.wk_cap, wk_bytes)) return rc;
+    std::vector<char> h(in_bytes, 0);
+    gnss_init_fill(c, b, 1, block, pl, (double*)(h.data() + o_eph), (double*)(h.data() + o_obs), (double*)(h.data() + o_rcv), g);
+    if (up(c, w.in, h.data(), in_bytes)) return INGVIO_E_HIP;
+    const NomTable nt = nom_table(c);
+    GnssFrontLaunch G;
+    memset(&G, 0, sizeof G);
+    G.eph = (const double*)(w.in + o_eph); G.obs = (const double*)(w.in + o_obs); G.rcv = (const double*)(w.in + o_rcv); G.smax = (int)S;
+    G.front = (double*)(w.wk + w_fr);
+    launch_gnss_front(G, 1, c->st, &nt, b);
+    launch_delayed_gnss_rw(nt, G.rcv, b, 1, (double*)(w.wk + w_rw), c->st);
+    DelayedGnssRows Rw;
+    memset(&Rw, 0, sizeof Rw);
+    Rw.nt = nt; Rw.front = G.front; Rw.eph = G.eph; Rw.obs = G.obs; Rw.rcv = G.rcv; Rw.smax = (int)S; Rw.Rw = (const double*)(w.wk + w_rw); Rw.g = g;
+    int* d_m = (int*)(w.wk + w_m);
+    if (launch_delayed_gnss_rows_debug(Rw, b, (double*)w.wk, d_m, c->st)) return INGVIO_E_CAPACITY;
+    std::vector<double> out(nrow);
+    int m = 0;
+    HIPCHK(c, hipMemcpyAsync(out.data(), w.wk, 8 * nrow, hipMemcpyDeviceToHost, c->st));
+    if (down_sync(c, &m, d_m, sizeof(int))) return INGVIO_E_HIP;                        // synchronises: the host vector above may go
+    if (int rc = last_launch(c)) return rc;
+    *m_out = m;
+    if (m == 0) return INGVIO_OK;
+    memcpy(H_old, out.data(), 8 * (size_t)m * 10);
+    memcpy(res, out.data() + (size_t)m * 10, 8 * (size_t)m);
+    *noise = out[(size_t)m * 11];
+    return INGVIO_OK;
+}
+
 int ingvio_replace_var_linear(ingvio_ctx* c, int b, int tidx, int tsize, const int* vidx, const int* vsize, int k, const double* H, int ldh)
 {
     ENTER(c);

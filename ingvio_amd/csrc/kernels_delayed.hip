@@ -14,6 +14,9 @@
 // k_delayed_front<true> (ingvio_landmark_init_nominal) replaces step 1: the rows are not loaded but FORMED in LDS, one lane per store
 // column of the candidate's track, from the track store's observations and the nominal table's clone poses
 // (calcResJacobianSingleFeatAll{Mono,Stereo}Obs, LandmarkUpdate.cpp:426-500 / :803-890); an accepted candidate is entered into the table.
+// k_delayed_front<DL_GNSS> (ingvio_gnss_init_nominal) forms them one lane per satellite from the records of k_gnss_front and the table's
+// extended pose (GnssUpdate::addNewTrackedSys, GnssUpdate.cpp:375-470), computes the round's noise itself and registers an accepted
+// clock state in the table.  The template argument is the row source: DL_HOST (<false> before), DL_LM (<true>), DL_GNSS.
 // No atomics, no global round trip inside the rotation loop.  FP64, gfx950 only.
 #include <type_traits>
 
@@ -111,14 +114,71 @@ __device__ __forceinline__ void rows_form(const DelayedRows& r, int b, int bl, u
     }
 }
 
-template <bool ROWS>
-__global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a, std::conditional_t<ROWS, DelayedRows, NoRows> r)
+// The satellites whose rows candidate r.g of filter entry bl takes (bit = satellite), ranked by ballot as k_gnss_front ranks its rows.
+// lane = satellite; every lane of the wave must be active.
+__device__ __forceinline__ unsigned long long gnss_rows_used(const DelayedGnssRows& r, int bl, int lane)
+{
+    bool sel = false;
+    if (lane < r.smax && lane < (int)r.rcv[(size_t)bl * GR_N + GR_NSAT]) {
+        const bool usable = r.front[((size_t)bl * 64 + lane) * GF_N + 9] != 0.0;
+        const int sys = (int)r.eph[((size_t)bl * r.smax + lane) * GE_N + GE_SYS];
+        sel = usable && (r.g == 0 || sys == r.g - 1);
+    }
+    return __ballot(sel);
+}
+
+// Lane = satellite of filter b (entry bl of r's arrays): its row of [H_old | res] into sA (column stride ldA, residual in column nc) and its
+// noise term ura std / sin^2 el into sW, both at the satellite's rank.  Only the non-zero blocks are written.
+__device__ __forceinline__ void gnss_rows_form(const DelayedGnssRows& r, int b, int bl, unsigned long long um, int lane, int nc,
+                                               double* sA, int ldA, double* sW)
+{
+    if (!((um >> lane) & 1ULL)) return;
+    const int row = __popcll(um & ((1ULL << lane) - 1ULL));
+    const bool fs = r.g == 0;
+    const int* I = r.nt.ih + (size_t)b * r.nt.ir;
+    const double* x = r.nt.dv + (size_t)b * r.nt.dr + NOM_DH + (size_t)I[NOM_V_POSE] * NOM_VD + (fs ? 12 : 9);      // v_w or p_w, as the table holds it now
+    const double* fr = r.front + ((size_t)bl * 64 + lane) * GF_N;
+    const double* Rw = r.Rw + 9 * (size_t)bl;
+    const double u[3] = { fr[2], fr[3], fr[4] };
+    double uR[3];                                                      // u^T R_w2ecef
+    for (int c = 0; c < 3; ++c) uR[c] = u[0] * Rw[c] + u[1] * Rw[3 + c] + u[2] * Rw[6 + c];
+    const double h[3] = { uR[1] * x[2] - uR[2] * x[1], uR[2] * x[0] - uR[0] * x[2], uR[0] * x[1] - uR[1] * x[0] };      // u^T R [x]x
+    for (int c = 0; c < 3; ++c) {
+        sA[row + (size_t)c * ldA] = h[c];
+        sA[row + (size_t)((fs ? 6 : 3) + c) * ldA] = -uR[c];
+    }
+    sA[row + (size_t)nc * ldA] = -(fs ? fr[1] : fr[0]);
+    const double* ep = r.eph + ((size_t)bl * r.smax + lane) * GE_N;
+    const double* ob = r.obs + ((size_t)bl * r.smax + lane) * GO_N;
+    double se = sin(fr[6]);
+    if (fabs(se) < 1e-6) se = 1e-6;
+    const double sd = fs ? ob[GO_DOPP_STD] * 2.99792458e8 / ob[GO_FREQ] : ob[GO_PSR_STD];
+    sW[row] = ep[GE_URA] * sd / (se * se);
+}
+
+// KIND: where the rows come from - DL_HOST the call's packed rows, DL_LM formed from the track store (ingvio_landmark_init_nominal),
+// DL_GNSS formed from the satellite records of k_gnss_front (ingvio_gnss_init_nominal)
+enum { DL_HOST = 0, DL_LM = 1, DL_GNSS = 2 };
+template <int KIND> struct RowSource { using type = NoRows; };
+template <> struct RowSource<DL_LM> { using type = DelayedRows; };
+template <> struct RowSource<DL_GNSS> { using type = DelayedGnssRows; };
+
+template <int KIND>
+__global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a, typename RowSource<KIND>::type r)
 {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int bl = blockIdx.x, b = a.b0 + bl, tid = threadIdx.x;
     int m_ = 0, s_ = 3, nc_ = 0;
     unsigned long long um = 0ULL, dm = 0ULL;
-    if constexpr (ROWS) {
+    if constexpr (KIND == DL_GNSS) {
+        // every wave evaluates the same 64-lane ballot (lane = satellite): m and the ranks are uniform over the workgroup before any barrier
+        if (r.cand[bl] && !(a.status[b] & 4)) um = gnss_rows_used(r, bl, tid & (WAVE - 1));
+        m_ = __popcll(um); s_ = 1; nc_ = 10;
+        if (m_ <= s_) {                                      // not tried, a failed update before it, or m <= 1 (StateManager.cpp:571-575)
+            if (tid == 0) { a.added[bl] = 0; a.new_idx[bl] = -1; a.chi2[bl] = 0.0; a.mu[bl] = 0; r.slot_out[bl] = -1; r.noise_out[bl] = 0.0; r.var_out[bl] = 1.0; }
+            return;
+        }
+    } else if constexpr (KIND == DL_LM) {
         const int track = r.track[bl];
         if (track >= 0 && !(a.status[b] & 4)) {
             const int cw = r.nt.ih[(size_t)b * r.nt.ir + NOM_N_CLONES];
@@ -150,7 +210,18 @@ __global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a, std::co
     double* sT = sA + (size_t)(nc + 1) * ldA;               // row c of T = column nc + 1 + c of sA
 
     // ---- 1. stage the rows --------------------------------------------------------------------------------------------
-    if constexpr (ROWS) {                                    // formed here: zero fill, then one lane per store column writes its blocks
+    if constexpr (KIND == DL_GNSS) {                         // formed here: zero fill (columns 3-5 or 6-8 and 9 stay zero), one lane per satellite
+        for (int e = tid; e < (nc + 1) * ldA; e += DL_NT) sA[e] = 0.0;
+        for (int e = tid; e < m; e += DL_NT) sHn[e] = 1.0;   // H_new: all ones
+        const int* I = r.nt.ih + (size_t)b * r.nt.ir;
+        if (tid < nc) {                                      // var_old_order: [SE23 (9), YOF (1)]
+            const int col = tid < 9 ? I[NOM_IH + 4 * I[NOM_V_POSE] + 1] + tid : I[NOM_IH + 4 * I[NOM_GNSS + NOM_G_YOF] + 1];
+            sCol[tid] = col; r.colmap_out[(size_t)bl * a.cs + tid] = col;
+        }
+        if (tid == 0) r.nc_out[bl] = nc;
+        __syncthreads();
+        if (tid < WAVE) gnss_rows_form(r, b, bl, um, tid, nc, sA, ldA, sS);      // sS: the rows' m noise terms until S is formed (S holds (mu + 1)^2 = m^2 >= m words and is first written two barriers on)
+    } else if constexpr (KIND == DL_LM) {                    // formed here: zero fill, then one lane per store column writes its blocks
         for (int e = tid; e < (nc + 1) * ldA; e += DL_NT) sA[e] = 0.0;
         for (int e = tid; e < s * m; e += DL_NT) sHn[e] = 0.0;
         const int* I = r.nt.ih + (size_t)b * r.nt.ir;
@@ -170,6 +241,15 @@ __global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a, std::co
         for (int c = tid; c < nc; c += DL_NT) sCol[c] = a.colmap[(size_t)bl * a.cs + c];
     }
     __syncthreads();
+    double var_ = a.var;
+    if constexpr (KIND == DL_GNSS) {                         // noise = amp sqrt(mean(ura std / sin^2 el)), summed in row order by every thread alike
+        double avg = 0.0;
+        for (int i = 0; i < m; ++i) avg += sS[i];
+        const double noise = r.rcv[(size_t)bl * GR_N + (r.g == 0 ? GR_DOPP_AMP : GR_PSR_AMP)] * sqrt(avg / m);
+        var_ = noise * noise;
+        if (tid == 0) { r.noise_out[bl] = noise; r.var_out[bl] = var_; }
+    }
+    const double var = var_;
     // ---- 2. the rotation list (one lane) beside T = Pcc H_old^T (the other waves) --------------------------------------
     if (tid < WAVE) {
         if (tid == 0)
@@ -229,7 +309,7 @@ __global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a, std::co
         if (i < i2) continue;
         double acc = 0.0;
         for (int c = 0; c < nc; ++c) acc += sA[(s + i) + (size_t)c * ldA] * sT[(s + i2) + (size_t)c * ldA];
-        if (i == i2) acc += a.var;
+        if (i == i2) acc += var;
         sS[i * LS + i2] = acc;
     }
     for (int e = tid; e <= mu; e += DL_NT) sS[mu * LS + e] = (e < mu) ? sA[(s + e) + (size_t)nc * ldA] : 0.0;
@@ -247,12 +327,12 @@ __global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a, std::co
     // ---- 5. the verdict (uniform: every thread reads the same LDS word) -------------------------------------------------
     const double chi2 = -sS[mu * LS + mu];
     bool refuse;
-    if constexpr (ROWS) refuse = !(chi2 <= r.chi2_mult * r.chi2[m]);      // the quantile at dof m (StateManager.cpp:610-612); a non-finite chi2 is refused
+    if constexpr (KIND != DL_HOST) refuse = !(chi2 <= r.chi2_mult * r.chi2[m]);      // the quantile at dof m (StateManager.cpp:610-612); a non-finite chi2 is refused
     else refuse = chi2 > a.thr[bl];
     if (refuse && a.do_chi2) {
         if (tid == 0) {
             a.added[bl] = 0; a.new_idx[bl] = -1; a.chi2[bl] = chi2; a.mu[bl] = 0;
-            if constexpr (ROWS) r.slot_out[bl] = -1;
+            if constexpr (KIND != DL_HOST) r.slot_out[bl] = -1;
         }
         return;
     }
@@ -280,7 +360,7 @@ __global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a, std::co
         const int i = tid % s, j = tid / s;
         double acc = 0.0;
         for (int c = 0; c < nc; ++c) acc += sA[i + (size_t)c * ldA] * sT[j + (size_t)c * ldA];
-        sS3[i + j * s] = acc + (i == j ? a.var : 0.0);
+        sS3[i + j * s] = acc + (i == j ? var : 0.0);
         sHf[i + j * s] = sHn[i + j * m];
     }
     __syncthreads();                                         // also: this thread's rows of Y are visible to the workgroup
@@ -314,7 +394,22 @@ __global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a, std::co
         }
     }
     if (tid == 0) { a.cv.n[b] = n + s; a.added[bl] = 1; a.new_idx[bl] = n; a.chi2[bl] = chi2; a.mu[bl] = mu; }
-    if constexpr (ROWS) {
+    if constexpr (KIND == DL_GNSS) {
+        // the scalar's table record in the slot the host reserved, registered as GNSS scalar r.g: k_imu_steps advances it and later
+        // epochs read it; the round's boxPlus retracts it with the rest
+        if (tid == 0) {
+            int* I = r.nt.ih + (size_t)b * r.nt.ir;
+            const int slot = r.slot[bl];
+            int* v = I + NOM_IH + 4 * slot;
+            v[0] = NOM_KIND_SCALAR; v[1] = n; v[2] = -1; v[3] = 0;
+            double* x = r.nt.dv + (size_t)b * r.nt.dr + NOM_DH + (size_t)slot * NOM_VD;
+            for (int i = 0; i < NOM_VD; ++i) x[i] = (i == 0 || i == 4 || i == 8) ? 1.0 : 0.0;
+            x[9] = r.value[bl];
+            I[NOM_GNSS + (r.g == 0 ? NOM_G_FS : r.g - 1)] = slot;
+            if (slot >= I[NOM_N_VAR]) I[NOM_N_VAR] = slot + 1;
+            r.slot_out[bl] = slot;
+        }
+    } else if constexpr (KIND == DL_LM) {
         // the landmark's table record, in the slot the host reserved: the round's boxPlus (k_nominal_update<false>, behind the
         // trailing update) retracts it with the rest (AnchoredLandmark.cpp:227-243)
         if (tid == 0) {
@@ -353,6 +448,47 @@ __global__ __launch_bounds__(WAVE) void k_delayed_rows_debug(DelayedRows r, int 
     for (int e = tid; e < m * nc; e += WAVE) out[e] = sA[(e % m) + (size_t)(e / m) * L.ldA];
     for (int e = tid; e < s * m; e += WAVE) out[(size_t)m * nc + e] = sHn[e];
     for (int e = tid; e < m; e += WAVE) out[(size_t)m * (nc + s) + e] = sA[e + (size_t)nc * L.ldA];
+}
+
+// test hook (ingvio_debug_gnss_init_rows): the row stage of k_delayed_front<DL_GNSS> alone, one wave, dense rows to global memory
+__global__ __launch_bounds__(WAVE) void k_delayed_gnss_rows_debug(DelayedGnssRows r, int b, double* __restrict__ out, int* __restrict__ m_out)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int tid = threadIdx.x, nc = 10;
+    const unsigned long long um = gnss_rows_used(r, 0, tid);
+    const int m = __popcll(um);
+    if (tid == 0) *m_out = m;
+    if (m == 0) return;
+    const DelayedLds L = delayed_carve(m, 1, nc);
+    double* base = reinterpret_cast<double*>(smem_raw);
+    double *sA = base + L.A, *sW = base + L.Hn;
+    for (int e = tid; e < (nc + 1) * L.ldA; e += WAVE) sA[e] = 0.0;
+    __syncthreads();
+    gnss_rows_form(r, b, 0, um, tid, nc, sA, L.ldA, sW);
+    __syncthreads();
+    for (int e = tid; e < m * (nc + 1); e += WAVE) out[e] = sA[(e % m) + (size_t)(e / m) * L.ldA];
+    if (tid == 0) {
+        double avg = 0.0;
+        for (int i = 0; i < m; ++i) avg += sW[i];
+        out[(size_t)m * (nc + 1)] = r.rcv[r.g == 0 ? GR_DOPP_AMP : GR_PSR_AMP] * sqrt(avg / m);
+    }
+}
+
+// R_w2ecef = R_enu2ecef Rz(YOF), row-major, as k_gnss_front forms it (GnssUpdate.cpp:332): one thread per filter
+__global__ __launch_bounds__(64) void k_delayed_gnss_rw(NomTable nt, const double* __restrict__ rcv, int b0, int nb, double* __restrict__ Rw)
+{
+    const int bl = blockIdx.x * 64 + threadIdx.x;
+    if (bl >= nb) return;
+    const int* I = nt.ih + (size_t)(b0 + bl) * nt.ir;
+    const int sy_ = I[NOM_GNSS + NOM_G_YOF];
+    const double yaw = sy_ >= 0 ? nt.dv[(size_t)(b0 + bl) * nt.dr + NOM_DH + (size_t)sy_ * NOM_VD + 9] : 0.0;
+    const double cy = cos(yaw), sy = sin(yaw);
+    const double* rc = rcv + (size_t)bl * GR_N;
+    for (int r = 0; r < 3; ++r) {
+        Rw[9 * bl + 3 * r] = rc[GR_RENU + 3 * r] * cy + rc[GR_RENU + 3 * r + 1] * sy;
+        Rw[9 * bl + 3 * r + 1] = -rc[GR_RENU + 3 * r] * sy + rc[GR_RENU + 3 * r + 1] * cy;
+        Rw[9 * bl + 3 * r + 2] = rc[GR_RENU + 3 * r + 2];
+    }
 }
 
 
@@ -685,16 +821,16 @@ size_t delayed_front_lds(int m, int s, int nc) { return delayed_carve(m, s, nc).
 int launch_delayed_front(const DelayedFront& L, size_t lds_bytes, hipStream_t st)
 {
     if (lds_bytes > 160 * 1024) return -1;
-    hipFuncSetAttribute((const void*)k_delayed_front<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL(k_delayed_front<false>, dim3(L.nb), dim3(DL_NT), lds_bytes, st, L, NoRows{});
+    hipFuncSetAttribute((const void*)k_delayed_front<DL_HOST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(k_delayed_front<DL_HOST>, dim3(L.nb), dim3(DL_NT), lds_bytes, st, L, NoRows{});
     return 0;
 }
 
 int launch_delayed_front_rows(const DelayedFront& L, const DelayedRows& R, size_t lds_bytes, hipStream_t st)
 {
     if (lds_bytes > 160 * 1024) return -1;
-    hipFuncSetAttribute((const void*)k_delayed_front<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL(k_delayed_front<true>, dim3(L.nb), dim3(DL_NT), lds_bytes, st, L, R);
+    hipFuncSetAttribute((const void*)k_delayed_front<DL_LM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(k_delayed_front<DL_LM>, dim3(L.nb), dim3(DL_NT), lds_bytes, st, L, R);
     return 0;
 }
 
@@ -727,5 +863,27 @@ int launch_delayed_front_rows_large(const DelayedFront& L, const DelayedRows& R,
 int launch_delayed_rows_debug_large(const DelayedRows& R, int b, double* out, int* m_out, hipStream_t st)
 {
     hipLaunchKernelGGL(k_delayed_rows_debug_large, dim3(1), dim3(WAVE), 0, st, R, b, out, m_out);
+    return 0;
+}
+
+void launch_delayed_gnss_rw(const NomTable& nt, const double* rcv, int b0, int nb, double* Rw, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_delayed_gnss_rw, dim3((nb + 63) / 64), dim3(64), 0, st, nt, rcv, b0, nb, Rw);
+}
+
+int launch_delayed_front_gnss(const DelayedFront& L, const DelayedGnssRows& R, size_t lds_bytes, hipStream_t st)
+{
+    if (lds_bytes > 160 * 1024 || R.smax > 64) return -1;
+    hipFuncSetAttribute((const void*)k_delayed_front<DL_GNSS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(k_delayed_front<DL_GNSS>, dim3(L.nb), dim3(DL_NT), lds_bytes, st, L, R);
+    return 0;
+}
+
+int launch_delayed_gnss_rows_debug(const DelayedGnssRows& R, int b, double* out, int* m_out, hipStream_t st)
+{
+    if (R.smax > 64) return -1;
+    const size_t lds_bytes = delayed_carve(64, 1, 10).bytes;
+    hipFuncSetAttribute((const void*)k_delayed_gnss_rows_debug, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(k_delayed_gnss_rows_debug, dim3(1), dim3(WAVE), lds_bytes, st, R, b, out, m_out);
     return 0;
 }

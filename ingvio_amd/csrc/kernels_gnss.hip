@@ -236,8 +236,10 @@ __global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L, NomTable n
         }
         const double* xs = D + (size_t)(vp >= 0 ? vp : 0) * NOM_VD;
         for (int q = 0; q < 3; ++q) { pw[q] = xs[9 + q]; vw[q] = xs[12 + q]; }
-        for (int q = 0; q < 4; ++q) cb4[q] = sl[q] >= 0 ? D[(size_t)sl[q] * NOM_VD + 9] : 0.0;
-        fs_v = sl[NOM_G_FS] >= 0 ? D[(size_t)sl[NOM_G_FS] * NOM_VD + 9] : 0.0;
+        // a scalar that is not registered takes the receiver record's value: zero from every stage of an epoch, the SPP fix's value for a
+        // clock state ingvio_gnss_init_nominal is about to add (GnssUpdate.cpp:343-372)
+        for (int q = 0; q < 4; ++q) cb4[q] = sl[q] >= 0 ? D[(size_t)sl[q] * NOM_VD + 9] : rc[GR_CB + q];
+        fs_v = sl[NOM_G_FS] >= 0 ? D[(size_t)sl[NOM_G_FS] * NOM_VD + 9] : rc[GR_FS];
         yaw_v = sl[NOM_G_YOF] >= 0 ? D[(size_t)sl[NOM_G_YOF] * NOM_VD + 9] : 0.0;
         ix_se23 = vp >= 0 ? var[4 * vp + 1] : -1;
         ix_yof = sl[NOM_G_YOF] >= 0 ? var[4 * sl[NOM_G_YOF] + 1] : -1;

@@ -28,5 +28,6 @@ struct GnssFrontLaunch {
 };
 
 // nom != nullptr (k_gnss_front<true>): p_w, v_w, cb, fs, yaw_offset and the idx_* of filter b0 + i come from its device-resident nominal
-// table (extended pose + the scalars registered with ingvio_nominal_set_gnss); those fields of the receiver record are not read
+// table (extended pose + the scalars registered with ingvio_nominal_set_gnss); those fields of the receiver record are not read, except cb[s]
+// / fs where the table has no such scalar registered (the stages of an epoch leave them zero; ingvio_gnss_init_nominal puts the SPP fix there)
 void launch_gnss_front(const GnssFrontLaunch& L, int nb, hipStream_t st, const NomTable* nom = nullptr, int b0 = 0);

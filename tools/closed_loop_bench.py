@@ -24,6 +24,11 @@ MSCKF write-back,
   in-frame form    run(i); stage_async(i+1); gnss_frame_stage_nominal(i+1); fetch_begin(i); run(i+1); fetch_end(i)
 Each form free-running (<form>_loop_ms_per_frame) and synchronised per frame (<form>_abi / _wall_ms_per_frame), the two-call form
 first, then the in-frame form, then the two-call form again (its spread); writes $RESULTS/closed_loop_bench_gnss_in_frame.json.
+--gnss-acquire: no loop - every filter lacks the frequency shift and the four clock biases, and the SPP fix reports all five
+(ingvio_amd/closed_loop_gnss_init.py): ONE ingvio_gnss_init_nominal for the batch against the round trip of today's entry points
+(host_acquire), --repeats timed rounds of each from the same snapshot; device_ms / roundtrip_ms are the best of them, wall time of
+this harness included (for the round trip mostly numpy rows and one ctypes call per candidate).  Writes
+$RESULTS/closed_loop_bench_gnss_acquire.json.
 --register-only: the loop without epochs but with the GNSS scalars registered, i.e. the clock recursion of k_imu_steps<true> switched on
 (against the plain run: that kernel's time with and without registered clocks).
 --landmarks L: every filter carries L in-state landmarks that are observed in every frame (ingvio_amd/closed_loop_lm.py), two forms on
@@ -229,6 +234,47 @@ def main_gnss_in_frame(a):
             ctx.close()
     out["max_abs_pose_in_frame_vs_two_call"] = max(float(np.max(np.abs(d["val"][0] - r["val"][0]))) for d, r in zip(noms["in_frame"], noms["two_call"]))
     finish(out, "closed_loop_bench_gnss_in_frame.json")
+
+
+def main_gnss_acquire(a):
+    """GnssUpdate::addNewTrackedSys for the whole batch, every filter lacking FS and the four clock biases: ONE ingvio_gnss_init_nominal
+    (device form) against closed_loop_gnss_init.host_acquire (ingvio_nominal_get, ingvio_gnss_sat_eval, numpy rows, one
+    ingvio_add_variable_delayed per candidate, host boxPlus, ingvio_nominal_set + _set_gnss), on the same build in one process.  Both
+    start from the same snapshot; the first call of either form (buffers, code objects) is not timed.  No threshold is set."""
+    from ingvio_amd import synth
+    from ingvio_amd import closed_loop_gnss_init as ci
+    B, F = a.batch, a.features
+    z = np.load(os.path.join(ROOT, "tests", "golden", "gnss_front.npz"))
+    t0 = time.perf_counter()
+    cases = ci.make_init_loop(z, B, 1, [ci.ALL5], F=F, ks=(a.k,), windows=(a.window,))
+    table = synth.chi2_table()
+    out = dict(batch=B, window=a.window, candidates_per_filter=ci.CAND, satellites=int(len(z["eph"])), repeats=a.repeats, setup_s=round(time.perf_counter() - t0, 1))
+    ctx = fresh_ctx(a, cases, gnss=True)
+    ctx.snapshot()
+    blocks = ci.init_blocks(cases, 0)
+    dev, host = [], []
+    for it in range(a.repeats + 1):
+        call = ctx.gnss_init_nominal_prepare(0, blocks, table, ci.CHI2_MULT, True, False)
+        ctx.sync()
+        t = time.perf_counter()
+        raw = call()                                                     # synchronises once, at its end
+        dev.append(time.perf_counter() - t)
+        dev_state = (ctx.nominal_get(), [ctx.cov_get(b) for b in range(min(B, 8))])
+        ctx.restore()
+        cs = ci.fresh(cases)
+        ctx.sync()
+        t = time.perf_counter()
+        ver = ci.host_acquire(ctx, cs, 0, table)
+        ctx.sync()
+        host.append(time.perf_counter() - t)
+        host_state = (ctx.nominal_get(), [ctx.cov_get(b) for b in range(min(B, 8))])
+        ctx.restore()
+    out["device_ms"] = round(1e3 * min(dev[1:]), 3); out["roundtrip_ms"] = round(1e3 * min(host[1:]), 3)
+    out["device_ms_all"] = [round(1e3 * x, 3) for x in dev[1:]]; out["roundtrip_ms_all"] = [round(1e3 * x, 3) for x in host[1:]]
+    out["added_device"] = int(raw["added"].sum()); out["added_roundtrip"] = int(sum(v[g]["added"] for v in ver for g in range(ci.CAND)))
+    out["max_rel_P_device_vs_roundtrip"] = max(float(np.linalg.norm(d - h) / np.linalg.norm(h)) for d, h in zip(dev_state[1], host_state[1]))
+    ctx.close()
+    finish(out, "closed_loop_bench_gnss_acquire.json")
 
 
 def main_landmarks(a):
@@ -464,6 +510,7 @@ def main():
     ap.add_argument("--gnss", action="store_true")
     ap.add_argument("--gnss-in-frame", action="store_true", help="the epoch staged with its frame next to the two-call device form")
     ap.add_argument("--sats", type=int, default=8, help="--gnss-in-frame: satellites per epoch (at most 8 for the fold)")
+    ap.add_argument("--gnss-acquire", action="store_true", help="ingvio_gnss_init_nominal for the batch against the round trip through the host (--repeats timed rounds)")
     ap.add_argument("--register-only", action="store_true", help="the loop without epochs, the GNSS scalars registered (clock recursion on)")
     ap.add_argument("--landmarks", type=int, default=0, help="L in-state landmarks per filter, updated in every frame")
     ap.add_argument("--tail", action="store_true", help="the oldest clone leaves and every landmark changes its anchor behind every frame")
@@ -474,6 +521,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=2, help="--odom: rounds of A B C")
     ap.add_argument("--stall-frames", type=int, default=3, help="--odom: timed frames of the stalling form")
     a = ap.parse_args()
+    if a.gnss_acquire:
+        return main_gnss_acquire(a)
     if a.odom:
         return main_odom(a)
     if a.two_updates:
