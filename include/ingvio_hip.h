@@ -194,7 +194,9 @@ int ingvio_mld(ingvio_ctx* ctx);                      /* row stride of keep_out 
  *     cuc, cus, crc, crs, cic, cis, af0, af1, af2, tgd[0], ura
  *     GLONASS (sys == 1, GloEphem): sys, prn, toe (GPS week seconds), 0, 0, pos[3], vel[3], acc[3] (m, m/s, m/s^2, PZ-90 ECEF),
  *     tau_n, gamma, zeros up to ura at [24]; the observation's frequency is the satellite's FDMA channel
- *   observation [INGVIO_OBS_N]: receive time, L1 pseudo-range (m), L1 Doppler (Hz), psr_std, dopp_std, L1 frequency (Hz, < 0: no L1) */
+ *   observation [INGVIO_OBS_N]: receive time, L1 pseudo-range (m), L1 Doppler (Hz), psr_std, dopp_std, L1 frequency (Hz, < 0: no L1;
+ *     a frequency of exactly 0 is not a defined input: the Doppler residual and its noise divide by it)
+ * An entry whose sys is none of 0 .. 3 is skipped like one without L1: unusable, no rows. */
 #define INGVIO_EPH_N 25
 #define INGVIO_OBS_N 6
 #define INGVIO_GNSS_MAX_SAT 64
@@ -223,6 +225,11 @@ int ingvio_gnss_front_fetch(ingvio_ctx* ctx, int b0, int nb, double* out);
  * ECEF set R_enu2ecef = I, yaw_offset = 0, p_w = 0, anchor_ecef = position, v_w = ECEF velocity.
  * out [n_epochs][INGVIO_GNSS_MAX_SAT][INGVIO_GNSS_SAT_REC]. */
 int ingvio_gnss_sat_eval(ingvio_ctx* ctx, int n_epochs, const ingvio_gnss_epoch* epochs, double* out);
+/* test hook: the candidate rows of filter b as the last GNSS stage of any form left them, before any gate (a run only reads them):
+ * H [ingvio_mld() x 32] column-major with leading dimension ingvio_mld() (rows 0 .. *m_out - 1: pseudo-range rows, then Doppler rows),
+ * res / noise [ingvio_mld()] (noise: the row variances), colmap [32]: state column of H's column c for c < *nc_out - the var_order
+ * [SE23 (9), YOF, clock biases in order of first appearance, FS] of GnssUpdate.cpp:148-272. */
+int ingvio_debug_gnss_staged_rows(ingvio_ctx* ctx, int b, double* H, double* res, double* noise, int* colmap, int* m_out, int* nc_out);
 
 /* ---- feature-sharded single filter (optional mode): the per-feature work (K3-K5 gate, K6/K7 in information form)
  * is independent given the prior, so G replicas of ONE filter can each take F/G of the frame's features:

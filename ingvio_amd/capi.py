@@ -30,7 +30,7 @@ EXPORTS = [
     "ingvio_profile_get", "ingvio_set_msckf_method", "ingvio_set_qr_method", "ingvio_landmark_stage", "ingvio_landmark_run",
     "ingvio_landmark_fetch", "ingvio_frame_run_phase", "ingvio_info_set", "ingvio_debug_read", "ingvio_triangulate",
     "ingvio_gnss_front_stage", "ingvio_gnss_front_fetch", "ingvio_gnss_update_batch", "ingvio_gnss_stage", "ingvio_gnss_run", "ingvio_gnss_fetch", "ingvio_mld", "ingvio_debug_msckf_info", "ingvio_debug_info_solution",
-    "ingvio_info_reduce", "ingvio_info_commit", "ingvio_gnss_sat_eval",
+    "ingvio_info_reduce", "ingvio_info_commit", "ingvio_gnss_sat_eval", "ingvio_debug_gnss_staged_rows",
     "ingvio_chi2_gamma_multi", "ingvio_ekf_update_batch", "ingvio_add_variable_delayed_invertible", "ingvio_add_variable_delayed", "ingvio_add_variable_delayed_batch", "ingvio_replace_var_linear",
     "ingvio_nominal_create", "ingvio_nominal_set", "ingvio_nominal_get", "ingvio_nominal_box_plus", "ingvio_frame_stage_tracks_nominal",
     "ingvio_nominal_set_gnss", "ingvio_nominal_get_gnss", "ingvio_gnss_front_stage_nominal", "ingvio_landmark_stage_nominal",
@@ -700,6 +700,14 @@ class Context:
         out = np.zeros((nb, 64, 20))
         self._chk(self.L.ingvio_gnss_front_fetch(self.h, b0, nb, _d(out)))
         return out
+
+    def debug_gnss_staged_rows(self, b):
+        """ingvio_debug_gnss_staged_rows: -> (H [m, nc], res [m], noise [m], colmap [nc]) of filter b's candidate rows as staged"""
+        mld = self.L.ingvio_mld(self.h)
+        H = np.zeros((mld, 32), order="F"); res = np.zeros(mld); noise = np.zeros(mld); cm = np.zeros(32, dtype=np.int32)
+        m = C.c_int(0); nc = C.c_int(0)
+        self._chk(self.L.ingvio_debug_gnss_staged_rows(self.h, int(b), _d(H), _d(res), _d(noise), _i(cm), C.byref(m), C.byref(nc)))
+        return H[:m.value, :nc.value].copy(), res[:m.value].copy(), noise[:m.value].copy(), cm[:nc.value].copy()
 
     def frame_run_phase(self, phase, restore_prior=False):
         """1: propagate + clone + gate + Gram of the staged features; 2: solve + apply + marginalise (ingvio_frame_run_phase)"""

@@ -2250,6 +2250,23 @@ int ingvio_gnss_front_fetch(ingvio_ctx* c, int b0, int nb, double* out)
     return last_launch(c);
 }
 
+// test hook: the candidate rows of filter b as the last stage left them (no gate has touched them; a run only reads them)
+int ingvio_debug_gnss_staged_rows(ingvio_ctx* c, int b, double* H, double* res, double* noise, int* colmap, int* m_out, int* nc_out)
+{
+    ENTER(c);
+    if (check_range(c, b, 1) || !H || !res || !noise || !colmap || !m_out || !nc_out) return INGVIO_E_ARG;
+    auto& g = c->gn;
+    if (!g.staged || !g.H) { c->err = "ingvio_debug_gnss_staged_rows: no GNSS rows are staged"; return INGVIO_E_ARG; }
+    const size_t mld = c->mld, hs = mld * GNSS_NCW;
+    HIPCHK(c, hipMemcpyAsync(H, g.H + (size_t)b * hs, 8 * hs, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(res, g.res + (size_t)b * mld, 8 * mld, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(noise, g.noise + (size_t)b * mld, 8 * mld, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(colmap, g.colmap + (size_t)b * GNSS_NCW, sizeof(int) * GNSS_NCW, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(m_out, g.m + b, sizeof(int), hipMemcpyDeviceToHost, c->st));
+    if (down_sync(c, nc_out, g.nc + b, sizeof(int))) return INGVIO_E_HIP;
+    return last_launch(c);
+}
+
 int ingvio_gnss_run(ingvio_ctx* c, int b0, int nb)
 {
     ENTER(c);

@@ -171,6 +171,8 @@ def geph2posvel(t, ep):                                        # geph2pos :692-7
 
 
 def ecef2geo(x):
+    if x[0] == 0 and x[1] == 0:                                # gnss_utility.cpp:347-388: a receiver on the polar axis keeps (0, 0, 0)
+        return np.zeros(3)
     e2, a = 6.69437999014e-3, 6378137.0
     a2 = a * a; b2 = a2 * (1 - e2); b = math.sqrt(b2); ep2 = (a2 - b2) / b2
     p = math.hypot(x[0], x[1])
@@ -264,7 +266,7 @@ def iono(tow, ion, lla, azel):
 
 
 def sat_state(ep, ob):
-    if ob[FREQ] < 0:
+    if ob[FREQ] < 0 or not 0 <= int(ep[SYS]) <= 3:             # no L1 signal / not one of the four constellations: unusable
         return None
     ttx = ob[TOW] - ob[PSR] / C_LIGHT
     if int(ep[SYS]) == 1:                                      # gnss_spp.cpp:72-79
@@ -290,8 +292,10 @@ def residuals(eph, obs, ion, doy, xyzt, velt):
         pos, vel, dt, ddt, tgd, ttx = st
         out["usable"][i] = 1
         out["sat"][i] = np.r_[pos, vel, dt, ddt, tgd, ttx]
-        azel = sat_azel(xyzt[:3], pos)
-        tro, io = trop(doy, lla, azel), (iono(ttx, ion, lla, azel) if ion is not None else 0.0)
+        azel, tro, io = np.array([0.0, math.pi / 2]), 0.0, 0.0
+        if np.linalg.norm(xyzt[:3]) > 0:                        # gnss_spp.cpp:123: a receiver at the origin (the first SPP iterate) has no sky
+            azel = sat_azel(xyzt[:3], pos)
+            tro, io = trop(doy, lla, azel), (iono(ttx, ion, lla, azel) if ion is not None else 0.0)
         d = pos - xyzt[:3]
         rng = np.linalg.norm(d)
         sag = OMG_GPS * (pos[0] * xyzt[1] - pos[1] * xyzt[0]) / C_LIGHT
