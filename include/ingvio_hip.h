@@ -132,7 +132,8 @@ int ingvio_ekf_update(ingvio_ctx* ctx, int b, const int* vidx, const int* vsize,
                       const double* R, int r_kind, double* dx_out);
 /* ekfUpdate for filters [b0, b0+nb) in ONE launch and one synchronisation (e.g. the GNSS update of a whole batch): block i
  * belongs to filter b0+i.  R per block: one double (INGVIO_R_SCALAR) or m doubles (INGVIO_R_DIAG).  dx_out [nb][ldp]
- * (ingvio_ldp), status_out [nb] = INGVIO_OK / INGVIO_NEG_DIAG per filter (may be NULL). */
+ * (ingvio_ldp), status_out [nb] = INGVIO_OK / INGVIO_NEG_DIAG / INGVIO_E_NOT_PD per filter (may be NULL); the call returns the last
+ * filter status that is not INGVIO_OK. */
 typedef struct {
     const int* vidx;          /* var_order as (idx, size)[k]                                        */
     const int* vsize;
@@ -971,6 +972,28 @@ int ingvio_set_apply_resident(ingvio_ctx* ctx, int on);
 /* The form the write-back of the context's last MSCKF update took: 1 k_info_apply_res, 0 any other kernel.  A negative error code for
  * a null context. */
 int ingvio_last_apply_form(ingvio_ctx* ctx);
+/* The route the context's last generic update took (ingvio_ekf_update, ingvio_ekf_update_batch; the dense-H landmark stack records
+ * its solve here too, with no product bits).  Read-only, no synchronisation; 0 before the first such update, a negative error code for
+ * a null context.  A call refused before its first launch leaves the value of the update before it.
+ *   bits 0-1  INGVIO_UPDATE_ROUTE_MASK: INGVIO_UPDATE_LDS k_ekf_core + k_downdate (S in LDS); INGVIO_UPDATE_DENSE_REG the dense-H route
+ *             with the register-resident solve k_lm_factor / k_lm_carry (dense workspace of up to 256 rows); INGVIO_UPDATE_DENSE_SWEEP
+ *             the dense-H route with the Cholesky sweep out of L2 (k_chol_first / k_chol_step, k_lm_finish).  The workspace only
+ *             grows: a context that has solved more than 256 rows keeps the sweep for every later dense-route update.
+ *   bits 4-8  (form >> INGVIO_UPDATE_NTM_SHIFT) & INGVIO_UPDATE_NTM_MASK: with INGVIO_UPDATE_DENSE_REG the tile class of the solve
+ *             (4, 8, 12, 14 or 16 tiles of 16 rows, chosen from the workspace's row capacity), else 0.
+ *   INGVIO_UPDATE_GEMM64_PHT / _S: the product P H^T / S = H (P H^T) ran on k_gemm64 (64 x 64 blocks) instead of k_gemm.
+ *   INGVIO_UPDATE_SPLIT_SWEEP: with INGVIO_UPDATE_DENSE_SWEEP, the carried rows were done by one k_chol_carried launch after the
+ *             factorisation instead of riding through the panel launches. */
+#define INGVIO_UPDATE_ROUTE_MASK 3
+#define INGVIO_UPDATE_LDS 1
+#define INGVIO_UPDATE_DENSE_REG 2
+#define INGVIO_UPDATE_DENSE_SWEEP 3
+#define INGVIO_UPDATE_NTM_SHIFT 4
+#define INGVIO_UPDATE_NTM_MASK 31
+#define INGVIO_UPDATE_GEMM64_PHT 0x200
+#define INGVIO_UPDATE_GEMM64_S 0x400
+#define INGVIO_UPDATE_SPLIT_SWEEP 0x800
+int ingvio_last_update_form(ingvio_ctx* ctx);
 /* Which form of the delayed-initialisation front ingvio_add_variable_delayed, ingvio_add_variable_delayed_batch and
  * ingvio_landmark_init_nominal take.  The LDS form keeps [H_old | res], T = Pcc H_old^T and S in LDS at once, which bounds
  * the window (stereo: 17 clones, mono: 21 - 26).  The large form keeps [H_old | res | T^T] in a per-filter workspace in device memory

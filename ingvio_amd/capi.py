@@ -18,6 +18,16 @@ c_up = C.POINTER(C.c_ulonglong)
 OK, NO_ROWS, NEG_DIAG, REJECTED = 0, 1, 2, 3
 E_ARG, E_CAPACITY, E_HIP, E_NOT_IN_STATE, E_UNSUPPORTED, E_NOT_PD = -1, -2, -3, -4, -5, -6
 R_SCALAR, R_DIAG, R_FULL = 0, 1, 2
+# ingvio_last_update_form (INGVIO_UPDATE_* of ingvio_hip.h)
+UPDATE_LDS, UPDATE_DENSE_REG, UPDATE_DENSE_SWEEP = 1, 2, 3
+UPDATE_GEMM64_PHT, UPDATE_GEMM64_S, UPDATE_SPLIT_SWEEP = 0x200, 0x400, 0x800
+
+
+def update_form(route, ntm=0, gemm64=False, split=False):
+    """the value ingvio_last_update_form reports for a route, the tile class of the register-resident solve, both products on
+    k_gemm64 and the split sweep"""
+    return route | (ntm << 4) | ((UPDATE_GEMM64_PHT | UPDATE_GEMM64_S) if gemm64 else 0) | (UPDATE_SPLIT_SWEEP if split else 0)
+
 
 EXPORTS = [
     "ingvio_ctx_create", "ingvio_ctx_destroy", "ingvio_sync", "ingvio_ctx_stream", "ingvio_f_max", "ingvio_c_max", "ingvio_last_error", "ingvio_ldp",
@@ -25,7 +35,7 @@ EXPORTS = [
     "ingvio_cov_set", "ingvio_cov_get", "ingvio_get_n", "ingvio_cov_get_marginal", "ingvio_cov_snapshot",
     "ingvio_cov_restore", "ingvio_propagate", "ingvio_propagate_fused", "ingvio_augment_clone", "ingvio_marginalize",
     "ingvio_append_independent", "ingvio_ekf_update", "ingvio_chi2_gamma", "ingvio_msckf_update", "ingvio_msckf_update_tri", "ingvio_qr_compress",
-    "ingvio_frame_stage", "ingvio_frame_stage_async", "ingvio_frame_set_imu_noise", "ingvio_frame_fetch_begin", "ingvio_frame_fetch_end", "ingvio_tracks_create", "ingvio_frame_stage_tracks", "ingvio_frame_run", "ingvio_set_frame_parts", "ingvio_set_gram_reduced", "ingvio_set_gram_decoupled", "ingvio_last_gram_form", "ingvio_set_apply_resident", "ingvio_last_apply_form", "ingvio_frame_fetch", "ingvio_profile_enable", "ingvio_profile_select",
+    "ingvio_frame_stage", "ingvio_frame_stage_async", "ingvio_frame_set_imu_noise", "ingvio_frame_fetch_begin", "ingvio_frame_fetch_end", "ingvio_tracks_create", "ingvio_frame_stage_tracks", "ingvio_frame_run", "ingvio_set_frame_parts", "ingvio_set_gram_reduced", "ingvio_set_gram_decoupled", "ingvio_last_gram_form", "ingvio_set_apply_resident", "ingvio_last_apply_form", "ingvio_last_update_form", "ingvio_frame_fetch", "ingvio_profile_enable", "ingvio_profile_select",
     "ingvio_profile_reset",
     "ingvio_profile_get", "ingvio_set_msckf_method", "ingvio_set_qr_method", "ingvio_landmark_stage", "ingvio_landmark_run",
     "ingvio_landmark_fetch", "ingvio_frame_run_phase", "ingvio_info_set", "ingvio_debug_read", "ingvio_triangulate",
@@ -1297,6 +1307,10 @@ class Context:
     def last_apply_form(self):
         """the form the last MSCKF update's write-back took: 1 k_info_apply_res, 0 any other kernel (ingvio_last_apply_form)"""
         return int(self.L.ingvio_last_apply_form(self.h))
+
+    def last_update_form(self):
+        """route and variants of the last generic update as the bit-field of ingvio_last_update_form (UPDATE_* / update_form())"""
+        return int(self.L.ingvio_last_update_form(self.h))
 
     def set_delayed_form(self, mode):
         """0 (default): delayed initialisation in its LDS form only; 1: the large form for candidates the LDS form cannot take (windows

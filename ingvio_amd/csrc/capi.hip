@@ -220,6 +220,7 @@ struct ingvio_ctx {
     int gram_form_last = 0;             // ingvio_last_gram_form: 0 full, 1 reduced k_feat_gram2, 2 reduced k_feat_gram3
     int apply_resident = 1;             // ingvio_set_apply_resident: the fused frame step's write-back runs as k_info_apply_res where launch_factored can take it
     int apply_form_last = 0;            // ingvio_last_apply_form: 0 k_info_apply (or a few-filter / large-window kernel), 1 k_info_apply_res
+    int update_form_last = 0;           // ingvio_last_update_form: route and variants of the last generic update (INGVIO_UPDATE_*)
     int gram_red_last = 0;              // the chunk partials in d_Rpart come from a reduced Gram launch (ingvio_debug_msckf_info refuses them)
     bool split_pending = false;         // slices of the last split step may still be running on their own streams
     hipEvent_t tok_last = nullptr;      // end of the throughput segment issued last (nullptr: none yet / chain broken)
@@ -1644,12 +1645,6 @@ static int ekf_update_dense_route(ingvio_ctx* c, int b, const int* vidx, const i
     return (status & 4) ? INGVIO_E_NOT_PD : ((status & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
 }
 
-// k_ekf_core keeps S (+ one border row/column) and the column map in LDS (launch_ekf_core): 160 KB per workgroup on gfx950
-static bool ekf_core_fits(int m, int nc)
-{
-    return sizeof(double) * (size_t)(m + 1) * (m + 1) + sizeof(int) * (size_t)nc + 16 <= 160 * 1024;
-}
-
 static int stage_generic(ingvio_ctx* c, int b, const int* vidx, const int* vsize, int k, const double* H, int ldh, int m,
                          const double* res, const double* R, int r_kind, int* nc_out)
 {
@@ -1704,6 +1699,7 @@ int ingvio_ekf_update(ingvio_ctx* c, int b, const int* vidx, const int* vsize, i
     E.status = c->d_status; E.m_cap = m; E.nc_cap = nc;
     { ProfScope p(c, PF_EKF_CORE); launch_ekf_core(E, c->st); }
     { ProfScope p(c, PF_DOWNDATE); launch_downdate(E, c->h_n[b], c->st); }
+    c->update_form_last = INGVIO_UPDATE_LDS;
     int status = 0;
     if (dx_out && down_sync(c, dx_out, c->d_dx + (size_t)b * c->ldp, 8 * (size_t)c->h_n[b])) return INGVIO_E_HIP;
     if (down_sync(c, &status, c->d_status + b, sizeof(int))) return INGVIO_E_HIP;
@@ -1740,6 +1736,7 @@ int ingvio_ekf_update_batch(ingvio_ctx* c, int b0, int nb, const ingvio_update_b
         if (nc > nc_cap) nc_cap = nc;
         if (c->h_n[b] > n_cap) n_cap = c->h_n[b];
     }
+    if (!ekf_core_fits(m_cap, nc_cap)) dense = true;      // one launch, its LDS sized by the most rows and the most columns of the call
     if (dense) {
         // GEMM + Cholesky sweep with carried rows + downdate on dense rows addressed by state column (kernels_lmbatch.hip /
         // kernels_chol.hip); the host scatters the columns, filter by filter
@@ -1823,6 +1820,7 @@ int ingvio_ekf_update_batch(ingvio_ctx* c, int b0, int nb, const ingvio_update_b
     E.status = c->d_status; E.m_cap = m_cap; E.nc_cap = nc_cap;
     { ProfScope p(c, PF_EKF_CORE); launch_ekf_core(E, c->st); }
     { ProfScope p(c, PF_DOWNDATE); launch_downdate(E, n_cap, c->st); }
+    c->update_form_last = INGVIO_UPDATE_LDS;
     std::vector<int> status(nb, 0);
     if (dx_out) HIPCHK(c, hipMemcpyAsync(dx_out, c->d_dx + (size_t)b0 * c->ldp, 8 * (size_t)nb * c->ldp, hipMemcpyDeviceToHost, c->st));
     if (down_sync(c, status.data(), c->d_status + b0, sizeof(int) * (size_t)nb)) return INGVIO_E_HIP;
@@ -3436,6 +3434,7 @@ static int run_dense_update(ingvio_ctx* c, int b0, int nb, double var, int r_kin
     const size_t pp = c->pp;
     double *Hd = w.Hd + (size_t)b0 * w.hstride, *X = w.X + (size_t)b0 * w.xstride, *Y = w.Y + (size_t)b0 * w.xstride;
     const int* act = w.m + b0;
+    int form = 0;
     if (!products_done) {
         ProfScope p(c, PF_LM_GEMM);
         GemmArgs g = {};
@@ -3444,7 +3443,7 @@ static int run_dense_update(ingvio_ctx* c, int b0, int nb, double var, int r_kin
         g.B = Hd; g.sb = w.hstride; g.ldb = w.n_ld; g.modeB = 1;
         g.C = X + mc; g.sc = w.xstride; g.rs = 1; g.cs = w.ldx;
         g.M = n_cap; g.N = mc; g.K = n_cap; g.m_lim = n_cap; g.n_lim = mc; g.ksplit = 1; g.active = act; g.batch = nb;
-        launch_gemm(g, c->st);
+        if (launch_gemm(g, c->st)) form |= INGVIO_UPDATE_GEMM64_PHT;
         // S = H (P H^T), lower blocks
         g = GemmArgs{};
         g.A = Hd; g.sa = w.hstride; g.lda = w.n_ld; g.modeA = 1;
@@ -3452,7 +3451,7 @@ static int run_dense_update(ingvio_ctx* c, int b0, int nb, double var, int r_kin
         g.C = X; g.sc = w.xstride; g.rs = 1; g.cs = w.ldx;
         g.M = mc; g.N = mc; g.K = n_cap; g.m_lim = mc; g.n_lim = mc; g.ksplit = 1; g.lower = 1; g.diag_add = r_kind < 0 ? var : 0.0;
         g.active = act; g.batch = nb;
-        launch_gemm(g, c->st);
+        if (launch_gemm(g, c->st)) form |= INGVIO_UPDATE_GEMM64_S;
         if (r_kind >= 0) launch_add_noise(X, w.xstride, w.ldx, d_noise, nstride, r_kind, act, mc, nb, c->st);
     }
     // S of up to 256 rows: one workgroup per filter, S in registers (kernels_lmchol.hip); larger: the sweep out of L2 (kernels_chol.hip)
@@ -3467,13 +3466,13 @@ static int run_dense_update(ingvio_ctx* c, int b0, int nb, double var, int r_kin
         a.cv = view(c); a.b0 = b0; a.nb = nb; a.X = X; a.Y = Y; a.xs = w.xstride; a.ldx = w.ldx; a.mc = mc; a.res_row = mc + w.n32;
         a.U = w.U + (size_t)b0 * w.ustride; a.us = w.ustride; a.m = act; a.status = c->d_status + b0; a.fail_bit = 4; a.dx = d_dx;
         a.rowmap = rowmap; a.rm_stride = mc;
-        launch_lm_chol(a, c->st);
+        form |= INGVIO_UPDATE_DENSE_REG | (launch_lm_chol(a, c->st) << INGVIO_UPDATE_NTM_SHIFT);
     } else {
         ProfScope p(c, PF_LM_CHOL);
         CholArgs a = {};
         a.W = X; a.Y = Y; a.xs = w.xstride; a.ld = w.ldx; a.Tb = w.Tb + (size_t)b0 * w.tstride; a.ts = w.tstride; a.t_slots = mc / 32;
         a.rows = w.ldx; a.ncols = mc; a.status = c->d_status + b0; a.fail_bit = 4; a.active = act; a.batch = nb;
-        launch_chol_sweep(a, c->st);
+        form |= INGVIO_UPDATE_DENSE_SWEEP | (launch_chol_sweep(a, c->st) ? INGVIO_UPDATE_SPLIT_SWEEP : 0);
         launch_lm_finish(view(c), b0, nb, Y, w.xstride, w.ldx, mc, mc + w.n32, act, d_dx, c->d_status, c->st);
     }
     {
@@ -3485,6 +3484,7 @@ static int run_dense_update(ingvio_ctx* c, int b0, int nb, double var, int r_kin
         if (marg_fused) *marg_fused = fused;
     }
     c->mut_seq++;
+    c->update_form_last = form;
     return last_launch(c);
 }
 
@@ -5031,6 +5031,12 @@ int ingvio_last_apply_form(ingvio_ctx* c)
 {
     if (!c) return INGVIO_E_ARG;
     return c->apply_form_last;
+}
+// route and variants of the last generic update (INGVIO_UPDATE_*); 0 before the first one
+int ingvio_last_update_form(ingvio_ctx* c)
+{
+    if (!c) return INGVIO_E_ARG;
+    return c->update_form_last;
 }
 // which form of the delayed-initialisation front the three entry points take (kernels_delayed.hip)
 int ingvio_set_delayed_form(ingvio_ctx* c, int mode)

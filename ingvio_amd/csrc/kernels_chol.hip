@@ -562,7 +562,7 @@ int dbg_read_chol(long long* out, int n) { return dbg_read_local(out, n); }
 #ifndef GEMM64_MIN_BATCH
 #define GEMM64_MIN_BATCH 8
 #endif
-void launch_gemm(const GemmArgs& g, hipStream_t st)
+int launch_gemm(const GemmArgs& g, hipStream_t st)
 {
     const int nbi = (g.M + 31) / 32, nbj = (g.N + 31) / 32;
     const int blocks = g.lower ? nbi * (nbi + 1) / 2 : nbi * nbj;
@@ -578,13 +578,14 @@ void launch_gemm(const GemmArgs& g, hipStream_t st)
         else if (g.modeA == 0 && g.modeB == 1) hipLaunchKernelGGL((k_gemm64<0, 1>), grid64, dim3(256), 0, st, h);
         else if (g.modeA == 1 && g.modeB == 0) hipLaunchKernelGGL((k_gemm64<1, 0>), grid64, dim3(256), 0, st, h);
         else hipLaunchKernelGGL((k_gemm64<1, 1>), grid64, dim3(256), 0, st, h);
-        return;
+        return 1;
     }
     const dim3 grid(xcd_grid(blocks * h.ksplit, g.batch));             // XCD-aware 1-D order, decoded in the kernel
     if (g.modeA == 0 && g.modeB == 0) hipLaunchKernelGGL((k_gemm<0, 0>), grid, dim3(256), 0, st, h);
     else if (g.modeA == 0 && g.modeB == 1) hipLaunchKernelGGL((k_gemm<0, 1>), grid, dim3(256), 0, st, h);
     else if (g.modeA == 1 && g.modeB == 0) hipLaunchKernelGGL((k_gemm<1, 0>), grid, dim3(256), 0, st, h);
     else hipLaunchKernelGGL((k_gemm<1, 1>), grid, dim3(256), 0, st, h);
+    return 0;
 }
 
 int gram_ksplit(int m, int n)
@@ -603,7 +604,7 @@ void launch_gram(const double* H, int ldh, const double* rv, int m, int n, doubl
     hipLaunchKernelGGL(k_gram_tn, dim3(nb * (nb + 1) / 2, ksplit), dim3(256), 0, st, H, ldh, rv, m, n, part, pstride, n_ld, ksplit);
 }
 
-void launch_chol_sweep(const CholArgs& a0, hipStream_t st)
+int launch_chol_sweep(const CholArgs& a0, hipStream_t st)
 {
     CholArgs a = a0;
     const int ncb = a.ncols / 32;
@@ -629,4 +630,5 @@ void launch_chol_sweep(const CholArgs& a0, hipStream_t st)
         a.rows = rows_all;
         hipLaunchKernelGGL(k_chol_carried, dim3(xcd_grid((rows_all - a.ncols) / 32, a.batch)), dim3(256), lds_row, st, a, (rows_all - a.ncols) / 32);
     }
+    return split ? 1 : 0;
 }

@@ -360,9 +360,26 @@ __global__ __launch_bounds__(256) void k_gamma_multi(CovView cv, int b, const do
                reinterpret_cast<double*>(smem_raw));
 }
 
+static size_t ekf_core_dynamic_lds(int m, int nc)
+{
+    return sizeof(double) * (size_t)(m + 1) * (m + 1) + sizeof(int) * (size_t)nc + 16;
+}
+
+// The dynamic part is not all of it: the compiler gives k_ekf_core 256 bytes of static LDS (the workgroup vote __syncthreads_or).
+// Counting the dynamic bytes alone let m = 142 through (163592 + ... <= 163840) and the dispatch was refused by the hardware queue.
+bool ekf_core_fits(int m, int nc)
+{
+    static const size_t fixed = [] {                           // what the runtime reports for the loaded kernel, never less than measured
+        hipFuncAttributes a;
+        const bool ok = hipFuncGetAttributes(&a, (const void*)k_ekf_core) == hipSuccess;
+        return std::max<size_t>(ok ? a.sharedSizeBytes : 0, 256);
+    }();
+    return ekf_core_dynamic_lds(m, nc) + fixed <= 160 * 1024;
+}
+
 void launch_ekf_core(const EkfLaunch& L, hipStream_t st)
 {
-    const size_t sm = sizeof(double) * (size_t)(L.m_cap + 1) * (L.m_cap + 1) + sizeof(int) * (size_t)L.nc_cap + 16;
+    const size_t sm = ekf_core_dynamic_lds(L.m_cap, L.nc_cap);
     hipFuncSetAttribute((const void*)k_ekf_core, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
     hipLaunchKernelGGL(k_ekf_core, dim3(L.nb), dim3(EKF_THREADS), sm, st, L.cv, L.b0, L.H, L.res, L.colmap, L.m, L.nc,
                        L.noise, L.r_kind, L.mld, L.hstride, L.cstride, L.nstride, L.Y, L.ystride, L.dx, L.status,

@@ -389,13 +389,15 @@ size_t lm_chol_ws_doubles(int mc)
     return (size_t)(tri_tiles(ntm) + ntm) * 256 + (size_t)16 * ntm;
 }
 
-void launch_lm_chol(const LmCholArgs& a, hipStream_t st)
+int launch_lm_chol(const LmCholArgs& a, hipStream_t st)
 {
-    switch (pick_ntm(a.mc)) {
+    const int ntm = pick_ntm(a.mc);
+    switch (ntm) {
     case 4: launch_t<4>(a, st); break;
     case 8: launch_t<8>(a, st); break;
     case 12: launch_t<12>(a, st); break;
     case 14: launch_t<14>(a, st); break;
     default: launch_t<16>(a, st); break;
     }
+    return ntm;
 }

@@ -31,7 +31,7 @@ struct GemmArgs {
     double* Cx; size_t scx; int cx_col;             // optional: column cx_col of the product goes to the VECTOR Cx[batch scx + i] instead of C (a
                                                     // matrix-vector product riding on the GEMM as one more column of opB); Cx == nullptr: off
 };
-void launch_gemm(const GemmArgs& g, hipStream_t st);
+int launch_gemm(const GemmArgs& g, hipStream_t st);      // returns 1 when the product ran on k_gemm64 (64 x 64 blocks), 0 on k_gemm
 
 // Lower triangle of [H | r]^T [H | r] (H m x n column-major, r the extra column n) as `ksplit` partial sums of the K split, each
 // column-major with n_ld rows at part + p * pstride; entries above the diagonal of a 64-block row may be written too.
@@ -57,7 +57,7 @@ struct CholArgs {
     double* Y2; size_t y2s; int ld_y2, y2_row0;  // optional: the CARRIED rows of the result (rows ncols.. of Y) are also written to rows y2_row0.. of Y2 (ld ld_y2,
                                                  // batch stride y2s) - the next sweep's working copy takes them without a copy launch in between
 };
-void launch_chol_sweep(const CholArgs& a, hipStream_t st);
+int launch_chol_sweep(const CholArgs& a, hipStream_t st);      // returns 1 for the split form (carried rows by k_chol_carried), 0 otherwise
 
 // The same solve for S of up to 256 rows with ONE workgroup per filter and S resident in registers (kernels_lmchol.hip): what
 // hundreds of filters want (the sweep above is one memory round trip per 32 x 32 block and launch).  Reads S (whole, symmetric)
@@ -76,6 +76,6 @@ struct LmCholArgs {
     int write_L;                                 // != 0: also write L into rows [0, m) of Y (upper part zero), as the sweep does
 };                                               // res_row < 0: no residual row (no z, no dx)
 size_t lm_chol_ws_doubles(int mc);
-void launch_lm_chol(const LmCholArgs& a, hipStream_t st);
+int launch_lm_chol(const LmCholArgs& a, hipStream_t st);      // returns the tile class NTM (4, 8, 12, 14 or 16) of the kernels it launched
 int dbg_read_lmchol(long long* out, int n);
 int dbg_read_chol(long long* out, int n);

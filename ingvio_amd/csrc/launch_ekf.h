@@ -31,6 +31,9 @@ struct EkfLaunch {
 };
 
 void launch_ekf_core(const EkfLaunch& L, hipStream_t st);
+// k_ekf_core keeps S (+ one border row / column) and the column map in LDS: whether m rows over nc columns fit the 160 KB of a
+// workgroup on gfx950 next to what the kernel holds there statically (in this build up to m = 141, whatever nc)
+bool ekf_core_fits(int m, int nc);
 // ldy / ystride (0: the covariance's ld / L.ystride): leading dimension and per-filter stride of Y when it lives in another workspace
 // marg_idx [nb] (optional, with marg_size): fused marginalisation - where the LDS-blocked variant runs (returns true) the updated
 // covariance goes compacted into the other ping-pong half (launch_post_marg must follow); false: not fused, nothing changed
