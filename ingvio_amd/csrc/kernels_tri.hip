@@ -374,6 +374,9 @@ __global__ __launch_bounds__(TRI_NT) void k_triangulate(TriLaunch L)
 
 }  // namespace
 
+// Eight instantiations, chosen from the CONTEXT's c_max (not from the windows of the call) and the call's feature count.  Seven can be
+// reached: <false, 0, 16> needs a mono c_max above 16 * TRI_NOBS16 = 64 and contexts stop at 36 clones, so it is unreachable while
+// c_max <= 36.  tests/test_gpu_triangulation_classes.py runs the other seven.
 int launch_triangulate(const TriLaunch& L, int nb, int fmax_used, int stereo, hipStream_t st)
 {
     if (L.fv.cmax > TRI_CMAX) return -1;

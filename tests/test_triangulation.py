@@ -182,6 +182,12 @@ def test_gpu_update_with_triangulation_equals_the_two_calls(stereo, selected):
     F, C = 96, 11
     ctx, frames = _frames(stereo, C, F, 1, True, 2e-3, 1200)
     fr = dict(frames[0])
+    # clone 3 looks the other way and observes nothing; every fourth feature is anchored there, so that its point lies behind its anchor
+    away = 3
+    fr["clone_R"] = np.array(fr["clone_R"], dtype=np.float64).reshape(C, 3, 3)
+    fr["clone_R"][away] = fr["clone_R"][away] @ np.diag([-1.0, 1.0, -1.0])
+    fr["obs_mask"] = np.asarray(fr["obs_mask"], dtype=np.uint64) & ~np.uint64(1 << away)
+    fr["anchor"] = np.where(np.arange(F) % 4 == 0, away, 0).astype(np.int32)
     fr["dof"] = np.array([max(1, bin(int(m)).count("1") - 1) for m in fr["obs_mask"]], dtype=np.int32)
     n = int(np.max(fr["clone_idx"])) + 6                    # a state that already holds every clone of the frame (the update alone, no frame step)
     rng = np.random.default_rng(77)
@@ -201,7 +207,7 @@ def test_gpu_update_with_triangulation_equals_the_two_calls(stereo, selected):
             keep.append(j)
         elif ok[0, j]:
             behind.append(j)
-    assert 20 < len(keep) < F
+    assert 20 < len(keep) < F and len(behind) >= 5
     fr2 = dict(fr)
     for k in ("uv", "anchor", "dof"):
         fr2[k] = np.asarray(fr[k])[keep]
