@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib")
-HIP_SOURCES = ["kernels_cov.hip", "kernels_msckf.hip", "kernels_ekf.hip", "kernels_factored.hip", "kernels_solve.hip", "kernels_bigwin.hip", "kernels_tri.hip", "kernels_lm.hip", "kernels_delayed.hip", "kernels_qr.hip", "kernels_chol.hip", "kernels_lmbatch.hip", "kernels_lmchol.hip", "kernels_gnss.hip", "kernels_tracks.hip", "kernels_nominal.hip", "kernels_tail.hip", "kernels_odom.hip", "capi.hip"]
+HIP_SOURCES = ["kernels_cov.hip", "kernels_msckf.hip", "kernels_ekf.hip", "kernels_factored.hip", "kernels_solve.hip", "kernels_bigwin.hip", "kernels_tri.hip", "kernels_lm.hip", "kernels_delayed.hip", "kernels_qr.hip", "kernels_chol.hip", "kernels_lmbatch.hip", "kernels_lmchol.hip", "kernels_gnss.hip", "kernels_tracks.hip", "kernels_nominal.hip", "kernels_tail.hip", "kernels_odom.hip", "capi.hip", "capi_delayed.hip", "capi_nominal.hip"]
 HIP_LIB = os.path.join(LIB, "libingvio_hip.so")
 HOST_LIB = os.path.join(LIB, "libingvio_host.so")
 
@@ -90,34 +90,37 @@ def _write_build_id(out_dir=None, variant_flags=()):
     return src
 
 
-def build_hip(force=False, verbose=False):
-    os.makedirs(LIB, exist_ok=True)
+def _build_lib(out_dir, defines=(), variant_flags=(), force=False, verbose=False):
+    """<out_dir>/libingvio_hip.so: HIP_SOURCES compiled side by side with `defines` (and each file's EXTRA_FLAGS), linked with the
+    build id of `variant_flags`."""
+    os.makedirs(out_dir, exist_ok=True)
+    lib = os.path.join(out_dir, "libingvio_hip.so")
     deps = _all_deps([CSRC, os.path.join(os.path.dirname(HERE), "include")])
-    objs, cmds = [], []
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    bid_src = _write_build_id()
-    bid_obj = os.path.join(LIB, "build_id.o")
-    if force or _newer(bid_obj, [bid_src]):
-        subprocess.check_call(["g++", "-O1", "-fPIC", "-c", bid_src, "-o", bid_obj])
+    objs, cmds = [], []
     for src in HIP_SOURCES:
-        obj = os.path.join(LIB, src.replace(".hip", ".o"))
+        obj = os.path.join(out_dir, src.replace(".hip", ".o"))
         objs.append(obj)
         if force or _newer(obj, deps):
-            cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value",
-                   ] + EXTRA_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
-            if os.environ.get("INGVIO_DBG_STAMPS"):
-                cmd.insert(1, "-DINGVIO_DBG_STAMPS")
+            cmds.append([hipcc] + list(defines) + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
+                        + EXTRA_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj])
             if verbose:
-                print(" ".join(cmd))
-            cmds.append(cmd)
+                print(" ".join(cmds[-1]))
     if cmds:                                    # the translation units are independent: compile them side by side
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=min(len(cmds), os.cpu_count() or 4)) as ex:
             list(ex.map(subprocess.check_call, cmds))
-    if force or _newer(HIP_LIB, objs + [bid_obj]):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", HIP_LIB] + objs + [bid_obj]
-        subprocess.check_call(cmd)
-    return HIP_LIB
+    bid_src = _write_build_id(out_dir, variant_flags)
+    bid_obj = os.path.join(out_dir, "build_id.o")
+    if force or _newer(bid_obj, [bid_src]):
+        subprocess.check_call(["g++", "-O1", "-fPIC", "-c", bid_src, "-o", bid_obj])
+    if force or _newer(lib, objs + [bid_obj]):
+        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [bid_obj])
+    return lib
+
+
+def build_hip(force=False, verbose=False):
+    return _build_lib(LIB, ["-DINGVIO_DBG_STAMPS"] if os.environ.get("INGVIO_DBG_STAMPS") else [], (), force, verbose)
 
 
 def build_alt(force=False, verbose=False):
@@ -125,29 +128,8 @@ def build_alt(force=False, verbose=False):
     the forced code-path switches (INGVIO_GATE=3, INGVIO_INFO_SOLVE=gj, INGVIO_BIG_SOLVE=regs|gj, INGVIO_BIG_APPLY=o|3|6, INGVIO_APPLY_TW=2,
     INGVIO_INFO_GAUGE=off, INGVIO_LM_FRONT=split, INGVIO_LM_SOLVE=sweep, INGVIO_GRAM_CHUNKS, INGVIO_P_PAD, INGVIO_MSCKF_METHOD) that the product
     library no longer carries (VERDICT r04 #7).  tests/test_gpu_alternatives.py loads it through INGVIO_HIP_LIB."""
-    out = os.path.join(os.path.dirname(HERE), "build_var", "alt")
-    os.makedirs(out, exist_ok=True)
-    lib = os.path.join(out, "libingvio_hip.so")
-    deps = _all_deps([CSRC, os.path.join(os.path.dirname(HERE), "include")])
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs, cmds = [], []
-    for src in HIP_SOURCES:
-        obj = os.path.join(out, src.replace(".hip", ".o"))
-        objs.append(obj)
-        if force or _newer(obj, deps):
-            cmds.append([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-DINGVIO_ALT_KERNELS"]
-                        + EXTRA_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj])
-    if cmds:
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=min(len(cmds), os.cpu_count() or 4)) as ex:
-            list(ex.map(subprocess.check_call, cmds))
-    bid_src = _write_build_id(out, ("-DINGVIO_ALT_KERNELS",))
-    bid_obj = os.path.join(out, "build_id.o")
-    if force or _newer(bid_obj, [bid_src]):
-        subprocess.check_call(["g++", "-O1", "-fPIC", "-c", bid_src, "-o", bid_obj])
-    if force or _newer(lib, objs + [bid_obj]):
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [bid_obj])
-    return lib
+    flags = ["-DINGVIO_ALT_KERNELS"]
+    return _build_lib(os.path.join(os.path.dirname(HERE), "build_var", "alt"), flags, tuple(flags), force, verbose)
 
 
 def build_host(force=False, verbose=False):

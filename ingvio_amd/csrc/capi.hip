@@ -1,304 +1,17 @@
 // capi.hip — the C ABI of libingvio_hip.so (include/ingvio_hip.h): context, staging, launches.
-// Host code only; kernels live in kernels_{cov,msckf,ekf}.hip.  gfx950 only, no CPU fallback:
+// (The delayed initialisations: capi_delayed.hip; nominal table, odometry, tail: capi_nominal.hip.)  gfx950 only, no CPU fallback:
 // every entry point fails with INGVIO_E_HIP if the HIP runtime has no device.
-#include "../../include/ingvio_hip.h"
-#include "dev_common.h"
-#include "launch_ekf.h"
-#include "launch_msckf.h"
-#include "launch_factored.h"
-#include "launch_tri.h"
-#include "launch_tracks.h"
-#include "launch_lm.h"
-#include "launch_delayed.h"
-#include "launch_qr.h"
-#include "launch_chol.h"
-#include "launch_gnss.h"
-#include "launch_lmbatch.h"
-#include "launch_nominal.h"
-#include "launch_tail.h"
-#include "launch_odom.h"
+#include "capi_internal.h"
 
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <unistd.h>
-#include <string>
-#include <atomic>
-#include <cmath>
 #include <condition_variable>
-#include <functional>
 #include <mutex>
-#include <thread>
-#include <utility>
-#include <vector>
 
 #define KMAX 64            // IMU steps per fused propagation call
-#ifndef UPLOAD_KERNEL_MAX      // host-to-device uploads up to this size travel as a kernel reading the pinned slab (Uploader::copy)
-#define UPLOAD_KERNEL_MAX (256u << 10)
-#endif
 #define IMU_SLAB_NB 4      // ingvio_propagate(_fused) for up to this many filters: inputs travel as one copy (ingvio_ctx::d_imu)
 #define CHI2_CAP 1024
 
-namespace {
-
-enum ProfId { PF_RESTORE, PF_PROPAGATE, PF_AUGMENT, PF_GATE, PF_FOLD, PF_MERGE, PF_EKF_CORE, PF_DOWNDATE, PF_MARG,
-              PF_GATE2, PF_GRAM, PF_INFO, PF_APPLY, PF_ROWGATE, PF_LM_BUILD, PF_LM_GEMM, PF_LM_CHOL, PF_POSTCOLS, PF_COUNT };
-const char* kProfNames[PF_COUNT] = { "restore", "k_propagate", "k_augment", "k_msckf_gate", "k_msckf_fold",
-                                     "k_msckf_merge", "k_ekf_core", "k_downdate", "k_marginalize",
-                                     "gate", "gram", "solve", "apply", "k_rows_gate",      // stage slots: bench.py names the kernel that ran
-                                     "k_lm_build", "k_lm_gemm", "k_lm_chol", "k_post_cols" };
-struct ProfRec { int id; hipEvent_t a, b; };
-
-}  // namespace
-
-struct ingvio_ctx {
-    ingvio_ctx_desc d;
-    int ldp, mld, nc_cap, G, rstride, hstride, cstride, ystride;
-    int cls;                       // CMAX class of the MSCKF kernels
-    hipStream_t st;
-    bool own_stream;
-    std::string err;
-    // covariances
-    double *Pbase, *Psnap;
-    size_t pp = 0;                 // doubles between consecutive filters' covariances (ldp * ldp + pad)
-    int *d_cur, *d_n, *d_n_snap;
-    std::vector<int> h_n, h_cur, h_n_snap;
-    bool has_snap;
-    // partial restore: valid while half 0 still equals the snapshot outside the propagation strips, i.e. right after a
-    // fused frame step that began with a restore; any other use of the covariance (view()) invalidates it
-    int prof_only = -1;          // >= 0: only this kernel id is bracketed by events (ingvio_profile_select)
-    bool strip_ok = false;
-    std::vector<int> h_nclones;      // per filter: n_clones of the staged frame (picks the window class of the MSCKF kernels)
-    // ingvio_gnss_sat_eval's device buffers, grown on demand and kept (psr_pos / dopp_vel call it once per Gauss-Newton iteration,
-    // the aligner once per buffered epoch: per-call hipMalloc / hipFree were hundreds of implicit device syncs)
-    struct { double *e = nullptr, *o = nullptr, *r = nullptr, *f = nullptr; int cap = 0; } se;
-    bool phase_restore = false;      // the pending split step was started with restore_prior
-    unsigned long long mut_seq = 0, strip_seq = 0;
-    // propagation / structure staging
-    double *d_Phi, *d_G, *d_dt, *d_R, *d_blk;      // d_Phi / d_G / d_dt of the frame path: filter b's steps at b * KMAX (fixed slots)
-    double* d_prm = nullptr;                        // [B][8] per-filter IMU parameters of the staged frame: sigma[4], sigma_cb, sigma_rw, k, 0
-    int *d_gnss, *d_idx;
-    int* d_zero_idx = nullptr;      // [B] zeros: "marginalise nothing at 0" = an out-of-place write-back without compaction (frame with landmarks)
-    // frame staging
-    char* d_result_slab = nullptr;                     // d_dx | d_gamma | d_used | d_m | d_status are views into it; h_result: pinned mirror
-    char* h_result = nullptr;
-    size_t result_bytes = 0, ro_gam = 0, ro_used = 0, ro_m = 0, ro_st = 0, ro_tok = 0, ro_tpf = 0;      // ro_tok / ro_tpf: triangulation flags and points (ingvio_msckf_update_tri)
-    char* d_frame_slab[2] = { nullptr, nullptr };      // the frame arrays below are views into these (frame_slab_carve); [1]: the async set
-    int *d_clone_idx, *d_nclones, *d_nfeat, *d_anchor, *d_dof;
-    double *d_clone_R, *d_clone_p, *d_pf, *d_uv, *d_chi2;
-    unsigned long long* d_mask;
-    // msckf / ekf workspaces
-    double *d_gamma, *d_Rpart, *d_H, *d_res, *d_noise, *d_noise1, *d_Y, *d_Yc, *d_dx, *d_rec, *d_hnew;
-    int method;                    // 0 dense TSQR path, 1 factored (information-form) path
-    int *d_accept, *d_used, *d_chunk_used, *d_colmap, *d_m, *d_nc, *d_status, *d_pcbase;
-    double *d_big_sg, *d_big_wk;        // large-window workspaces (c_max > 16)
-    double* d_Asum = nullptr;           // [B][rstride]: the chunk partials of a filter summed (k_chunk_sum), windows up to 16 clones with G > 1
-    int* d_used_sum = nullptr;          // [B]
-    // what d_chi2 and d_noise hold (single-filter latency: an update re-sent the same gate table and the same noise variance with every
-    // call, two host-to-device copies of ~7 us each in front of the kernels); invalidated by every other writer of those buffers
-    struct { std::vector<double> chi2; bool chi2_ok = false; double var = 0.0; int b0 = -1, nb = 0; bool noise_ok = false; } upc;
-    int apply_flipped = 0;              // set by run_msckf_factored: the fused marginalisation's flip (cur, n) was done by the write-back kernel itself (k_info_apply)
-    bool fork_recorded = false;         // large windows: ev_fork already recorded on the main stream by the caller of run_msckf_factored
-    unsigned long long* d_tri_mask = nullptr;      // [B][f_max], allocated on first use: triangulation masks of ingvio_msckf_update_tri
-    char* d_imu = nullptr;              // [IMU_SLAB_NB filters] Phi | G | dt | gnss_idx of ingvio_propagate(_fused) in one piece (few filters per call)
-    double* d_Tflat = nullptr;          // [min(B, APPLY_FLAT_NB)][ldp * 100]: T of the few-filter apply (k_apply_T_flat), windows up to 16 clones
-
-    int* d_tri_ok;                      // [B][f_max] triangulation flags
-    // ingvio_qr_compress, general path: device buffers and the captured launch sequence (~300 kernels) of the last shape
-    struct QrCache { int m = 0, n = 0, ldh = 0, chol = 0; double *dA = nullptr, *db = nullptr, *ws = nullptr, *dT = nullptr; hipGraphExec_t exec = nullptr; } qr;
-    int qr_method = 0;                  // ingvio_set_qr_method: 0 auto, 1 Householder, 2 Cholesky-QR
-    double* d_noiseB = nullptr;         // ingvio_ekf_update_batch: [B][mld] scalar / diagonal noise per filter
-    // ingvio_gnss_stage / _run / _fetch: the staged candidate rows of the batch (pristine: every run gates and compacts them
-    // into the generic update's working buffers d_H / d_res / d_noiseB)
-    struct GnssStage {
-        double *H = nullptr, *res = nullptr, *noise = nullptr, *gamma = nullptr, *chi2 = nullptr;
-        int *m = nullptr, *nc = nullptr, *colmap = nullptr, *keep = nullptr;
-        double *feph = nullptr, *fobs = nullptr, *frcv = nullptr, *front = nullptr;      // ingvio_gnss_front_stage inputs / per-satellite results
-        int ncw = 0, m_cap = 0, n_vars_hi = 0, chi2_len = 0, gate_rows = 0, strong = 0;
-        double thr1 = 0.0;
-        std::vector<int> hi;            // per filter: highest state index named by the staged var_order (+1)
-        bool staged = false;
-        // in-frame stage (ingvio_gnss_opts::in_frame): applied by ingvio_frame_run.  W [B][ldp * 16]: the var_order columns of the MSCKF
-        // posterior (k_post_cols); Yf [B][ldp * 16]: the update's Cholesky-form gain, folded into k_info_apply; its own working rows
-        // count / column count / dx (the frame's m, nc and dx slots belong to the MSCKF update)
-        bool in_frame = false, fused_last = false;
-        bool folded_last = false;      // the update that ran last rode on the MSCKF write-back (ingvio_debug_gnss_fused_last)
-        bool results = false;           // an update has run on the current stage: ingvio_gnss_fetch has something to return.  A non-restoring
-                                        // ingvio_frame_run CONSUMES an in-frame stage (staged = false, as it does a landmark stage: the rows
-                                        // belong to one frame); its results stay fetchable until the next stage
-        int nc_max = 0;
-        double *W = nullptr, *Yf = nullptr, *dxf = nullptr;
-        int *mf = nullptr, *ncf = nullptr;
-        // stage from the device nominal state (ingvio_gnss_front_stage_nominal): its run keeps row count, column count, dx
-        // AND status apart from the frame's (stf [B]), ends with the retraction of the table and therefore runs once
-        // own_status: the status words of the update that ran last are in stf, not in the frame's d_status.  Set by the nominal
-        // ingvio_gnss_run and kept after it, so that ingvio_gnss_fetch reads the right words for as long as those results are the
-        // current ones; cleared by the next stage of any form (ingvio_gnss_stage, both front stages).
-        bool nominal = false, nom_pending = false, own_status = false;
-        // frame_nom: the raw epoch of the frame staged from the table (ingvio_gnss_frame_stage_nominal): in_frame and nominal, its front
-        // runs inside ingvio_frame_run (the rows exist only there); hi holds the column range BEFORE the frame's marginalisation
-        bool frame_nom = false;
-        int nom_b0 = 0, nom_nb = 0;
-        int* stf = nullptr;
-    } gn;
-    // dense-H update workspace (kernels_lmbatch.hip + kernels_chol.hip): the batched landmark update and generic updates whose S
-    // does not fit in LDS.  Rows live in Hd [m_cap][n_ld] per filter, the sweep in X / Y [ldx][m_cap].
-    struct DenseWs {
-        double *Hd = nullptr, *X = nullptr, *Y = nullptr, *Tb = nullptr, *U = nullptr, *noise = nullptr, *noiseB = nullptr;      // U: factor tiles of the register-resident solve (m_cap <= 256); noise: one filter's R (ingvio_ekf_update); noiseB [B][m_cap]: scalar / diagonal R per filter (batch)
-        int *m = nullptr, *cidx = nullptr, *rowmap = nullptr;      // rowmap [B][m_cap]: the landmark front's accepted rows (k_lm_front)
-        int m_cap = 0, n_ld = 0, n32 = 0, ldx = 0;
-        size_t hstride = 0, xstride = 0, tstride = 0, ustride = 0;
-    } dw;
-    struct LmStage {
-        double *pose = nullptr, *pf = nullptr, *uv = nullptr, *gamma = nullptr, *dx = nullptr;      // dx: its own [B][ldp] (the frame's MSCKF dx stays in d_dx)
-        int *idx = nullptr, *n_lm = nullptr, *lm_idx = nullptr, *anchor_idx = nullptr, *tracked = nullptr, *accept = nullptr;
-        LmOpts op;
-        int l_hi = 0, in_frame = 0;
-        bool alloc = false, staged = false;
-        // stage from the device nominal state (ingvio_landmark_stage_nominal): only uv / tracked / n_lm and the landmarks'
-        // table slots are uploaded; pose, idx, lm_idx, anchor_idx and pf are filled from the table when the rows are formed
-        // (launch_nominal_gather).  nom_pending: the stand-alone form, staged and not yet run (it runs once: its run moves the table)
-        int* slot = nullptr;            // [B][LM_MAX]
-        bool nominal = false, nom_pending = false;
-        int nom_b0 = 0, nom_nb = 0;
-        std::vector<int> hi;            // per filter: one past the highest state index the staged rows name (re-checked against the live n at run time)
-    } lm;
-    char* d_multi = nullptr;            // ingvio_chi2_gamma_multi: packed blocks (grown on demand)
-    // ingvio_add_variable_delayed_batch (kernels_delayed.hip), grown on demand: the packed candidates of a call, the rows / row
-    // counts its fronts hand to the update kernels, and the results of every round with their pinned mirror
-    struct DelayedWs {
-        char *in = nullptr, *wk = nullptr, *out = nullptr, *h_out = nullptr; size_t in_cap = 0, wk_cap = 0, out_cap = 0;
-        char* ws = nullptr; size_t ws_cap = 0;      // the large form's [H_old | res | T^T] per filter (ingvio_set_delayed_form); no part of a snapshot
-    } dl;
-    size_t multi_cap = 0;
-    // staged frame state
-    int st_stereo, st_enable_gnss, st_fmax_used;
-    std::vector<double> st_prm;    // [B][8] host copy of d_prm (the input set the d_* pointers name)
-    MsckfOpts st_op;
-    std::vector<int> st_gnss;      // [B][5] clock-state indices of the staged steps (a stage with the same ones keeps the strip restore valid)
-    std::vector<int> st_marg;      // per filter marg idx
-    std::vector<int> st_cidx_hi;   // per filter: highest staged clone idx (checked against the live state by frame_run)
-    bool staged;
-    double* d_xchg = nullptr;      // [B][rstride + 8]: [A | b | n_accepted] of the split step's exchange (ingvio_info_reduce / _commit)
-    bool phase_pending = false;    // ingvio_frame_run_phase(.., 1) ran and (.., 2) has not yet: the filters are half-stepped (n + 6, no update)
-    // second set of device input buffers + copy stream (ingvio_frame_stage_async): the inputs of frame i+1 travel over
-    // PCIe while frame i computes; the sets swap roles at every asynchronous stage
-    struct InputSet {
-        double *Phi = nullptr, *G = nullptr, *dt = nullptr, *R = nullptr, *clone_R = nullptr, *clone_p = nullptr, *pf = nullptr, *uv = nullptr,
-               *chi2 = nullptr, *noise = nullptr, *prm = nullptr;
-        int *gnss = nullptr, *idx = nullptr, *clone_idx = nullptr, *nclones = nullptr, *nfeat = nullptr, *anchor = nullptr, *dof = nullptr;
-        unsigned long long* mask = nullptr;
-    } alt;
-    bool alt_ready = false;
-    // large windows: the measurement-independent front of the Kalman solve runs here, under the gate and the Gram kernel (run_msckf_factored)
-    hipStream_t st2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_ref = nullptr;
-    hipEvent_t ev_fetch = nullptr;      // ingvio_frame_fetch_begin / _end
-    int fetch_b0 = 0, fetch_nb = 0;
-    hipStream_t st_copy = nullptr;
-    hipEvent_t ev_copy = nullptr, ev_free[2] = { nullptr, nullptr };      // inputs landed / set no longer read by the compute stream
-    bool copy_pending = false, free_valid[2] = { false, false };
-    int set_id = 0;                                                        // which physical set the d_* pointers name
-    // pinned host staging ring: inputs are packed straight into page-locked memory and copied asynchronously; a slab is
-    // reused only after the copies issued from it have completed (its event), so no call has to synchronise the stream
-    struct PinSlab { char* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool busy = false; };
-    PinSlab pin[4];
-    int pin_next = 0;
-    // Split frame step (round 6): ingvio_frame_run deals the batch to `parts` slices, each with its own stream and
-    // its own chain restore -> propagate -> gate -> Gram -> solve -> apply.  The gates are chained by events (slice p's gate starts
-    // when slice p - 1's has ended; slice 0's when the LAST slice's of the previous step has), so the slices run half a step apart:
-    // the HBM-bound kernels of one slice (apply, propagate, restore) sit under the FP64-bound ones of the other (gate, Gram).
-    // The slices' streams are NOT joined at the end of the call - consecutive steps pipeline; every other entry point that touches
-    // the context joins them first (join_parts, called through enter()).
-    struct PartStream { hipStream_t st = nullptr; hipEvent_t ev_gate = nullptr, ev_apply = nullptr, ev_done = nullptr; };
-    PartStream part[4];
-    int parts_alloc = 0;
-    int parts_req = -1;                 // ingvio_set_frame_parts: -1 automatic, 1 off, 2..4 forced
-    int gram_reduced = 1;               // ingvio_set_gram_reduced: the fused frame step may run k_feat_gram2 in its reduced form
-    int delayed_form = 0;               // ingvio_set_delayed_form: 0 LDS form only, 1 the large form where the LDS form does not fit, 2 the large form everywhere
-    int gram_decoupled = 1;             // ingvio_set_gram_decoupled: the reduced form runs as k_feat_gram3 in the window classes 6 and 11
-    int gram_form_last = 0;             // ingvio_last_gram_form: 0 full, 1 reduced k_feat_gram2, 2 reduced k_feat_gram3
-    int apply_resident = 1;             // ingvio_set_apply_resident: the fused frame step's write-back runs as k_info_apply_res where launch_factored can take it
-    int apply_form_last = 0;            // ingvio_last_apply_form: 0 k_info_apply (or a few-filter / large-window kernel), 1 k_info_apply_res
-    int update_form_last = 0;           // ingvio_last_update_form: route and variants of the last generic update (INGVIO_UPDATE_*)
-    int gram_red_last = 0;              // the chunk partials in d_Rpart come from a reduced Gram launch (ingvio_debug_msckf_info refuses them)
-    bool split_pending = false;         // slices of the last split step may still be running on their own streams
-    hipEvent_t tok_last = nullptr;      // end of the throughput segment issued last (nullptr: none yet / chain broken)
-    hipEvent_t ev_split_fork = nullptr;
-    hipStream_t run_st = nullptr;       // the stream run_msckf_factored and ProfScope issue on (c->st except inside a split step)
-    hipEvent_t tok_wait = nullptr, tok_rec = nullptr;      // run_msckf_factored: wait before / record after its throughput segment (phase 1: gate + Gram, phase 2: apply)
-    // device-resident track store (ingvio_tracks_create / ingvio_frame_stage_tracks, kernels_tracks.hip)
-    struct Tracks { double *uv = nullptr, *pf = nullptr; unsigned long long* mask = nullptr; int t_max = 0; char* stage[2] = { nullptr, nullptr }; size_t stage_cap = 0; } trk;
-    // device-resident nominal state (ingvio_nominal_*, kernels_nominal.hip).  Every change of the integer records (slots,
-    // idx, window list) is decided by the host, so it keeps a mirror of them and validates a stage without a device round trip.
-    struct Nominal {
-        int vmax = 0, ir = 0, dr = 0;
-        int* ih = nullptr; double* dv = nullptr;              // the table (launch_nominal.h)
-        int* ih_snap = nullptr; double* dv_snap = nullptr;    // ingvio_cov_snapshot's copy
-        double* dx = nullptr;                                 // [B][ldp] dx of ingvio_nominal_box_plus
-        std::vector<int> h_ih, h_ih_snap;                     // host mirror of the integer records
-        bool has_snap = false;
-        bool pending = false;                                 // a frame staged from the table has not run yet
-        bool frame = false;                                   // the staged frame came from the table (it runs once)
-        hipEvent_t ev = nullptr; bool ev_valid = false;       // behind the post-frame kernel of the frame enqueued last
-        // update-only frame from the table (ingvio_update_stage_tracks_nominal): no propagation, no new clone; tri_on: its run
-        // triangulates the listed features first (tri: the settings); tri_ran: the result slab holds that run's flags and points
-        bool noprop = false, tri_on = false, tri_ran = false;
-        int tri_fmx = 0;                                      // the largest feature count of the stage that set tri_on
-        bool tri_fetched = false; int tri_b0 = 0, tri_nb = 0; // the pinned result mirror holds a triangulating run's flags and points of this range
-        ingvio_tri_opts tri;
-        int* d_tri_track = nullptr;                           // [B][f_max] track of each listed feature (k_tracks_gather_upd)
-        // the triangulating ORDINARY frame from the table (ingvio_frame_stage_tracks_nominal_tri): tri_place 0 - k_triangulate on the compute
-        // stream in front of the gate, 1 - at the stage behind the gather (the copy stream of an asynchronous stage), flags and points into
-        // d_tri_ok_st / d_tri_pf_st [B][f_max] of its own (the result slab may still wait for the previous frame's fetch); tri_staged: the
-        // staged frame's triangulation was issued that way, its run only copies the two into the result slab
-        int tri_place = 0;
-        bool tri_staged = false;
-        int* d_tri_ok_st = nullptr; double* d_tri_pf_st = nullptr;
-    } nom;
-    // ingvio_nominal_tail (kernels_tail.hip), grown on demand: the uploaded lists, the panel kernel's workspace (transient: nothing in it
-    // outlives the call, so a snapshot has nothing to copy) and the pinned mirror of the verdicts and the new dimensions
-    struct TailWs { char *in = nullptr, *ws = nullptr, *h_out = nullptr; size_t in_cap = 0, ws_cap = 0, out_cap = 0; } tl;
-    // odometry output (ingvio_odom_begin / _end, kernels_odom.hip), allocated by the first _begin: the records [B][ODOM_REC] on the device
-    // and their pinned mirror - its own, h_result is shared between the fetches - with the event behind the copy; one slot pending.
-    // cols / ns / blk: ingvio_cov_get_marginal_batch's column lists and blocks, grown on demand
-    struct OdomOut {
-        double *d = nullptr, *h = nullptr; hipEvent_t ev = nullptr; bool pending = false; int b0 = 0, nb = 0;
-        int *cols = nullptr, *ns = nullptr; double* blk = nullptr; size_t cols_cap = 0, blk_cap = 0;
-    } od;
-    // profiling
-    bool prof;
-    std::vector<ProfRec> recs;
-    double prof_ms[PF_COUNT];
-    int prof_calls[PF_COUNT];
-};
-
-namespace {
-
-#define HIPCHK(ctx, expr)                                                                       \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                    \
-            return INGVIO_E_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
-template <class T>
-int dalloc(ingvio_ctx* c, T** p, size_t count)
-{
-    HIPCHK(c, hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
-    HIPCHK(c, hipMemsetAsync(*p, 0, sizeof(T) * (count ? count : 1), c->st));
-    return 0;
-}
-
-CovView view(ingvio_ctx* c)
-{
-    CovView v;
-    v.Pbase = c->Pbase; v.cur = c->d_cur; v.n = c->d_n; v.ldp = c->ldp; v.B = c->d.batch; v.pstride = c->pp;
-    ++c->mut_seq;
-    return v;
-}
+// ---- the shared helpers capi_internal.h declares ---------------------------------------------------------------------------
+namespace capi {
 
 FrameView fview(ingvio_ctx* c)
 {
@@ -309,27 +22,7 @@ FrameView fview(ingvio_ctx* c)
     return f;
 }
 
-struct ProfScope {
-    ingvio_ctx* c; int id; hipEvent_t a, b; bool on;
-    ProfScope(ingvio_ctx* c_, int id_) : c(c_), id(id_), on(c_->prof && (c_->prof_only < 0 || c_->prof_only == id_))
-    {
-        if (on) { hipEventCreate(&a); hipEventCreate(&b); hipEventRecord(a, c->run_st); }
-    }
-    ~ProfScope()
-    {
-        if (on) { hipEventRecord(b, c->run_st); c->recs.push_back({ id, a, b }); }
-    }
-};
-
-int check_range(ingvio_ctx* c, int b0, int nb)
-{
-    if (!c || b0 < 0 || nb < 1 || b0 + nb > c->d.batch) return INGVIO_E_ARG;
-    return 0;
-}
-
-// Entry points that change (or snapshot) the covariance refuse to run between the two halves of a split frame step
-// (ingvio_frame_run_phase 1 -> 2): the filters are half-stepped there (cloned, not yet updated / marginalised).
-static int phase_busy(ingvio_ctx* c)
+int phase_busy(ingvio_ctx* c)
 {
     if (c && c->phase_pending) {
         c->err = "a split frame step is pending: finish it with ingvio_frame_run_phase(ctx, 0, 2) first";
@@ -358,8 +51,6 @@ int last_launch(ingvio_ctx* c)
     return 0;
 }
 
-// The input set a frame step has read may be refilled (ingvio_frame_stage_async) once the kernels enqueued on the compute stream so
-// far are done with it.
 int release_input_set(ingvio_ctx* c)
 {
     if (!c->alt_ready) return 0;
@@ -368,8 +59,6 @@ int release_input_set(ingvio_ctx* c)
     return 0;
 }
 
-// Split frame step: the compute stream waits for the slices' streams (a device-side wait, the host does not block).  Called by every
-// entry point other than ingvio_frame_run itself before it touches the context.
 int join_parts(ingvio_ctx* c)
 {
     if (!c->split_pending) return 0;
@@ -377,10 +66,7 @@ int join_parts(ingvio_ctx* c)
     c->split_pending = false;
     return release_input_set(c);                   // the slices' input set, once they are done with it
 }
-#define ENTER(c) do { if ((c) && (c)->split_pending && join_parts(c)) return INGVIO_E_HIP; } while (0)
 
-// device-resident nominal state: the event an asynchronous stage from the table waits for, recorded behind every use of the table on
-// the compute stream
 int nom_mark(ingvio_ctx* c)
 {
     if (!c->nom.ev) HIPCHK(c, hipEventCreateWithFlags(&c->nom.ev, hipEventDisableTiming));
@@ -388,10 +74,7 @@ int nom_mark(ingvio_ctx* c)
     c->nom.ev_valid = true;
     return 0;
 }
-NomTable nom_table(ingvio_ctx* c) { return NomTable{ c->nom.ih, c->nom.dv, c->nom.vmax, c->nom.ir, c->nom.dr }; }
-// a GNSS epoch staged from the table (ingvio_gnss_front_stage_nominal) whose update has not run: its rows are linearised at the table's
-// present values, so nothing else may move the table or the covariance's bookkeeping in between
-// (the same holds for a stand-alone landmark update staged from the table, ingvio_landmark_stage_nominal)
+
 int gnss_nom_busy(ingvio_ctx* c, const char* who)
 {
     if (!c || (!c->gn.nom_pending && !c->lm.nom_pending)) return 0;
@@ -400,7 +83,6 @@ int gnss_nom_busy(ingvio_ctx* c, const char* who)
     return 1;
 }
 
-// the marginalisation on the host mirror of filter b's integer record, exactly as k_nominal_update<true> does it on the device
 void nom_mirror_marg(ingvio_ctx* c, int b, int m)
 {
     if (m < 0) return;
@@ -421,110 +103,7 @@ void nom_mirror_marg(ingvio_ctx* c, int b, int m)
     }
 }
 
-int parts_prepare(ingvio_ctx* c, int P)
-{
-    while (c->parts_alloc < P) {
-        auto& q = c->part[c->parts_alloc];
-        HIPCHK(c, hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking));
-        HIPCHK(c, hipEventCreateWithFlags(&q.ev_gate, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&q.ev_apply, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&q.ev_done, hipEventDisableTiming));
-        ++c->parts_alloc;
-    }
-    if (!c->ev_split_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_split_fork, hipEventDisableTiming));
-    return 0;
-}
-
-// INGVIO_RESTORE=pass: ingvio_frame_run(restore_prior) keeps the separate restore pass in front of the propagation (comparison runs)
-static bool no_snap_propagate()
-{
-    static const bool v = [] { const char* e = getenv("INGVIO_RESTORE"); return e && !strcmp(e, "pass"); }();
-    return v;
-}
-
-// INGVIO_FLIP=launch: the fused marginalisation's flip of the halves stays a launch of its own (k_post_marg; comparison runs)
-static bool no_apply_flip()
-{
-    static const bool v = [] { const char* e = getenv("INGVIO_FLIP"); return e && !strcmp(e, "launch"); }();
-    return v;
-}
-
-// ---- pinned staging ------------------------------------------------------------------------------------------------
-struct Uploader {
-    ingvio_ctx* c;
-    hipStream_t stream = nullptr;      // nullptr: the context's compute stream
-    ingvio_ctx::PinSlab* slab = nullptr;
-    size_t off = 0;
-    int rc = 0;
-    int begin(size_t bytes)
-    {
-        slab = &c->pin[c->pin_next];
-        c->pin_next = (c->pin_next + 1) & 3;
-        if (slab->busy) { HIPCHK(c, hipEventSynchronize(slab->ev)); slab->busy = false; }
-        if (slab->cap < bytes) {
-            if (slab->p) hipHostFree(slab->p);
-            slab->p = nullptr; slab->cap = 0;
-            const size_t cap = (bytes + (1u << 20)) & ~((size_t)(1u << 20) - 1);
-            HIPCHK(c, hipHostMalloc((void**)&slab->p, cap, hipHostMallocDefault));
-            memset(slab->p, 0, cap);
-            slab->cap = cap;
-        }
-        if (!slab->ev) HIPCHK(c, hipEventCreateWithFlags(&slab->ev, hipEventDisableTiming));
-        off = 0;
-        return 0;
-    }
-    template <class T>
-    T* take(size_t count)
-    {
-        off = (off + 63) & ~(size_t)63;
-        T* p = reinterpret_cast<T*>(slab->p + off);
-        off += sizeof(T) * count;
-        return p;
-    }
-    template <class T>
-    void copy(T* dst, const T* src, size_t count)
-    {
-        const size_t bytes = sizeof(T) * count;
-        if (!count) return;
-        // small uploads on the compute stream: a kernel that reads the pinned slab (k_upload_words) - no copy-engine hand-over
-        if (!stream && bytes <= UPLOAD_KERNEL_MAX && (bytes & 3) == 0 && (((uintptr_t)dst | (uintptr_t)src) & 3) == 0) {
-            launch_upload_words(dst, src, bytes, c->st);
-            if (hipGetLastError() != hipSuccess) rc = INGVIO_E_HIP;
-            return;
-        }
-        if (hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream ? stream : c->st) != hipSuccess) rc = INGVIO_E_HIP;
-    }
-    // rows of `width` elements at src + r * spitch into dst + r * dpitch: ONE copy (or upload kernel) for a batch of strided rows
-    template <class T>
-    void copy_rows(T* dst, size_t dpitch, const T* src, size_t spitch, size_t width, size_t rows)
-    {
-        if (rows == 1 || (width == spitch && width == dpitch)) { copy(dst, src, rows == 1 ? width : width * rows); return; }
-        const size_t bytes = sizeof(T) * width * rows;
-        if (!width || !rows) return;
-        if (!stream && bytes <= UPLOAD_KERNEL_MAX && ((sizeof(T) * (width | spitch | dpitch)) & 3) == 0 && (((uintptr_t)dst | (uintptr_t)src) & 3) == 0) {
-            launch_upload_rows(dst, sizeof(T) * dpitch, src, sizeof(T) * spitch, sizeof(T) * width, rows, c->st);
-            if (hipGetLastError() != hipSuccess) rc = INGVIO_E_HIP;
-            return;
-        }
-        if (hipMemcpy2DAsync(dst, sizeof(T) * dpitch, src, sizeof(T) * spitch, sizeof(T) * width, rows, hipMemcpyHostToDevice, stream ? stream : c->st) != hipSuccess)
-            rc = INGVIO_E_HIP;
-    }
-    int end()
-    {
-        if (rc) { c->err = "upload from the pinned staging slab failed (hipMemcpyAsync / k_upload_words launch)"; return rc; }
-        HIPCHK(c, hipEventRecord(slab->ev, stream ? stream : c->st));
-        slab->busy = true;
-        return 0;
-    }
-};
-static size_t pad64(size_t b) { return (b + 63) & ~(size_t)63; }
-
-// Small host inputs of the covariance operations that return nothing from the device (propagate, clone, marginalise, append):
-// copied into the pinned ring first, so the call neither reads caller memory after it returns nor has to wait for the stream -
-// a stream synchronisation per call was 15-30 us, four of them made up most of a single filter's 0.09 ms frame (round 4).  A
-// failed launch is reported by the call that made it (hipGetLastError), a device fault by the next synchronising call.
-struct UpItem { void* dst; const void* src; size_t bytes; };
-static int stage_small(ingvio_ctx* c, const UpItem* it, int n)
+int stage_small(ingvio_ctx* c, const UpItem* it, int n)
 {
     size_t tot = 0;
     for (int i = 0; i < n; ++i) tot += pad64(it[i].bytes);
@@ -540,10 +119,48 @@ static int stage_small(ingvio_ctx* c, const UpItem* it, int n)
     return up.end();
 }
 
-// fn(i) for i in [0, n): a few host threads when the batch is large enough to pay for them.  The workers are a process-wide POOL
-// (round 6): spawning seven std::threads per call was ~0.2 ms of a 0.3 ms stage call once the hand-over itself had shrunk to 8 KB per
-// update.  One user at a time; a second caller (another context staging from another host thread) runs its loop with freshly spawned
-// threads as before instead of waiting.
+int dev_grow(ingvio_ctx* c, char** p, size_t* cap, size_t need)
+{
+    if (*cap >= need) return 0;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (*p) hipFree(*p);
+    *p = nullptr; *cap = 0;
+    const size_t bytes = (need + (1u << 20)) & ~((size_t)(1u << 20) - 1);
+    if (dalloc(c, p, bytes)) return INGVIO_E_HIP;
+    *cap = bytes;
+    return 0;
+}
+
+int stage_generic(ingvio_ctx* c, int b, const int* vidx, const int* vsize, int k, const double* H, int ldh, int m,
+                         const double* res, const double* R, int r_kind, int* nc_out)
+{
+    if (check_range(c, b, 1) || !vidx || !vsize || !H || !res || !R || k < 1 || m < 1 || ldh < m) return INGVIO_E_ARG;
+    if (r_kind < 0 || r_kind > 2) return INGVIO_E_ARG;
+    if ((m > c->d.m_max && m > 6 * c->d.c_max) || m > c->mld) return INGVIO_E_CAPACITY;
+    int nc = 0;
+    std::vector<int> cm;
+    for (int i = 0; i < k; ++i) {
+        if (vidx[i] < 0 || vidx[i] + vsize[i] > c->h_n[b]) return INGVIO_E_NOT_IN_STATE;      // checkSubOrder
+        for (int j = 0; j < vsize[i]; ++j) cm.push_back(vidx[i] + j);
+        nc += vsize[i];
+    }
+    if (nc > c->nc_cap) return INGVIO_E_CAPACITY;
+    std::vector<double> Hp((size_t)c->mld * nc, 0.0);
+    for (int cc = 0; cc < nc; ++cc) memcpy(&Hp[(size_t)cc * c->mld], H + (size_t)cc * ldh, 8 * (size_t)m);
+    int rc = up(c, c->d_H + (size_t)b * c->hstride, Hp.data(), 8 * Hp.size());
+    rc |= up(c, c->d_res + (size_t)b * c->mld, res, 8 * (size_t)m);
+    rc |= up(c, c->d_colmap + (size_t)b * c->cstride, cm.data(), sizeof(int) * (size_t)nc);
+    rc |= up(c, c->d_m + b, &m, sizeof(int));
+    rc |= up(c, c->d_nc + b, &nc, sizeof(int));
+    rc |= up(c, c->d_noise1, R, 8 * (size_t)(r_kind == 0 ? 1 : (r_kind == 1 ? m : m * m)));
+    if (rc) return INGVIO_E_HIP;
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    *nc_out = nc;
+    return 0;
+}
+
+// the process-wide worker pool behind parallel_for
+namespace {
 class HostPool {
 public:
     static HostPool& get() { static HostPool p; return p; }
@@ -610,26 +227,51 @@ private:
     unsigned gen_ = 0;
     bool stop_ = false;
 };
+}  // namespace
+bool host_pool_run(int T, const std::function<void(int)>& job) { return HostPool::get().run(T, job); }
 
-template <class F>
-void parallel_for(int n, F fn)
+// the compute stream must not read staged inputs before the copy stream has delivered them
+int wait_inputs(ingvio_ctx* c)
 {
-    unsigned hw = std::thread::hardware_concurrency();
-    int T = (int)(hw ? hw : 1);
-    if (T > 8) T = 8;
-    if (T > n / 16) T = n / 16;
-    if (T <= 1) { for (int i = 0; i < n; ++i) fn(i); return; }
-    const std::function<void(int)> stripe = [&](int t) { for (int i = t; i < n; i += T) fn(i); };
-    if (HostPool::get().run(T, stripe)) return;
-    std::vector<std::thread> th;
-    int started = 1;                                                     // stripe 0 is this thread's
-    try {
-        for (int t = 1; t < T; ++t) { th.emplace_back([=]() { for (int i = t; i < n; i += T) fn(i); }); ++started; }
-    } catch (...) {                                                      // thread limit reached: the stripes not started run here
+    if (c->copy_pending) {
+        HIPCHK(c, hipStreamWaitEvent(c->st, c->ev_copy, 0));
+        c->copy_pending = false;
     }
-    for (int i = 0; i < n; i += T) fn(i);
-    for (int t = started; t < T; ++t) for (int i = t; i < n; i += T) fn(i);
-    for (auto& x : th) x.join();
+    return 0;
+}
+
+}  // namespace capi
+
+using namespace capi;
+
+namespace {
+
+int parts_prepare(ingvio_ctx* c, int P)
+{
+    while (c->parts_alloc < P) {
+        auto& q = c->part[c->parts_alloc];
+        HIPCHK(c, hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking));
+        HIPCHK(c, hipEventCreateWithFlags(&q.ev_gate, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&q.ev_apply, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&q.ev_done, hipEventDisableTiming));
+        ++c->parts_alloc;
+    }
+    if (!c->ev_split_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_split_fork, hipEventDisableTiming));
+    return 0;
+}
+
+// INGVIO_RESTORE=pass: ingvio_frame_run(restore_prior) keeps the separate restore pass in front of the propagation (comparison runs)
+static bool no_snap_propagate()
+{
+    static const bool v = [] { const char* e = getenv("INGVIO_RESTORE"); return e && !strcmp(e, "pass"); }();
+    return v;
+}
+
+// INGVIO_FLIP=launch: the fused marginalisation's flip of the halves stays a launch of its own (k_post_marg; comparison runs)
+static bool no_apply_flip()
+{
+    static const bool v = [] { const char* e = getenv("INGVIO_FLIP"); return e && !strcmp(e, "launch"); }();
+    return v;
 }
 
 // The ten device arrays of a staged frame set live in ONE allocation, laid out exactly as pack_frames lays them out in the pinned
@@ -657,16 +299,6 @@ int frame_slab_alloc(ingvio_ctx* c, char** slab, FrameSlabPtrs* out)
     const size_t bytes = frame_slab_carve(c, nullptr, nullptr);
     if (dalloc(c, slab, bytes)) return INGVIO_E_HIP;
     frame_slab_carve(c, *slab, out);
-    return 0;
-}
-
-// the compute stream must not read staged inputs before the copy stream has delivered them
-int wait_inputs(ingvio_ctx* c)
-{
-    if (c->copy_pending) {
-        HIPCHK(c, hipStreamWaitEvent(c->st, c->ev_copy, 0));
-        c->copy_pending = false;
-    }
     return 0;
 }
 
@@ -1292,15 +924,12 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
                      c->d_chi2, c->d_result_slab, c->d_accept, c->d_Rpart, c->d_chunk_used,
                      c->d_H, c->d_res, c->d_colmap, c->d_nc, c->d_noise, c->d_noise1, c->d_Y, c->d_Yc, c->d_rec, c->d_pcbase, c->d_big_sg, c->d_big_wk, c->d_tri_ok, c->d_hnew, c->d_multi, c->d_noiseB,
                      c->gn.H, c->gn.res, c->gn.noise, c->gn.gamma, c->gn.chi2, c->gn.m, c->gn.nc, c->gn.colmap, c->gn.keep,
-                     c->gn.feph, c->gn.fobs, c->gn.frcv, c->gn.front,
+                     c->gn.feph, c->gn.fobs, c->gn.frcv, c->gn.front, c->gn.stf,
                      c->dw.Hd, c->dw.X, c->dw.Y, c->dw.Tb, c->dw.noise, c->dw.noiseB, c->dw.m, c->dw.cidx, c->lm.pose, c->lm.pf, c->lm.uv, c->lm.gamma, c->lm.idx, c->lm.n_lm,
                      c->lm.lm_idx, c->lm.anchor_idx, c->lm.tracked, c->lm.accept, c->lm.slot, c->lm.dx, c->d_xchg, c->dw.U, c->dw.rowmap, c->d_zero_idx,
                      c->d_Asum, c->d_used_sum, c->d_Tflat, c->d_imu, c->d_tri_mask, c->d_prm };
     for (void* p : ptrs) if (p) hipFree(p);
-    for (void* p : { (void*)c->dl.in, (void*)c->dl.wk, (void*)c->dl.out, (void*)c->dl.ws }) if (p) hipFree(p);
-    if (c->dl.h_out) hipHostFree(c->dl.h_out);
-    for (void* p : { (void*)c->tl.in, (void*)c->tl.ws }) if (p) hipFree(p);
-    if (c->tl.h_out) hipHostFree(c->tl.h_out);
+    c->dl.release(); c->tl.release(); c->od.release(); c->nom.release();
     for (auto& sl : c->pin) { if (sl.p) hipHostFree(sl.p); if (sl.ev) hipEventDestroy(sl.ev); }
     if (c->h_result) hipHostFree(c->h_result);
     if (c->qr.exec) hipGraphExecDestroy(c->qr.exec);
@@ -1315,12 +944,6 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
         for (auto e : c->ev_free) if (e) hipEventDestroy(e);
     }
     for (void* p : { (void*)c->trk.uv, (void*)c->trk.pf, (void*)c->trk.mask, (void*)c->trk.stage[0], (void*)c->trk.stage[1] }) if (p) hipFree(p);
-    for (void* p : { (void*)c->nom.ih, (void*)c->nom.dv, (void*)c->nom.ih_snap, (void*)c->nom.dv_snap, (void*)c->nom.dx, (void*)c->nom.d_tri_track,
-                     (void*)c->nom.d_tri_ok_st, (void*)c->nom.d_tri_pf_st }) if (p) hipFree(p);
-    if (c->nom.ev) hipEventDestroy(c->nom.ev);
-    for (void* p : { (void*)c->od.d, (void*)c->od.cols, (void*)c->od.ns, (void*)c->od.blk }) if (p) hipFree(p);
-    if (c->od.h) hipHostFree(c->od.h);
-    if (c->od.ev) hipEventDestroy(c->od.ev);
     for (auto& r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (int p = 0; p < c->parts_alloc; ++p) { hipStreamDestroy(c->part[p].st); hipEventDestroy(c->part[p].ev_gate); hipEventDestroy(c->part[p].ev_apply); hipEventDestroy(c->part[p].ev_done); }
     if (c->ev_split_fork) hipEventDestroy(c->ev_split_fork);
@@ -1407,14 +1030,6 @@ int ingvio_cov_get_marginal(ingvio_ctx* c, int b, const int* vidx, const int* vs
         r0 += vsize[a];
     }
     return INGVIO_OK;
-}
-
-// The read-only view of the covariances: view() counts a use that may change P (it ends the validity of the propagation strips).
-static CovView view_ro(ingvio_ctx* c)
-{
-    CovView v;
-    v.Pbase = c->Pbase; v.cur = c->d_cur; v.n = c->d_n; v.ldp = c->ldp; v.B = c->d.batch; v.pstride = c->pp;
-    return v;
 }
 
 int ingvio_cov_get_marginal_batch(ingvio_ctx* c, int b0, int nb, const int* vidx, const int* vsize, int k, int ns_max, double* out)
@@ -1642,35 +1257,7 @@ static int ekf_update_dense_route(ingvio_ctx* c, int b, const int* vidx, const i
     int status = 0;
     if (dx_out && down_sync(c, dx_out, c->d_dx + (size_t)b * c->ldp, 8 * (size_t)c->h_n[b])) return INGVIO_E_HIP;
     if (down_sync(c, &status, c->d_status + b, sizeof(int))) return INGVIO_E_HIP;
-    return (status & 4) ? INGVIO_E_NOT_PD : ((status & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
-}
-
-static int stage_generic(ingvio_ctx* c, int b, const int* vidx, const int* vsize, int k, const double* H, int ldh, int m,
-                         const double* res, const double* R, int r_kind, int* nc_out)
-{
-    if (check_range(c, b, 1) || !vidx || !vsize || !H || !res || !R || k < 1 || m < 1 || ldh < m) return INGVIO_E_ARG;
-    if (r_kind < 0 || r_kind > 2) return INGVIO_E_ARG;
-    if ((m > c->d.m_max && m > 6 * c->d.c_max) || m > c->mld) return INGVIO_E_CAPACITY;
-    int nc = 0;
-    std::vector<int> cm;
-    for (int i = 0; i < k; ++i) {
-        if (vidx[i] < 0 || vidx[i] + vsize[i] > c->h_n[b]) return INGVIO_E_NOT_IN_STATE;      // checkSubOrder
-        for (int j = 0; j < vsize[i]; ++j) cm.push_back(vidx[i] + j);
-        nc += vsize[i];
-    }
-    if (nc > c->nc_cap) return INGVIO_E_CAPACITY;
-    std::vector<double> Hp((size_t)c->mld * nc, 0.0);
-    for (int cc = 0; cc < nc; ++cc) memcpy(&Hp[(size_t)cc * c->mld], H + (size_t)cc * ldh, 8 * (size_t)m);
-    int rc = up(c, c->d_H + (size_t)b * c->hstride, Hp.data(), 8 * Hp.size());
-    rc |= up(c, c->d_res + (size_t)b * c->mld, res, 8 * (size_t)m);
-    rc |= up(c, c->d_colmap + (size_t)b * c->cstride, cm.data(), sizeof(int) * (size_t)nc);
-    rc |= up(c, c->d_m + b, &m, sizeof(int));
-    rc |= up(c, c->d_nc + b, &nc, sizeof(int));
-    rc |= up(c, c->d_noise1, R, 8 * (size_t)(r_kind == 0 ? 1 : (r_kind == 1 ? m : m * m)));
-    if (rc) return INGVIO_E_HIP;
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    *nc_out = nc;
-    return 0;
+    return soft_status(status);
 }
 
 int ingvio_ekf_update(ingvio_ctx* c, int b, const int* vidx, const int* vsize, int k, const double* H, int ldh, int m,
@@ -1705,7 +1292,7 @@ int ingvio_ekf_update(ingvio_ctx* c, int b, const int* vidx, const int* vsize, i
     if (down_sync(c, &status, c->d_status + b, sizeof(int))) return INGVIO_E_HIP;
     rc = last_launch(c);
     if (rc) return rc;
-    return (status & 4) ? INGVIO_E_NOT_PD : ((status & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
+    return soft_status(status);
 }
 
 // ekfUpdate for filters [b0, b0+nb) in one launch and one synchronisation (the GNSS update of a whole batch, config 3 x 4):
@@ -1772,7 +1359,7 @@ int ingvio_ekf_update_batch(ingvio_ctx* c, int b0, int nb, const ingvio_update_b
         if (down_sync(c, status.data(), c->d_status + b0, sizeof(int) * (size_t)nb)) return INGVIO_E_HIP;
         int soft = INGVIO_OK;
         for (int i = 0; i < nb; ++i) {
-            const int st = (status[i] & 4) ? INGVIO_E_NOT_PD : ((status[i] & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
+            const int st = soft_status(status[i]);
             if (status_out) status_out[i] = st;
             if (st != INGVIO_OK) soft = st;
         }
@@ -1828,7 +1415,7 @@ int ingvio_ekf_update_batch(ingvio_ctx* c, int b0, int nb, const ingvio_update_b
     if (rc) return rc;
     int soft = INGVIO_OK;
     for (int i = 0; i < nb; ++i) {
-        const int st = (status[i] & 4) ? INGVIO_E_NOT_PD : ((status[i] & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
+        const int st = soft_status(status[i]);
         if (status_out) status_out[i] = st;
         if (st != INGVIO_OK) soft = st;
     }
@@ -2058,12 +1645,6 @@ int ingvio_gnss_front_stage(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epo
 {
     ENTER(c);
     return gnss_front_stage_impl(c, b0, nb, ep, o, false);
-}
-
-// the host mirror of filter b's integer record: idx of the variable in slot `slot` (-1: none)
-static int nom_idx_of(const ingvio_ctx* c, int b, int slot)
-{
-    return slot >= 0 ? c->nom.h_ih[(size_t)b * c->nom.ir + NOM_IH + 4 * slot + 1] : -1;
 }
 
 int ingvio_gnss_front_stage_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_epoch_nominal* ep, const ingvio_gnss_opts* o)
@@ -2355,7 +1936,7 @@ int ingvio_gnss_fetch(ingvio_ctx* c, int b0, int nb, double* dx_out, int* rows_o
     if (rc) return rc;
     int soft = INGVIO_OK;
     for (int i = 0; i < nb; ++i) {
-        const int st = (status[i] & 8) ? INGVIO_REJECTED : ((status[i] & 4) ? INGVIO_E_NOT_PD : ((status[i] & 2) ? INGVIO_NEG_DIAG : INGVIO_OK));
+        const int st = (status[i] & 8) ? INGVIO_REJECTED : soft_status(status[i]);
         if (status_out) status_out[i] = st;
         if (st == INGVIO_NEG_DIAG) soft = st;
     }
@@ -2414,13 +1995,7 @@ int ingvio_chi2_gamma_multi(ingvio_ctx* c, int b, int nblk, const ingvio_gate_bl
     if (lds > 150 * 1024) return INGVIO_E_CAPACITY;
     const size_t bytes_d = pad64(8 * nd), bytes_i = pad64(4 * ni), bytes_desc = pad64(4 * 5 * (size_t)nblk), bytes_g = pad64(8 * (size_t)nblk);
     const size_t total = bytes_d + bytes_i + bytes_desc + bytes_g;
-    if (c->multi_cap < total) {
-        HIPCHK(c, hipStreamSynchronize(c->st));
-        if (c->d_multi) hipFree(c->d_multi);
-        c->d_multi = nullptr; c->multi_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_multi, total * 2));
-        c->multi_cap = total * 2;
-    }
+    if (c->multi_cap < total) if (int rc = dev_grow(c, &c->d_multi, &c->multi_cap, total * 2)) return rc;
     Uploader upl{ c };
     int rc = upl.begin(total + 1024);
     if (rc) return rc;
@@ -2557,799 +2132,6 @@ int ingvio_msckf_update_tri(ingvio_ctx* c, int b0, int nb, const ingvio_msckf_fr
 }
 
 // ---- SLAM-landmark covariance operations -------------------------------------------------------
-static int stage_hnew(ingvio_ctx* c, const double* H_new, int ldn, int m, int s)
-{
-    if (!H_new || s < 1 || s > 6 || ldn < m || m > c->mld) return INGVIO_E_ARG;
-    std::vector<double> Hn((size_t)c->mld * s, 0.0);
-    for (int j = 0; j < s; ++j) memcpy(&Hn[(size_t)j * c->mld], H_new + (size_t)j * ldn, 8 * (size_t)m);
-    if (up(c, c->d_hnew, Hn.data(), 8 * Hn.size())) return INGVIO_E_HIP;
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    return 0;
-}
-
-int ingvio_add_variable_delayed_invertible(ingvio_ctx* c, int b, const int* vidx, const int* vsize, int k, const double* H_old, int ldh,
-                                           const double* H_new, int ldn, int s, double noise, int* new_idx)
-{
-    ENTER(c);
-    if (phase_busy(c)) return INGVIO_E_ARG;
-    if (check_range(c, b, 1)) return INGVIO_E_ARG;
-    if (c->h_n[b] + s > c->d.n_max) return INGVIO_E_CAPACITY;
-    int nc = 0;
-    const double var = noise * noise;
-    std::vector<double> zero((size_t)(s > 0 ? s : 1), 0.0);
-    int rc = stage_generic(c, b, vidx, vsize, k, H_old, ldh, s, zero.data(), &var, 0, &nc);
-    if (rc) return rc;
-    rc = stage_hnew(c, H_new, ldn, s, s);
-    if (rc) return rc;
-    if (launch_delayed_add(view(c), b, c->d_H + (size_t)b * c->hstride, c->d_hnew, c->d_colmap + (size_t)b * c->cstride, s, nc, c->mld,
-                           var, c->d_Y + (size_t)b * c->ystride, c->st)) return INGVIO_E_CAPACITY;
-    if (new_idx) *new_idx = c->h_n[b];
-    c->h_n[b] += s;
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    return last_launch(c);
-}
-
-int ingvio_add_variable_delayed(ingvio_ctx* c, int b, const int* vidx, const int* vsize, int k, const double* H_old, int ldh,
-                                const double* H_new, int ldn, int m, int s, const double* res, double noise, double chi2_mult,
-                                int do_chi2, double chi2_check, double* dx_out, int* added, int* new_idx, double* chi2_out)
-{
-    ENTER(c);
-    if (phase_busy(c)) return INGVIO_E_ARG;
-    if (check_range(c, b, 1) || !added) return INGVIO_E_ARG;
-    *added = 0;
-    if (m <= s) return INGVIO_OK;                                                  // StateManager.cpp:571-575
-    if (c->h_n[b] + s > c->d.n_max) return INGVIO_E_CAPACITY;
-    if (c->delayed_form && vidx && vsize && k >= 1) {
-        // ingvio_set_delayed_form: a candidate beyond the gate's bound (mode 2: every candidate) runs as a one-filter call of the batch path
-        size_t ncq = 0;
-        for (int t = 0; t < k; ++t) ncq += vsize[t] > 0 ? vsize[t] : 0;
-        const size_t muq = (size_t)(m - s);
-        if (c->delayed_form == 2 || 8 * (ncq * muq + (muq + 1) * (muq + 1)) > 150 * 1024) {
-            const ingvio_delayed_cand q{ vidx, vsize, k, H_old, ldh, H_new, ldn, res, m, s, chi2_check };
-            const ingvio_delayed_block blk{ 1, &q };
-            std::vector<double> dxb(dx_out ? (size_t)c->ldp : 0);
-            int idx = -1, st = INGVIO_OK;
-            double chi2 = 0.0;
-            const int rc = ingvio_add_variable_delayed_batch(c, b, 1, &blk, noise, chi2_mult, do_chi2, 1, added, &idx, &chi2, dx_out ? dxb.data() : nullptr, &st);
-            if (chi2_out && (rc == INGVIO_OK || rc == INGVIO_NEG_DIAG || rc == INGVIO_E_NOT_PD)) *chi2_out = chi2;
-            if (*added) {
-                if (new_idx) *new_idx = idx;
-                if (dx_out) memcpy(dx_out, dxb.data(), 8 * (size_t)c->h_n[b]);
-            }
-            return rc;
-        }
-    }
-    int nc = 0;
-    const double var = noise * noise;
-    int rc = stage_generic(c, b, vidx, vsize, k, H_old, ldh, m, res, &var, 0, &nc);
-    if (rc) return rc;
-    rc = stage_hnew(c, H_new, ldn, m, s);
-    if (rc) return rc;
-    if (!ekf_core_fits(m - s, nc)) return INGVIO_E_CAPACITY;     // the trailing EKF update must fit before the state is touched
-    double* dH = c->d_H + (size_t)b * c->hstride;
-    double* dres = c->d_res + (size_t)b * c->mld;
-    const int* dcm = c->d_colmap + (size_t)b * c->cstride;
-    if (launch_delayed_qr(dH, dres, c->d_hnew, m, s, nc, c->mld, c->st)) return INGVIO_E_CAPACITY;      // :577-589
-    const int mu = m - s;
-    if ((size_t)8 * ((size_t)nc * mu + (size_t)(mu + 1) * (mu + 1)) > 150 * 1024) return INGVIO_E_CAPACITY;
-    launch_gamma(view(c), b, dH + s, dres + s, dcm, mu, nc, c->d_noise1, 0, c->mld, c->d_gamma + (size_t)b * c->d.f_max, c->st);   // :601-608
-    double chi2 = 0.0;
-    if (down_sync(c, &chi2, c->d_gamma + (size_t)b * c->d.f_max, 8)) return INGVIO_E_HIP;
-    if (chi2_out) *chi2_out = chi2;
-    if (chi2 > chi2_mult * chi2_check && do_chi2) return last_launch(c);           // :614-618
-    if (launch_delayed_add(view(c), b, dH, c->d_hnew, dcm, s, nc, c->mld, var, c->d_Y + (size_t)b * c->ystride, c->st))
-        return INGVIO_E_CAPACITY;
-    if (new_idx) *new_idx = c->h_n[b];
-    c->h_n[b] += s;
-    *added = 1;
-    // :623-624 ekfUpdate with the lower rows on the extended state
-    int zero = 0;
-    if (up(c, c->d_status + b, &zero, sizeof(int)) || up(c, c->d_m + b, &mu, sizeof(int))) return INGVIO_E_HIP;
-    EkfLaunch E;
-    memset(&E, 0, sizeof E);
-    E.cv = view(c); E.b0 = b; E.nb = 1; E.H = dH + s; E.res = dres + s; E.colmap = dcm; E.m = c->d_m + b; E.nc = c->d_nc + b;
-    E.noise = c->d_noise1; E.r_kind = 0; E.mld = c->mld; E.hstride = c->hstride; E.cstride = c->cstride;
-    E.nstride = c->mld * c->mld; E.Y = c->d_Y + (size_t)b * c->ystride; E.ystride = c->ystride; E.dx = c->d_dx;
-    E.status = c->d_status; E.m_cap = mu; E.nc_cap = nc;
-    launch_ekf_core(E, c->st);
-    launch_downdate(E, c->h_n[b], c->st);
-    int status = 0;
-    if (dx_out && down_sync(c, dx_out, c->d_dx + (size_t)b * c->ldp, 8 * (size_t)c->h_n[b])) return INGVIO_E_HIP;
-    if (down_sync(c, &status, c->d_status + b, sizeof(int))) return INGVIO_E_HIP;
-    rc = last_launch(c);
-    if (rc) return rc;
-    return (status & 4) ? INGVIO_E_NOT_PD : ((status & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
-}
-
-// ---- addVariableDelayed for filters [b0, b0 + nb), several candidates per filter (kernels_delayed.hip) --------------------------
-// Round j = candidate j of every filter that has one: k_delayed_front (rotations, gate, verdict, append) + the batched
-// k_ekf_core / k_downdate on the row counts the front wrote.  Nothing comes back to the host between the rounds.
-static int dl_grow(ingvio_ctx* c, char** p, size_t* cap, size_t need)
-{
-    if (*cap >= need) return 0;
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (*p) hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t bytes = (need + (1u << 20)) & ~((size_t)(1u << 20) - 1);
-    if (dalloc(c, p, bytes)) return INGVIO_E_HIP;
-    *cap = bytes;
-    return 0;
-}
-
-int ingvio_add_variable_delayed_batch(ingvio_ctx* c, int b0, int nb, const ingvio_delayed_block* blocks, double noise, double chi2_mult,
-                                      int do_chi2, int cand_cap, int* added, int* new_idx, double* chi2, double* dx, int* status)
-{
-    ENTER(c);
-    if (phase_busy(c)) return INGVIO_E_ARG;
-    if (check_range(c, b0, nb) || !blocks || cand_cap < 1 || !added || !new_idx) return INGVIO_E_ARG;
-    if (c->nom.pending) { c->err = "ingvio_add_variable_delayed_batch: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
-    if (gnss_nom_busy(c, "ingvio_add_variable_delayed_batch")) return INGVIO_E_ARG;
-    // ---- everything that can be wrong, before anything changes ----
-    int R = 0, mu_cap = 0, nc_cap = 0, n_cap = 0, ldw = 0, ncw = 0;
-    size_t lds = 0, lds_large = 0, dtot = 0;
-    const int form = c->delayed_form;             // ingvio_set_delayed_form
-    for (int i = 0; i < nb; ++i) if (blocks[i].n_cand > R) R = blocks[i].n_cand;      // rounds (a wrong n_cand is refused below)
-    if (R > cand_cap) return INGVIO_E_ARG;
-    const size_t RN = (size_t)R * nb;
-    std::vector<int> ncs(RN, 0);                  // [round][filter]: columns of the candidate, 0 = none / skipped
-    std::vector<char> large(RN, 0);               // [round][filter]: the candidate takes the large form of the front
-    std::vector<int> n_lds(R > 0 ? R : 1, 0), n_large(R > 0 ? R : 1, 0);      // per round: candidates of either form
-    std::vector<size_t> offs(RN, 0);
-    for (int i = 0; i < nb; ++i) {
-        const ingvio_delayed_block& blk = blocks[i];
-        const int b = b0 + i;
-        if (blk.n_cand < 0 || (blk.n_cand > 0 && !blk.cand)) return INGVIO_E_ARG;
-        int grow = 0;
-        for (int j = 0; j < blk.n_cand; ++j) {
-            const ingvio_delayed_cand& q = blk.cand[j];
-            if (q.s < 1 || q.s > 6 || q.m < 0) return INGVIO_E_ARG;
-            if (q.m <= q.s) continue;                                                   // StateManager.cpp:574-578: skipped
-            if (!q.vidx || !q.vsize || !q.H_old || !q.H_new || !q.res || q.k < 1 || q.ldh < q.m || q.ldn < q.m) return INGVIO_E_ARG;
-            int nc = 0;
-            for (int t = 0; t < q.k; ++t) {
-                if (q.vidx[t] < 0 || q.vsize[t] < 0 || q.vidx[t] + q.vsize[t] > c->h_n[b]) return INGVIO_E_NOT_IN_STATE;      // checkSubOrder
-                nc += q.vsize[t];
-            }
-            if (nc < 1) return INGVIO_E_ARG;
-            const int mu = q.m - q.s;
-            if (q.m > c->mld || nc > c->nc_cap || !ekf_core_fits(mu, nc)) return INGVIO_E_CAPACITY;
-            if (!form && (size_t)8 * ((size_t)nc * mu + (size_t)(mu + 1) * (mu + 1)) > 150 * 1024) return INGVIO_E_CAPACITY;      // the single-filter gate's bound
-            const size_t l = delayed_front_lds(q.m, q.s, nc);
-            if (form == 2 || (form == 1 && l > 160 * 1024)) {                           // the large form: rows and T in the workspace
-                const size_t ll = delayed_front_large_lds(q.m, q.s, nc);
-                if (ll > 160 * 1024) return INGVIO_E_CAPACITY;
-                if (ll > lds_large) lds_large = ll;
-                if (q.m > ldw) ldw = q.m;
-                if (nc > ncw) ncw = nc;
-                large[(size_t)j * nb + i] = 1; ++n_large[j];
-            } else {
-                if (l > 160 * 1024) return INGVIO_E_CAPACITY;                           // the front's own: rows and T stay in LDS
-                if (l > lds) lds = l;
-                ++n_lds[j];
-            }
-            if (mu > mu_cap) mu_cap = mu;
-            if (nc > nc_cap) nc_cap = nc;
-            grow += q.s;
-            ncs[(size_t)j * nb + i] = nc;
-            offs[(size_t)j * nb + i] = dtot;
-            dtot += (size_t)q.m * (nc + q.s + 1);
-        }
-        if (c->h_n[b] + grow > c->d.n_max) return INGVIO_E_CAPACITY;                    // every candidate of the filter may be added
-        if (c->h_n[b] + grow > n_cap) n_cap = c->h_n[b] + grow;
-    }
-    const size_t CC = (size_t)nb * cand_cap;
-    for (size_t e = 0; e < CC; ++e) { added[e] = 0; new_idx[e] = -1; if (chi2) chi2[e] = 0.0; }
-    if (dx) memset(dx, 0, 8 * CC * c->ldp);
-    if (status) for (int i = 0; i < nb; ++i) status[i] = INGVIO_OK;
-    if (R == 0 || nc_cap == 0) return INGVIO_OK;                                        // nothing to try anywhere
-    // ---- one slab up: [m | s | nc | colmap | offsets | thresholds | var | rows] ----
-    const size_t cs = nc_cap;
-    // (rounds that mix the two forms: the LDS launch's row counts with the large form's candidates struck, the large launch's selection)
-    const size_t o_m = 0, o_s = o_m + pad64(4 * RN), o_nc = o_s + pad64(4 * RN), o_cm = o_nc + pad64(4 * RN), o_off = o_cm + pad64(4 * RN * cs),
-                 o_thr = o_off + pad64(8 * RN), o_var = o_thr + pad64(8 * RN), o_ml = o_var + 64, o_sel = o_ml + (ldw ? pad64(4 * RN) : 0),
-                 o_d = o_sel + (ldw ? pad64(4 * RN) : 0), in_bytes = o_d + pad64(8 * dtot);
-    ldw = (ldw + 1) & ~1;
-    const size_t ws_stride = (size_t)(2 * ncw + 1) * ldw;
-    const int mldu = (mu_cap + 15) & ~15;
-    const size_t hsu = (size_t)mldu * nc_cap;
-    const size_t w_res = pad64(8 * (size_t)nb * hsu), w_mu = w_res + pad64(8 * (size_t)nb * mldu), wk_bytes = w_mu + pad64(4 * (size_t)nb);
-    const size_t B = c->d.batch;
-    const size_t r_idx = pad64(4 * RN), r_st = r_idx + pad64(4 * RN), r_chi = r_st + pad64(4 * B), r_dx = r_chi + pad64(8 * RN),
-                 out_bytes = r_dx + (dx ? 8 * RN * c->ldp : 0);
-    auto& w = c->dl;
-    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
-    if (int rc = dl_grow(c, &w.wk, &w.wk_cap, wk_bytes)) return rc;
-    if (ldw) if (int rc = dl_grow(c, &w.ws, &w.ws_cap, 8 * (size_t)nb * ws_stride)) return rc;
-    if (w.out_cap < out_bytes && w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; }      // the pinned mirror grows with the device slab
-    if (int rc = dl_grow(c, &w.out, &w.out_cap, out_bytes)) return rc;
-    if (!w.h_out) HIPCHK(c, hipHostMalloc((void**)&w.h_out, w.out_cap, hipHostMallocDefault));
-    Uploader upl{ c };
-    if (int rc = upl.begin(in_bytes + 64)) return rc;
-    char* h = upl.take<char>(in_bytes);
-    memset(h, 0, o_d);
-    int *hm = (int*)(h + o_m), *hs = (int*)(h + o_s), *hnc = (int*)(h + o_nc), *hcm = (int*)(h + o_cm);
-    size_t* hoff = (size_t*)(h + o_off);
-    double *hthr = (double*)(h + o_thr), *hd = (double*)(h + o_d);
-    *(double*)(h + o_var) = noise * noise;
-    int *hml = (int*)(h + o_ml), *hsel = (int*)(h + o_sel);
-    parallel_for(nb, [=, &ncs, &offs, &large](int i) {
-        const ingvio_delayed_block& blk = blocks[i];
-        for (int j = 0; j < blk.n_cand; ++j) {
-            const size_t e = (size_t)j * nb + i;
-            const int nc = ncs[e];
-            if (!nc) continue;
-            const ingvio_delayed_cand& q = blk.cand[j];
-            hm[e] = q.m; hs[e] = q.s; hnc[e] = nc; hoff[e] = offs[e]; hthr[e] = chi2_mult * q.chi2_check;
-            if (ldw) { hml[e] = large[e] ? 0 : q.m; hsel[e] = large[e]; }
-            int* cm = hcm + e * cs;
-            int wr = 0;
-            for (int t = 0; t < q.k; ++t) for (int u = 0; u < q.vsize[t]; ++u) cm[wr++] = q.vidx[t] + u;
-            double* d = hd + offs[e];
-            for (int cc = 0; cc < nc; ++cc) memcpy(d + (size_t)cc * q.m, q.H_old + (size_t)cc * q.ldh, 8 * (size_t)q.m);
-            d += (size_t)nc * q.m;
-            for (int cc = 0; cc < q.s; ++cc) memcpy(d + (size_t)cc * q.m, q.H_new + (size_t)cc * q.ldn, 8 * (size_t)q.m);
-            memcpy(d + (size_t)q.s * q.m, q.res, 8 * (size_t)q.m);
-        }
-    });
-    upl.copy(w.in, h, in_bytes);
-    if (int rc = upl.end()) return rc;
-    int* d_st = (int*)(w.out + r_st);
-    HIPCHK(c, hipMemsetAsync(d_st + b0, 0, sizeof(int) * (size_t)nb, c->st));
-    HIPCHK(c, hipMemsetAsync(c->d_dx + (size_t)b0 * c->ldp, 0, 8 * (size_t)nb * c->ldp, c->st));      // entries past a filter's n stay zero
-    const CovView cv = view(c);
-    for (int j = 0; j < R; ++j) {
-        const size_t r0 = (size_t)j * nb;
-        DelayedFront F;
-        memset(&F, 0, sizeof F);
-        F.cv = cv; F.b0 = b0; F.nb = nb; F.dbuf = (const double*)(w.in + o_d); F.doff = (const size_t*)(w.in + o_off) + r0;
-        F.m = (const int*)(w.in + o_m) + r0; F.s = (const int*)(w.in + o_s) + r0; F.nc = (const int*)(w.in + o_nc) + r0;
-        F.colmap = (const int*)(w.in + o_cm) + r0 * cs; F.cs = (int)cs; F.thr = (const double*)(w.in + o_thr) + r0;
-        F.do_chi2 = do_chi2 ? 1 : 0; F.var = noise * noise;
-        F.Hu = (double*)w.wk; F.resu = (double*)(w.wk + w_res); F.mldu = mldu; F.hsu = hsu; F.mu = (int*)(w.wk + w_mu);
-        F.Y = c->d_Y + (size_t)b0 * c->ystride; F.ystride = (size_t)c->ystride; F.status = d_st;
-        F.added = (int*)w.out + r0; F.new_idx = (int*)(w.out + r_idx) + r0; F.chi2 = (double*)(w.out + r_chi) + r0;
-        // one launch per form: the LDS form first (it writes "nothing tried" for the filters it does not take), then the large
-        // form, which skips every filter that is not its own
-        if (!n_large[j]) { if (launch_delayed_front(F, lds, c->st)) return INGVIO_E_CAPACITY; }
-        else {
-            const int* m_all = F.m;
-            if (n_lds[j]) { F.m = (const int*)(w.in + o_ml) + r0; if (launch_delayed_front(F, lds, c->st)) return INGVIO_E_CAPACITY; F.m = m_all; }
-            DelayedLarge G{ (double*)w.ws, ws_stride, ldw, n_lds[j] ? (const int*)(w.in + o_sel) + r0 : nullptr };
-            if (launch_delayed_front_large(F, G, lds_large, c->st)) return INGVIO_E_CAPACITY;
-        }
-        EkfLaunch E;                                                                    // :623-624 ekfUpdate with the lower rows on the extended state
-        memset(&E, 0, sizeof E);
-        E.cv = cv; E.b0 = b0; E.nb = nb; E.H = F.Hu; E.res = F.resu; E.colmap = F.colmap; E.m = F.mu; E.nc = F.nc;
-        E.noise = (const double*)(w.in + o_var); E.r_kind = 0; E.mld = mldu; E.hstride = (int)hsu; E.cstride = (int)cs; E.nstride = 0;
-        E.Y = c->d_Y + (size_t)b0 * c->ystride; E.ystride = c->ystride; E.dx = c->d_dx; E.status = d_st; E.m_cap = mu_cap; E.nc_cap = nc_cap;
-        { ProfScope p(c, PF_EKF_CORE); launch_ekf_core(E, c->st); }
-        { ProfScope p(c, PF_DOWNDATE); launch_downdate(E, n_cap, c->st); }
-        if (dx) HIPCHK(c, hipMemcpyAsync(w.out + r_dx + 8 * r0 * c->ldp, c->d_dx + (size_t)b0 * c->ldp, 8 * (size_t)nb * c->ldp, hipMemcpyDeviceToDevice, c->st));
-    }
-    HIPCHK(c, hipMemcpyAsync(w.h_out, w.out, out_bytes, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (int rc = last_launch(c)) return rc;
-    const int *ra = (const int*)w.h_out, *ri = (const int*)(w.h_out + r_idx), *rs = (const int*)(w.h_out + r_st) + b0;
-    const double *rc2 = (const double*)(w.h_out + r_chi), *rdx = (const double*)(w.h_out + r_dx);
-    int soft = INGVIO_OK;
-    for (int i = 0; i < nb; ++i) {
-        for (int j = 0; j < blocks[i].n_cand; ++j) {
-            const size_t e = (size_t)j * nb + i, o = (size_t)i * cand_cap + j;
-            added[o] = ra[e]; new_idx[o] = ri[e];
-            if (chi2) chi2[o] = rc2[e];
-            if (ra[e]) c->h_n[b0 + i] += blocks[i].cand[j].s;
-            if (dx && ra[e]) memcpy(dx + o * c->ldp, rdx + e * c->ldp, 8 * (size_t)c->ldp);
-        }
-        const int st = (rs[i] & 4) ? INGVIO_E_NOT_PD : ((rs[i] & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
-        if (status) status[i] = st;
-        if (st != INGVIO_OK) soft = st;
-    }
-    return soft;
-}
-
-// ---- LandmarkUpdate::initNewLandmark{Mono,Stereo} (LandmarkUpdate.cpp:363-424, :892-956) from the track store and the nominal table ----
-// The rounds of ingvio_add_variable_delayed_batch with the rows formed by the front itself (k_delayed_front<true>) at the clone poses
-// the table holds when the round starts, the accepted landmark entered into the table by the front, and boxPlus of the round's dx on
-// the table behind the trailing update: candidate j + 1 is linearised where the reference linearises it.  Validation on the host
-// mirror only, no decision between the rounds, one synchronisation.
-struct LmInitPlan {
-    int R = 0, mu_cap = 0, nc_cap = 0, n_cap = 0, per = 2;
-    size_t lds = 0;
-    bool large = false;                 // ingvio_set_delayed_form: the call's fronts take the large form (chosen at the worst-case m of the widest window)
-    size_t lds_large = 0;
-    int ldw = 0;
-    std::vector<int> slots;             // [round][filter] reserved table slot (-1: no candidate)
-    std::vector<unsigned long long> dropm;
-};
-
-// rows_only: the parity hook - it appends nothing, so neither a free table slot nor room in the state is asked for
-static int lm_init_validate(ingvio_ctx* c, const char* who, int b0, int nb, const ingvio_lm_init_block* blocks, const ingvio_msckf_opts* o, int cand_cap,
-                            LmInitPlan& pl, bool rows_only = false)
-{
-    auto& m = c->nom;
-    if (phase_busy(c)) return INGVIO_E_ARG;
-    if (check_range(c, b0, nb) || !blocks || !o || cand_cap < 1) return INGVIO_E_ARG;
-    if (!m.vmax) { c->err = std::string(who) + " without ingvio_nominal_create"; return INGVIO_E_ARG; }
-    if (!c->trk.t_max) { c->err = std::string(who) + " without ingvio_tracks_create"; return INGVIO_E_ARG; }
-    if (m.pending) { c->err = std::string(who) + ": a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
-    if (gnss_nom_busy(c, who)) return INGVIO_E_ARG;
-    if (!(o->noise > 0.0) || !o->chi2_table || o->chi2_len < 1) return INGVIO_E_ARG;
-    const int cm = c->d.c_max, per = o->stereo ? 4 : 2;
-    pl.per = per;
-    for (int i = 0; i < nb; ++i) if (blocks[i].n_cand > pl.R) pl.R = blocks[i].n_cand;
-    if (pl.R > cand_cap) return INGVIO_E_ARG;
-    pl.slots.assign((size_t)pl.R * nb, -1);
-    pl.dropm.assign((size_t)nb, 0ULL);
-    int cap_err = 0;
-    for (int i = 0; i < nb; ++i) {
-        const ingvio_lm_init_block& blk = blocks[i];
-        const int b = b0 + i;
-        const int* I = &m.h_ih[(size_t)b * m.ir];
-        const int* var = I + NOM_IH;
-        const int cw = I[NOM_N_CLONES];
-        if (blk.n_cand < 0 || (blk.n_cand > 0 && !blk.cand) || blk.n_drop < 0 || (blk.n_drop > 0 && !blk.drop_cols)) return INGVIO_E_ARG;
-        for (int q = 0; q < blk.n_drop; ++q) {
-            if (blk.drop_cols[q] < 0 || blk.drop_cols[q] >= cm || (q && blk.drop_cols[q] <= blk.drop_cols[q - 1])) {
-                c->err = std::string(who) + ": drop_cols is not ascending or names a column outside c_max"; return INGVIO_E_ARG;
-            }
-            pl.dropm[i] |= 1ULL << blk.drop_cols[q];
-        }
-        if (cw + blk.n_drop > cm) { c->err = std::string(who) + ": the window and the pending drops exceed c_max"; return INGVIO_E_ARG; }
-        if (blk.n_cand == 0) continue;
-        for (int j = 0; j < blk.n_cand; ++j) {
-            const ingvio_lm_init_cand& q = blk.cand[j];
-            if (q.track < 0 || q.track >= c->trk.t_max) { c->err = std::string(who) + ": a track lies outside the store"; return INGVIO_E_ARG; }
-            if (q.anchor < 0 || q.anchor >= cw) { c->err = std::string(who) + ": an anchor lies outside the window"; return INGVIO_E_ARG; }
-        }
-        if (o->chi2_len < per * cw + 1) { c->err = std::string(who) + ": chi2_table is shorter than the widest candidate needs"; return INGVIO_E_ARG; }
-        for (int q = 0; q < cw; ++q) {
-            const int ix = var[4 * I[NOM_CLONES + q] + 1];
-            if (ix < 0 || ix + 6 > c->h_n[b]) return INGVIO_E_NOT_IN_STATE;
-        }
-        // capacity (reported after every argument of the call has been looked at)
-        int got = 0;
-        for (int v = 0; v < m.vmax && got < blk.n_cand; ++v) if (var[4 * v] == NOM_KIND_NONE) pl.slots[(size_t)(got++) * nb + i] = v;
-        const int mw = per * cw, nc = 6 * cw, mu = mw - 3;
-        if (!rows_only && (got < blk.n_cand || c->h_n[b] + 3 * blk.n_cand > c->d.n_max)) { cap_err = 1; continue; }
-        if (mw > c->mld || nc > c->nc_cap) { cap_err = 1; continue; }
-        if (mu > 0) {
-            const size_t l = delayed_front_lds(mw, 3, nc);
-            const int form = c->delayed_form;
-            if ((!form && l > 160 * 1024) || !ekf_core_fits(mu, nc)) { cap_err = 1; continue; }
-            if (!form && (size_t)8 * ((size_t)nc * mu + (size_t)(mu + 1) * (mu + 1)) > 150 * 1024) { cap_err = 1; continue; }      // as ingvio_add_variable_delayed_batch
-            if (form) {
-                const size_t ll = delayed_front_large_lds(mw, 3, nc);
-                if (ll > 160 * 1024) { cap_err = 1; continue; }
-                if (ll > pl.lds_large) pl.lds_large = ll;
-                if (mw > pl.ldw) pl.ldw = mw;
-                if (form == 2 || l > 160 * 1024) pl.large = true;
-            }
-            if (l <= 160 * 1024 && l > pl.lds) pl.lds = l;
-            if (mu > pl.mu_cap) pl.mu_cap = mu;
-        }
-        if (nc > pl.nc_cap) pl.nc_cap = nc;
-        if (c->h_n[b] + 3 * blk.n_cand > pl.n_cap) pl.n_cap = c->h_n[b] + 3 * blk.n_cand;
-    }
-    return cap_err ? INGVIO_E_CAPACITY : INGVIO_OK;
-}
-
-static void lm_init_rows_common(ingvio_ctx* c, const ingvio_msckf_opts* o, double chi2_mult, DelayedRows& Rw)
-{
-    Rw.nt = nom_table(c);
-    Rw.ts = TrackStore{ c->trk.uv, c->trk.mask, c->trk.pf, c->trk.t_max, c->d.c_max };
-    Rw.chi2_mult = chi2_mult; Rw.stereo = o->stereo ? 1 : 0;
-    memcpy(Rw.R_lr, o->R_cl2cr, 72); memcpy(Rw.t_lr, o->t_cl2cr, 24);
-}
-
-int ingvio_landmark_init_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_lm_init_block* blocks, const ingvio_msckf_opts* o, double chi2_mult,
-                                 int do_chi2, int cand_cap, int* added, int* new_idx, int* slot, double* chi2, double* dx, int* status)
-{
-    ENTER(c);
-    if (!c) return INGVIO_E_ARG;
-    if (!added || !new_idx || !slot) return INGVIO_E_ARG;
-    LmInitPlan pl;
-    if (int rc = lm_init_validate(c, "ingvio_landmark_init_nominal", b0, nb, blocks, o, cand_cap, pl)) return rc;
-    const int R = pl.R;
-    const size_t RN = (size_t)R * nb, CC = (size_t)nb * cand_cap;
-    for (size_t e = 0; e < CC; ++e) { added[e] = 0; new_idx[e] = -1; slot[e] = -1; if (chi2) chi2[e] = 0.0; }
-    if (dx) memset(dx, 0, 8 * CC * c->ldp);
-    if (status) for (int i = 0; i < nb; ++i) status[i] = INGVIO_OK;
-    if (R == 0 || pl.mu_cap == 0) return INGVIO_OK;                                    // nothing to try anywhere (or no window wider than m <= 3)
-    // ---- one slab up: 40 bytes per candidate, the pending drops, the chi2 table ----
-    const size_t ntab = (size_t)pl.mu_cap + 4;                                          // chi2_table[0 .. widest m]
-    const size_t o_tr = 0, o_an = o_tr + pad64(4 * RN), o_sl = o_an + pad64(4 * RN), o_pf = o_sl + pad64(4 * RN), o_dm = o_pf + pad64(24 * RN),
-                 o_tab = o_dm + pad64(8 * (size_t)nb), o_var = o_tab + pad64(8 * ntab), in_bytes = o_var + 64;
-    const int mldu = (pl.mu_cap + 15) & ~15;
-    const size_t cs = pl.nc_cap, hsu = (size_t)mldu * pl.nc_cap;
-    const size_t w_res = pad64(8 * (size_t)nb * hsu), w_mu = w_res + pad64(8 * (size_t)nb * mldu), w_nc = w_mu + pad64(4 * (size_t)nb),
-                 w_cm = w_nc + pad64(4 * (size_t)nb), wk_bytes = w_cm + pad64(4 * (size_t)nb * cs);
-    const size_t B = c->d.batch;
-    const size_t r_idx = pad64(4 * RN), r_st = r_idx + pad64(4 * RN), r_chi = r_st + pad64(4 * B), r_sl = r_chi + pad64(8 * RN), r_dx = r_sl + pad64(4 * RN),
-                 out_bytes = r_dx + (dx ? 8 * RN * c->ldp : 0);
-    auto& w = c->dl;
-    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
-    if (int rc = dl_grow(c, &w.wk, &w.wk_cap, wk_bytes)) return rc;
-    const int ldw = (pl.ldw + 1) & ~1;
-    const size_t ws_stride = (size_t)(2 * pl.nc_cap + 1) * ldw;
-    if (pl.large) if (int rc = dl_grow(c, &w.ws, &w.ws_cap, 8 * (size_t)nb * ws_stride)) return rc;
-    if (w.out_cap < out_bytes && w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; }
-    if (int rc = dl_grow(c, &w.out, &w.out_cap, out_bytes)) return rc;
-    if (!w.h_out) HIPCHK(c, hipHostMalloc((void**)&w.h_out, w.out_cap, hipHostMallocDefault));
-    Uploader upl{ c };
-    if (int rc = upl.begin(in_bytes + 64)) return rc;
-    char* h = upl.take<char>(in_bytes);
-    memset(h, 0, in_bytes);
-    int *htr = (int*)(h + o_tr), *han = (int*)(h + o_an), *hsl = (int*)(h + o_sl);
-    double* hpf = (double*)(h + o_pf);
-    for (size_t e = 0; e < RN; ++e) htr[e] = -1;
-    for (int i = 0; i < nb; ++i)
-        for (int j = 0; j < blocks[i].n_cand; ++j) {
-            const size_t e = (size_t)j * nb + i;
-            const ingvio_lm_init_cand& q = blocks[i].cand[j];
-            htr[e] = q.track; han[e] = q.anchor; hsl[e] = pl.slots[e];
-            memcpy(hpf + 3 * e, q.pf, 24);
-        }
-    memcpy(h + o_dm, pl.dropm.data(), 8 * (size_t)nb);
-    memcpy(h + o_tab, o->chi2_table, 8 * ntab);
-    const double var = o->noise * o->noise;
-    *(double*)(h + o_var) = var;
-    upl.copy(w.in, h, in_bytes);
-    if (int rc = upl.end()) return rc;
-    if (wait_inputs(c)) return INGVIO_E_HIP;                                            // the store's last delta may have travelled on the copy stream
-    int* d_st = (int*)(w.out + r_st);
-    HIPCHK(c, hipMemsetAsync(d_st + b0, 0, sizeof(int) * (size_t)nb, c->st));
-    HIPCHK(c, hipMemsetAsync(c->d_dx + (size_t)b0 * c->ldp, 0, 8 * (size_t)nb * c->ldp, c->st));
-    const CovView cv = view(c);
-    DelayedRows Rw;
-    memset(&Rw, 0, sizeof Rw);
-    lm_init_rows_common(c, o, chi2_mult, Rw);
-    Rw.dropm = (const unsigned long long*)(w.in + o_dm); Rw.chi2 = (const double*)(w.in + o_tab);
-    Rw.nc_out = (int*)(w.wk + w_nc); Rw.colmap_out = (int*)(w.wk + w_cm);
-    for (int j = 0; j < R; ++j) {
-        const size_t r0 = (size_t)j * nb;
-        DelayedFront F;
-        memset(&F, 0, sizeof F);
-        F.cv = cv; F.b0 = b0; F.nb = nb; F.cs = (int)cs; F.do_chi2 = do_chi2 ? 1 : 0; F.var = var;
-        F.Hu = (double*)w.wk; F.resu = (double*)(w.wk + w_res); F.mldu = mldu; F.hsu = hsu; F.mu = (int*)(w.wk + w_mu);
-        F.Y = c->d_Y + (size_t)b0 * c->ystride; F.ystride = (size_t)c->ystride; F.status = d_st;
-        F.added = (int*)w.out + r0; F.new_idx = (int*)(w.out + r_idx) + r0; F.chi2 = (double*)(w.out + r_chi) + r0;
-        Rw.track = (const int*)(w.in + o_tr) + r0; Rw.anchor = (const int*)(w.in + o_an) + r0; Rw.slot = (const int*)(w.in + o_sl) + r0;
-        Rw.pf = (const double*)(w.in + o_pf) + 3 * r0; Rw.slot_out = (int*)(w.out + r_sl) + r0;
-        if (pl.large) {
-            const DelayedLarge G{ (double*)w.ws, ws_stride, ldw, nullptr };
-            if (launch_delayed_front_rows_large(F, Rw, G, pl.lds_large, c->st)) return INGVIO_E_CAPACITY;
-        } else if (launch_delayed_front_rows(F, Rw, pl.lds, c->st)) return INGVIO_E_CAPACITY;
-        EkfLaunch E;                                                                    // :623-624 ekfUpdate with the lower rows on the extended state
-        memset(&E, 0, sizeof E);
-        E.cv = cv; E.b0 = b0; E.nb = nb; E.H = F.Hu; E.res = F.resu; E.colmap = Rw.colmap_out; E.m = F.mu; E.nc = Rw.nc_out;
-        E.noise = (const double*)(w.in + o_var); E.r_kind = 0; E.mld = mldu; E.hstride = (int)hsu; E.cstride = (int)cs; E.nstride = 0;
-        E.Y = c->d_Y + (size_t)b0 * c->ystride; E.ystride = c->ystride; E.dx = c->d_dx; E.status = d_st; E.m_cap = pl.mu_cap; E.nc_cap = pl.nc_cap;
-        { ProfScope p(c, PF_EKF_CORE); launch_ekf_core(E, c->st); }
-        { ProfScope p(c, PF_DOWNDATE); launch_downdate(E, pl.n_cap, c->st); }
-        // boxPlus of the round's dx (zero where nothing was added) on the table, the new landmark included (stream_filter.py:772-775)
-        launch_nominal_update(nom_table(c), c->d_dx, c->ldp, nullptr, b0, nb, c->st);
-        if (dx) HIPCHK(c, hipMemcpyAsync(w.out + r_dx + 8 * r0 * c->ldp, c->d_dx + (size_t)b0 * c->ldp, 8 * (size_t)nb * c->ldp, hipMemcpyDeviceToDevice, c->st));
-    }
-    HIPCHK(c, hipMemcpyAsync(w.h_out, w.out, out_bytes, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (int rc = last_launch(c)) return rc;
-    const int *ra = (const int*)w.h_out, *ri = (const int*)(w.h_out + r_idx), *rs = (const int*)(w.h_out + r_st) + b0, *rl = (const int*)(w.h_out + r_sl);
-    const double *rc2 = (const double*)(w.h_out + r_chi), *rdx = (const double*)(w.h_out + r_dx);
-    int soft = INGVIO_OK;
-    for (int i = 0; i < nb; ++i) {
-        int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
-        for (int j = 0; j < blocks[i].n_cand; ++j) {
-            const size_t e = (size_t)j * nb + i, oo = (size_t)i * cand_cap + j;
-            added[oo] = ra[e]; new_idx[oo] = ri[e]; slot[oo] = ra[e] ? rl[e] : -1;
-            if (chi2) chi2[oo] = rc2[e];
-            if (dx && ra[e]) memcpy(dx + oo * c->ldp, rdx + e * c->ldp, 8 * (size_t)c->ldp);
-            if (!ra[e]) continue;
-            c->h_n[b0 + i] += 3;                                                        // the mirror follows the front's record
-            int* v = I + NOM_IH + 4 * rl[e];
-            v[0] = NOM_KIND_LM; v[1] = ri[e]; v[2] = I[NOM_CLONES + blocks[i].cand[j].anchor]; v[3] = 0;
-            if (rl[e] >= I[NOM_N_VAR]) I[NOM_N_VAR] = rl[e] + 1;
-        }
-        const int st = (rs[i] & 4) ? INGVIO_E_NOT_PD : ((rs[i] & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
-        if (status) status[i] = st;
-        if (st != INGVIO_OK) soft = st;
-    }
-    if (nom_mark(c)) return INGVIO_E_HIP;
-    return soft;
-}
-
-// parity hook (tests): the row stage of ingvio_landmark_init_nominal alone, for one filter and one candidate; changes nothing
-int ingvio_debug_landmark_init_rows(ingvio_ctx* c, int b, const ingvio_lm_init_cand* cand, const ingvio_msckf_opts* o, int n_drop, const int* drop_cols,
-                                    double* H_old, double* H_new, double* res, int* m_out)
-{
-    ENTER(c);
-    if (!c || !cand || !H_old || !H_new || !res || !m_out) return INGVIO_E_ARG;
-    ingvio_lm_init_block blk{ 1, cand, n_drop, drop_cols };
-    LmInitPlan pl;
-    if (int rc = lm_init_validate(c, "ingvio_debug_landmark_init_rows", b, 1, &blk, o, 1, pl, true)) return rc;
-    const int cw = c->nom.h_ih[(size_t)b * c->nom.ir + NOM_N_CLONES], mw = pl.per * cw, nc = 6 * cw;
-    const size_t rows = (size_t)mw * (nc + 4), o_pf = 64, o_dm = 128, in_bytes = 192, out_bytes = pad64(8 * rows) + 64;
-    auto& w = c->dl;
-    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
-    if (int rc = dl_grow(c, &w.wk, &w.wk_cap, out_bytes)) return rc;
-    char h[192];
-    memset(h, 0, sizeof h);
-    ((int*)h)[0] = cand->track; ((int*)h)[1] = cand->anchor;
-    memcpy(h + o_pf, cand->pf, 24); memcpy(h + o_dm, pl.dropm.data(), 8);
-    if (up(c, w.in, h, in_bytes)) return INGVIO_E_HIP;
-    if (wait_inputs(c)) return INGVIO_E_HIP;
-    DelayedRows Rw;
-    memset(&Rw, 0, sizeof Rw);
-    lm_init_rows_common(c, o, 1.0, Rw);
-    Rw.track = (const int*)w.in; Rw.anchor = (const int*)w.in + 1; Rw.pf = (const double*)(w.in + o_pf); Rw.dropm = (const unsigned long long*)(w.in + o_dm);
-    int* d_m = (int*)(w.wk + pad64(8 * rows));
-    const size_t lds = delayed_front_lds(mw > 0 ? mw : 1, 3, nc);
-    const bool big = c->delayed_form && lds > 160 * 1024;      // rows formed in global memory: [H_old | res | H_new]
-    if (big) launch_delayed_rows_debug_large(Rw, b, (double*)w.wk, d_m, c->st);
-    else if (launch_delayed_rows_debug(Rw, b, (double*)w.wk, d_m, lds, c->st)) return INGVIO_E_CAPACITY;
-    std::vector<double> out(rows);
-    int m = 0;
-    HIPCHK(c, hipMemcpyAsync(out.data(), w.wk, 8 * rows, hipMemcpyDeviceToHost, c->st));
-    if (down_sync(c, &m, d_m, sizeof(int))) return INGVIO_E_HIP;
-    if (int rc = last_launch(c)) return rc;
-    *m_out = m;
-    memcpy(H_old, out.data(), 8 * (size_t)m * nc);
-    memcpy(H_new, out.data() + (size_t)m * (big ? nc + 1 : nc), 8 * (size_t)m * 3);
-    memcpy(res, out.data() + (size_t)m * (big ? nc : nc + 3), 8 * (size_t)m);
-    return INGVIO_OK;
-}
-
-// ---- GnssUpdate::addNewTrackedSys (GnssUpdate.cpp:295-470) from the nominal table: the twin of ingvio_landmark_init_nominal ----
-// k_gnss_front<true> once at the receiver the SPP fix overrides, R_w2ecef once, then one round per candidate scalar (FS, clock GPS, GLO,
-// GAL, BDS): k_delayed_front<DL_GNSS> (rows, noise, rotations, gate, verdict, append, table record), the trailing update, boxPlus on the
-// table.  Validation on the host mirror only, no decision between the rounds, one synchronisation.
-struct GnssInitPlan {
-    int smax = 1, n_cap = 0;
-    bool any = false;
-    std::vector<int> cand, slots;       // [round][filter]: tried / reserved table slot
-    bool round[INGVIO_GNSS_INIT_CAND] = { false, false, false, false, false };
-};
-
-// rows_only: the parity hook - it appends nothing, so neither a free table slot nor room in the state is asked for, and the candidate
-// it names need not be one the call would try
-static int gnss_init_validate(ingvio_ctx* c, const char* who, int b0, int nb, const ingvio_gnss_init_block* blocks, const double* chi2_table, int chi2_len,
-                              GnssInitPlan& pl, bool rows_only = false)
-{
-    auto& m = c->nom;
-    if (phase_busy(c)) return INGVIO_E_ARG;
-    if (check_range(c, b0, nb) || !blocks) return INGVIO_E_ARG;
-    if (!m.vmax) { c->err = std::string(who) + " without ingvio_nominal_create"; return INGVIO_E_ARG; }
-    if (m.pending) { c->err = std::string(who) + ": a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
-    if (gnss_nom_busy(c, who)) return INGVIO_E_ARG;
-    if ((c->gn.frame_nom && c->gn.staged) || (c->lm.nominal && c->lm.staged)) {
-        c->err = std::string(who) + ": an in-frame GNSS epoch or landmark update staged from the device nominal state has not run yet"; return INGVIO_E_ARG;
-    }
-    const int NC = INGVIO_GNSS_INIT_CAND;
-    pl.cand.assign((size_t)NC * nb, 0);
-    pl.slots.assign((size_t)NC * nb, -1);
-    int cap_err = 0;
-    for (int i = 0; i < nb; ++i) {
-        const ingvio_gnss_epoch_nominal& e = blocks[i].epoch;
-        if (e.n_sat < 0 || e.n_sat > INGVIO_GNSS_MAX_SAT || (e.n_sat && (!e.eph || !e.obs))) { c->err = std::string(who) + ": n_sat outside 0..64 or a missing array"; return INGVIO_E_ARG; }
-        if (!rows_only && (!chi2_table || chi2_len <= e.n_sat)) { c->err = std::string(who) + ": chi2_table is shorter than n_sat + 1"; return INGVIO_E_ARG; }
-        if (e.n_sat == 0) continue;
-        if (e.n_sat > pl.smax) pl.smax = e.n_sat;
-        const int b = b0 + i;
-        const int* I = &m.h_ih[(size_t)b * m.ir];
-        const int* var = I + NOM_IH;
-        if (I[NOM_GNSS + NOM_G_YOF] < 0) continue;                    // GnssUpdate.cpp:300-301 returns silently: no candidates, not an error
-        int nc = 0;
-        if (rows_only) nc = 1;
-        else {
-            if (fabs(blocks[i].vel_spp[3]) > 1e-3 && I[NOM_GNSS + NOM_G_FS] < 0) { pl.cand[(size_t)0 * nb + i] = 1; ++nc; }
-            for (int s4 = 0; s4 < 4; ++s4)
-                if (fabs(blocks[i].pos_spp[3 + s4]) > 1e-3 && I[NOM_GNSS + s4] < 0) { pl.cand[(size_t)(1 + s4) * nb + i] = 1; ++nc; }
-        }
-        if (!nc) continue;
-        const int ix_pose = nom_idx_of(c, b, I[NOM_V_POSE]), ix_yof = nom_idx_of(c, b, I[NOM_GNSS + NOM_G_YOF]);
-        if (ix_pose < 0 || ix_pose + 9 > c->h_n[b] || ix_yof < 0 || ix_yof + 1 > c->h_n[b]) {
-            c->err = std::string(who) + ": the extended pose or YOF lies beyond the live state"; return INGVIO_E_NOT_IN_STATE;
-        }
-        pl.any = true;
-        if (rows_only) continue;
-        // capacity (reported after every argument of the call has been looked at)
-        int got = 0, v = 0;
-        for (int g = 0; g < NC; ++g) {
-            if (!pl.cand[(size_t)g * nb + i]) continue;
-            while (v < m.vmax && var[4 * v] != NOM_KIND_NONE) ++v;
-            if (v < m.vmax) { pl.slots[(size_t)g * nb + i] = v++; ++got; }
-            pl.round[g] = true;
-        }
-        if (got < nc || c->h_n[b] + nc > c->d.n_max || e.n_sat > c->mld) { cap_err = 1; continue; }
-        if (c->h_n[b] + nc > pl.n_cap) pl.n_cap = c->h_n[b] + nc;
-    }
-    if (!cap_err && pl.any && !rows_only && !ekf_core_fits(63, 10)) cap_err = 1;
-    return cap_err ? INGVIO_E_CAPACITY : INGVIO_OK;
-}
-
-// the call's epochs, ephemerides and receiver records (the SPP fix in the scalars the table lacks) into the host slab h
-static void gnss_init_fill(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_init_block* blocks, const GnssInitPlan& pl, double* he, double* ho, double* hr,
-                           int only_g = -1)
-{
-    const size_t S = pl.smax;
-    for (int i = 0; i < nb; ++i) {
-        const ingvio_gnss_epoch_nominal& e = blocks[i].epoch;
-        if (e.n_sat) {
-            memcpy(he + (size_t)i * S * GE_N, e.eph, 8 * (size_t)e.n_sat * GE_N);
-            memcpy(ho + (size_t)i * S * GO_N, e.obs, 8 * (size_t)e.n_sat * GO_N);
-        }
-        double* r = hr + (size_t)i * GR_N;
-        r[GR_NSAT] = e.n_sat; r[GR_DOY] = e.doy; r[GR_HAVE_ION] = e.ion ? 1.0 : 0.0;
-        if (e.ion) memcpy(r + GR_ION, e.ion, 64);
-        memcpy(r + GR_RENU, e.R_enu2ecef, 72); memcpy(r + GR_ANCHOR, e.anchor_ecef, 24);
-        r[GR_PSR_AMP] = e.psr_noise_amp; r[GR_DOPP_AMP] = e.dopp_noise_amp;
-        // the scalars to add take the SPP fix (:343-372); k_gnss_front reads these fields only where the table has no such scalar
-        const int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
-        const bool fs_add = only_g >= 0 ? (fabs(blocks[i].vel_spp[3]) > 1e-3 && I[NOM_GNSS + NOM_G_FS] < 0) : pl.cand[(size_t)0 * nb + i] != 0;
-        r[GR_FS] = fs_add ? blocks[i].vel_spp[3] : 0.0;
-        for (int s4 = 0; s4 < 4; ++s4) {
-            const bool add = only_g >= 0 ? (fabs(blocks[i].pos_spp[3 + s4]) > 1e-3 && I[NOM_GNSS + s4] < 0) : pl.cand[(size_t)(1 + s4) * nb + i] != 0;
-            r[GR_CB + s4] = add ? blocks[i].pos_spp[3 + s4] : 0.0;
-        }
-    }
-}
-
-int ingvio_gnss_init_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_init_block* blocks, const double* chi2_table, int chi2_len, double chi2_mult,
-                             int do_chi2, int* added, int* new_idx, int* slot, double* chi2, double* noise, double* dx, int* status)
-{
-    ENTER(c);
-    if (!c) return INGVIO_E_ARG;
-    if (!added || !new_idx || !slot || !chi2 || !noise) return INGVIO_E_ARG;
-    GnssInitPlan pl;
-    if (int rc = gnss_init_validate(c, "ingvio_gnss_init_nominal", b0, nb, blocks, chi2_table, chi2_len, pl)) return rc;
-    const int NC = INGVIO_GNSS_INIT_CAND;
-    const size_t RN = (size_t)NC * nb, S = pl.smax;
-    for (size_t e = 0; e < RN; ++e) { added[e] = 0; new_idx[e] = -1; slot[e] = -1; chi2[e] = 0.0; noise[e] = 0.0; }
-    if (dx) memset(dx, 0, 8 * RN * c->ldp);
-    if (status) for (int i = 0; i < nb; ++i) status[i] = INGVIO_OK;
-    if (!pl.any) return INGVIO_OK;                                                      // nothing to try anywhere: nothing is launched
-    // ---- one slab up: candidates, slots, values, the chi2 table, ephemerides, observations, receiver records ----
-    const size_t ntab = 65;
-    const size_t o_cd = 0, o_sl = o_cd + pad64(4 * RN), o_val = o_sl + pad64(4 * RN), o_tab = o_val + pad64(8 * RN), o_eph = o_tab + pad64(8 * ntab),
-                 o_obs = o_eph + pad64(8 * (size_t)nb * S * GE_N), o_rcv = o_obs + pad64(8 * (size_t)nb * S * GO_N), in_bytes = o_rcv + pad64(8 * (size_t)nb * GR_N);
-    const int mu_cap = 63, nc_cap = 10, mldu = 64;
-    const size_t cs = nc_cap, hsu = (size_t)mldu * nc_cap;
-    const size_t w_res = pad64(8 * (size_t)nb * hsu), w_mu = w_res + pad64(8 * (size_t)nb * mldu), w_nc = w_mu + pad64(4 * (size_t)nb),
-                 w_cm = w_nc + pad64(4 * (size_t)nb), w_var = w_cm + pad64(4 * (size_t)nb * cs), w_rw = w_var + pad64(8 * (size_t)nb),
-                 w_fr = w_rw + pad64(72 * (size_t)nb), wk_bytes = w_fr + pad64(8 * (size_t)nb * 64 * GF_N);
-    const size_t B = c->d.batch;
-    const size_t r_idx = pad64(4 * RN), r_st = r_idx + pad64(4 * RN), r_chi = r_st + pad64(4 * B), r_sl = r_chi + pad64(8 * RN), r_nz = r_sl + pad64(4 * RN),
-                 r_dx = r_nz + pad64(8 * RN), out_bytes = r_dx + (dx ? 8 * RN * c->ldp : 0);
-    auto& w = c->dl;
-    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
-    if (int rc = dl_grow(c, &w.wk, &w.wk_cap, wk_bytes)) return rc;
-    if (w.out_cap < out_bytes && w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; }
-    if (int rc = dl_grow(c, &w.out, &w.out_cap, out_bytes)) return rc;
-    if (!w.h_out) HIPCHK(c, hipHostMalloc((void**)&w.h_out, w.out_cap, hipHostMallocDefault));
-    Uploader upl{ c };
-    if (int rc = upl.begin(in_bytes + 64)) return rc;
-    char* h = upl.take<char>(in_bytes);
-    memset(h, 0, in_bytes);
-    memcpy(h + o_cd, pl.cand.data(), 4 * RN); memcpy(h + o_sl, pl.slots.data(), 4 * RN);
-    double* hval = (double*)(h + o_val);
-    for (int i = 0; i < nb; ++i) {
-        hval[i] = blocks[i].vel_spp[3];
-        for (int s4 = 0; s4 < 4; ++s4) hval[(size_t)(1 + s4) * nb + i] = blocks[i].pos_spp[3 + s4];
-    }
-    memcpy(h + o_tab, chi2_table, 8 * std::min((size_t)chi2_len, ntab));
-    gnss_init_fill(c, b0, nb, blocks, pl, (double*)(h + o_eph), (double*)(h + o_obs), (double*)(h + o_rcv));
-    upl.copy(w.in, h, in_bytes);
-    if (int rc = upl.end()) return rc;
-    int* d_st = (int*)(w.out + r_st);
-    HIPCHK(c, hipMemsetAsync(w.out, 0, r_dx, c->st));                                    // rounds nobody tries are never launched: their slots read "nothing"
-    HIPCHK(c, hipMemsetAsync(c->d_dx + (size_t)b0 * c->ldp, 0, 8 * (size_t)nb * c->ldp, c->st));
-    const NomTable nt = nom_table(c);
-    // ---- the residuals, once (:343-372), and R_w2ecef from YOF as it stands now (:332) ----
-    GnssFrontLaunch G;
-    memset(&G, 0, sizeof G);
-    G.eph = (const double*)(w.in + o_eph); G.obs = (const double*)(w.in + o_obs); G.rcv = (const double*)(w.in + o_rcv); G.smax = (int)S;
-    G.front = (double*)(w.wk + w_fr);                                                   // G.H == nullptr: no staged rows
-    launch_gnss_front(G, nb, c->st, &nt, b0);
-    launch_delayed_gnss_rw(nt, G.rcv, b0, nb, (double*)(w.wk + w_rw), c->st);
-    const CovView cv = view(c);
-    const size_t lds = delayed_front_lds(64, 1, 10);
-    DelayedGnssRows Rw;
-    memset(&Rw, 0, sizeof Rw);
-    Rw.nt = nt; Rw.front = G.front; Rw.eph = G.eph; Rw.obs = G.obs; Rw.rcv = G.rcv; Rw.smax = (int)S; Rw.Rw = (const double*)(w.wk + w_rw);
-    Rw.chi2 = (const double*)(w.in + o_tab); Rw.chi2_mult = chi2_mult;
-    Rw.var_out = (double*)(w.wk + w_var); Rw.nc_out = (int*)(w.wk + w_nc); Rw.colmap_out = (int*)(w.wk + w_cm);
-    for (int g = 0; g < NC; ++g) {
-        if (!pl.round[g]) continue;
-        const size_t r0 = (size_t)g * nb;
-        DelayedFront F;
-        memset(&F, 0, sizeof F);
-        F.cv = cv; F.b0 = b0; F.nb = nb; F.cs = (int)cs; F.do_chi2 = do_chi2 ? 1 : 0;
-        F.Hu = (double*)w.wk; F.resu = (double*)(w.wk + w_res); F.mldu = mldu; F.hsu = hsu; F.mu = (int*)(w.wk + w_mu);
-        F.Y = c->d_Y + (size_t)b0 * c->ystride; F.ystride = (size_t)c->ystride; F.status = d_st;
-        F.added = (int*)w.out + r0; F.new_idx = (int*)(w.out + r_idx) + r0; F.chi2 = (double*)(w.out + r_chi) + r0;
-        Rw.g = g; Rw.cand = (const int*)(w.in + o_cd) + r0; Rw.slot = (const int*)(w.in + o_sl) + r0; Rw.value = (const double*)(w.in + o_val) + r0;
-        Rw.slot_out = (int*)(w.out + r_sl) + r0; Rw.noise_out = (double*)(w.out + r_nz) + r0;
-        if (launch_delayed_front_gnss(F, Rw, lds, c->st)) return INGVIO_E_CAPACITY;
-        EkfLaunch E;                                                                    // StateManager.cpp:623-624: ekfUpdate with the lower rows, R = the round's noise^2
-        memset(&E, 0, sizeof E);
-        E.cv = cv; E.b0 = b0; E.nb = nb; E.H = F.Hu; E.res = F.resu; E.colmap = Rw.colmap_out; E.m = F.mu; E.nc = Rw.nc_out;
-        E.noise = Rw.var_out; E.r_kind = 0; E.mld = mldu; E.hstride = (int)hsu; E.cstride = (int)cs; E.nstride = 1;
-        E.Y = c->d_Y + (size_t)b0 * c->ystride; E.ystride = c->ystride; E.dx = c->d_dx; E.status = d_st; E.m_cap = mu_cap; E.nc_cap = nc_cap;
-        { ProfScope p(c, PF_EKF_CORE); launch_ekf_core(E, c->st); }
-        { ProfScope p(c, PF_DOWNDATE); launch_downdate(E, pl.n_cap, c->st); }
-        launch_nominal_update(nt, c->d_dx, c->ldp, nullptr, b0, nb, c->st);             // boxPlus of the round's dx, the new scalar included (:631-632)
-        if (dx) HIPCHK(c, hipMemcpyAsync(w.out + r_dx + 8 * r0 * c->ldp, c->d_dx + (size_t)b0 * c->ldp, 8 * (size_t)nb * c->ldp, hipMemcpyDeviceToDevice, c->st));
-    }
-    HIPCHK(c, hipMemcpyAsync(w.h_out, w.out, out_bytes, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (int rc = last_launch(c)) return rc;
-    const int *ra = (const int*)w.h_out, *ri = (const int*)(w.h_out + r_idx), *rs = (const int*)(w.h_out + r_st) + b0, *rl = (const int*)(w.h_out + r_sl);
-    const double *rc2 = (const double*)(w.h_out + r_chi), *rnz = (const double*)(w.h_out + r_nz), *rdx = (const double*)(w.h_out + r_dx);
-    int soft = INGVIO_OK;
-    for (int i = 0; i < nb; ++i) {
-        int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
-        for (int g = 0; g < NC; ++g) {
-            const size_t e = (size_t)g * nb + i, oo = (size_t)i * NC + g;
-            if (!pl.cand[e]) continue;
-            added[oo] = ra[e]; new_idx[oo] = ri[e]; slot[oo] = ra[e] ? rl[e] : -1; chi2[oo] = rc2[e]; noise[oo] = rnz[e];
-            if (!ra[e]) continue;
-            if (dx) memcpy(dx + oo * c->ldp, rdx + e * c->ldp, 8 * (size_t)c->ldp);
-            c->h_n[b0 + i] += 1;                                                        // the mirror follows the front's record
-            int* v = I + NOM_IH + 4 * rl[e];
-            v[0] = NOM_KIND_SCALAR; v[1] = ri[e]; v[2] = -1; v[3] = 0;
-            I[NOM_GNSS + (g == 0 ? NOM_G_FS : g - 1)] = rl[e];
-            if (rl[e] >= I[NOM_N_VAR]) I[NOM_N_VAR] = rl[e] + 1;
-        }
-        const int st = (rs[i] & 4) ? INGVIO_E_NOT_PD : ((rs[i] & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);
-        if (status) status[i] = st;
-        if (st != INGVIO_OK) soft = st;
-    }
-    if (nom_mark(c)) return INGVIO_E_HIP;
-    return soft;
-}
-
-// parity hook (tests): the row stage of ingvio_gnss_init_nominal alone, for one filter and candidate g; changes nothing
-int ingvio_debug_gnss_init_rows(ingvio_ctx* c, int b, const ingvio_gnss_init_block* block, int g, double* H_old, double* res, double* noise, int* m_out)
-{
-    ENTER(c);
-    if (!c || !block || g < 0 || g >= INGVIO_GNSS_INIT_CAND || !H_old || !res || !noise || !m_out) return INGVIO_E_ARG;
-    GnssInitPlan pl;
-    if (int rc = gnss_init_validate(c, "ingvio_debug_gnss_init_rows", b, 1, block, nullptr, 0, pl, true)) return rc;
-    *m_out = 0; *noise = 0.0;
-    if (!pl.any) return INGVIO_OK;
-    const size_t S = pl.smax, nrow = 64 * 11 + 1;
-    const size_t o_eph = 0, o_obs = o_eph + pad64(8 * S * GE_N), o_rcv = o_obs + pad64(8 * S * GO_N), in_bytes = o_rcv + pad64(8 * GR_N);
-    const size_t w_rw = pad64(8 * nrow), w_fr = w_rw + 128, w_m = w_fr + pad64(8 * 64 * GF_N), wk_bytes = w_m + 64;
-    auto& w = c->dl;
-    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
-    if (int rc = dl_grow(c, &w.wk, &w.wk_cap, wk_bytes)) return rc;
-    std::vector<char> h(in_bytes, 0);
-    gnss_init_fill(c, b, 1, block, pl, (double*)(h.data() + o_eph), (double*)(h.data() + o_obs), (double*)(h.data() + o_rcv), g);
-    if (up(c, w.in, h.data(), in_bytes)) return INGVIO_E_HIP;
-    const NomTable nt = nom_table(c);
-    GnssFrontLaunch G;
-    memset(&G, 0, sizeof G);
-    G.eph = (const double*)(w.in + o_eph); G.obs = (const double*)(w.in + o_obs); G.rcv = (const double*)(w.in + o_rcv); G.smax = (int)S;
-    G.front = (double*)(w.wk + w_fr);
-    launch_gnss_front(G, 1, c->st, &nt, b);
-    launch_delayed_gnss_rw(nt, G.rcv, b, 1, (double*)(w.wk + w_rw), c->st);
-    DelayedGnssRows Rw;
-    memset(&Rw, 0, sizeof Rw);
-    Rw.nt = nt; Rw.front = G.front; Rw.eph = G.eph; Rw.obs = G.obs; Rw.rcv = G.rcv; Rw.smax = (int)S; Rw.Rw = (const double*)(w.wk + w_rw); Rw.g = g;
-    int* d_m = (int*)(w.wk + w_m);
-    if (launch_delayed_gnss_rows_debug(Rw, b, (double*)w.wk, d_m, c->st)) return INGVIO_E_CAPACITY;
-    std::vector<double> out(nrow);
-    int m = 0;
-    HIPCHK(c, hipMemcpyAsync(out.data(), w.wk, 8 * nrow, hipMemcpyDeviceToHost, c->st));
-    if (down_sync(c, &m, d_m, sizeof(int))) return INGVIO_E_HIP;                        // synchronises: the host vector above may go
-    if (int rc = last_launch(c)) return rc;
-    *m_out = m;
-    if (m == 0) return INGVIO_OK;
-    memcpy(H_old, out.data(), 8 * (size_t)m * 10);
-    memcpy(res, out.data() + (size_t)m * 10, 8 * (size_t)m);
-    *noise = out[(size_t)m * 11];
-    return INGVIO_OK;
-}
-
 int ingvio_replace_var_linear(ingvio_ctx* c, int b, int tidx, int tsize, const int* vidx, const int* vsize, int k, const double* H, int ldh)
 {
     ENTER(c);
@@ -3733,7 +2515,7 @@ int ingvio_landmark_fetch(ingvio_ctx* c, int b0, int nb, double* dx, int* rows, 
     if (gamma) HIPCHK(c, hipMemcpyAsync(gamma, c->lm.gamma + (size_t)b0 * LM_MAX, 8 * (size_t)nb * LM_MAX, hipMemcpyDeviceToHost, c->st));
     if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_status + b0, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
-    if (status) for (int i = 0; i < nb; ++i) status[i] = (status[i] & 4) ? INGVIO_E_NOT_PD : ((status[i] & 2) ? INGVIO_NEG_DIAG : INGVIO_OK);   // bit 4: S not positive definite
+    if (status) for (int i = 0; i < nb; ++i) status[i] = soft_status(status[i]);   // bit 4: S not positive definite
     return last_launch(c);
 }
 
@@ -4062,428 +2844,6 @@ int ingvio_frame_stage_tracks(ingvio_ctx* c, int b0, int nb, const ingvio_frame_
 {
     ENTER(c);
     return frame_stage_tracks_impl(c, b0, nb, steps, frames, opts, sigma, enable_gnss, scb, srw, async, nullptr);
-}
-
-// ---- device-resident nominal state -----------------------------------------------------------------------------
-static int nom_size(int kind) { return kind == NOM_KIND_SE23 ? 9 : kind == NOM_KIND_SE3 ? 6 : kind == NOM_KIND_SCALAR ? 1 : 3; }
-
-int ingvio_nominal_create(ingvio_ctx* c, int v_max)
-{
-    ENTER(c);
-    if (!c || phase_busy(c) || v_max < 1 || v_max > 4096) return INGVIO_E_ARG;
-    if (c->d.c_max > NOM_IH - NOM_CLONES) return INGVIO_E_UNSUPPORTED;
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (c->st_copy) HIPCHK(c, hipStreamSynchronize(c->st_copy));
-    auto& m = c->nom;
-    const size_t B = c->d.batch;
-    if (m.vmax != v_max) {
-        for (void* p : { (void*)m.ih, (void*)m.dv, (void*)m.ih_snap, (void*)m.dv_snap, (void*)m.dx }) if (p) hipFree(p);
-        m.ih = nullptr; m.dv = nullptr; m.ih_snap = nullptr; m.dv_snap = nullptr; m.dx = nullptr; m.vmax = 0;
-        const int ir = NOM_IH + 4 * v_max, dr = NOM_DH + NOM_VD * v_max;
-        if (dalloc(c, &m.ih, B * ir) || dalloc(c, &m.dv, B * dr) || dalloc(c, &m.ih_snap, B * ir) || dalloc(c, &m.dv_snap, B * dr) ||
-            dalloc(c, &m.dx, B * c->ldp)) return INGVIO_E_HIP;
-        m.vmax = v_max; m.ir = ir; m.dr = dr;
-    }
-    m.h_ih.assign(B * m.ir, 0);
-    for (size_t b = 0; b < B; ++b) {
-        int* I = &m.h_ih[b * m.ir];
-        I[NOM_V_EXT] = I[NOM_V_POSE] = I[NOM_V_BG] = I[NOM_V_BA] = -1;
-        for (int s = 0; s < 6; ++s) I[NOM_GNSS + s] = -1;
-        for (int v = 0; v < v_max; ++v) { I[NOM_IH + 4 * v] = NOM_KIND_NONE; I[NOM_IH + 4 * v + 1] = -1; I[NOM_IH + 4 * v + 2] = -1; }
-    }
-    HIPCHK(c, hipMemcpyAsync(m.ih, m.h_ih.data(), sizeof(int) * m.h_ih.size(), hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipMemsetAsync(m.dv, 0, sizeof(double) * B * m.dr, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    m.has_snap = false;
-    if (m.pending) { c->staged = false; m.pending = false; }
-    m.frame = false;
-    if (c->gn.nom_pending) { c->gn.nom_pending = false; c->gn.staged = false; }
-    if (c->lm.nominal && c->lm.staged) { c->lm.nom_pending = false; c->lm.staged = false; }
-    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
-}
-
-int ingvio_nominal_set(ingvio_ctx* c, int b0, int nb, const ingvio_nominal* nom)
-{
-    ENTER(c);
-    if (phase_busy(c) || check_range(c, b0, nb) || !nom) return INGVIO_E_ARG;
-    auto& m = c->nom;
-    if (!m.vmax) { c->err = "ingvio_nominal_set without ingvio_nominal_create"; return INGVIO_E_ARG; }
-    if (m.pending) { c->err = "ingvio_nominal_set: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
-    if (gnss_nom_busy(c, "ingvio_nominal_set")) return INGVIO_E_ARG;
-    // ---- validation of every filter before anything is written ----
-    for (int i = 0; i < nb; ++i) {
-        const ingvio_nominal& q = nom[i];
-        if (q.n_var < 0 || q.n_var > m.vmax || q.n_clones < 0 || q.n_clones > c->d.c_max) return INGVIO_E_CAPACITY;
-        if (q.n_var && (!q.kind || !q.idx || !q.anchor || !q.val)) return INGVIO_E_ARG;
-        if (q.n_clones && !q.clone_var) return INGVIO_E_ARG;
-        auto kind_of = [&](int v) { return v >= 0 && v < q.n_var ? q.kind[v] : -2; };
-        for (int v = 0; v < q.n_var; ++v) {
-            const int k = q.kind[v];
-            if (k < NOM_KIND_NONE || k > NOM_KIND_LM) return INGVIO_E_ARG;
-            if (k == NOM_KIND_NONE) continue;
-            if (q.idx[v] < 0 || q.idx[v] + nom_size(k) > c->d.n_max) return INGVIO_E_ARG;
-            if (k == NOM_KIND_LM && kind_of(q.anchor[v]) != NOM_KIND_SE3) return INGVIO_E_ARG;
-        }
-        for (int a = 0; a < q.n_clones; ++a) {
-            if (kind_of(q.clone_var[a]) != NOM_KIND_SE3) return INGVIO_E_ARG;
-            for (int b = 0; b < a; ++b) if (q.clone_var[b] == q.clone_var[a]) return INGVIO_E_ARG;
-        }
-        if ((q.v_ext >= 0 && kind_of(q.v_ext) != NOM_KIND_SE3) || (q.v_pose >= 0 && kind_of(q.v_pose) != NOM_KIND_SE23) ||
-            (q.v_bg >= 0 && kind_of(q.v_bg) != NOM_KIND_VEC3) || (q.v_ba >= 0 && kind_of(q.v_ba) != NOM_KIND_VEC3)) return INGVIO_E_ARG;
-    }
-    std::vector<int> ih((size_t)nb * m.ir, 0);
-    std::vector<double> dv((size_t)nb * m.dr, 0.0);
-    for (int i = 0; i < nb; ++i) {
-        const ingvio_nominal& q = nom[i];
-        int* I = &ih[(size_t)i * m.ir];
-        double* D = &dv[(size_t)i * m.dr];
-        I[NOM_N_VAR] = q.n_var; I[NOM_N_CLONES] = q.n_clones;
-        I[NOM_V_EXT] = q.v_ext; I[NOM_V_POSE] = q.v_pose; I[NOM_V_BG] = q.v_bg; I[NOM_V_BA] = q.v_ba;
-        for (int s = 0; s < 6; ++s) I[NOM_GNSS + s] = -1;                  // a new table: the GNSS scalars are registered again
-        for (int a = 0; a < q.n_clones; ++a) I[NOM_CLONES + a] = q.clone_var[a];
-        for (int v = 0; v < m.vmax; ++v) {
-            const bool used = v < q.n_var && q.kind[v] != NOM_KIND_NONE;
-            I[NOM_IH + 4 * v] = used ? q.kind[v] : NOM_KIND_NONE;
-            I[NOM_IH + 4 * v + 1] = used ? q.idx[v] : -1;
-            I[NOM_IH + 4 * v + 2] = used && q.kind[v] == NOM_KIND_LM ? q.anchor[v] : -1;
-            if (used) memcpy(D + NOM_DH + (size_t)v * NOM_VD, q.val + (size_t)v * INGVIO_NOM_VAL, 8 * INGVIO_NOM_VAL);
-        }
-        memcpy(D, q.gravity, 24);
-    }
-    HIPCHK(c, hipMemcpyAsync(m.ih + (size_t)b0 * m.ir, ih.data(), sizeof(int) * ih.size(), hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipMemcpyAsync(m.dv + (size_t)b0 * m.dr, dv.data(), sizeof(double) * dv.size(), hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    memcpy(&m.h_ih[(size_t)b0 * m.ir], ih.data(), sizeof(int) * ih.size());
-    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
-}
-
-int ingvio_nominal_get(ingvio_ctx* c, int b0, int nb, ingvio_nominal* out)
-{
-    ENTER(c);
-    if (check_range(c, b0, nb) || !out) return INGVIO_E_ARG;
-    auto& m = c->nom;
-    if (!m.vmax) { c->err = "ingvio_nominal_get without ingvio_nominal_create"; return INGVIO_E_ARG; }
-    for (int i = 0; i < nb; ++i) if (!out[i].kind || !out[i].idx || !out[i].anchor || !out[i].val || !out[i].clone_var) return INGVIO_E_ARG;
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (c->st_copy) HIPCHK(c, hipStreamSynchronize(c->st_copy));      // an asynchronous stage from the table writes it there
-    std::vector<int> ih((size_t)nb * m.ir);
-    std::vector<double> dv((size_t)nb * m.dr);
-    HIPCHK(c, hipMemcpyAsync(ih.data(), m.ih + (size_t)b0 * m.ir, sizeof(int) * ih.size(), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipMemcpyAsync(dv.data(), m.dv + (size_t)b0 * m.dr, sizeof(double) * dv.size(), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    for (int i = 0; i < nb; ++i) {
-        ingvio_nominal& q = out[i];
-        const int* I = &ih[(size_t)i * m.ir];
-        const double* D = &dv[(size_t)i * m.dr];
-        q.n_var = I[NOM_N_VAR]; q.n_clones = I[NOM_N_CLONES];
-        q.v_ext = I[NOM_V_EXT]; q.v_pose = I[NOM_V_POSE]; q.v_bg = I[NOM_V_BG]; q.v_ba = I[NOM_V_BA];
-        for (int a = 0; a < q.n_clones; ++a) q.clone_var[a] = I[NOM_CLONES + a];
-        for (int v = 0; v < q.n_var; ++v) {
-            q.kind[v] = I[NOM_IH + 4 * v]; q.idx[v] = I[NOM_IH + 4 * v + 1]; q.anchor[v] = I[NOM_IH + 4 * v + 2];
-            memcpy(q.val + (size_t)v * INGVIO_NOM_VAL, D + NOM_DH + (size_t)v * NOM_VD, 8 * INGVIO_NOM_VAL);
-        }
-        memcpy(q.gravity, D, 24);
-    }
-    return INGVIO_OK;
-}
-
-int ingvio_nominal_box_plus(ingvio_ctx* c, int b0, int nb, const double* dx)
-{
-    ENTER(c);
-    if (phase_busy(c) || check_range(c, b0, nb) || !dx) return INGVIO_E_ARG;
-    auto& m = c->nom;
-    if (!m.vmax) { c->err = "ingvio_nominal_box_plus without ingvio_nominal_create"; return INGVIO_E_ARG; }
-    if (m.pending) { c->err = "ingvio_nominal_box_plus: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
-    if (gnss_nom_busy(c, "ingvio_nominal_box_plus")) return INGVIO_E_ARG;
-    const size_t bytes = 8 * (size_t)nb * c->ldp;
-    Uploader upl{ c };
-    if (int rc = upl.begin(bytes + 64)) return rc;
-    double* h = upl.take<double>((size_t)nb * c->ldp);
-    memcpy(h, dx, bytes);
-    upl.copy(m.dx + (size_t)b0 * c->ldp, h, (size_t)nb * c->ldp);
-    if (int rc = upl.end()) return rc;
-    launch_nominal_update(nom_table(c), m.dx, c->ldp, nullptr, b0, nb, c->st);
-    if (int rc = last_launch(c)) return rc;
-    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
-}
-
-// Test hook: k_nominal_update_post alone on the TABLE of filters [b0, b0 + nb) - boxPlus of dx [nb][ldp] given in the index space behind
-// the marginalisation of marg_idx[i] (a window clone, >= 0), then the drop and the shift.  The covariance is not touched: the caller
-// compares the table with its host model and discards the context.
-int ingvio_debug_nominal_update_post(ingvio_ctx* c, int b0, int nb, const double* dx, const int* marg_idx)
-{
-    ENTER(c);
-    if (phase_busy(c) || check_range(c, b0, nb) || !dx || !marg_idx) return INGVIO_E_ARG;
-    auto& m = c->nom;
-    if (!m.vmax || m.pending || gnss_nom_busy(c, "ingvio_debug_nominal_update_post")) return INGVIO_E_ARG;
-    static const int size_of[5] = { 9, 6, 3, 1, 3 };
-    for (int i = 0; i < nb; ++i) {
-        const int* I = &m.h_ih[(size_t)(b0 + i) * m.ir];
-        const int* var = I + NOM_IH;
-        const int mg = marg_idx[i];
-        bool clone = false;
-        for (int q = 0; q < I[NOM_N_CLONES]; ++q) if (mg >= 0 && var[4 * I[NOM_CLONES + q] + 1] == mg) clone = true;
-        if (!clone) return INGVIO_E_NOT_IN_STATE;
-        for (int v = 0; v < I[NOM_N_VAR]; ++v) {                       // every word of dx a lane will read lies inside the row
-            const int kind = var[4 * v], idx = var[4 * v + 1];
-            if (kind == NOM_KIND_NONE || idx == mg) continue;
-            if (kind < 0 || kind > NOM_KIND_LM || idx < 0 || (idx > mg ? idx - 6 : idx) + size_of[kind] > c->ldp) return INGVIO_E_NOT_IN_STATE;
-        }
-    }
-    int* d_marg = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d_marg, sizeof(int) * (size_t)c->d.batch));
-    int rc = up(c, d_marg + b0, marg_idx, sizeof(int) * (size_t)nb) | up(c, m.dx + (size_t)b0 * c->ldp, dx, 8 * (size_t)nb * c->ldp);
-    if (!rc) launch_nominal_update_post(nom_table(c), m.dx, c->ldp, d_marg, b0, nb, c->st);
-    hipStreamSynchronize(c->st);                                        // (pageable sources, the temporary)
-    hipFree(d_marg);
-    if (rc) return INGVIO_E_HIP;
-    if (int rc2 = last_launch(c)) return rc2;
-    for (int i = 0; i < nb; ++i) nom_mirror_marg(c, b0 + i, marg_idx[i]);
-    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
-}
-
-// the table slots of the GNSS scalars (State::GNSSType order: clock GPS, GLO, GAL, BDS, FS, YOF); they live in the integer record
-int ingvio_nominal_set_gnss(ingvio_ctx* c, int b0, int nb, const int* slots)
-{
-    ENTER(c);
-    if (phase_busy(c) || check_range(c, b0, nb) || !slots) return INGVIO_E_ARG;
-    auto& m = c->nom;
-    if (!m.vmax) { c->err = "ingvio_nominal_set_gnss without ingvio_nominal_create"; return INGVIO_E_ARG; }
-    if (m.pending) { c->err = "ingvio_nominal_set_gnss: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
-    if (gnss_nom_busy(c, "ingvio_nominal_set_gnss")) return INGVIO_E_ARG;
-    for (int i = 0; i < nb; ++i) {
-        const int* I = &m.h_ih[(size_t)(b0 + i) * m.ir];
-        for (int s = 0; s < 6; ++s) {
-            const int v = slots[6 * i + s];
-            if (v == -1) continue;
-            if (v < 0 || v >= I[NOM_N_VAR] || I[NOM_IH + 4 * v] != NOM_KIND_SCALAR) {
-                c->err = "ingvio_nominal_set_gnss: a slot is out of range or holds no Scalar"; return INGVIO_E_ARG;
-            }
-            for (int t = 0; t < s; ++t) if (slots[6 * i + t] == v) { c->err = "ingvio_nominal_set_gnss: a slot is named twice"; return INGVIO_E_ARG; }
-        }
-    }
-    // behind the kernels that read the record (the stream orders the copies); the six ints of a filter are contiguous
-    Uploader upl{ c };
-    if (int rc = upl.begin(pad64(sizeof(int) * 6 * (size_t)nb) + 64)) return rc;
-    int* h = upl.take<int>(6 * (size_t)nb);
-    memcpy(h, slots, sizeof(int) * 6 * (size_t)nb);
-    // (no frame is staged from the table here - refused above - so nothing on the copy stream reads the record)
-    upl.copy_rows(m.ih + (size_t)b0 * m.ir + NOM_GNSS, (size_t)m.ir, h, (size_t)6, (size_t)6, (size_t)nb);
-    if (int rc = upl.end()) return rc;
-    for (int i = 0; i < nb; ++i) memcpy(&m.h_ih[(size_t)(b0 + i) * m.ir + NOM_GNSS], slots + 6 * (size_t)i, sizeof(int) * 6);
-    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
-}
-
-int ingvio_nominal_get_gnss(ingvio_ctx* c, int b0, int nb, int* slots)
-{
-    ENTER(c);
-    if (check_range(c, b0, nb) || !slots) return INGVIO_E_ARG;
-    auto& m = c->nom;
-    if (!m.vmax) { c->err = "ingvio_nominal_get_gnss without ingvio_nominal_create"; return INGVIO_E_ARG; }
-    for (int i = 0; i < nb; ++i) memcpy(slots + 6 * (size_t)i, &m.h_ih[(size_t)(b0 + i) * m.ir + NOM_GNSS], sizeof(int) * 6);      // the mirror is the record
-    return INGVIO_OK;
-}
-
-// ---- odometry output (kernels_odom.hip) -----------------------------------------------------------------------------
-static_assert(sizeof(ingvio_odom) == 8 * ODOM_REC, "ingvio_odom and the kernel's record differ");
-static_assert(offsetof(ingvio_odom, R_i2w) == 8 * (ODOM_HDR + ODOM_O_VAL) && offsetof(ingvio_odom, diag_min) == 8 * (ODOM_HDR + ODOM_O_DIAG) &&
-              offsetof(ingvio_odom, cov_err) == 8 * (ODOM_HDR + ODOM_O_ERR) && offsetof(ingvio_odom, cov_pose) == 8 * (ODOM_HDR + ODOM_O_POSE) &&
-              offsetof(ingvio_odom, cov_vel) == 8 * (ODOM_HDR + ODOM_O_VEL) && offsetof(ingvio_odom, gnss) == 8 * (ODOM_HDR + ODOM_O_VAL + 33),
-              "ingvio_odom and the kernel's record differ");
-static_assert(INGVIO_ODOM_COV == ODOM_W_COV && INGVIO_ODOM_EUCL == ODOM_W_EUCL && INGVIO_ODOM_DIAG == ODOM_W_DIAG &&
-              INGVIO_ODOM_NONFINITE == ODOM_S_NONFINITE && INGVIO_ODOM_NEG_DIAG == ODOM_S_NEG_DIAG && INGVIO_ODOM_ABSENT == ODOM_S_ABSENT &&
-              INGVIO_MARGINAL_NS_MAX == MARG_NS_MAX, "ingvio_hip.h and launch_odom.h differ");
-
-// Only enqueues: the kernel, the table event behind it (an asynchronous stage from the table waits for that one before its IMU steps
-// advance the pose), the copy of the records into their pinned mirror, the event ingvio_odom_end waits for.  Every refusal comes first.
-int ingvio_odom_begin(ingvio_ctx* c, int b0, int nb, int what)
-{
-    if (!c || check_range(c, b0, nb)) return INGVIO_E_ARG;
-    auto& m = c->nom;
-    auto& o = c->od;
-    if (what & ~(INGVIO_ODOM_COV | INGVIO_ODOM_EUCL | INGVIO_ODOM_DIAG)) { c->err = "ingvio_odom_begin: an unknown bit in what"; return INGVIO_E_ARG; }
-    if (phase_busy(c)) return INGVIO_E_ARG;
-    if (!m.vmax) { c->err = "ingvio_odom_begin without ingvio_nominal_create"; return INGVIO_E_ARG; }
-    if (m.pending) { c->err = "ingvio_odom_begin: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
-    if (gnss_nom_busy(c, "ingvio_odom_begin")) return INGVIO_E_ARG;
-    if ((c->gn.frame_nom && c->gn.staged) || (c->lm.nominal && c->lm.staged)) {
-        c->err = "ingvio_odom_begin: an in-frame GNSS epoch or landmark update staged from the device nominal state has not run yet";
-        return INGVIO_E_ARG;
-    }
-    if (o.pending) { c->err = "ingvio_odom_begin: the previous ingvio_odom_begin has not been ended"; return INGVIO_E_ARG; }
-    ENTER(c);
-    if (!o.d) {                                                        // the first call of the context
-        HIPCHK(c, hipMalloc((void**)&o.d, 8 * (size_t)c->d.batch * ODOM_REC));
-        if (hipHostMalloc((void**)&o.h, 8 * (size_t)c->d.batch * ODOM_REC, hipHostMallocDefault) != hipSuccess) {
-            hipFree(o.d); o.d = nullptr; o.h = nullptr;
-            c->err = "ingvio_odom_begin: hipHostMalloc"; return INGVIO_E_HIP;
-        }
-    }
-    if (!o.ev) HIPCHK(c, hipEventCreateWithFlags(&o.ev, hipEventDisableTiming));
-    if (what & INGVIO_ODOM_EUCL) what |= INGVIO_ODOM_COV;
-    launch_odom_out(nom_table(c), view_ro(c), o.d, b0, nb, what, c->st);
-    if (int rc = last_launch(c)) return rc;
-    if (nom_mark(c)) return INGVIO_E_HIP;
-    HIPCHK(c, hipMemcpyAsync(o.h + (size_t)b0 * ODOM_REC, o.d + (size_t)b0 * ODOM_REC, 8 * (size_t)nb * ODOM_REC, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipEventRecord(o.ev, c->st));
-    o.pending = true; o.b0 = b0; o.nb = nb;
-    return INGVIO_OK;
-}
-
-int ingvio_odom_end(ingvio_ctx* c, ingvio_odom* out)
-{
-    if (!c || !out) return INGVIO_E_ARG;                                // (no ENTER: the records are already on their way)
-    auto& o = c->od;
-    if (!o.pending) { c->err = "ingvio_odom_end without a pending ingvio_odom_begin"; return INGVIO_E_ARG; }
-    HIPCHK(c, hipEventSynchronize(o.ev));
-    o.pending = false;
-    memcpy(out, o.h + (size_t)o.b0 * ODOM_REC, 8 * (size_t)o.nb * ODOM_REC);
-    return INGVIO_OK;
-}
-
-// ---- the landmark tail of a frame on the device (kernels_tail.hip) ------------------------------------------------
-// changeLandmarkAnchor (LandmarkUpdate.cpp:273-361), margSwPose and margAnchoredLandmarkInState (StateManager.cpp:340-353) for filters
-// [b0, b0 + nb) in one sweep over P.  Everything is validated on the host mirror before the first launch; the verdicts of the depth test
-// come back with the one synchronisation at the end, and the mirror follows them.
-int ingvio_nominal_tail(ingvio_ctx* c, int b0, int nb, const ingvio_nominal_tail_block* blocks, int lm_cap, int* verdict, int* status)
-{
-    ENTER(c);
-    if (!c || phase_busy(c) || check_range(c, b0, nb) || !blocks || lm_cap < 0) return INGVIO_E_ARG;
-    auto& m = c->nom;
-    const char* who = "ingvio_nominal_tail";
-    if (!m.vmax) { c->err = "ingvio_nominal_tail without ingvio_nominal_create"; return INGVIO_E_ARG; }
-    if (m.pending) { c->err = "ingvio_nominal_tail: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
-    if (gnss_nom_busy(c, who)) return INGVIO_E_ARG;
-    auto fail = [&](int code, const char* what) { c->err = std::string(who) + ": " + what; return code; };
-    int kcap = 0, ecap = 0, mcap = 0, active = 0;
-    std::vector<char> mark((size_t)m.vmax);
-    for (int i = 0; i < nb; ++i) {
-        const ingvio_nominal_tail_block& q = blocks[i];
-        const int b = b0 + i;
-        if (q.n_reanchor < 0 || q.n_erase < 0 || q.n_marg < 0) return fail(INGVIO_E_ARG, "a negative count");
-        if (q.n_reanchor > lm_cap || q.n_reanchor > TAIL_LM_MAX) return fail(INGVIO_E_ARG, "n_reanchor exceeds lm_cap or 64");
-        if ((q.n_reanchor && (!q.lm_slot || !verdict)) || (q.n_erase && !q.erase_slot) || (q.n_marg && !q.marg_slot)) return fail(INGVIO_E_ARG, "NULL where data is needed");
-        if (q.n_erase > m.vmax || q.n_marg > NOM_IH - NOM_CLONES) return fail(INGVIO_E_ARG, "more slots listed than the table holds");
-        if (q.n_reanchor + q.n_erase + q.n_marg == 0) continue;
-        ++active;
-        kcap = std::max(kcap, q.n_reanchor); ecap = std::max(ecap, q.n_erase); mcap = std::max(mcap, q.n_marg);
-        const int* I = &m.h_ih[(size_t)b * m.ir];
-        const int* var = I + NOM_IH;
-        const int nv = I[NOM_N_VAR], nc = I[NOM_N_CLONES], n = c->h_n[b];
-        auto in_window = [&](int sl) { for (int w = 0; w < nc; ++w) if (I[NOM_CLONES + w] == sl) return true; return false; };
-        auto is_marg = [&](int sl) { for (int e = 0; e < q.n_marg; ++e) if (q.marg_slot[e] == sl) return true; return false; };
-        // every column index the kernels form comes from the table: all of it has to lie inside the live state
-        for (int v = 0; v < nv; ++v)
-            if (var[4 * v] != NOM_KIND_NONE && (var[4 * v + 1] < 0 || var[4 * v + 1] + nom_size(var[4 * v]) > n)) return fail(INGVIO_E_NOT_IN_STATE, "a table variable lies beyond the filter's n");
-        std::fill(mark.begin(), mark.end(), 0);
-        for (int e = 0; e < q.n_reanchor + q.n_erase; ++e) {
-            const int sl = e < q.n_reanchor ? q.lm_slot[e] : q.erase_slot[e - q.n_reanchor];
-            if (sl < 0 || sl >= nv || var[4 * sl] != NOM_KIND_LM) return fail(INGVIO_E_NOT_IN_STATE, "a listed slot is free or holds no landmark");
-            if (mark[sl]) return fail(INGVIO_E_ARG, "a landmark slot is named twice");
-            mark[sl] = 1;
-        }
-        for (int e = 0; e < q.n_marg; ++e) {
-            const int sl = q.marg_slot[e];
-            if (sl < 0 || sl >= nv || var[4 * sl] != NOM_KIND_SE3 || !in_window(sl)) return fail(INGVIO_E_NOT_IN_STATE, "a marg_slot is no window clone");
-            for (int t = 0; t < e; ++t) if (q.marg_slot[t] == sl) return fail(INGVIO_E_ARG, "a marg_slot is named twice");
-        }
-        if (q.n_reanchor) {
-            const int na = q.new_anchor;
-            if (na < 0 || na >= nv || var[4 * na] != NOM_KIND_SE3 || !in_window(na)) return fail(INGVIO_E_NOT_IN_STATE, "new_anchor is no window clone");
-            if (is_marg(na)) return fail(INGVIO_E_ARG, "new_anchor is listed in marg_slot");
-            if (nc < 2) return fail(INGVIO_E_ARG, "an anchor change needs two window clones (MapServerManager.cpp:347)");
-            for (int e = 0; e < q.n_reanchor; ++e) {
-                const int an = var[4 * q.lm_slot[e] + 2];
-                if (an == na) return fail(INGVIO_E_ARG, "a landmark is already anchored to new_anchor");
-                if (an < 0 || an >= nv || var[4 * an] != NOM_KIND_SE3) return fail(INGVIO_E_ARG, "a landmark without a live anchor");
-            }
-        }
-        for (int v = 0; v < nv; ++v)
-            if (var[4 * v] == NOM_KIND_LM && !mark[v] && is_marg(var[4 * v + 2])) return fail(INGVIO_E_ARG, "a surviving landmark would stay anchored to a clone that leaves");
-    }
-    if (tail_panel_lds(c->ldp) > TAIL_LDS_MAX) return fail(INGVIO_E_CAPACITY, "the state is too wide for the panel kernel's index maps");
-    if (status) for (int i = 0; i < nb; ++i) status[i] = INGVIO_OK;
-    if (verdict) for (size_t e = 0; e < (size_t)nb * lm_cap; ++e) verdict[e] = 0;
-    if (!active) return INGVIO_OK;                                                      // nothing to do anywhere: nothing is launched
-    // ---- lists up, workspace ----
-    const int istride = TAIL_HDR + kcap + ecap + mcap, ld = c->ldp;
-    const size_t in_bytes = pad64(sizeof(int) * (size_t)nb * istride);
-    const size_t zstride = (size_t)ld * 3 * kcap;
-    const size_t w_ver = pad64(sizeof(int) * (size_t)nb), w_map = w_ver + pad64(sizeof(int) * (size_t)nb * std::max(kcap, 1)),
-                 w_tag = w_map + pad64(sizeof(int) * (size_t)nb * ld), w_Z = w_tag + pad64(sizeof(int) * (size_t)nb * ld),
-                 ws_bytes = w_Z + 8 * (size_t)nb * zstride + 64, out_bytes = w_map;      // nnew | verdict come back
-    auto& w = c->tl;
-    if (int rc = dl_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
-    if (int rc = dl_grow(c, &w.ws, &w.ws_cap, ws_bytes)) return rc;
-    if (w.out_cap < out_bytes) {
-        if (w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; w.out_cap = 0; }
-        HIPCHK(c, hipHostMalloc((void**)&w.h_out, out_bytes + 4096, hipHostMallocDefault));
-        w.out_cap = out_bytes + 4096;
-    }
-    Uploader upl{ c };
-    if (int rc = upl.begin(in_bytes + 64)) return rc;
-    int* h = upl.take<int>(in_bytes / sizeof(int));
-    memset(h, 0, in_bytes);
-    for (int i = 0; i < nb; ++i) {
-        const ingvio_nominal_tail_block& q = blocks[i];
-        int* r = h + (size_t)i * istride;
-        r[TAIL_N_RE] = q.n_reanchor; r[TAIL_NEW] = q.n_reanchor ? q.new_anchor : 0; r[TAIL_N_ER] = q.n_erase; r[TAIL_N_MG] = q.n_marg;
-        for (int e = 0; e < q.n_reanchor; ++e) r[TAIL_HDR + e] = q.lm_slot[e];
-        for (int e = 0; e < q.n_erase; ++e) r[TAIL_HDR + kcap + e] = q.erase_slot[e];
-        for (int e = 0; e < q.n_marg; ++e) r[TAIL_HDR + kcap + ecap + e] = q.marg_slot[e];
-    }
-    upl.copy((int*)w.in, h, in_bytes / sizeof(int));
-    if (int rc = upl.end()) return rc;
-    if (wait_inputs(c)) return INGVIO_E_HIP;                                            // nothing on the copy stream may still read the table
-    TailLaunch L;
-    L.cv = view(c); L.t = nom_table(c); L.b0 = b0; L.nb = nb;
-    L.in = (const int*)w.in; L.istride = istride; L.kcap = kcap; L.ecap = ecap; L.mcap = mcap;
-    L.nnew = (int*)w.ws; L.verdict = (int*)(w.ws + w_ver); L.map = (int*)(w.ws + w_map); L.tag = (int*)(w.ws + w_tag);
-    L.Z = (double*)(w.ws + w_Z); L.zstride = zstride;
-    if (launch_tail(L, c->d.n_max, c->st)) return fail(INGVIO_E_CAPACITY, "a workspace bound of the tail kernels does not hold");
-    HIPCHK(c, hipMemcpyAsync(w.h_out, w.ws, out_bytes, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));                                             // only the device knows the verdicts
-    if (int rc = last_launch(c)) return rc;
-    // ---- the mirror follows the verdicts: the arithmetic of k_tail_panel's table pass on the host's copy ----
-    const int* h_nnew = (const int*)w.h_out;
-    const int* h_ver = (const int*)(w.h_out + w_ver);
-    for (int i = 0; i < nb; ++i) {
-        const ingvio_nominal_tail_block& q = blocks[i];
-        if (q.n_reanchor + q.n_erase + q.n_marg == 0) continue;
-        const int b = b0 + i;
-        int* I = &m.h_ih[(size_t)b * m.ir];
-        int* var = I + NOM_IH;
-        const int nv = I[NOM_N_VAR];
-        std::fill(mark.begin(), mark.end(), 0);                                         // 1: the slot leaves
-        for (int e = 0; e < q.n_reanchor; ++e) {
-            const int v = h_ver[(size_t)i * kcap + e];
-            verdict[(size_t)i * lm_cap + e] = v;
-            if (v) var[4 * q.lm_slot[e] + 2] = q.new_anchor; else mark[q.lm_slot[e]] = 1;
-        }
-        for (int e = 0; e < q.n_erase; ++e) mark[q.erase_slot[e]] = 1;
-        for (int e = 0; e < q.n_marg; ++e) mark[q.marg_slot[e]] = 1;
-        int wq = 0;
-        for (int a = 0; a < I[NOM_N_CLONES]; ++a) if (!mark[I[NOM_CLONES + a]]) I[NOM_CLONES + wq++] = I[NOM_CLONES + a];
-        I[NOM_N_CLONES] = wq;
-        std::vector<int> nidx((size_t)nv, -1);
-        int gone = 0;
-        for (int v = 0; v < nv; ++v) {
-            if (var[4 * v] == NOM_KIND_NONE) continue;
-            if (mark[v]) { gone += nom_size(var[4 * v]); continue; }
-            int sh = 0;
-            for (int u = 0; u < nv; ++u) if (mark[u] && var[4 * u] != NOM_KIND_NONE && var[4 * u + 1] < var[4 * v + 1]) sh += nom_size(var[4 * u]);
-            nidx[v] = var[4 * v + 1] - sh;
-        }
-        for (int v = 0; v < nv; ++v) {
-            if (var[4 * v] == NOM_KIND_NONE) continue;
-            if (mark[v]) { var[4 * v] = NOM_KIND_NONE; var[4 * v + 1] = -1; var[4 * v + 2] = -1; }
-            else var[4 * v + 1] = nidx[v];
-        }
-        if (h_nnew[i] != c->h_n[b] - gone) return fail(INGVIO_E_HIP, "the device's dimension after the tail disagrees with the host mirror");
-        c->h_n[b] = h_nnew[i];
-        c->h_cur[b] ^= 1;
-    }
-    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
 }
 
 int ingvio_frame_stage_tracks_nominal(ingvio_ctx* c, int b0, int nb, const ingvio_frame_step_nominal* steps, const ingvio_track_frame* frames,
