@@ -735,6 +735,61 @@ typedef struct {
 } ingvio_odom;
 int ingvio_odom_begin(ingvio_ctx* ctx, int b0, int nb, int what);
 int ingvio_odom_end(ingvio_ctx* ctx, ingvio_odom* out /* [nb] */);
+/* ---- MSCKF anchor change and invalid-feature erase on the track store --------------------------------------------
+ * changeMSCKFAnchor (KeyframeUpdate.cpp:280-328, SwMargUpdate.cpp:367-413) and eraseInvalidFeatures (MapServerManager.cpp:456-491) for
+ * the tracks the host lists from its integer bookkeeping; the depth tests read the store's points and the table's clone poses, which
+ * exist only on the device.  Per filter one list of entries  track | anchor_pos << 16 | move << 24:
+ *   anchor_pos  a position in the table's window list as it stands at the call's place in the stream (after a run that dropped a clone
+ *               the list has closed up; the store's slot numbering plays no part)
+ *   move = 1    the track's anchor leaves the window: anchor_pos names the NEW anchor (the reference takes the window's newest clone);
+ *   move = 0    anchor_pos names the track's current anchor.
+ * has_point is the reference's sticky _isTri (MapServerManager.cpp:292-296, 326-330): set when a point enters the store (pf_track of a
+ * delta, a successful device triangulation), cleared by free_tracks, by ingvio_tracks_create and by an erasure of this call.  Per entry:
+ *   no point:            move ? INGVIO_MAINTAIN_ERASED_UNTRIANGULATED : INGVIO_MAINTAIN_KEEP
+ *   d = (R_a^T (p_f - p_a)).z with the store's point and the pose of the table's clone at anchor_pos
+ *   move && d <= move_min_depth (0.3 key-frame mode, 0.0 sliding-window mode):  INGVIO_MAINTAIN_ERASED_MOVE
+ *   d <= min_depth (0.2):  INGVIO_MAINTAIN_ERASED_INVALID   (a moved track is tested at its new anchor: no pose changes between the
+ *                                                            reference's two steps)
+ *   otherwise INGVIO_MAINTAIN_MOVED / INGVIO_MAINTAIN_KEEP.
+ * The comparisons are C++'s: a NaN depth is not <= anything and KEEPS the track, as body.z() <= 0.2 does in the reference and in the
+ * host shim; -inf erases, +inf keeps.  An erased track loses its mask and has_point exactly as one named in free_tracks; nothing else
+ * changes in the store, the table, P or n.  depth is 0 for an entry without a point.
+ * lm_slot (optional): table slots of in-state landmarks; each reports INGVIO_MAINTAIN_ERASED_INVALID when the depth of the table's value
+ * at its table anchor is <= min_depth, else INGVIO_MAINTAIN_KEEP.  Report only: the caller marginalises them with ingvio_nominal_tail
+ * (its erase_slot list).
+ * _begin enqueues on the context's stream, behind everything already there: the lists (a small upload kernel reading pinned memory, or a copy), ONE kernel over the filters, the table event (an asynchronous
+ * stage on the copy stream - from the table or host-fed - is ordered behind the erasures), one device-to-host copy into a pinned buffer of its own, an event.  _end
+ * waits for that event only and copies the verdicts out: row i of verdict / depth has list_cap entries, of lm_verdict lm_cap entries;
+ * depth may be NULL.  ingvio_tracks_maintain is _begin + _end.  A partial range is allowed (only the listed filters' store is touched);
+ * one call is pending per context; a filter whose lists are empty is untouched, a call whose lists are all empty launches nothing.
+ * (A call with longer lists than any before allocates; the context's first call does.)
+ * The free-running form  run(i); maintain_begin(i); stage_tracks_nominal(i + 1, async); run(i + 1); maintain_end(i):  the stage of entry
+ * i + 1 is built WITHOUT entry i's verdicts.  An erased track to which that stage appends is a restarted track holding that one
+ * observation and no point; an erased track that the stage lists as a feature has an empty mask under its selection and drops out of the
+ * update as accepted = 0, by the mechanism of a failed triangulation.  At _end the host corrects its bookkeeping of an erased track:
+ * mask = the observations since _begin, anchor = the first of them.
+ * Refused before anything is enqueued or changed.  INGVIO_E_ARG: no table or no store, a bad range, NULL where data is needed, a list
+ * longer than t_max or list_cap (lm_cap), a track outside the store, a track named twice in a filter's list, bits above move, any stage
+ * from the table that has not run, a split frame step pending, _begin while one is pending, _end without _begin.
+ * INGVIO_E_NOT_IN_STATE: an anchor_pos beyond the host mirror's window, a landmark slot that is free or holds no landmark. */
+#define INGVIO_MAINTAIN_KEEP 0
+#define INGVIO_MAINTAIN_MOVED 1
+#define INGVIO_MAINTAIN_ERASED_UNTRIANGULATED 2
+#define INGVIO_MAINTAIN_ERASED_MOVE 3
+#define INGVIO_MAINTAIN_ERASED_INVALID 4
+typedef struct {
+    int n_tracks; const int* tracks;      /* track | anchor_pos << 16 | move << 24                                                  */
+    int n_lm; const int* lm_slot;         /* in-state landmarks (table slots), report only                                          */
+} ingvio_maintain_block;
+typedef struct {
+    double move_min_depth, min_depth;
+    int list_cap, lm_cap;                 /* entries per filter in the result arrays                                                */
+} ingvio_maintain_opts;
+int ingvio_tracks_maintain_begin(ingvio_ctx* ctx, int b0, int nb, const ingvio_maintain_block* blocks /* [nb] */, const ingvio_maintain_opts* opts);
+int ingvio_tracks_maintain_end(ingvio_ctx* ctx, unsigned char* verdict /* [nb][list_cap] */, double* depth /* [nb][list_cap], may be NULL */,
+                               unsigned char* lm_verdict /* [nb][lm_cap] */);
+int ingvio_tracks_maintain(ingvio_ctx* ctx, int b0, int nb, const ingvio_maintain_block* blocks, const ingvio_maintain_opts* opts,
+                           unsigned char* verdict, double* depth, unsigned char* lm_verdict);
 /* ingvio_gnss_front_stage with the receiver taken from the device table: the epoch carries only what the host owns.  p_w, v_w
  * (State::_extended_pose), the clock biases, FS and YOF (GnssUpdate.cpp:98-122 reads them from the state) and every Type::idx() come
  * from the filter's table as the frame that has just run left it - IngvioFilter.cpp:329-362 runs after :276-327 and after margSwPose,
@@ -1031,6 +1086,8 @@ int ingvio_debug_info_solution(ingvio_ctx* ctx, int b, double* out, int count);
  * INGVIO_E_ARG for a b outside the batch or without a store.  Measurements are meaningful where the mask bit is set: closing a
  * track's row up leaves the old values in the columns it vacates. */
 int ingvio_debug_tracks_read(ingvio_ctx* ctx, int b, unsigned long long* mask, double* uv, double* pf);
+/* parity hook (tests): filter b's point flags has_point [t_max] of the track store (0 / 1); synchronises as ingvio_debug_tracks_read. */
+int ingvio_debug_tracks_flags(ingvio_ctx* ctx, int b, unsigned char* has_point);
 
 /* parity hook (tests): filter b's arrays of the input set the NEXT ingvio_frame_run reads (after an asynchronous stage: the set just
  * staged into), whichever of ingvio_frame_stage(_async) / ingvio_frame_stage_tracks(_nominal) filled it: n_clones [1], n_feat [1],

@@ -51,6 +51,7 @@ EXPORTS = [
     "ingvio_odom_begin", "ingvio_odom_end", "ingvio_cov_get_marginal_batch",
     "ingvio_frame_stage_tracks_nominal_tri", "ingvio_set_first_tri_placement",
     "ingvio_gnss_init_nominal", "ingvio_debug_gnss_init_rows",
+    "ingvio_tracks_maintain_begin", "ingvio_tracks_maintain_end", "ingvio_tracks_maintain", "ingvio_debug_tracks_flags",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -61,6 +62,8 @@ ODOM_COV, ODOM_EUCL, ODOM_DIAG = 1, 2, 4
 ODOM_ALL = ODOM_COV | ODOM_EUCL | ODOM_DIAG
 ODOM_NONFINITE, ODOM_NEG_DIAG, ODOM_ABSENT = 1, 2, 4
 MARGINAL_NS_MAX = 64
+# verdicts of ingvio_tracks_maintain (INGVIO_MAINTAIN_* of ingvio_hip.h)
+MAINTAIN_KEEP, MAINTAIN_MOVED, MAINTAIN_ERASED_UNTRIANGULATED, MAINTAIN_ERASED_MOVE, MAINTAIN_ERASED_INVALID = 0, 1, 2, 3, 4
 
 
 class GateBlock(C.Structure):
@@ -145,6 +148,19 @@ def make_lm_init_blocks(blocks):
 class NominalTailBlock(C.Structure):
     _fields_ = [("n_reanchor", C.c_int), ("lm_slot", C.POINTER(C.c_int)), ("new_anchor", C.c_int), ("n_erase", C.c_int),
                 ("erase_slot", C.POINTER(C.c_int)), ("n_marg", C.c_int), ("marg_slot", C.POINTER(C.c_int))]
+
+
+class MaintainBlock(C.Structure):
+    _fields_ = [("n_tracks", C.c_int), ("tracks", C.POINTER(C.c_int)), ("n_lm", C.c_int), ("lm_slot", C.POINTER(C.c_int))]
+
+
+class MaintainOpts(C.Structure):
+    _fields_ = [("move_min_depth", C.c_double), ("min_depth", C.c_double), ("list_cap", C.c_int), ("lm_cap", C.c_int)]
+
+
+def maintain_word(track, anchor_pos, move):
+    """one entry of a maintenance list: track | anchor_pos << 16 | move << 24"""
+    return int(track) | (int(anchor_pos) << 16) | (int(move) << 24)
 
 
 class GnssOpts(C.Structure):
@@ -1039,6 +1055,54 @@ class Context:
         mask = np.zeros(max(T, 1), dtype=np.uint64); uv = np.zeros((max(T, 1), self.c_max, 4)); pf = np.zeros((max(T, 1), 3))
         self._chk(self.L.ingvio_debug_tracks_read(self.h, int(b), mask.ctypes.data_as(c_up), _d(uv), _d(pf)))
         return mask, uv, pf
+
+    def debug_tracks_flags(self, b):
+        """filter b's point flags [t_max] uint8 of the track store (ingvio_debug_tracks_flags)"""
+        has = np.zeros(max(getattr(self, "t_max", 0), 1), dtype=np.uint8)
+        self._chk(self.L.ingvio_debug_tracks_flags(self.h, int(b), has.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return has
+
+    # ---- MSCKF anchor change and invalid-feature erase on the store (DESIGN 4.11) ------------------------------------------------
+    def _maintain_args(self, blocks, move_min_depth, min_depth, list_cap, lm_cap):
+        nb = len(blocks)
+        arr = (MaintainBlock * max(nb, 1))(); keep = []
+        for i, bk in enumerate(blocks):
+            tr, lm = i32(bk.get("tracks", [])), i32(bk.get("lm_slot", []))
+            keep.append((tr, lm))
+            arr[i].n_tracks = len(tr); arr[i].n_lm = len(lm)
+            if len(tr):
+                arr[i].tracks = _i(tr)
+            if len(lm):
+                arr[i].lm_slot = _i(lm)
+        o = MaintainOpts()
+        o.move_min_depth = float(move_min_depth); o.min_depth = float(min_depth)
+        o.list_cap = max([len(k[0]) for k in keep] + [1]) if list_cap is None else int(list_cap)
+        o.lm_cap = max([len(k[1]) for k in keep] + [1]) if lm_cap is None else int(lm_cap)
+        return nb, arr, o, keep
+
+    def tracks_maintain_begin(self, b0, blocks, move_min_depth=0.0, min_depth=0.2, list_cap=None, lm_cap=None):
+        """enqueues the anchor change / invalid-feature erase of filters b0, b0 + 1, ... (ingvio_tracks_maintain_begin); blocks are dicts
+        with tracks (words as maintain_word makes them) and lm_slot, each optional.  No synchronisation."""
+        nb, arr, o, keep = self._maintain_args(blocks, move_min_depth, min_depth, list_cap, lm_cap)
+        self._chk(self.L.ingvio_tracks_maintain_begin(self.h, int(b0), nb, arr, C.byref(o)))
+        self._maintain = (nb, o.list_cap, o.lm_cap, [(len(k[0]), len(k[1])) for k in keep])
+
+    def tracks_maintain_end(self):
+        """waits for the pending call; -> per filter a dict verdict [n_tracks] uint8, depth [n_tracks], lm_verdict [n_lm] uint8"""
+        nb, lc, mc, cnt = getattr(self, "_maintain", (0, 1, 1, []))
+        ver = np.zeros((max(nb, 1), max(lc, 1)), dtype=np.uint8); dep = np.zeros((max(nb, 1), max(lc, 1))); lmv = np.zeros((max(nb, 1), max(mc, 1)), dtype=np.uint8)
+        ub = C.POINTER(C.c_ubyte)
+        self._chk(self.L.ingvio_tracks_maintain_end(self.h, ver.ctypes.data_as(ub), _d(dep), lmv.ctypes.data_as(ub)))
+        return [dict(verdict=ver[i, :nt].copy(), depth=dep[i, :nt].copy(), lm_verdict=lmv[i, :nl].copy()) for i, (nt, nl) in enumerate(cnt)]
+
+    def tracks_maintain(self, b0, blocks, move_min_depth=0.0, min_depth=0.2, list_cap=None, lm_cap=None):
+        """ingvio_tracks_maintain: begin + end in one call; returns as tracks_maintain_end"""
+        nb, arr, o, keep = self._maintain_args(blocks, move_min_depth, min_depth, list_cap, lm_cap)
+        ver = np.zeros((max(nb, 1), max(o.list_cap, 1)), dtype=np.uint8); dep = np.zeros((max(nb, 1), max(o.list_cap, 1)))
+        lmv = np.zeros((max(nb, 1), max(o.lm_cap, 1)), dtype=np.uint8)
+        ub = C.POINTER(C.c_ubyte)
+        self._chk(self.L.ingvio_tracks_maintain(self.h, int(b0), nb, arr, C.byref(o), ver.ctypes.data_as(ub), _d(dep), lmv.ctypes.data_as(ub)))
+        return [dict(verdict=ver[i, :len(k[0])].copy(), depth=dep[i, :len(k[0])].copy(), lm_verdict=lmv[i, :len(k[1])].copy()) for i, k in enumerate(keep)]
 
     def debug_staged_frame(self, b):
         """filter b's arrays of the input set the next frame_run reads (ingvio_debug_staged_frame): a dict n_clones, n_feat, clone_idx

@@ -943,7 +943,8 @@ int ingvio_ctx_destroy(ingvio_ctx* c)
         if (c->ev_copy) hipEventDestroy(c->ev_copy);
         for (auto e : c->ev_free) if (e) hipEventDestroy(e);
     }
-    for (void* p : { (void*)c->trk.uv, (void*)c->trk.pf, (void*)c->trk.mask, (void*)c->trk.stage[0], (void*)c->trk.stage[1] }) if (p) hipFree(p);
+    for (void* p : { (void*)c->trk.uv, (void*)c->trk.pf, (void*)c->trk.mask, (void*)c->trk.has, (void*)c->trk.stage[0], (void*)c->trk.stage[1] }) if (p) hipFree(p);
+    c->mt.release();
     for (auto& r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     for (int p = 0; p < c->parts_alloc; ++p) { hipStreamDestroy(c->part[p].st); hipEventDestroy(c->part[p].ev_gate); hipEventDestroy(c->part[p].ev_apply); hipEventDestroy(c->part[p].ev_done); }
     if (c->ev_split_fork) hipEventDestroy(c->ev_split_fork);
@@ -2651,9 +2652,9 @@ int ingvio_tracks_create(ingvio_ctx* c, int t_max)
     auto& t = c->trk;
     const size_t B = c->d.batch, T = t_max, C = c->d.c_max, F = c->d.f_max;
     if (t.t_max != t_max) {
-        for (void* p : { (void*)t.uv, (void*)t.pf, (void*)t.mask, (void*)t.stage[0], (void*)t.stage[1] }) if (p) hipFree(p);
+        for (void* p : { (void*)t.uv, (void*)t.pf, (void*)t.mask, (void*)t.has, (void*)t.stage[0], (void*)t.stage[1] }) if (p) hipFree(p);
         t = ingvio_ctx::Tracks();
-        if (dalloc(c, &t.uv, B * T * C * 4) || dalloc(c, &t.pf, B * T * 3) || dalloc(c, &t.mask, B * T)) return INGVIO_E_HIP;
+        if (dalloc(c, &t.uv, B * T * C * 4) || dalloc(c, &t.pf, B * T * 3) || dalloc(c, &t.mask, B * T) || dalloc(c, &t.has, B * T)) return INGVIO_E_HIP;
         // worst case of one staged delta per filter: header + ints (drop C, free T, obs T, pf T, clone idx C, features F, gnss 5) +
         // masks F + doubles (obs 4 T, points 3 T, clone poses 12 C, IMU 7 KMAX, state 24)
         t.stage_cap = B * (4 * (TRK_HDR + 3 * T + 2 * C + F + 8) + 8 * F + 8 * (7 * T + 12 * C + 7 * KMAX + 24) + 256) + 4096;
@@ -2662,6 +2663,7 @@ int ingvio_tracks_create(ingvio_ctx* c, int t_max)
     } else {
         HIPCHK(c, hipMemsetAsync(t.mask, 0, 8 * B * T, c->st));
         HIPCHK(c, hipMemsetAsync(t.pf, 0, 8 * B * T * 3, c->st));
+        HIPCHK(c, hipMemsetAsync(t.has, 0, B * T, c->st));
     }
     HIPCHK(c, hipStreamSynchronize(c->st));
     return INGVIO_OK;
@@ -2713,7 +2715,7 @@ static int nom_triangulate(ingvio_ctx* c, hipStream_t st, int* ok2, double* pf2)
     T.ok2 = ok2; T.pf2 = pf2;
     T.tri_mask = c->d_tri_mask;
     if (launch_triangulate(T, B, c->nom.tri_fmx > 0 ? c->nom.tri_fmx : 1, o.stereo, st)) return INGVIO_E_UNSUPPORTED;
-    const TrackStore store{ c->trk.uv, c->trk.mask, c->trk.pf, c->trk.t_max, c->d.c_max };
+    const TrackStore store = track_store(c);
     launch_tracks_store_points(store, 0, B, c->d_nfeat, c->d.f_max, c->nom.d_tri_track, ok2, pf2, st);
     return 0;
 }
@@ -2821,11 +2823,13 @@ static int frame_stage_tracks_impl(ingvio_ctx* c, int b0, int nb, const ingvio_f
     if (!upd) stage.upload_imu(steps);
     TrackStage ts{ reinterpret_cast<const int*>(dstage), reinterpret_cast<const int*>(dstage + off_i),
                    reinterpret_cast<const double*>(dstage + off_d), reinterpret_cast<const unsigned long long*>(dstage + off_m) };
-    TrackStore store{ c->trk.uv, c->trk.mask, c->trk.pf, T, cm };
+    const TrackStore store = track_store(c);
     FrameOut fo{ c->d_clone_idx, c->d_clone_R, c->d_clone_p, c->d_nclones, c->d_nfeat, c->d_pf, c->d_anchor, c->d_mask, c->d_uv, c->d_dof, cm, fm };
     const NomTable nt = nom_table(c);
     // from the device table on the copy stream: the uploads above overlap the running frame, the kernels wait for its post-frame step
     if (plan && async && c->nom.ev_valid && hipStreamWaitEvent(S, c->nom.ev, 0) != hipSuccess) return stage.fail(INGVIO_E_HIP);
+    // a host-fed asynchronous stage too lands behind the erasures of an ingvio_tracks_maintain_begin enqueued before it (both write masks and flags)
+    if (!plan && async && c->mt.ev_recorded && hipStreamWaitEvent(S, c->mt.ev, 0) != hipSuccess) return stage.fail(INGVIO_E_HIP);
     if (!upd) launch_imu_steps(ts, b0, nb, KMAX, c->d_Phi, c->d_G, c->d_dt, c->d_R, S, plan ? &nt : nullptr);
     if (hipGetLastError() != hipSuccess) return stage.fail(INGVIO_E_HIP);       // before the store kernels change the track store
     launch_tracks_apply(ts, store, b0, nb, S);
@@ -3643,6 +3647,18 @@ int ingvio_debug_tracks_read(ingvio_ctx* c, int b, unsigned long long* mask, dou
     const size_t T = c->trk.t_max, C = c->d.c_max;
     if (debug_down(c, mask, c->trk.mask + (size_t)b * T, 8 * T) || debug_down(c, uv, c->trk.uv + (size_t)b * T * C * 4, 8 * T * C * 4) ||
         debug_down(c, pf, c->trk.pf + (size_t)b * T * 3, 8 * T * 3)) return INGVIO_E_HIP;
+    return INGVIO_OK;
+}
+
+// parity hook: filter b's point flags of the track store
+int ingvio_debug_tracks_flags(ingvio_ctx* c, int b, unsigned char* has_point)
+{
+    ENTER(c);
+    if (check_range(c, b, 1)) return INGVIO_E_ARG;
+    if (!c->trk.t_max) { c->err = "ingvio_debug_tracks_flags without ingvio_tracks_create"; return INGVIO_E_ARG; }
+    if (debug_quiesce(c)) return INGVIO_E_HIP;
+    const size_t T = c->trk.t_max;
+    if (debug_down(c, has_point, c->trk.has + (size_t)b * T, T)) return INGVIO_E_HIP;
     return INGVIO_OK;
 }
 

@@ -432,7 +432,7 @@ static int lm_init_validate(ingvio_ctx* c, const char* who, int b0, int nb, cons
 static void lm_init_rows_common(ingvio_ctx* c, const ingvio_msckf_opts* o, double chi2_mult, DelayedRows& Rw)
 {
     Rw.nt = nom_table(c);
-    Rw.ts = TrackStore{ c->trk.uv, c->trk.mask, c->trk.pf, c->trk.t_max, c->d.c_max };
+    Rw.ts = track_store(c);
     Rw.chi2_mult = chi2_mult; Rw.stereo = o->stereo ? 1 : 0;
     memcpy(Rw.R_lr, o->R_cl2cr, 72); memcpy(Rw.t_lr, o->t_cl2cr, 24);
 }

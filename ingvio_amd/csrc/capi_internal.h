@@ -227,7 +227,17 @@ struct ingvio_ctx {
     hipStream_t run_st = nullptr;       // the stream run_msckf_factored and ProfScope issue on (c->st except inside a split step)
     hipEvent_t tok_wait = nullptr, tok_rec = nullptr;      // run_msckf_factored: wait before / record after its throughput segment (phase 1: gate + Gram, phase 2: apply)
     // device-resident track store (ingvio_tracks_create / ingvio_frame_stage_tracks, kernels_tracks.hip)
-    struct Tracks { double *uv = nullptr, *pf = nullptr; unsigned long long* mask = nullptr; int t_max = 0; char* stage[2] = { nullptr, nullptr }; size_t stage_cap = 0; } trk;
+    struct Tracks { double *uv = nullptr, *pf = nullptr; unsigned long long* mask = nullptr; int t_max = 0; char* stage[2] = { nullptr, nullptr }; size_t stage_cap = 0;
+                    unsigned char* has = nullptr; } trk;      // has [B][t_max]: the track holds a point (TrackStore::has)
+    // ingvio_tracks_maintain_begin / _end (k_tracks_maintain, capi_nominal.hip), grown on demand: the uploaded lists, the verdicts and
+    // depths on the device and their pinned mirror - its own, as the odometry record's - with the event behind the copy; one call pending
+    struct MaintainWs {
+        char *in = nullptr, *out = nullptr, *h_out = nullptr; size_t in_cap = 0, out_cap = 0, h_cap = 0;
+        hipEvent_t ev = nullptr; bool pending = false, launched = false, ev_recorded = false;      // ev_recorded: a call has launched on this context
+        int nb = 0, tcap = 0, lcap = 0, list_cap = 0, lm_cap = 0;
+        std::vector<int> cnt;           // [nb][2] the pending call's list lengths
+        void release();                 // capi_nominal.hip
+    } mt;
     // device-resident nominal state (ingvio_nominal_*, kernels_nominal.hip).  Every change of the integer records (slots,
     // idx, window list) is decided by the host, so it keeps a mirror of them and validates a stage without a device round trip.
     struct Nominal {
@@ -352,6 +362,7 @@ int join_parts(ingvio_ctx* c);
 // the compute stream
 int nom_mark(ingvio_ctx* c);
 inline NomTable nom_table(ingvio_ctx* c) { return NomTable{ c->nom.ih, c->nom.dv, c->nom.vmax, c->nom.ir, c->nom.dr }; }
+inline TrackStore track_store(ingvio_ctx* c) { return TrackStore{ c->trk.uv, c->trk.mask, c->trk.pf, c->trk.t_max, c->d.c_max, c->trk.has }; }
 // a GNSS epoch staged from the table (ingvio_gnss_front_stage_nominal) whose update has not run: its rows are linearised at the table's
 // present values, so nothing else may move the table or the covariance's bookkeeping in between
 // (the same holds for a stand-alone landmark update staged from the table, ingvio_landmark_stage_nominal)

@@ -428,7 +428,142 @@ int ingvio_nominal_tail(ingvio_ctx* c, int b0, int nb, const ingvio_nominal_tail
     return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
 }
 
+// ---- MSCKF anchor change and invalid-feature erase on the track store (k_tracks_maintain) ---------------------------
+// changeMSCKFAnchor (KeyframeUpdate.cpp:280-328, SwMargUpdate.cpp:367-413) and eraseInvalidFeatures (MapServerManager.cpp:456-491) for the
+// tracks the host lists.  _begin only enqueues, in the pattern of ingvio_odom_begin: the lists up, one kernel, the table event behind it (an
+// asynchronous stage on the copy stream is then ordered behind the erasures), the copy of verdicts and depths into a pinned mirror of
+// their own, the event _end waits for.  Every refusal is made on the host mirror before anything is enqueued or changed.
+static_assert(INGVIO_MAINTAIN_KEEP == TM_KEEP && INGVIO_MAINTAIN_MOVED == TM_MOVED && INGVIO_MAINTAIN_ERASED_UNTRIANGULATED == TM_ERASED_UNTRIANGULATED &&
+              INGVIO_MAINTAIN_ERASED_MOVE == TM_ERASED_MOVE && INGVIO_MAINTAIN_ERASED_INVALID == TM_ERASED_INVALID, "ingvio_hip.h and launch_tracks.h differ");
+
+int ingvio_tracks_maintain_begin(ingvio_ctx* c, int b0, int nb, const ingvio_maintain_block* blocks, const ingvio_maintain_opts* opts)
+{
+    if (!c || check_range(c, b0, nb) || !blocks || !opts) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    auto& w = c->mt;
+    const char* who = "ingvio_tracks_maintain_begin";
+    auto fail = [&](int code, const char* what) { c->err = std::string(who) + ": " + what; return code; };
+    if (phase_busy(c)) return INGVIO_E_ARG;
+    if (!m.vmax) return fail(INGVIO_E_ARG, "no nominal table (ingvio_nominal_create)");
+    if (!c->trk.t_max) return fail(INGVIO_E_ARG, "no track store (ingvio_tracks_create)");
+    if (m.pending) return fail(INGVIO_E_ARG, "a frame staged from the device nominal state has not run yet");
+    if (gnss_nom_busy(c, who)) return INGVIO_E_ARG;
+    if ((c->gn.frame_nom && c->gn.staged) || (c->lm.nominal && c->lm.staged))
+        return fail(INGVIO_E_ARG, "an in-frame GNSS epoch or landmark update staged from the device nominal state has not run yet");
+    if (w.pending) return fail(INGVIO_E_ARG, "the previous ingvio_tracks_maintain_begin has not been ended");
+    if (opts->list_cap < 0 || opts->lm_cap < 0) return fail(INGVIO_E_ARG, "a negative capacity");
+    const int T = c->trk.t_max;
+    int tcap = 0, lcap = 0;
+    std::vector<char> mark((size_t)T);
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_maintain_block& q = blocks[i];
+        const int* I = &m.h_ih[(size_t)(b0 + i) * m.ir];
+        if (q.n_tracks < 0 || q.n_lm < 0) return fail(INGVIO_E_ARG, "a negative count");
+        if (q.n_tracks > T || q.n_tracks > opts->list_cap) return fail(INGVIO_E_ARG, "a list is longer than t_max or list_cap");
+        if (q.n_lm > m.vmax || q.n_lm > opts->lm_cap) return fail(INGVIO_E_ARG, "more landmark slots listed than the table holds or lm_cap");
+        if ((q.n_tracks && !q.tracks) || (q.n_lm && !q.lm_slot)) return fail(INGVIO_E_ARG, "NULL where data is needed");
+        tcap = std::max(tcap, q.n_tracks); lcap = std::max(lcap, q.n_lm);
+        if (q.n_tracks) std::fill(mark.begin(), mark.end(), 0);
+        for (int e = 0; e < q.n_tracks; ++e) {
+            const unsigned wd = (unsigned)q.tracks[e];
+            const int t = (int)(wd & 0xffffu), pos = (int)((wd >> 16) & 0xffu);
+            if (wd >> 25) return fail(INGVIO_E_ARG, "an entry has bits above move set");
+            if (t >= T) return fail(INGVIO_E_ARG, "a track lies outside the store");
+            if (mark[t]) return fail(INGVIO_E_ARG, "a track is named twice");
+            mark[t] = 1;
+            if (pos >= I[NOM_N_CLONES]) return fail(INGVIO_E_NOT_IN_STATE, "an anchor_pos lies beyond the window");
+        }
+        for (int e = 0; e < q.n_lm; ++e) {
+            const int sl = q.lm_slot[e];
+            if (sl < 0 || sl >= I[NOM_N_VAR] || I[NOM_IH + 4 * sl] != NOM_KIND_LM) return fail(INGVIO_E_NOT_IN_STATE, "a landmark slot is free or holds no landmark");
+            const int an = I[NOM_IH + 4 * sl + 2];
+            if (an < 0 || an >= I[NOM_N_VAR] || I[NOM_IH + 4 * an] != NOM_KIND_SE3) return fail(INGVIO_E_NOT_IN_STATE, "a landmark without a live anchor");
+        }
+    }
+    ENTER(c);
+    w.cnt.resize((size_t)nb * 2);
+    for (int i = 0; i < nb; ++i) { w.cnt[2 * i] = blocks[i].n_tracks; w.cnt[2 * i + 1] = blocks[i].n_lm; }
+    w.nb = nb; w.tcap = tcap; w.lcap = lcap; w.list_cap = opts->list_cap; w.lm_cap = opts->lm_cap;
+    w.launched = tcap + lcap > 0;
+    if (!w.launched) { w.pending = true; return INGVIO_OK; }              // every list empty: nothing is launched
+    const int istride = TM_HDR + tcap + lcap;
+    const size_t ostride = (size_t)tcap + lcap;
+    const size_t in_bytes = pad64(sizeof(int) * (size_t)nb * istride), o_ver = pad64(8 * (size_t)nb * ostride), out_bytes = o_ver + pad64((size_t)nb * ostride);
+    if (int rc = dev_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
+    if (int rc = dev_grow(c, &w.out, &w.out_cap, out_bytes)) return rc;
+    if (w.h_cap < out_bytes) {
+        if (w.h_out) { hipHostFree(w.h_out); w.h_out = nullptr; w.h_cap = 0; }
+        HIPCHK(c, hipHostMalloc((void**)&w.h_out, out_bytes + 4096, hipHostMallocDefault));
+        w.h_cap = out_bytes + 4096;
+    }
+    if (!w.ev) HIPCHK(c, hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+    Uploader upl{ c };
+    if (int rc = upl.begin(in_bytes + 64)) return rc;
+    int* h = upl.take<int>(in_bytes / sizeof(int));
+    memset(h, 0, in_bytes);
+    for (int i = 0; i < nb; ++i) {
+        const ingvio_maintain_block& q = blocks[i];
+        int* r = h + (size_t)i * istride;
+        r[TM_N_TRK] = q.n_tracks; r[TM_N_LM] = q.n_lm;
+        if (q.n_tracks) memcpy(r + TM_HDR, q.tracks, sizeof(int) * (size_t)q.n_tracks);
+        if (q.n_lm) memcpy(r + TM_HDR + tcap, q.lm_slot, sizeof(int) * (size_t)q.n_lm);
+    }
+    upl.copy((int*)w.in, h, in_bytes / sizeof(int));
+    if (int rc = upl.end()) return rc;
+    if (wait_inputs(c)) return INGVIO_E_HIP;                              // nothing on the copy stream may still write the store
+    TrackMaintain tm;
+    tm.in = (const int*)w.in; tm.istride = istride; tm.tcap = tcap; tm.lcap = lcap;
+    tm.move_min_depth = opts->move_min_depth; tm.min_depth = opts->min_depth;
+    tm.depth = (double*)w.out; tm.verdict = (unsigned char*)(w.out + o_ver);
+    launch_tracks_maintain(track_store(c), nom_table(c), tm, b0, nb, c->st);
+    if (int rc = last_launch(c)) return rc;
+    if (nom_mark(c)) return INGVIO_E_HIP;
+    HIPCHK(c, hipMemcpyAsync(w.h_out, w.out, out_bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipEventRecord(w.ev, c->st));
+    w.ev_recorded = true;
+    w.pending = true;
+    return INGVIO_OK;
+}
+
+int ingvio_tracks_maintain_end(ingvio_ctx* c, unsigned char* verdict, double* depth, unsigned char* lm_verdict)
+{
+    if (!c) return INGVIO_E_ARG;                                          // (no ENTER: the verdicts are already on their way)
+    auto& w = c->mt;
+    if (!w.pending) { c->err = "ingvio_tracks_maintain_end without a pending ingvio_tracks_maintain_begin"; return INGVIO_E_ARG; }
+    if ((w.tcap && !verdict) || (w.lcap && !lm_verdict)) { c->err = "ingvio_tracks_maintain_end: NULL where data is needed"; return INGVIO_E_ARG; }
+    if (w.launched) HIPCHK(c, hipEventSynchronize(w.ev));
+    w.pending = false;
+    if (!w.launched) return INGVIO_OK;
+    const size_t ostride = (size_t)w.tcap + w.lcap, o_ver = pad64(8 * (size_t)w.nb * ostride);
+    const double* hd = (const double*)w.h_out;
+    const unsigned char* hv = (const unsigned char*)(w.h_out + o_ver);
+    for (int i = 0; i < w.nb; ++i) {
+        const int nt = w.cnt[2 * i], nl = w.cnt[2 * i + 1];
+        if (nt) memcpy(verdict + (size_t)i * w.list_cap, hv + (size_t)i * ostride, (size_t)nt);
+        if (nt && depth) memcpy(depth + (size_t)i * w.list_cap, hd + (size_t)i * ostride, 8 * (size_t)nt);
+        if (nl) memcpy(lm_verdict + (size_t)i * w.lm_cap, hv + (size_t)i * ostride + w.tcap, (size_t)nl);
+    }
+    return INGVIO_OK;
+}
+
+int ingvio_tracks_maintain(ingvio_ctx* c, int b0, int nb, const ingvio_maintain_block* blocks, const ingvio_maintain_opts* opts,
+                           unsigned char* verdict, double* depth, unsigned char* lm_verdict)
+{
+    if (!c || check_range(c, b0, nb) || !blocks || !opts) return INGVIO_E_ARG;
+    for (int i = 0; i < nb; ++i)
+        if ((blocks[i].n_tracks > 0 && !verdict) || (blocks[i].n_lm > 0 && !lm_verdict)) { c->err = "ingvio_tracks_maintain: NULL where data is needed"; return INGVIO_E_ARG; }
+    if (int rc = ingvio_tracks_maintain_begin(c, b0, nb, blocks, opts)) return rc;
+    return ingvio_tracks_maintain_end(c, verdict, depth, lm_verdict);
+}
+
 }  // extern "C"
+
+void ingvio_ctx::MaintainWs::release()
+{
+    for (char* p : { in, out }) if (p) hipFree(p);
+    if (h_out) hipHostFree(h_out);
+    if (ev) hipEventDestroy(ev);
+}
 
 // ---- what ingvio_ctx_destroy gives back for the three structs above (the table's triangulation buffers of the frame stage included) ----
 void ingvio_ctx::Nominal::release()

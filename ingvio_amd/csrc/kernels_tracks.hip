@@ -320,7 +320,8 @@ __global__ __launch_bounds__(256) void k_tracks_apply(TrackStage ts, TrackStore 
     }
     __syncthreads();
     const int* fr = ip + h[TRK_I_FREE];
-    for (int q = tid; q < n_free; q += 256) mkB[fr[q]] = 0ULL;
+    unsigned char* hsB = st.has + (size_t)b * T;
+    for (int q = tid; q < n_free; q += 256) { mkB[fr[q]] = 0ULL; hsB[fr[q]] = 0; }
     __syncthreads();
     const int* ot = ip + h[TRK_I_OBS];
     const double* ouv = dp + h[TRK_D_OBS];
@@ -335,6 +336,7 @@ __global__ __launch_bounds__(256) void k_tracks_apply(TrackStage ts, TrackStore 
     for (int q = tid; q < n_pf; q += 256) {
         const int t = pt[q];
         pfB[3 * t] = pv[3 * q]; pfB[3 * t + 1] = pv[3 * q + 1]; pfB[3 * t + 2] = pv[3 * q + 2];
+        hsB[t] = 1;
     }
 }
 
@@ -433,6 +435,57 @@ __global__ __launch_bounds__(256) void k_tracks_store_points(TrackStore st, int 
         const int t = track[o];
         if (ok[o] != 1 || t < 0 || t >= st.tmax) continue;
         pfB[3 * t] = pf[3 * o]; pfB[3 * t + 1] = pf[3 * o + 1]; pfB[3 * t + 2] = pf[3 * o + 2];
+        st.has[(size_t)b * st.tmax + t] = 1;
+    }
+}
+
+// changeMSCKFAnchor (KeyframeUpdate.cpp:280-328, SwMargUpdate.cpp:367-413) and eraseInvalidFeatures (MapServerManager.cpp:456-491) on
+// the listed tracks of a filter: one workgroup per filter, threads striding over the list; the host guarantees that no track is named
+// twice, so no two threads share a track.  Per entry track | window position << 16 | move << 24:
+//   no point:  move ? ERASED_UNTRIANGULATED : KEEP (eraseInvalidFeatures skips a feature that was never triangulated)
+//   d = (R_a^T (p_f - p_a)).z at the table's clone at that window position - for a moved track the window's newest clone, and no pose
+//   changes between the reference's two steps, so the validity test of a moved track is taken at the same d
+//   move && d <= move_min_depth: ERASED_MOVE;  d <= min_depth: ERASED_INVALID;  else MOVED / KEEP
+// The comparisons are C++'s: a NaN depth keeps the track, as body.z() <= 0.2 does in the reference.  An erased track loses mask and
+// flag exactly as a released one (k_tracks_apply); nothing else is written.  The listed landmark slots are report only: depth of
+// the table's landmark at its table anchor against min_depth.
+// FP64 on the vector ALU, latency-bound: three subtractions, three products, two sums per entry.
+__global__ __launch_bounds__(256) void k_tracks_maintain(TrackStore st, NomTable nt, TrackMaintain tm, int b0)
+{
+    const int bl = blockIdx.x, b = b0 + bl;
+    const int* in = tm.in + (size_t)bl * tm.istride;
+    const int nt_ = in[TM_N_TRK], nl = in[TM_N_LM];
+    if (nt_ + nl == 0) return;
+    const int* I = nt.ih + (size_t)b * nt.ir;
+    const double* D = nt.dv + (size_t)b * nt.dr + NOM_DH;
+    const size_t ostride = (size_t)tm.tcap + tm.lcap;
+    unsigned char* ver = tm.verdict + (size_t)bl * ostride;
+    double* dep = tm.depth + (size_t)bl * ostride;
+    unsigned long long* mkB = st.mask + (size_t)b * st.tmax;
+    unsigned char* hsB = st.has + (size_t)b * st.tmax;
+    const double* pfB = st.pf + (size_t)b * st.tmax * 3;
+    for (int q = threadIdx.x; q < nt_; q += 256) {
+        const unsigned w = (unsigned)in[TM_HDR + q];
+        const int t = (int)(w & 0xffffu), pos = (int)((w >> 16) & 0xffu), move = (int)((w >> 24) & 1u);
+        int v; double d = 0.0;
+        if (!hsB[t]) v = move ? TM_ERASED_UNTRIANGULATED : TM_KEEP;
+        else {
+            const double* a = D + (size_t)I[NOM_CLONES + pos] * NOM_VD;      // R (row-major), p
+            const double x = pfB[3 * t] - a[9], y = pfB[3 * t + 1] - a[10], z = pfB[3 * t + 2] - a[11];
+            d = a[2] * x + a[5] * y + a[8] * z;                            // third row of R^T
+            v = (move && d <= tm.move_min_depth) ? TM_ERASED_MOVE : (d <= tm.min_depth ? TM_ERASED_INVALID : (move ? TM_MOVED : TM_KEEP));
+        }
+        if (v >= TM_ERASED_UNTRIANGULATED) { mkB[t] = 0ULL; hsB[t] = 0; }
+        ver[q] = (unsigned char)v; dep[q] = d;
+    }
+    for (int q = threadIdx.x; q < nl; q += 256) {
+        const int sl = in[TM_HDR + tm.tcap + q];
+        const double* l = D + (size_t)sl * NOM_VD;
+        const double* a = D + (size_t)I[NOM_IH + 4 * sl + 2] * NOM_VD;
+        const double x = l[9] - a[9], y = l[10] - a[10], z = l[11] - a[11];
+        const double d = a[2] * x + a[5] * y + a[8] * z;
+        ver[tm.tcap + q] = (unsigned char)(d <= tm.min_depth ? TM_ERASED_INVALID : TM_KEEP);
+        dep[tm.tcap + q] = d;
     }
 }
 
@@ -459,4 +512,8 @@ void launch_tracks_gather_tri(const TrackStage& ts, const TrackStore& store, con
 void launch_tracks_store_points(const TrackStore& store, int b0, int nb, const int* n_feat, int fmax, const int* track, const int* ok, const double* pf, hipStream_t st)
 {
     hipLaunchKernelGGL(k_tracks_store_points, dim3(nb), dim3(256), 0, st, store, b0, n_feat, fmax, track, ok, pf);
+}
+void launch_tracks_maintain(const TrackStore& store, const NomTable& nom, const TrackMaintain& tm, int b0, int nb, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_tracks_maintain, dim3(nb), dim3(256), 0, st, store, nom, tm, b0);
 }

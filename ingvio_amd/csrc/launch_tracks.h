@@ -27,6 +27,7 @@ struct TrackStore {                     // persistent, per context
     unsigned long long* mask;           // [B][tmax]
     double* pf;                         // [B][tmax][3]
     int tmax, cmax;
+    unsigned char* has;                 // [B][tmax] 1: the track holds a point (FeatureInfo::_isTri, sticky: MapServerManager.cpp:292-296, 326-330)
 };
 
 struct FrameOut {                       // FrameView with writable pointers (the gather kernel fills the staged frame)
@@ -47,3 +48,16 @@ void launch_tracks_gather_tri(const TrackStage& ts, const TrackStore& store, con
                               const NomTable& nom, unsigned long long* tri_mask, int* tri_track);
 // triangulated points (ok == 1) of the listed features into the store's pf
 void launch_tracks_store_points(const TrackStore& store, int b0, int nb, const int* n_feat, int fmax, const int* track, const int* ok, const double* pf, hipStream_t st);
+
+// ---- k_tracks_maintain: changeMSCKFAnchor + eraseInvalidFeatures on the store ----
+// Per filter of the call a row of `istride` ints in `in`: [TM_N_TRK] listed tracks, [TM_N_LM] listed landmark slots, then tcap entries
+// track | window position << 16 | move << 24, then lcap table slots.  Results per filter at the same stride tcap + lcap: a verdict byte
+// and the depth (0 where no depth was formed) per entry, the landmarks behind the tracks.
+enum { TM_N_TRK, TM_N_LM, TM_HDR = 4 };
+enum { TM_KEEP = 0, TM_MOVED = 1, TM_ERASED_UNTRIANGULATED = 2, TM_ERASED_MOVE = 3, TM_ERASED_INVALID = 4 };
+struct TrackMaintain {
+    const int* in; int istride, tcap, lcap;
+    double move_min_depth, min_depth;
+    unsigned char* verdict; double* depth;      // [nb][tcap + lcap]
+};
+void launch_tracks_maintain(const TrackStore& store, const NomTable& nom, const TrackMaintain& tm, int b0, int nb, hipStream_t st);

@@ -431,6 +431,125 @@ def main_tri_first(a):
     finish(out, "closed_loop_bench_tri_first.json")
 
 
+def main_maintain(a):
+    """--maintain: the MSCKF anchor change / invalid-feature erase behind every camera frame of the two-update loop with triangulating first
+    updates and three decoy tracks per filter (ingvio_amd/closed_loop_maintain.py), on one build in one process, the forms alternated
+    N Fc Sc F S R, --repeats times over, every stage prepared beforehand, free-running between two synchronisations:
+      N  the loop without maintenance
+      F  ingvio_tracks_maintain_begin behind the second update's run, _end behind the next first update's run
+      S  the synchronous ingvio_tracks_maintain as a late form
+      R  the round trip: ingvio_nominal_get (a synchronisation and every filter's table), the host model on the host's own points; its
+         erasures are not sent on (the prepared stages' free_tracks are fixed), so the figure is the download and the model
+      Fc / Sc  F and S with the calls' arguments prebuilt, as the stages are: the lists of a first, untimed F run are replayed through
+         the C exports with the ctypes blocks and the result buffers made beforehand and no bookkeeping - what the calls themselves
+         cost a host that has its lists ready (the loop is deterministic, so the lists are the ones F builds)
+    --device-only: form Fc alone (the kernel-trace run).  Writes $RESULTS/closed_loop_bench_maintain.json."""
+    from ingvio_amd import closed_loop as cl
+    from ingvio_amd import closed_loop_maintain as cm
+    from ingvio_amd import closed_loop_update as cu
+    B, F, NF, W = a.batch, a.features, a.frames, a.warmup
+    t0 = time.perf_counter()
+    cases = cm.add_decoys(cu.make_update_loop(B, NF, F=F, n_lost=F - a.second, carry_point=False, first_tri=True, ks=(a.k,), windows=(a.window,)), F, "sw")
+    out = dict(batch=B, features=F, second=a.second, window=a.window, k=a.k, frames_timed=NF - W, maintain=True, setup_s=round(time.perf_counter() - t0, 1))
+    entries = cu.two_update_entries(range(NF))
+
+    class RoundTrip(cl.Form):
+        late = True
+
+        def __init__(self):
+            self.books, self.stores = [cm.Book(c) for c in cases], [cu.HostStore(F + cm.DECOYS, a.window + 1) for _ in cases]
+
+        def staged(self, loop, i):
+            for bk in self.books:
+                bk.staged()
+
+        def after(self, loop, i):
+            e = loop.frames[i]
+            if not isinstance(e, cl.UpdateEntry):
+                return
+            noms = loop.ctx.nominal_get()
+            for c, bk, st, nm in zip(cases, self.books, self.stores, noms):
+                fr = c["frames"][e.f]
+                cm.decoy_points(st, fr)
+                cm.host_maintain(cu.host_table_of(nm), st, bk.an, bk.leave(fr), cm.MOVE_MIN_DEPTH["sw"])
+
+    recorded = []                                                        # the blocks of every call, in order (filled by the first F run)
+
+    class Replay(cl.Form):
+        def __init__(self, ctx, free):
+            import ctypes as C
+            self.free, self.late, self.open, self.k = free, not free, False, 0
+            self.args = [ctx._maintain_args(blocks, cm.MOVE_MIN_DEPTH["sw"], cm.MIN_DEPTH, None, None) for blocks in recorded]
+            cap = max(o.list_cap for _, _, o, _ in self.args)
+            self.ver, self.dep, self.lmv = np.zeros((B, cap), dtype=np.uint8), np.zeros((B, cap)), np.zeros((B, 1), dtype=np.uint8)
+            ub = C.POINTER(C.c_ubyte)
+            self.out = (self.ver.ctypes.data_as(ub), self.dep.ctypes.data_as(C.POINTER(C.c_double)), self.lmv.ctypes.data_as(ub))
+            self.byref = C.byref
+
+        def end(self, ctx):
+            if self.open:
+                ctx._chk(ctx.L.ingvio_tracks_maintain_end(ctx.h, *self.out))
+                self.open = False
+
+        def ran(self, loop, i):
+            if not self.free:
+                return
+            ctx = loop.ctx
+            self.end(ctx)
+            if isinstance(loop.frames[i], cl.UpdateEntry):
+                nb, arr, o, _ = self.args[self.k]
+                self.k += 1
+                ctx._chk(ctx.L.ingvio_tracks_maintain_begin(ctx.h, 0, nb, arr, self.byref(o)))
+                self.open = True
+                if i + 1 == len(loop.frames):
+                    self.end(ctx)
+
+        def after(self, loop, i):
+            if self.free or not isinstance(loop.frames[i], cl.UpdateEntry):
+                return
+            ctx = loop.ctx
+            nb, arr, o, _ = self.args[self.k]
+            self.k += 1
+            ctx._chk(ctx.L.ingvio_tracks_maintain(ctx.h, 0, nb, arr, self.byref(o), *self.out))
+
+    def run(name, record=False):
+        ctx = fresh_ctx(a, cases)
+        ctx.tracks_create(F + cm.DECOYS)
+        verdicts = {}
+        if record:
+            begin = ctx.tracks_maintain_begin
+            ctx.tracks_maintain_begin = lambda b0, blocks, *args, **kw: (recorded.append(blocks), begin(b0, blocks, *args, **kw))[1]
+        form = {"N": lambda: None, "R": RoundTrip, "Fc": lambda: Replay(ctx, True), "Sc": lambda: Replay(ctx, False),
+                "F": lambda: cm.decoy_form(cases, [cm.Book(c) for c in cases], verdicts, True),
+                "S": lambda: cm.decoy_form(cases, [cm.Book(c) for c in cases], verdicts, False)}[name]()
+        loop = cl.DeviceLoop(ctx, cases, entries, form, collect=False, update_stage=cu.update_stage).prepare()
+        loop.start()
+        for f in range(NF):
+            if f == W:
+                ctx.sync()
+                t1 = time.perf_counter()
+            loop.frame(2 * f), loop.frame(2 * f + 1)
+        ctx.sync()
+        ms = round(1e3 * (time.perf_counter() - t1) / (NF - W), 4)
+        ctx.close()
+        if verdicts:
+            v = np.concatenate([np.asarray(x[1]) for per in verdicts.values() for x in per])
+            out[name + "_verdict_counts"] = [int(n) for n in np.bincount(v, minlength=5)]
+        return ms
+    run("F", record=True)                                                # untimed: the lists
+    if a.device_only:
+        out["Fc_ms_per_frame"] = run("Fc")
+        return finish(out)
+    names = ("N", "Fc", "Sc", "F", "S", "R")
+    times = {k: [] for k in names}
+    for rep in range(a.repeats):
+        for name in names:
+            times[name].append(run(name))
+    for name, t in times.items():
+        out[name + "_ms_per_frame"] = t
+    finish(out, "closed_loop_bench_maintain.json")
+
+
 def main_odom(a):
     import ctypes
     from ingvio_amd import capi
@@ -517,6 +636,7 @@ def main():
     ap.add_argument("--two-updates", action="store_true", help="both MSCKF updates of the camera callback: the second as an update-only frame from the table")
     ap.add_argument("--second", type=int, default=40, help="--two-updates: features of the second update")
     ap.add_argument("--tri-first", action="store_true", help="--two-updates: the first update's points triangulated on the device, against host-sent points and the stalling form")
+    ap.add_argument("--maintain", action="store_true", help="the two-update loop with the MSCKF anchor change / invalid-feature erase: free-running, synchronous, round trip, none")
     ap.add_argument("--odom", action="store_true", help="the plain loop against the loop with the odometry record, and the stalling form")
     ap.add_argument("--repeats", type=int, default=2, help="--odom: rounds of A B C")
     ap.add_argument("--stall-frames", type=int, default=3, help="--odom: timed frames of the stalling form")
@@ -525,6 +645,8 @@ def main():
         return main_gnss_acquire(a)
     if a.odom:
         return main_odom(a)
+    if a.maintain:
+        return main_maintain(a)
     if a.two_updates:
         return main_tri_first(a) if a.tri_first else main_two_updates(a)
     if a.tail:
