@@ -189,6 +189,9 @@ int ingvio_mld(ingvio_ctx* ctx);                      /* row stride of keep_out 
  * rows where ingvio_gnss_stage would have put them: follow with ingvio_gnss_run / ingvio_gnss_fetch.  GLONASS satellites take
  * geph2svdt / geph2pos / geph2vel (gnss_utility.cpp:642-731: Runge-Kutta integration of the broadcast PZ-90 state vector).
  * Times are seconds of the GPS week.
+ * The rows are GnssUpdate.cpp:148-272 with _is_adjust_yof = 0, the YOF column (column 9 of every row) zero, unless
+ * ingvio_set_gnss_adjust_yof is on: then a pseudo-range row carries -u^T R_enu2ecef dRz(yaw) p_w there and a Doppler row the same with
+ * v_w (:164-167, :239-242; dRz = GnssManager::dotRw2enu).  Column count, var_order and the row gates are the same either way.
  * Flat records of doubles:
  *   ephemeris [INGVIO_EPH_N]: sys (gnss_comm::sys2idx: GPS 0, GLO 1, GAL 2, BDS 3), prn, toe, toe in the constellation's own
  *     week (BDS: BDT of toe - 14 s, gnss_utility.cpp:489; else = toe), toc, A, e, i0, omg, OMG0, M0, delta_n, OMG_dot, i_dot,
@@ -657,6 +660,32 @@ int ingvio_frame_fetch_tri(ingvio_ctx* ctx, int b0, int nb, double* pf_out, int*
  * a frame or a GNSS epoch staged from the table that has not run.  A filter that never registers runs exactly as before. */
 int ingvio_nominal_set_gnss(ingvio_ctx* ctx, int b0, int nb, const int* slots /* [nb][6] */);
 int ingvio_nominal_get_gnss(ingvio_ctx* ctx, int b0, int nb, int* slots /* [nb][6] */);
+/* GnssUpdate::_is_adjust_yof for every GNSS launch of the context that forms rows: ingvio_gnss_front_stage, ingvio_gnss_front_stage_nominal
+ * + ingvio_gnss_run, both orders of ingvio_gnss_frame_stage_nominal, ingvio_gnss_init_nominal and ingvio_debug_gnss_init_rows (the
+ * columns are given with those calls).  ingvio_gnss_sat_eval has no rows and is unaffected.  on: 0 (the default; every launch produces
+ * the bits it produces without this call) / != 0.  INGVIO_E_ARG: a GNSS epoch of any form staged and not yet run, or a split frame step
+ * pending. */
+int ingvio_set_gnss_adjust_yof(ingvio_ctx* ctx, int on);
+/* StateManager::addGNSSVariable (StateManager.cpp:194-231; checkYofStatus adds YOF with it) on the table, for filters [b0, b0 + nb):
+ * gtype[i] is the position of ingvio_nominal_set_gnss (0..3 the clock biases, 4 FS, 5 YOF), -1: nothing for this filter.  P gains an
+ * independent 1 x 1 block at the live n (row and column n zero over [0, n), the diagonal var[i] - what ingvio_append_independent does),
+ * the lowest free table slot becomes an INGVIO_NOM_SCALAR with idx = n and value[i], registered at that position.  All of it on the
+ * device, on the context's stream, with no synchronisation; the host mirror (live sizes, table, slots) follows deterministically and
+ * slot_out / idx_out [nb] (-1 where gtype is -1) come from it.  ingvio_cov_snapshot / _restore cover the scalar as they cover the table.
+ * Refused before anything changes: INGVIO_E_ARG (no table, range, NULL, gtype outside -1..5, a scalar already registered at that
+ * position, and the pending work ingvio_nominal_set_gnss refuses); INGVIO_E_CAPACITY (no free slot, or n + 1 > n_max). */
+int ingvio_nominal_add_gnss(ingvio_ctx* ctx, int b0, int nb, const int* gtype /* [nb] */, const double* value /* [nb] */,
+                            const double* var /* [nb] */, int* slot_out /* [nb] */, int* idx_out /* [nb] */);
+/* StateManager::margGNSSVariable (StateManager.cpp:233-242 with marginalize :155-192) on the table, for filters [b0, b0 + nb): bit s of
+ * mask[i] names the scalar registered at position s of ingvio_nominal_set_gnss.  Their rows and columns leave P in ONE read of P and one
+ * write into the other ping-pong half, however many leave (the compaction of ingvio_nominal_tail); their slots become INGVIO_NOM_NONE,
+ * their registrations -1, every surviving idx moves down by the number of removed columns below it, no surviving value changes.  No
+ * synchronisation; the host mirror follows deterministically.  A filter with mask 0 is untouched; a call in which every mask is 0
+ * launches nothing.  The clock indices of the next frame's ingvio_frame_step_nominal::gnss_idx are the host's to shrink.
+ * Refused before anything changes: INGVIO_E_NOT_IN_STATE (a named position that is not registered, a table variable beyond the
+ * filter's n); INGVIO_E_ARG (no table, range, NULL, bits above 5, and the pending work ingvio_nominal_tail refuses);
+ * INGVIO_E_CAPACITY (a state too wide for the compaction's index maps). */
+int ingvio_nominal_marg_gnss(ingvio_ctx* ctx, int b0, int nb, const unsigned* mask /* [nb] */);
 /* ---- the landmark tail of a frame on the device -----------------------------------------------------------------
  * What callbackStereoFrame / callbackMonoFrame do behind the updates for the in-state landmarks, for filters [b0, b0 + nb) from what the
  * device holds, per filter in the reference's order:
@@ -793,7 +822,8 @@ int ingvio_tracks_maintain(ingvio_ctx* ctx, int b0, int nb, const ingvio_maintai
 /* ingvio_gnss_front_stage with the receiver taken from the device table: the epoch carries only what the host owns.  p_w, v_w
  * (State::_extended_pose), the clock biases, FS and YOF (GnssUpdate.cpp:98-122 reads them from the state) and every Type::idx() come
  * from the filter's table as the frame that has just run left it - IngvioFilter.cpp:329-362 runs after :276-327 and after margSwPose,
- * so the idx are the shifted ones - on the context's stream, without a host round trip; the host-side checks of ingvio_gnss_front_stage
+ * so the idx are the shifted ones, and with ingvio_set_gnss_adjust_yof on the YOF column is formed from the table's yaw, p_w and v_w -
+ * on the context's stream, without a host round trip; the host-side checks of ingvio_gnss_front_stage
  * (INGVIO_E_NOT_IN_STATE, the capacity checks) are made on the host mirror of the table.  n_sat = 0: no epoch for that filter.
  * The following ingvio_gnss_run (same range, once: a second one is INGVIO_E_ARG) ends with StateManager::boxPlus of the update's dx on
  * the table, on the device (StateManager.cpp:244-251 after GnssUpdate.cpp:290), and keeps its dx / row count / status apart from the
@@ -949,8 +979,11 @@ int ingvio_debug_landmark_init_rows(ingvio_ctx* ctx, int b, const ingvio_lm_init
  *   One round per candidate, in the order above, each against the state the previous round left:
  *     - rows (getResJacobianOfSys, :472-521), one per usable satellite (FS) or per usable satellite of the constellation (a clock), in
  *       ascending satellite order: Hx [m x 10] over [SE23 (9), YOF (1)] with u^T R_w2ecef [x]x in columns 0-2 and -u^T R_w2ecef in columns
- *       6-8 (FS, x = v_w) or 3-5 (a clock, x = p_w); x is read from the table in this round (:397 / :458).  Column 9 is zero:
- *       is_adjust_yof = 0 only, as in every golden stream.  H_new is all ones, s = 1; res = -res_vel (FS) or -res_pos (a clock).
+ *       6-8 (FS, x = v_w) or 3-5 (a clock, x = p_w); x is read from the table in this round (:397 / :458).  Column 9 is zero, as in
+ *       every golden stream, unless ingvio_set_gnss_adjust_yof is on: then it is -u^T R_enu2ecef^T dRz(YOF) x, the reference AS WRITTEN
+ *       (:401-404, :462-465: getRecef2enu(), the transpose of what the update rows take), with YOF read from the table in this round
+ *       like x (dotRw2enu(state) is evaluated inside the reference's loop) while R_w2ecef of the other columns stays the call's.
+ *       H_new is all ones, s = 1; res = -res_vel (FS) or -res_pos (a clock).
  *     - noise = amp * sqrt(mean(ura * std / sin^2 el)) over the rows, computed on the device: std = psr_std, amp = psr_noise_amp for a
  *       clock; std = dopp_std * c / freq, amp = dopp_noise_amp for FS; |sin el| floored at 1e-6.  It is the R of the Givens rounds, of
  *       the gate and of the trailing update, and is returned per candidate.
@@ -971,8 +1004,8 @@ int ingvio_debug_landmark_init_rows(ingvio_ctx* ctx, int b, const ingvio_lm_init
  * free table slots than candidates, n + candidates > n_max, n_sat > ingvio_mld).
  * The call runs where ingvio_landmark_init_nominal runs: between frames, after the epoch's ingvio_gnss_run or after an ingvio_frame_run
  * that carried the epoch in-frame.  It is not part of ingvio_frame_run.  The clock indices the next frame's propagation takes
- * (ingvio_frame_step_nominal::gnss_idx) are the host's to extend with new_idx.  checkYofStatus' addGNSSVariable and batchAlign stay
- * host policy. */
+ * (ingvio_frame_step_nominal::gnss_idx) are the host's to extend with new_idx.  checkYofStatus' addGNSSVariable is
+ * ingvio_nominal_add_gnss; batchAlign and the SPP fix stay host policy. */
 #define INGVIO_GNSS_INIT_CAND 5          /* candidate j: 0 = FS, 1..4 = clock bias GPS, GLO, GAL, BDS: the order of
                                             stream_filter.py:908-911 and host/GnssUpdate.cpp:206-207 */
 typedef struct {

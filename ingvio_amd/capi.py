@@ -52,6 +52,7 @@ EXPORTS = [
     "ingvio_frame_stage_tracks_nominal_tri", "ingvio_set_first_tri_placement",
     "ingvio_gnss_init_nominal", "ingvio_debug_gnss_init_rows",
     "ingvio_tracks_maintain_begin", "ingvio_tracks_maintain_end", "ingvio_tracks_maintain", "ingvio_debug_tracks_flags",
+    "ingvio_set_gnss_adjust_yof", "ingvio_nominal_add_gnss", "ingvio_nominal_marg_gnss",
 ]
 
 # device-resident nominal state (ingvio_nominal_*): variable kinds, doubles per value
@@ -1181,6 +1182,28 @@ class Context:
         sl = np.zeros((nb, 6), dtype=np.int32)
         self._chk(self.L.ingvio_nominal_get_gnss(self.h, int(b0), nb, _i(sl)))
         return sl
+
+    def set_gnss_adjust_yof(self, on):
+        """GnssUpdate::_is_adjust_yof for every GNSS launch of the context that forms rows: the YOF column (column 9) of the update rows
+        and of the acquisition rows (ingvio_set_gnss_adjust_yof).  Default 0."""
+        self._chk(self.L.ingvio_set_gnss_adjust_yof(self.h, int(bool(on))))
+
+    def nominal_add_gnss(self, b0, gtype, value, var):
+        """StateManager::addGNSSVariable on the device table and covariance (ingvio_nominal_add_gnss): gtype [nb] the position of
+        nominal_set_gnss (0..3 clocks, 4 FS, 5 YOF; -1: nothing for this filter), value / var [nb].  No synchronisation.
+        -> (slot [nb], idx [nb]); -1 where gtype is -1"""
+        g = i32(np.asarray(gtype, dtype=np.int32).reshape(-1))
+        nb = g.shape[0]
+        val, vr = f64(np.broadcast_to(np.asarray(value, dtype=np.float64), (nb,))), f64(np.broadcast_to(np.asarray(var, dtype=np.float64), (nb,)))
+        slot, idx = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(max(nb, 1), dtype=np.int32)
+        self._chk(self.L.ingvio_nominal_add_gnss(self.h, int(b0), nb, _i(g), _d(val), _d(vr), _i(slot), _i(idx)))
+        return slot[:nb], idx[:nb]
+
+    def nominal_marg_gnss(self, b0, mask):
+        """StateManager::margGNSSVariable on the device (ingvio_nominal_marg_gnss): mask [nb], bit s = the scalar registered at position
+        s of nominal_set_gnss; their rows and columns leave P in one sweep.  No synchronisation."""
+        mk = np.ascontiguousarray(np.asarray(mask, dtype=np.uint32).reshape(-1))
+        self._chk(self.L.ingvio_nominal_marg_gnss(self.h, int(b0), mk.shape[0], mk.ctypes.data_as(C.POINTER(C.c_uint))))
 
     # ---- odometry output (DESIGN 4.11) -----------------------------------------------------------------------------------------
     def odom_begin(self, b0=0, nb=None, what=ODOM_ALL):

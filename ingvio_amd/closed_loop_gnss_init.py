@@ -170,8 +170,10 @@ def oracle_records(ep):
     return rec
 
 
-def rows_of(g, ep, rec, Rw, x):
-    """getResJacobianOfSys (:472-521) for candidate g from the satellite records: (Hx [m, 10], res [m], noise, satellites used)"""
+def rows_of(g, ep, rec, Rw, x, yaw=None):
+    """getResJacobianOfSys (:472-521) for candidate g from the satellite records: (Hx [m, 10], res [m], noise, satellites used).
+    yaw: is_adjust_yof - the YOF value the round reads; column 9 is then the reference's as written (:401-404, :462-465), with
+    getRecef2enu() = R_enu2ecef^T.  None (the default): column 9 stays zero"""
     fs = g == 0
     eph, obs = np.asarray(ep["eph"]), np.asarray(ep["obs"])
     sats = [i for i in range(len(eph)) if rec[i, 9] != 0 and (fs or int(eph[i, 0]) == g - 1)]
@@ -182,6 +184,9 @@ def rows_of(g, ep, rec, Rw, x):
         u = rec[i, 2:5]
         Hx[r, 0:3] = u @ RS
         Hx[r, (6 if fs else 3):(9 if fs else 6)] = -(u @ Rw)
+        if yaw is not None:
+            cy, sy = math.cos(yaw), math.sin(yaw)
+            Hx[r, 9] = -(u @ (np.asarray(ep["R_enu2ecef"]).T @ np.array([-sy * x[0] - cy * x[1], cy * x[0] - sy * x[1], 0.0])))
         res[r] = -(rec[i, 1] if fs else rec[i, 0])
         se = math.sin(rec[i, 6])
         se = 1e-6 if abs(se) < 1e-6 else se
@@ -191,10 +196,11 @@ def rows_of(g, ep, rec, Rw, x):
     return Hx, res, noise, sats
 
 
-def acquire(tab, slots, ep, spp, rec, add, chi2_table, read_once=False):
+def acquire(tab, slots, ep, spp, rec, add, chi2_table, read_once=False, adjust_yof=False):
     """addNewTrackedSys on a HostTable (moved in place, with `slots`).  rec: the satellite records at receiver(tab, slots, ep, spp);
     add(vidx, vsize, Hx, Hf, res, noise, chi2_check) -> (added, dx, chi2, new_idx): the backend's addVariableDelayed.
     read_once: p, v are read once before the loop instead of per round (what the reference does NOT do, :397 / :458).
+    adjust_yof: is_adjust_yof - the rows carry the YOF column, from YOF as the table holds it in the round.
     -> {g: dict(added, new_idx, slot, chi2, noise, dx, m)} for the five candidates"""
     out = {g: dict(added=False, new_idx=-1, slot=-1, chi2=0.0, noise=0.0, dx=None, m=0) for g in range(CAND)}
     if ep is None or len(ep["eph"]) == 0 or slots[5] < 0:
@@ -208,7 +214,7 @@ def acquire(tab, slots, ep, spp, rec, add, chi2_table, read_once=False):
     p0, v0 = np.array(e["p"]), np.array(e["v"])
     for g in cands:
         x = (v0 if g == 0 else p0) if read_once else (e["v"] if g == 0 else e["p"])
-        Hx, res, noise, sats = rows_of(g, ep, rec, Rw, x)
+        Hx, res, noise, sats = rows_of(g, ep, rec, Rw, x, float(yof["p"][0]) if adjust_yof else None)
         m = out[g]["m"] = len(sats)
         if m <= 1:                                                       # StateManager.cpp:571-575
             continue
@@ -226,7 +232,7 @@ def acquire(tab, slots, ep, spp, rec, add, chi2_table, read_once=False):
     return out
 
 
-def oracle_acquire(P, tab, slots, ep, spp, chi2_table, read_once=False, ld=None, rec=None):
+def oracle_acquire(P, tab, slots, ep, spp, chi2_table, read_once=False, ld=None, rec=None, adjust_yof=False):
     """acquire() on orc.Cov.add_variable_delayed, no GPU; -> (verdicts, the posterior P); tab and slots are moved in place.
     rec: satellite records to take instead of the oracle's own (the device front's: the two agree to 1e-6 m in res_pos only)"""
     from oracle import oracle as orc
@@ -239,14 +245,14 @@ def oracle_acquire(P, tab, slots, ep, spp, chi2_table, read_once=False, ld=None,
         lam.append(float(np.linalg.eigvalsh(np.array(cov.P() if callable(cov.P) else cov.P)).max()))
         return added, dx, chi2, cov.n - 1
     lam = []                                                             # lambda_max of P behind every round that was tried, in order
-    out = acquire(tab, slots, ep, spp, oracle_records(receiver(tab, slots, ep, spp)) if rec is None else rec, add, chi2_table, read_once)
+    out = acquire(tab, slots, ep, spp, oracle_records(receiver(tab, slots, ep, spp)) if rec is None else rec, add, chi2_table, read_once, adjust_yof)
     for g, l in zip([g for g in range(CAND) if "hnorm" in out[g]], lam):
         out[g]["lam_post"] = l
     Pn = cov.P() if callable(cov.P) else cov.P
     return out, np.array(Pn)
 
 
-def ctx_acquire(ctx, cases, tabs, f, chi2_table, read_once=False):
+def ctx_acquire(ctx, cases, tabs, f, chi2_table, read_once=False, adjust_yof=False):
     """acquire() for every filter on today's single-filter entry points of a context that holds the covariances: ingvio_gnss_sat_eval at
     the overridden receivers (one call), then ingvio_add_variable_delayed per candidate with its own noise, host boxPlus on tabs.
     The cases' gnss_slots move with the verdicts."""
@@ -260,7 +266,7 @@ def ctx_acquire(ctx, cases, tabs, f, chi2_table, read_once=False):
     for b, c in enumerate(cases):
         def add(vidx, vsize, Hx, Hf, res, noise, chk, b=b):
             return ctx.add_variable_delayed(b, vidx, vsize, Hx, Hf, res, noise, chi2_mult=CHI2_MULT, do_chi2=True, chi2_check=chk)
-        out.append(acquire(tabs[b], c["gnss_slots"], eps[b] if b in recs else None, c["spp"], recs.get(b), add, chi2_table, read_once))
+        out.append(acquire(tabs[b], c["gnss_slots"], eps[b] if b in recs else None, c["spp"], recs.get(b), add, chi2_table, read_once, adjust_yof))
     return out
 
 

@@ -1550,6 +1550,7 @@ static int gnss_front_upload(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_ep
     if (rc) return rc;
     double* he = upl.take<double>((size_t)nb * S * GE_N); double* ho = upl.take<double>((size_t)nb * S * GO_N);
     double* hr = upl.take<double>((size_t)nb * GR_N); double* hchi = upl.take<double>(CHI2_CAP);
+    const double adj_yof = c->gnss_adjust_yof ? 1.0 : 0.0;
     parallel_for(nb, [=](int i) {
         const ingvio_gnss_epoch& e = ep[i];
         memcpy(he + (size_t)i * S * GE_N, e.eph, 8 * (size_t)e.n_sat * GE_N);
@@ -1564,6 +1565,7 @@ static int gnss_front_upload(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_ep
         r[GR_IDX_SE23] = e.idx_se23; r[GR_IDX_YOF] = e.idx_yof; r[GR_IDX_FS] = e.idx_fs;
         for (int s = 0; s < 4; ++s) r[GR_IDX_CB + s] = e.idx_cb[s];
         r[GR_PSR_AMP] = e.psr_noise_amp; r[GR_DOPP_AMP] = e.dopp_noise_amp;
+        r[GR_ADJ_YOF] = adj_yof;
     });
     upl.copy(g.feph + (size_t)b0 * S * GE_N, he, (size_t)nb * S * GE_N);
     upl.copy(g.fobs + (size_t)b0 * S * GO_N, ho, (size_t)nb * S * GO_N);
@@ -3411,6 +3413,30 @@ int ingvio_set_delayed_form(ingvio_ctx* c, int mode)
     if (phase_busy(c)) return INGVIO_E_ARG;
     if (c->nom.pending) { c->err = "ingvio_set_delayed_form: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
     c->delayed_form = mode;
+    return INGVIO_OK;
+}
+// A GNSS stage of any form whose update has not run.  Which flags each stage leaves:
+//   ingvio_gnss_stage, ingvio_gnss_front_stage   staged = true, results = false; their run sets results and KEEPS staged (the pristine
+//                                                rows may run again); an in-frame ingvio_gnss_stage is consumed by its frame's run
+//   ingvio_gnss_front_stage_nominal              the same plus nom_pending, which its one run clears
+//   ingvio_gnss_frame_stage_nominal              staged and frame_nom, results untouched (they are the frame before's); the frame's run
+//                                                clears staged and frame_nom
+static bool gnss_stage_waiting(const ingvio_ctx* c)
+{
+    const auto& g = c->gn;
+    return g.staged && (g.frame_nom || g.nom_pending || !g.results);
+}
+
+// GnssUpdate::_is_adjust_yof: carried to the kernels in the receiver record (GR_ADJ_YOF), so it is fixed when an epoch is staged
+int ingvio_set_gnss_adjust_yof(ingvio_ctx* c, int on)
+{
+    if (!c) return INGVIO_E_ARG;
+    ENTER(c);
+    if (phase_busy(c)) return INGVIO_E_ARG;
+    if (gnss_stage_waiting(c)) {
+        c->err = "ingvio_set_gnss_adjust_yof: a GNSS epoch is staged and has not run yet"; return INGVIO_E_ARG;
+    }
+    c->gnss_adjust_yof = on ? 1 : 0;
     return INGVIO_OK;
 }
 int ingvio_frame_run_phase(ingvio_ctx* c, int restore_prior, int phase)

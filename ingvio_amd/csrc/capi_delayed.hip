@@ -641,6 +641,7 @@ static void gnss_init_fill(ingvio_ctx* c, int b0, int nb, const ingvio_gnss_init
         if (e.ion) memcpy(r + GR_ION, e.ion, 64);
         memcpy(r + GR_RENU, e.R_enu2ecef, 72); memcpy(r + GR_ANCHOR, e.anchor_ecef, 24);
         r[GR_PSR_AMP] = e.psr_noise_amp; r[GR_DOPP_AMP] = e.dopp_noise_amp;
+        r[GR_ADJ_YOF] = c->gnss_adjust_yof ? 1.0 : 0.0;
         // the scalars to add take the SPP fix (:343-372); k_gnss_front reads these fields only where the table has no such scalar
         const int* I = &c->nom.h_ih[(size_t)(b0 + i) * c->nom.ir];
         const bool fs_add = only_g >= 0 ? (fabs(blocks[i].vel_spp[3]) > 1e-3 && I[NOM_GNSS + NOM_G_FS] < 0) : pl.cand[(size_t)0 * nb + i] != 0;

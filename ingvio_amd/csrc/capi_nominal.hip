@@ -428,6 +428,157 @@ int ingvio_nominal_tail(ingvio_ctx* c, int b0, int nb, const ingvio_nominal_tail
     return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
 }
 
+// ---- the GNSS scalars enter and leave the table on the device --------------------------------------------------------
+// StateManager::addGNSSVariable (StateManager.cpp:194-231): one kernel appends the 1 x 1 block and writes the table record.  Only
+// enqueues; slot and idx are decided on the host mirror, which then follows.
+int ingvio_nominal_add_gnss(ingvio_ctx* c, int b0, int nb, const int* gtype, const double* value, const double* var, int* slot_out, int* idx_out)
+{
+    ENTER(c);
+    if (!c || phase_busy(c) || check_range(c, b0, nb) || !gtype || !value || !var || !slot_out || !idx_out) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    if (!m.vmax) { c->err = "ingvio_nominal_add_gnss without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = "ingvio_nominal_add_gnss: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, "ingvio_nominal_add_gnss")) return INGVIO_E_ARG;
+    int active = 0;
+    for (int i = 0; i < nb; ++i) {
+        if (gtype[i] < -1 || gtype[i] > 5) { c->err = "ingvio_nominal_add_gnss: gtype is -1 or a position 0..5"; return INGVIO_E_ARG; }
+        if (gtype[i] < 0) continue;
+        ++active;
+        if (m.h_ih[(size_t)(b0 + i) * m.ir + NOM_GNSS + gtype[i]] >= 0) {
+            c->err = "ingvio_nominal_add_gnss: a scalar is already registered at that position"; return INGVIO_E_ARG;
+        }
+    }
+    std::vector<int> slots((size_t)nb, -1);
+    for (int i = 0; i < nb; ++i) {
+        if (gtype[i] < 0) continue;
+        const int* I = &m.h_ih[(size_t)(b0 + i) * m.ir];
+        int v = 0;
+        while (v < m.vmax && I[NOM_IH + 4 * v] != NOM_KIND_NONE) ++v;
+        if (v >= m.vmax) { c->err = "ingvio_nominal_add_gnss: no free table slot"; return INGVIO_E_CAPACITY; }
+        if (c->h_n[b0 + i] + 1 > c->d.n_max) { c->err = "ingvio_nominal_add_gnss: n + 1 > n_max"; return INGVIO_E_CAPACITY; }
+        slots[i] = v;
+    }
+    for (int i = 0; i < nb; ++i) { slot_out[i] = -1; idx_out[i] = -1; }
+    if (!active) return INGVIO_OK;                                                      // nothing to do anywhere: nothing is launched
+    const size_t o_vv = pad64(sizeof(int) * 2 * (size_t)nb), in_bytes = o_vv + pad64(8 * 2 * (size_t)nb);
+    auto& w = c->tl;
+    if (int rc = dev_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
+    Uploader upl{ c };
+    if (int rc = upl.begin(in_bytes + 64)) return rc;
+    char* h = upl.take<char>(in_bytes);
+    memset(h, 0, in_bytes);
+    int* hg = (int*)h;
+    double* hv = (double*)(h + o_vv);
+    for (int i = 0; i < nb; ++i) { hg[2 * i] = gtype[i]; hg[2 * i + 1] = slots[i]; hv[2 * i] = value[i]; hv[2 * i + 1] = var[i]; }
+    upl.copy((int*)w.in, (const int*)h, in_bytes / sizeof(int));
+    if (int rc = upl.end()) return rc;
+    if (wait_inputs(c)) return INGVIO_E_HIP;                                            // nothing on the copy stream may still read the table
+    launch_nominal_add_gnss(view(c), nom_table(c), b0, nb, (const int*)w.in, (const double*)(w.in + o_vv), c->st);
+    if (int rc = last_launch(c)) return rc;
+    for (int i = 0; i < nb; ++i) {
+        if (gtype[i] < 0) continue;
+        const int b = b0 + i, sl = slots[i];
+        int* I = &m.h_ih[(size_t)b * m.ir];
+        int* v = I + NOM_IH + 4 * sl;
+        v[0] = NOM_KIND_SCALAR; v[1] = c->h_n[b]; v[2] = -1; v[3] = 0;
+        I[NOM_GNSS + gtype[i]] = sl;
+        if (sl >= I[NOM_N_VAR]) I[NOM_N_VAR] = sl + 1;
+        slot_out[i] = sl; idx_out[i] = c->h_n[b];
+        c->h_n[b] += 1;
+    }
+    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
+}
+
+// StateManager::margGNSSVariable (StateManager.cpp:233-242): the compaction of ingvio_nominal_tail with the named scalars as its erase
+// list - one read of P, one write into the other half, the table pass of k_tail_panel.  Nothing comes back from the device, so the call
+// only enqueues and the mirror follows on its own.
+int ingvio_nominal_marg_gnss(ingvio_ctx* c, int b0, int nb, const unsigned* mask)
+{
+    ENTER(c);
+    if (!c || phase_busy(c) || check_range(c, b0, nb) || !mask) return INGVIO_E_ARG;
+    auto& m = c->nom;
+    const char* who = "ingvio_nominal_marg_gnss";
+    if (!m.vmax) { c->err = "ingvio_nominal_marg_gnss without ingvio_nominal_create"; return INGVIO_E_ARG; }
+    if (m.pending) { c->err = "ingvio_nominal_marg_gnss: a frame staged from the device nominal state has not run yet"; return INGVIO_E_ARG; }
+    if (gnss_nom_busy(c, who)) return INGVIO_E_ARG;
+    auto fail = [&](int code, const char* what) { c->err = std::string(who) + ": " + what; return code; };
+    int ecap = 0, active = 0;
+    for (int i = 0; i < nb; ++i) if (mask[i] & ~63u) return fail(INGVIO_E_ARG, "a mask names a position above 5");
+    for (int i = 0; i < nb; ++i) {
+        if (!mask[i]) continue;
+        ++active;
+        const int b = b0 + i;
+        const int* I = &m.h_ih[(size_t)b * m.ir];
+        const int* var = I + NOM_IH;
+        const int nv = I[NOM_N_VAR], n = c->h_n[b];
+        for (int v = 0; v < nv; ++v)
+            if (var[4 * v] != NOM_KIND_NONE && (var[4 * v + 1] < 0 || var[4 * v + 1] + nom_size(var[4 * v]) > n)) return fail(INGVIO_E_NOT_IN_STATE, "a table variable lies beyond the filter's n");
+        int cnt = 0;
+        for (int s = 0; s < 6; ++s) {
+            if (!((mask[i] >> s) & 1u)) continue;
+            const int sl = I[NOM_GNSS + s];
+            if (sl < 0 || sl >= nv || var[4 * sl] != NOM_KIND_SCALAR) return fail(INGVIO_E_NOT_IN_STATE, "a named position is not registered");
+            ++cnt;
+        }
+        ecap = std::max(ecap, cnt);
+    }
+    if (!active) return INGVIO_OK;                                                      // nothing to do anywhere: nothing is launched
+    if (tail_panel_lds(c->ldp) > TAIL_LDS_MAX) return fail(INGVIO_E_CAPACITY, "the state is too wide for the panel kernel's index maps");
+    const int istride = TAIL_HDR + ecap, ld = c->ldp;
+    const size_t in_bytes = pad64(sizeof(int) * (size_t)nb * istride);
+    const size_t w_ver = pad64(sizeof(int) * (size_t)nb), w_map = w_ver + pad64(sizeof(int) * (size_t)nb),
+                 w_tag = w_map + pad64(sizeof(int) * (size_t)nb * ld), w_Z = w_tag + pad64(sizeof(int) * (size_t)nb * ld), ws_bytes = w_Z + 64;
+    auto& w = c->tl;
+    if (int rc = dev_grow(c, &w.in, &w.in_cap, in_bytes)) return rc;
+    if (int rc = dev_grow(c, &w.ws, &w.ws_cap, ws_bytes)) return rc;
+    Uploader upl{ c };
+    if (int rc = upl.begin(in_bytes + 64)) return rc;
+    int* h = upl.take<int>(in_bytes / sizeof(int));
+    memset(h, 0, in_bytes);
+    for (int i = 0; i < nb; ++i) {
+        const int* I = &m.h_ih[(size_t)(b0 + i) * m.ir];
+        int* r = h + (size_t)i * istride;
+        int cnt = 0;
+        for (int s = 0; s < 6; ++s) if ((mask[i] >> s) & 1u) r[TAIL_HDR + cnt++] = I[NOM_GNSS + s];
+        r[TAIL_N_ER] = cnt;
+    }
+    upl.copy((int*)w.in, h, in_bytes / sizeof(int));
+    if (int rc = upl.end()) return rc;
+    if (wait_inputs(c)) return INGVIO_E_HIP;                                            // nothing on the copy stream may still read the table
+    TailLaunch L;
+    L.cv = view(c); L.t = nom_table(c); L.b0 = b0; L.nb = nb;
+    L.in = (const int*)w.in; L.istride = istride; L.kcap = 0; L.ecap = ecap; L.mcap = 0;
+    L.nnew = (int*)w.ws; L.verdict = (int*)(w.ws + w_ver); L.map = (int*)(w.ws + w_map); L.tag = (int*)(w.ws + w_tag);
+    L.Z = (double*)(w.ws + w_Z); L.zstride = 0;
+    if (launch_tail(L, c->d.n_max, c->st)) return fail(INGVIO_E_CAPACITY, "a workspace bound of the tail kernels does not hold");
+    if (int rc = last_launch(c)) return rc;
+    // ---- the mirror: the table pass of k_tail_panel on the host's copy ----
+    for (int i = 0; i < nb; ++i) {
+        if (!mask[i]) continue;
+        const int b = b0 + i;
+        int* I = &m.h_ih[(size_t)b * m.ir];
+        int* var = I + NOM_IH;
+        const int nv = I[NOM_N_VAR];
+        int gone[6], ng = 0;
+        for (int s = 0; s < 6; ++s) {
+            if (!((mask[i] >> s) & 1u)) continue;
+            const int sl = I[NOM_GNSS + s];
+            gone[ng++] = var[4 * sl + 1];
+            var[4 * sl] = NOM_KIND_NONE; var[4 * sl + 1] = -1; var[4 * sl + 2] = -1;
+            I[NOM_GNSS + s] = -1;
+        }
+        for (int v = 0; v < nv; ++v) {
+            if (var[4 * v] == NOM_KIND_NONE) continue;
+            int sh = 0;
+            for (int e = 0; e < ng; ++e) if (gone[e] < var[4 * v + 1]) ++sh;
+            var[4 * v + 1] -= sh;
+        }
+        c->h_n[b] -= ng;
+        c->h_cur[b] ^= 1;
+    }
+    return nom_mark(c) ? INGVIO_E_HIP : INGVIO_OK;
+}
+
 // ---- MSCKF anchor change and invalid-feature erase on the track store (k_tracks_maintain) ---------------------------
 // changeMSCKFAnchor (KeyframeUpdate.cpp:280-328, SwMargUpdate.cpp:367-413) and eraseInvalidFeatures (MapServerManager.cpp:456-491) for the
 // tracks the host lists.  _begin only enqueues, in the pattern of ingvio_odom_begin: the lists up, one kernel, the table event behind it (an

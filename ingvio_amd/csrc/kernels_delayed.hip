@@ -147,6 +147,17 @@ __device__ __forceinline__ void gnss_rows_form(const DelayedGnssRows& r, int b, 
         sA[row + (size_t)c * ldA] = h[c];
         sA[row + (size_t)((fs ? 6 : 3) + c) * ldA] = -uR[c];
     }
+    const double* rc = r.rcv + (size_t)bl * GR_N;
+    if (rc[GR_ADJ_YOF] != 0.0) {
+        // is_adjust_yof, as the reference writes it (GnssUpdate.cpp:401-404, :462-465): -u^T R_ecef2enu dRz(yaw) x with getRecef2enu(), the
+        // TRANSPOSE of the R_enu2ecef the update rows take, and yaw read from the table in the round like x (dotRw2enu(state) sits inside
+        // the reference's loop).  dRz x = (-s x0 - c x1, c x0 - s x1, 0): rows 0 and 1 of R_enu2ecef against u.
+        const double yaw = r.nt.dv[(size_t)b * r.nt.dr + NOM_DH + (size_t)I[NOM_GNSS + NOM_G_YOF] * NOM_VD + 9];
+        const double cy = cos(yaw), sy = sin(yaw);
+        const double uE0 = u[0] * rc[GR_RENU] + u[1] * rc[GR_RENU + 1] + u[2] * rc[GR_RENU + 2];
+        const double uE1 = u[0] * rc[GR_RENU + 3] + u[1] * rc[GR_RENU + 4] + u[2] * rc[GR_RENU + 5];
+        sA[row + (size_t)9 * ldA] = -(uE0 * (-sy * x[0] - cy * x[1]) + uE1 * (cy * x[0] - sy * x[1]));
+    }
     sA[row + (size_t)nc * ldA] = -(fs ? fr[1] : fr[0]);
     const double* ep = r.eph + ((size_t)bl * r.smax + lane) * GE_N;
     const double* ob = r.obs + ((size_t)bl * r.smax + lane) * GO_N;
@@ -210,7 +221,7 @@ __global__ __launch_bounds__(DL_NT) void k_delayed_front(DelayedFront a, typenam
     double* sT = sA + (size_t)(nc + 1) * ldA;               // row c of T = column nc + 1 + c of sA
 
     // ---- 1. stage the rows --------------------------------------------------------------------------------------------
-    if constexpr (KIND == DL_GNSS) {                         // formed here: zero fill (columns 3-5 or 6-8 and 9 stay zero), one lane per satellite
+    if constexpr (KIND == DL_GNSS) {                         // formed here: zero fill (columns 3-5 or 6-8 stay zero, and 9 unless is_adjust_yof), one lane per satellite
         for (int e = tid; e < (nc + 1) * ldA; e += DL_NT) sA[e] = 0.0;
         for (int e = tid; e < m; e += DL_NT) sHn[e] = 1.0;   // H_new: all ones
         const int* I = r.nt.ih + (size_t)b * r.nt.ir;

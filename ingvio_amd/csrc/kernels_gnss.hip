@@ -209,7 +209,8 @@ __device__ double iono_delay(double tow, const double* __restrict__ ion, const d
 // after its marginalisation shift) instead of the receiver record, which then carries only what the host owns (n_sat, doy, ionosphere,
 // R_enu2ecef, anchor, noise amplitudes).  The table loads are wave-uniform and two levels deep (slot, then value / idx): they are issued
 // here at the top around the lane's first satellite loads, so that all of them are in flight together; from there on both variants run
-// the same arithmetic on the same values.
+// the same arithmetic on the same values.  GR_ADJ_YOF of the receiver record (ingvio_set_gnss_adjust_yof, GnssUpdate::_is_adjust_yof) adds
+// the yaw-offset column to every candidate row, from the yaw, p_w and v_w the kernel holds; without it the column stays zero.
 template <bool NOM>
 __global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L, NomTable nt, int b0)
 {
@@ -364,6 +365,14 @@ __global__ __launch_bounds__(64) void k_gnss_front(GnssFrontLaunch L, NomTable n
             H[r0 + (size_t)(3 + c) * mld] = -uR[c];
             H[r1 + (size_t)c * mld] = hv[c];
             H[r1 + (size_t)(6 + c) * mld] = -uR[c];
+        }
+        if (rc[GR_ADJ_YOF] != 0.0) {
+            // is_adjust_yof: -u^T R_enu2ecef dRz(yaw) x in the YOF column (:164-167, :239-242), dRz = [[-s, -c, 0], [c, -s, 0], [0, 0, 0]]
+            // (GnssManager.cpp:101-113).  Off, the column keeps the zero fill above.
+            double uE[2];                                              // u^T R_enu2ecef: dRz x has no third component
+            for (int c = 0; c < 2; ++c) uE[c] = u[0] * rc[GR_RENU + c] + u[1] * rc[GR_RENU + 3 + c] + u[2] * rc[GR_RENU + 6 + c];
+            H[r0 + (size_t)9 * mld] = -(uE[0] * (-sy * p[0] - cy * p[1]) + uE[1] * (cy * p[0] - sy * p[1]));
+            H[r1 + (size_t)9 * mld] = -(uE[0] * (-sy * v[0] - cy * v[1]) + uE[1] * (cy * v[0] - sy * v[1]));
         }
         H[r0 + (size_t)sCbCol[sys] * mld] = 1.0;
         H[r1 + (size_t)fs_col * mld] = 1.0;

@@ -198,6 +198,40 @@ __global__ __launch_bounds__(64) void k_nominal_update_post(NomTable t, const do
     }
 }
 
+// StateManager::addGNSSVariable (StateManager.cpp:194-231) for filter b0 + blockIdx.x: an independent 1 x 1 block at the live n (row and
+// column n zero over [0, n), the diagonal var - k_append's arithmetic), the scalar's record in the table slot the host chose, registered
+// at NOM_GNSS + gtype.  gs [nb][2] = {gtype (-1: nothing for this filter), slot}, vv [nb][2] = {value, var}.  The host has checked on its
+// mirror that the slot is free and inside the table and that n + 1 columns fit.
+__global__ __launch_bounds__(256) void k_nominal_add_gnss(CovView cv, NomTable t, int b0, const int* __restrict__ gs, const double* __restrict__ vv)
+{
+    const int bl = blockIdx.x, b = b0 + bl, tid = threadIdx.x;
+    const int gtype = gs[2 * bl], slot = gs[2 * bl + 1];
+    if (gtype < 0) return;                                             // (uniform over the workgroup: ahead of the barrier)
+    const int n = cv.n[b], ld = cv.ldp;
+    double* P = cov_ptr(cv, b);
+    for (int r = tid; r < n; r += 256) {
+        P[r + (size_t)n * ld] = 0.0;
+        P[n + (size_t)r * ld] = 0.0;
+    }
+    __syncthreads();                                                   // every wave has read n before thread 0 stores n + 1 (as k_append)
+    if (tid != 0) return;
+    P[n + (size_t)n * ld] = vv[2 * bl + 1];
+    int* I = t.ih + (size_t)b * t.ir;
+    int* v = I + NOM_IH + 4 * slot;
+    v[0] = NOM_KIND_SCALAR; v[1] = n; v[2] = -1; v[3] = 0;
+    double* x = t.dv + (size_t)b * t.dr + NOM_DH + (size_t)slot * NOM_VD;
+    for (int i = 0; i < NOM_VD; ++i) x[i] = (i == 0 || i == 4 || i == 8) ? 1.0 : 0.0;
+    x[9] = vv[2 * bl];
+    I[NOM_GNSS + gtype] = slot;
+    if (slot >= I[NOM_N_VAR]) I[NOM_N_VAR] = slot + 1;
+    cv.n[b] = n + 1;
+}
+
+void launch_nominal_add_gnss(const CovView& cv, const NomTable& t, int b0, int nb, const int* gs, const double* vv, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_nominal_add_gnss, dim3(nb), dim3(256), 0, st, cv, t, b0, gs, vv);
+}
+
 void launch_nominal_update(const NomTable& t, const double* dx, int ldx, const int* marg, int b0, int nb, hipStream_t st)
 {
     if (marg) hipLaunchKernelGGL(k_nominal_update<true>, dim3(nb), dim3(64), 0, st, t, dx, ldx, marg, b0, NomGather{});

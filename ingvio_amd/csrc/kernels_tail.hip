@@ -70,7 +70,8 @@ __global__ __launch_bounds__(TAIL_NT) void k_tail_panel(TailLaunch L)
     if (tid == 0) s_nw = k ? var[4 * nws + 1] : 0;
     __syncthreads();
     if (tid < k) for (int c = 0; c < 3; ++c) flag[s_L[tid] + c] = s_v[tid] ? 3 * tid + c : -2;
-    for (int e = tid; e < ne; e += TAIL_NT) { const int ix = var[4 * er_slot[e] + 1]; for (int c = 0; c < 3; ++c) flag[ix + c] = -2; }
+    // (an erased slot holds a landmark, 3 columns, or a GNSS scalar, 1 column: ingvio_nominal_marg_gnss)
+    for (int e = tid; e < ne; e += TAIL_NT) { const int ix = var[4 * er_slot[e] + 1], sz = tail_var_size(var[4 * er_slot[e]]); for (int c = 0; c < sz; ++c) flag[ix + c] = -2; }
     for (int e = tid; e < nm; e += TAIL_NT) { const int ix = var[4 * mg_slot[e] + 1]; for (int c = 0; c < 6; ++c) flag[ix + c] = -2; }
     // ---- Y_a = P H_a^T for every re-anchored landmark (StateManager.cpp:671-681), from the original P ----
     const int nw = s_nw;
@@ -150,8 +151,11 @@ __global__ __launch_bounds__(TAIL_NT) void k_tail_panel(TailLaunch L)
     for (int v = tid; v < nv; v += TAIL_NT) {
         if (var[4 * v] == NOM_KIND_NONE) continue;
         const int ix = var[4 * v + 1];
-        if (flag[ix] == -2) { var[4 * v] = NOM_KIND_NONE; var[4 * v + 1] = -1; var[4 * v + 2] = -1; }
-        else var[4 * v + 1] = pre[ix];
+        if (flag[ix] == -2) {
+            if (var[4 * v] == NOM_KIND_SCALAR)                         // a GNSS scalar that leaves is no longer registered (StateManager.cpp:233-242)
+                for (int q = 0; q < 6; ++q) if (I[NOM_GNSS + q] == v) I[NOM_GNSS + q] = -1;
+            var[4 * v] = NOM_KIND_NONE; var[4 * v + 1] = -1; var[4 * v + 2] = -1;
+        } else var[4 * v + 1] = pre[ix];
     }
     if (tid < k && s_v[tid]) var[4 * lm_slot[tid] + 2] = nws;
 }

@@ -57,7 +57,9 @@ struct DelayedRows {
 // (GnssUpdate.cpp:375-470, getResJacobianOfSys :472-521) for candidate scalar g of every filter - g = 0 the frequency shift (rows: every
 // usable satellite, x = v_w, -u^T R_w2ecef in columns 6-8, res = -res_vel), g = 1..4 the clock bias of GPS, GLO, GAL, BDS (rows: the usable
 // satellites of that constellation, x = p_w, columns 3-5, res = -res_pos).  Hx has 10 columns over [SE23 (9), YOF (1)]; u^T R_w2ecef [x]x
-// in columns 0-2; column 9 stays zero (is_adjust_yof = 0 only); H_new is all ones, s = 1.  x is read from the table when the round runs;
+// in columns 0-2; column 9 stays zero unless the receiver record's GR_ADJ_YOF is set (ingvio_set_gnss_adjust_yof), then it is
+// -u^T R_enu2ecef^T dRz(YOF) x as the reference writes it (:401-404, :462-465: getRecef2enu(), not the getRenu2ecef() of the update rows),
+// YOF read from the table when the round runs like x; H_new is all ones, s = 1.  x is read from the table when the round runs;
 // the residuals, lines of sight and elevations are those of k_gnss_front at the call's start, and so is R_w2ecef (Rw).  The noise of the
 // round, amp * sqrt(mean(ura * std / sin^2 el)) over the rows, is computed by the front and is the R of its gate and of the trailing update.
 // With it the front ignores dbuf / doff / m / s / nc / colmap / thr / var of DelayedFront.

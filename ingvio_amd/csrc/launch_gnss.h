@@ -12,7 +12,7 @@ enum { GO_TOW = 0, GO_PSR, GO_DOPP, GO_PSR_STD, GO_DOPP_STD, GO_FREQ, GO_N };
 // per-filter receiver record
 enum { GR_NSAT = 0, GR_DOY, GR_HAVE_ION, GR_ION, GR_PW = GR_ION + 8, GR_VW = GR_PW + 3, GR_CB = GR_VW + 3, GR_FS = GR_CB + 4, GR_YAW,
        GR_RENU, GR_ANCHOR = GR_RENU + 9, GR_IDX_SE23 = GR_ANCHOR + 3, GR_IDX_YOF, GR_IDX_FS, GR_IDX_CB, GR_PSR_AMP = GR_IDX_CB + 4,
-       GR_DOPP_AMP, GR_N };
+       GR_DOPP_AMP, GR_ADJ_YOF /* GnssUpdate::_is_adjust_yof (ingvio_set_gnss_adjust_yof): != 0, the rows carry the yaw-offset column */, GR_N };
 enum { GF_N = 20 };            // per-satellite outputs: res_pos, res_vel, los 3, az, el, ion, tro, usable, then the SatState: pos 3, vel 3, dt, ddt, tgd, ttx
 #define GNSS_FRONT_NCW 32      // == GNSS_NCW of capi.hip: column stride of the staged rows
 

@@ -29,6 +29,11 @@ void launch_nominal_update(const NomTable& t, const double* dx, int ldx, const i
 // the write-back): each variable reads dx at its shifted idx, the clone that leaves reads nothing, then drop and shift (k_nominal_update_post)
 void launch_nominal_update_post(const NomTable& t, const double* dx, int ldx, const int* marg, int b0, int nb, hipStream_t st);
 
+// StateManager::addGNSSVariable (StateManager.cpp:194-231, ingvio_nominal_add_gnss) for filters [b0, b0 + nb): P gains an independent
+// 1 x 1 block at the live n and the table a Scalar registered as GNSS scalar.  gs [nb][2] = {position behind NOM_GNSS (-1: nothing for
+// this filter), table slot}, vv [nb][2] = {value, variance}, both in device memory
+void launch_nominal_add_gnss(const CovView& cv, const NomTable& t, int b0, int nb, const int* gs, const double* vv, hipStream_t st);
+
 // The landmark update's staged inputs (LmView, launch_lmbatch.h) filled from the table: per filter the extended pose and the extrinsics
 // into pose [B][24] and their idx into idx [B][2], and for each of the n_lm[b] staged landmarks (slot [B][lmax]: its table slot)
 // lm_idx = idx[slot], anchor_idx = idx[anchor[slot]] (-1: no live anchor), pf = p[slot].  Indexed by the ABSOLUTE filter b.

@@ -6,6 +6,7 @@
 // Per filter i of the call (i = b - b0) the uploaded lists, ints at in + i * istride:
 //   [TAIL_N_RE] landmarks to re-anchor, [TAIL_NEW] table slot of the target clone, [TAIL_N_ER] landmarks to erase, [TAIL_N_MG] clones that
 //   leave, then lm_slot [kcap], erase_slot [ecap], marg_slot [mcap].  A filter whose three counts are zero is skipped by every kernel.
+//   An erase_slot may also hold a registered GNSS scalar (ingvio_nominal_marg_gnss): one column leaves and its registration is cleared.
 // and the workspace the panel kernel fills for the write-back:
 //   nnew [nb]        the state dimension after the call
 //   verdict [nb][kcap]   1: re-anchored, 0: behind the new anchor, marginalised (LandmarkUpdate.cpp:298-302)
